@@ -11,7 +11,10 @@ and tails; the roofline block times the kernel of one image restored alone.  N>1
 (per-image mode of the reference: no data-path collective, weak scaling); --shared-water adds the one
 all-reduce per iteration of the shared-water extension.
 
-Prints ONE JSON line on rank 0 (see DESIGN.md section 6 for how each field is measured).
+Prints ONE JSON line on rank 0 (see DESIGN.md section 6 for how each field is measured).  A plain run sets up, warms up,
+times the --steps steps and prints the headline figure; --full adds everything else the line can carry (the second timed
+region against views already packed, the roofline pass of images restored alone, the committed profiles' traffic, the CPU
+baseline).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -79,6 +82,15 @@ def parse():
     p.add_argument('--digest', action='store_true',
                    help='config.J_sha256_per_rank: SHA-256 of the last J every rank produced (per-image mode shards with no '
                         'collective: a rank\'s J must be the bits a 1-GPU run of the same image gives)')
+    p.add_argument('--full', action='store_true',
+                   help='measure more than the headline figure: a second timed region against views already packed, the roofline '
+                        'pass (--solo-images images restored strictly one at a time), the committed profiles\' traffic and the CPU '
+                        'baseline (unless --no-cpu-baseline); a plain run times the steps and prints the headline figure only')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps, write what the last timed step returned to its caller -- J of every image '
+                        '(float32; a fixed, seeded sample of pixels when all of it would pass 60 MiB) and the fit trace '
+                        '(float64) -- as DIR/<name>.npy (rank 0); finite values only: NaN (a pixel without valid depth) is '
+                        'written as 0 and flagged in DIR/<name>_nonfinite.npy')
     p.add_argument('--no-cpu-baseline', action='store_true')
     p.add_argument('--cpu-views', type=int, default=65, help='views in the CPU-baseline sample (65 = all of config 2)')
     p.add_argument('--cpu-iters', type=int, default=100, help='Adam iterations in the CPU-baseline sample (~15 s of CPU '
@@ -90,6 +102,8 @@ def parse():
     for key, val in preset.items():
         if key not in given:   # a flag given explicitly keeps its value (also when that value is the default)
             setattr(args, key, val)
+    if args.steps < 1:
+        p.error('--steps must be at least 1 (the timed region is --steps steps)')
     return args
 
 
@@ -216,6 +230,44 @@ def cpu_baseline(scene, n_obs_full, n_views_full, num_iter, sample_views, sample
         'ns_per_obs_iter': t_fit / sample_iters / max(n_obs_s, 1) * 1e9,
         'reference_equivalent': ref_eq,
     }
+
+
+DUMP_LIMIT_BYTES = 60 * 2**20   # what --dump-outputs may write: under 64 MB however counted, .npy headers included
+
+
+def dump_outputs(out_dir, images) -> list[str]:
+    """--dump-outputs: ``images`` = [(J, trace)] of every image of the last timed step, as its caller received them (J: (H, W, 3)
+    float32 device image; trace: the fit's float64 log, or None; the images of a shared-water group share one trace).
+    Writes J.npy (n, H, W, 3) and trace.npy (n_traces, T, width); when J would take the file set past DUMP_LIMIT_BYTES, J_sample.npy
+    (n, k, 3) holds the same k pixels of every image (seed 0, ascending linear index) and J_sample_pixels.npy their indices.
+    Every file holds finite values only: J is NaN where a pixel has no valid depth (sucre.py:86-87), so a non-finite element is
+    written as 0 and <name>_nonfinite.npy (same shape, float32) is 1 exactly there -- always for J, for the others when needed."""
+    import numpy as np
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    traces = list({id(t): t for _, t in images if t is not None}.values())
+    files = {}
+    if traces:
+        files['trace'] = np.stack([t.cpu().numpy() for t in traces]).astype(np.float64)
+    H, W, _ = images[0][0].shape
+    n = len(images)
+    room = DUMP_LIMIT_BYTES - 2 * sum(a.nbytes for a in files.values())   # (room for a mask of the trace too)
+    if n * H * W * 3 * 8 <= room:   # J + its mask
+        files['J'] = np.stack([J.cpu().numpy() for J, _ in images]).astype(np.float32)
+    else:
+        k = room // (n * 3 * 8 + 8)
+        pick = torch.randperm(H * W, generator=torch.Generator().manual_seed(0))[:k].sort().values
+        idx = pick.to(images[0][0].device)
+        files['J_sample'] = np.stack([J.reshape(H * W, 3)[idx].cpu().numpy() for J, _ in images]).astype(np.float32)
+        files['J_sample_pixels'] = pick.numpy().astype(np.float64)
+    for name in list(files):
+        bad = ~np.isfinite(files[name])
+        if name in ('J', 'J_sample') or bad.any():
+            files[name] = np.where(bad, 0, files[name]).astype(files[name].dtype)
+            files[name + '_nonfinite'] = bad.astype(np.float32)
+    for name, a in files.items():
+        np.save(out / f'{name}.npy', a)
+    return sorted(files)
 
 
 def spawn_ranks(args) -> int:
@@ -373,6 +425,14 @@ def main():
             st.wait_stream(cur)
 
     fit_events = []
+    last_step = []   # --dump-outputs: (J, trace) of every image of the latest step
+
+    def returned(J, trace, new_step):
+        """What the step handed its caller for one image (kept for --dump-outputs only); ``new_step``: the image opens a step."""
+        if args.dump_outputs:
+            if new_step:
+                last_step.clear()
+            last_step.append((J, trace))
 
     group_restos = None
     if args.shared_water and len(jobs) > 1:
@@ -385,11 +445,13 @@ def main():
         """``n_steps`` steps of the workload: n_steps x len(jobs) images, consecutive images ``--fit-batch`` at a time."""
         if group_restos is not None:
             for _ in range(n_steps):
+                last_step.clear()
                 pack_survey()
                 shared_water_step(record)
             return
         if args.batch_images > 1:
             for _ in range(n_steps):
+                last_step.clear()
                 pack_survey()
                 for c in range(0, len(jobs), B):
                     restore_chunk(jobs[c:c + B], record)
@@ -419,6 +481,7 @@ def main():
             fit_events.append((e0, e1))
         for r in group_restos:
             J_out[0] = r.J()
+            returned(J_out[0], water_trace[0], False)
 
     def restore_chunk(chunk, record, slot=None, count=1):
         nonlocal submitted
@@ -450,7 +513,10 @@ def main():
         if record:
             e1.record()
             fit_events.append((e0, e1))
-        J_out[slot] = [r.J() for r in rs][0]
+        Js = [r.J() for r in rs]
+        J_out[slot] = Js[0]
+        for r, J in zip(rs, Js):   # (a single-image chunk holds consecutive steps: the last image is the latest step)
+            returned(J, r.trace, single)
 
     def restore_on(resto, slot, tgt, views, record):
         resto.match(tgt, views, min_cover=1e-6, packed=packed_arg())
@@ -466,6 +532,7 @@ def main():
             e1.record()
             fit_events.append((e0, e1))
         J_out[slot] = resto.J()
+        returned(J_out[slot], water_trace[0] if args.shared_water else resto.trace, single)
 
     def barrier():
         torch.cuda.synchronize()
@@ -498,11 +565,14 @@ def main():
         te = torch.tensor([elapsed], dtype=torch.float64, device=device if dist.get_backend() == 'nccl' else 'cpu')
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
         elapsed = float(te.item())
+    if args.dump_outputs and rank == 0:
+        note(rank, 'dump outputs', ', '.join(dump_outputs(args.dump_outputs, last_step)))
+    last_step.clear()
 
     # The same K steps once more with every view's records already built (a survey whose views were met before; what `value`
     # was until round 5): reported next to `value`, never as it.
     elapsed_prepacked = None
-    if pack[0]:
+    if pack[0] and args.full:
         pack[0] = False
         was_plain, plain[0] = plain[0], False
         note(rank, 'second timed region (views already packed)')
@@ -531,106 +601,107 @@ def main():
     # what this rank holds in HBM for the fit: every workspace (one per in-flight slot, or one per image of a shared-water group)
     held = group_restos if group_restos is not None else [r for sl in slots for r in sl]
     workspace_bytes = sum(r.ws.numel() + (r.lws.numel() if r.lws is not None else 0) for r in held)
-    timed_region_iter_ms = None
-    if S > 1:
-        # the fits of different slots overlap: what the timed region sustained is the union of their intervals
-        spans = sorted((base.elapsed_time(a), base.elapsed_time(b)) for a, b in fit_events)
-        union, lo, hi = 0.0, spans[0][0], spans[0][1]
-        for a, b in spans[1:]:
-            if a > hi:
-                union, lo, hi = union + hi - lo, a, b
-            else:
-                hi = max(hi, b)
-        union += hi - lo
-        timed_region_iter_ms = union / (n_fits * T)
-    else:
-        # (a shared-water group: one launch per iteration walks every image of the rank -- the launch is the unit)
-        timed_region_iter_ms = sum(a.elapsed_time(b) for a, b in fit_events) / n_fits / T
-
-    # Roofline pass: the dominant kernel by itself.  `--solo-images` more restorations of the same image, strictly one
-    # at a time on slot 0 (nothing else on the GPU), HIP events on the stream the kernels are launched on: one pair
-    # around the 200 fit launches, one around match + finalize.  This is the configuration rocprofv3 is run in
-    # (tools/profile.sh: --images-in-flight 1), so its per-kernel average is directly comparable.
-    solo_fit, solo_match, solo_pack, solo_all = [], [], [], []
-    if group_restos is None:
-        with torch.cuda.stream(streams[0]):
-            # (one untimed image first: the match stage of the first image after the barrier was seen at 3.5 ms instead of
-            # 1.0 -- the GPU had idled through the host's bookkeeping between the timed region and here)
-            solo_chunk = (list(jobs) * B)[:B]   # --fit-batch: the launch is the unit -- one chunk of B images at a time
-            for i in range(1 + max(1, args.solo_images)):
-                tgt, views = jobs[0]
-                p0, m0, m1, f0, f1, x1 = (torch.cuda.Event(enable_timing=True) for _ in range(6))
-                p0.record()
-                if args.batch_images == 1:
-                    for _, vs in solo_chunk:   # sucre_pack_view of every view of every image of the chunk, as in the timed step
-                        pack_views(vs)
-                else:
-                    pack_views(views)
-                m0.record()
-                restos[0].match(tgt, views, min_cover=1e-6, packed=packed_arg())
-                m1.record()
-                restos[0].fit_init(tgt)
-                for r, (tg, vs) in list(zip(slots[0], solo_chunk))[1:]:
-                    r.match(tg, vs, min_cover=1e-6, packed=packed_arg())
-                    r.fit_init(tg)
-                f0.record()
-                if args.shared_water:
-                    sdist.fit_shared_water(engine.HipWaterGroup([restos[0]], use_closed_form=args.use_closed_form), T)
-                elif B > 1:
-                    engine.fit_batch(slots[0][:B], T, use_closed_form=args.use_closed_form, record_trace=True)
-                else:
-                    restos[0].fit(T, use_closed_form=args.use_closed_form, record_trace=True)
-                f1.record()
-                J_solo = [r.J() for r in slots[0][:B]]
-                x1.record()
-                if i > 0:
-                    solo_fit.append((f0, f1))
-                    solo_match.append((m0, m1))
-                    solo_pack.append((p0, m0))
-                    solo_all.append((p0, x1))
-        torch.cuda.synchronize()
-        del J_solo
-        iter_ms = sum(a.elapsed_time(b) for a, b in solo_fit) / len(solo_fit) / T
-        match_ms = sum(a.elapsed_time(b) for a, b in solo_match) / len(solo_match)
-        match_ms_each = [a.elapsed_time(b) for a, b in solo_match]
-        # sucre_pack_view of all views of ONE image (a survey packs a view once for all its targets: there this is an upper bound)
-        pack_ms = (sum(a.elapsed_time(b) for a, b in solo_pack) / len(solo_pack) / (B if args.batch_images == 1 else 1)) if (pack[0] and not plain[0]) else None
-        solo_ms_per_image = sum(a.elapsed_time(b) for a, b in solo_all) / len(solo_all) / B   # pack + match + init + T iterations + export, alone
-    else:
-        iter_ms, match_ms, match_ms_each, pack_ms, solo_ms_per_image = timed_region_iter_ms, None, None, None, None
-
-    fit_ms = iter_ms * T
-    obs_passes = 2 if (args.use_closed_form and args.light_model) else 1  # light + closed form: J pass, then gradient pass
-    state_bytes = 12 * H * W if args.use_closed_form else STATE_BYTES_PER_PX * H * W
-    obs_bytes = 5 if args.obs_format == 'u16mm' else OBS_BYTES   # c = 5 B/obs for config 5
-    # observations one launch streams: a shared-water group's, a --fit-batch chunk's, or the one image's
-    launch_obs = (sum(r.n_obs() for r in group_restos) if group_restos is not None
-                  else sum(r.n_obs() for r in slots[0][:B]) if B > 1 else n_obs)
-    launch_images = len(group_restos) if group_restos is not None else B
-    algo_bytes = (obs_bytes + (12 if args.light_model else 0)) * launch_obs + state_bytes * launch_images  # A_fit / T
-    achieved = algo_bytes / (iter_ms * 1e-3) / 1e9
-    # What the store really holds: an 'f32' store whose ranges fit is kept as 24-bit codes by the device's own
-    # decision -- 6 B/observation, same bits -- so the launch MOVES fewer bytes than SURVEY 8(d)'s 7 B figure charges it for.
-    # `achieved` / `frac` stay the algorithmic work rate SURVEY 8(d) defines (the figure the judge recomputes); the bytes the
-    # HBM has to deliver are reported next to it and are what `frac_of_achievable` (a physical copy ceiling) is measured in.
-    store = int(resto.store_format()[0].item())
-    stored_obs_bytes = {0: 7, 1: 5, 2: 6, 3: 6.25}[store]   # _lib.STORE_F32 / STORE_U16MM / STORE_Z24 / STORE_Z26
-    stored_bytes = (stored_obs_bytes + (12 if args.light_model else 0)) * launch_obs * obs_passes + state_bytes * launch_images
-    moved = stored_bytes / (iter_ms * 1e-3) / 1e9
     counts = resto.view_counts().cpu().numpy()
     cover = counts / float(W * H)
-    # A_match = 4 HW + sum_k (4 H_k W_k + 3 n_k + c n_k)   (every view here has the target's size)
-    match_bytes = 4 * H * W + int(sum(4 * H * W + (3 + OBS_BYTES) * int(n) for n in counts))
+    if args.full:
+        timed_region_iter_ms = None
+        if S > 1:
+            # the fits of different slots overlap: what the timed region sustained is the union of their intervals
+            spans = sorted((base.elapsed_time(a), base.elapsed_time(b)) for a, b in fit_events)
+            union, lo, hi = 0.0, spans[0][0], spans[0][1]
+            for a, b in spans[1:]:
+                if a > hi:
+                    union, lo, hi = union + hi - lo, a, b
+                else:
+                    hi = max(hi, b)
+            union += hi - lo
+            timed_region_iter_ms = union / (n_fits * T)
+        else:
+            # (a shared-water group: one launch per iteration walks every image of the rank -- the launch is the unit)
+            timed_region_iter_ms = sum(a.elapsed_time(b) for a, b in fit_events) / n_fits / T
 
-    # committed rocprofv3 evidence for the same mode and workload (profiles/rNN_<mode>_traffic.json from tools/profile.sh,
-    # newest round first; the mode names are tools/profile.sh's)
-    tag = profile_tag(args, B)
-    traffic = prof = None
-    for tf in profile_candidates(tag):
-        rec = json.loads(tf.read_text())
-        if rec.get('n_obs') == n_obs and 'hbm_bytes_per_launch' in rec:   # same workload as the profiled one
-            traffic, prof = rec['hbm_bytes_per_launch'], (tf.name, rec)
-            break
+        # Roofline pass: the dominant kernel by itself.  `--solo-images` more restorations of the same image, strictly one
+        # at a time on slot 0 (nothing else on the GPU), HIP events on the stream the kernels are launched on: one pair
+        # around the 200 fit launches, one around match + finalize.  This is the configuration rocprofv3 is run in
+        # (tools/profile.sh: --images-in-flight 1), so its per-kernel average is directly comparable.
+        solo_fit, solo_match, solo_pack, solo_all = [], [], [], []
+        if group_restos is None:
+            with torch.cuda.stream(streams[0]):
+                # (one untimed image first: the match stage of the first image after the barrier was seen at 3.5 ms instead of
+                # 1.0 -- the GPU had idled through the host's bookkeeping between the timed region and here)
+                solo_chunk = (list(jobs) * B)[:B]   # --fit-batch: the launch is the unit -- one chunk of B images at a time
+                for i in range(1 + max(1, args.solo_images)):
+                    tgt, views = jobs[0]
+                    p0, m0, m1, f0, f1, x1 = (torch.cuda.Event(enable_timing=True) for _ in range(6))
+                    p0.record()
+                    if args.batch_images == 1:
+                        for _, vs in solo_chunk:   # sucre_pack_view of every view of every image of the chunk, as in the timed step
+                            pack_views(vs)
+                    else:
+                        pack_views(views)
+                    m0.record()
+                    restos[0].match(tgt, views, min_cover=1e-6, packed=packed_arg())
+                    m1.record()
+                    restos[0].fit_init(tgt)
+                    for r, (tg, vs) in list(zip(slots[0], solo_chunk))[1:]:
+                        r.match(tg, vs, min_cover=1e-6, packed=packed_arg())
+                        r.fit_init(tg)
+                    f0.record()
+                    if args.shared_water:
+                        sdist.fit_shared_water(engine.HipWaterGroup([restos[0]], use_closed_form=args.use_closed_form), T)
+                    elif B > 1:
+                        engine.fit_batch(slots[0][:B], T, use_closed_form=args.use_closed_form, record_trace=True)
+                    else:
+                        restos[0].fit(T, use_closed_form=args.use_closed_form, record_trace=True)
+                    f1.record()
+                    J_solo = [r.J() for r in slots[0][:B]]
+                    x1.record()
+                    if i > 0:
+                        solo_fit.append((f0, f1))
+                        solo_match.append((m0, m1))
+                        solo_pack.append((p0, m0))
+                        solo_all.append((p0, x1))
+            torch.cuda.synchronize()
+            del J_solo
+            iter_ms = sum(a.elapsed_time(b) for a, b in solo_fit) / len(solo_fit) / T
+            match_ms = sum(a.elapsed_time(b) for a, b in solo_match) / len(solo_match)
+            match_ms_each = [a.elapsed_time(b) for a, b in solo_match]
+            # sucre_pack_view of all views of ONE image (a survey packs a view once for all its targets: there this is an upper bound)
+            pack_ms = (sum(a.elapsed_time(b) for a, b in solo_pack) / len(solo_pack) / (B if args.batch_images == 1 else 1)) if (pack[0] and not plain[0]) else None
+            solo_ms_per_image = sum(a.elapsed_time(b) for a, b in solo_all) / len(solo_all) / B   # pack + match + init + T iterations + export, alone
+        else:
+            iter_ms, match_ms, match_ms_each, pack_ms, solo_ms_per_image = timed_region_iter_ms, None, None, None, None
+
+        fit_ms = iter_ms * T
+        obs_passes = 2 if (args.use_closed_form and args.light_model) else 1  # light + closed form: J pass, then gradient pass
+        state_bytes = 12 * H * W if args.use_closed_form else STATE_BYTES_PER_PX * H * W
+        obs_bytes = 5 if args.obs_format == 'u16mm' else OBS_BYTES   # c = 5 B/obs for config 5
+        # observations one launch streams: a shared-water group's, a --fit-batch chunk's, or the one image's
+        launch_obs = (sum(r.n_obs() for r in group_restos) if group_restos is not None
+                      else sum(r.n_obs() for r in slots[0][:B]) if B > 1 else n_obs)
+        launch_images = len(group_restos) if group_restos is not None else B
+        algo_bytes = (obs_bytes + (12 if args.light_model else 0)) * launch_obs + state_bytes * launch_images  # A_fit / T
+        achieved = algo_bytes / (iter_ms * 1e-3) / 1e9
+        # What the store really holds: an 'f32' store whose ranges fit is kept as 24-bit codes by the device's own
+        # decision -- 6 B/observation, same bits -- so the launch MOVES fewer bytes than SURVEY 8(d)'s 7 B figure charges it for.
+        # `achieved` / `frac` stay the algorithmic work rate SURVEY 8(d) defines (the figure the judge recomputes); the bytes the
+        # HBM has to deliver are reported next to it and are what `frac_of_achievable` (a physical copy ceiling) is measured in.
+        store = int(resto.store_format()[0].item())
+        stored_obs_bytes = {0: 7, 1: 5, 2: 6, 3: 6.25}[store]   # _lib.STORE_F32 / STORE_U16MM / STORE_Z24 / STORE_Z26
+        stored_bytes = (stored_obs_bytes + (12 if args.light_model else 0)) * launch_obs * obs_passes + state_bytes * launch_images
+        moved = stored_bytes / (iter_ms * 1e-3) / 1e9
+        # A_match = 4 HW + sum_k (4 H_k W_k + 3 n_k + c n_k)   (every view here has the target's size)
+        match_bytes = 4 * H * W + int(sum(4 * H * W + (3 + OBS_BYTES) * int(n) for n in counts))
+
+        # committed rocprofv3 evidence for the same mode and workload (profiles/rNN_<mode>_traffic.json from tools/profile.sh,
+        # newest round first; the mode names are tools/profile.sh's)
+        tag = profile_tag(args, B)
+        traffic = prof = None
+        for tf in profile_candidates(tag):
+            rec = json.loads(tf.read_text())
+            if rec.get('n_obs') == n_obs and 'hbm_bytes_per_launch' in rec:   # same workload as the profiled one
+                traffic, prof = rec['hbm_bytes_per_launch'], (tf.name, rec)
+                break
 
     digests = None
     if args.digest:
@@ -660,35 +731,6 @@ def main():
         ranks_seen, names = 1, [f'rank 0: {torch.cuda.get_device_name(device)} (cuda:{device.index})']
 
     if rank == 0:
-        kernel = ('group_iter_kernel' if group_restos is not None else 'light_grad_kernel' if args.light_model
-                  else 'batch_iter_kernel' if B > 1 else 'fit_closed_kernel' if args.use_closed_form else 'fit_grad_kernel')
-        roof = {'bound': 'hbm', 'kernel': kernel, 'achieved': achieved, 'peak': HBM_PEAK_GBS,
-                'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS, 'traffic': traffic,
-                'frac_is': 'ALGORITHMIC work rate: SURVEY 8(d) bytes (7 B/obs at configs 1-4, 5 B at config 5, +12 B light model, + state) '
-                           '/ launch time / 8 TB/s -- not the HBM utilisation, which is stored_bytes_frac',
-                'store_format': {0: 'f32 words (7 B/obs)', 1: 'u16 mm (5 B/obs)', 2: '24-bit range codes (6 B/obs, lossless)',
-                                 3: '26-bit range codes (6.25 B/obs, lossless)'}[store],
-                'stored_bytes_per_launch': stored_bytes, 'stored_bytes_rate': moved, 'stored_bytes_frac': moved / HBM_PEAK_GBS,
-                # (frac_of_achievable is the r01-r04 definition again -- algorithmic bytes against the copy ceiling;
-                # the stored-bytes variant round 5 had put under that name has its own key)
-                'frac_of_achievable': achieved / HBM_ACHIEVABLE_GBS, 'stored_bytes_frac_of_achievable': moved / HBM_ACHIEVABLE_GBS,
-                'achievable_peak': HBM_ACHIEVABLE_GBS,
-                'algorithmic_bytes_per_launch': algo_bytes, 'ms_per_launch': iter_ms,
-                'measured': (f'HIP events (on the launch stream) around the {T} launches of each of {len(solo_fit)} image(s) '
-                             f'restored strictly one at a time after the timed region -- the configuration '
-                             f'tools/profile.sh runs rocprofv3 in; includes the ~1.5 us launch gaps') if solo_fit else
-                            'HIP events around the lock-step iterations of the timed region',
-                'timed_region_ms_per_launch': timed_region_iter_ms,
-                # (a --fit-batch run whose last chunk is short: the timed region's launches hold chunk_fill x B images on average)
-                'timed_region_frac': chunk_fill * algo_bytes / (timed_region_iter_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                'timed_region_stored_bytes_frac': chunk_fill * stored_bytes / (timed_region_iter_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                'obs_passes_per_launch': obs_passes}
-        if prof is not None:
-            name, rec = prof
-            roof['traffic_source'] = f'profiles/{name} (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, separate passes)'
-            if 'rocprofv3_avg_ns' in rec:   # the judge's recomputation: same bytes / the committed profile's average
-                roof['profile_ms_per_launch'] = rec['rocprofv3_avg_ns'] * 1e-6
-                roof['profile_frac'] = algo_bytes / (rec['rocprofv3_avg_ns'] * 1e-9) / 1e9 / HBM_PEAK_GBS
         out = {
             'metric': 'restored Mpixels/sec/GPU at 1080p, 64 neighbour views; % HBM roofline',
             'value': world * args.steps * len(jobs) * W * H / 1e6 / elapsed,
@@ -711,7 +753,6 @@ def main():
                        'workspace_bytes_per_rank': workspace_bytes,
                        'n_obs': n_obs, 'mean_cover': float(cover.mean()), 'images_in_flight': S, 'fit_batch': B,
                        'images_per_s_per_gpu': args.steps * len(jobs) / elapsed,
-                       'fit_ms_per_launch_sequence_alone': fit_ms, 'fit_ms_alone_per_image': fit_ms / B,
                        'ms_per_image': elapsed / args.steps / len(jobs) * 1e3,
                        'ms_per_image_per_rank': {'min': min(per_rank), 'max': max(per_rank), 'all': per_rank},
                        'J_sha256_per_rank': digests,
@@ -721,32 +762,64 @@ def main():
                                                  'for its views costs eight times what they save; --pack-views builds them inside the step)') if plain[0]
                                                 else 'sucre_pack_view records built inside every step' if pack[0] else 'as they are (SUCRE_PACKED_VIEWS=0)',
                        'pack_view_in_timed_region': bool(pack[0] and not plain[0]),
-                       'pack_view_ms_per_image': pack_ms,
                        'pack_view_note': 'a survey step (configs 3, 4: the targets share the views) builds the sucre_pack_view records of the survey\'s views '
                                          'INSIDE every timed step since round 6; a single-image step matches against the plain planes (or, --pack-views, '
                                          'builds the records inside the step); value_views_prepacked = the same steps against records already built '
                                          '(the steady state of a survey)',
-                       # the three throughputs of VERDICT round 5 (weak point 5), all in this line: `value` (pack_view inside, images in
-                       # flight), the same with every view's records already built, and one image strictly alone (pack_view inside)
-                       'value_views_prepacked': (world * args.steps * len(jobs) * W * H / 1e6 / elapsed_prepacked) if elapsed_prepacked else None,
-                       'value_one_image_alone': (W * H / 1e6 / (solo_ms_per_image * 1e-3)) if solo_ms_per_image else None,
-                       'ms_one_image_alone': solo_ms_per_image,
                        'ranks_seen': ranks_seen, 'devices': names,
                        'dist_backend': dist.get_backend() if world > 1 else None},
-            'roofline': roof,
         }
-        if match_ms is not None:
-            out['roofline_match'] = {'bound': 'hbm', 'kernel': 'match_kernel + finalize (view_count, compaction: pixel_count .. scatter_kernel)',
-                                     'achieved': match_bytes / (match_ms * 1e-3) / 1e9, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                                     'frac': match_bytes / (match_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                     'algorithmic_bytes': match_bytes, 'ms': match_ms, 'ms_each_solo_image': match_ms_each,
-                                     'traffic': prof[1].get('match_stage_hbm_bytes') if prof is not None else None,
-                                     'traffic_source': (f'profiles/{prof[0]}: sum over the stage\'s kernels of 2 x FETCH_SIZE + WRITE_SIZE'
-                                                        if prof is not None and 'match_stage_hbm_bytes' in prof[1] else None),
-                                     'measured': 'HIP events around sucre_match_views + sucre_finalize_matches of the same solo images'
-                                                 + (f' (the FIRST image of each chunk of {B}: the others are matched between this pair and the fit)' if B > 1 else '')}
-        if world == 1 and not args.no_cpu_baseline:
-            out['cpu_baseline'] = cpu_baseline(scene, n_obs, n_views, T, args.cpu_views, args.cpu_iters)
+        if args.full:
+            out['config'].update({
+                'fit_ms_per_launch_sequence_alone': fit_ms, 'fit_ms_alone_per_image': fit_ms / B,
+                'pack_view_ms_per_image': pack_ms,
+                # the three throughputs of VERDICT round 5 (weak point 5), all in this line: `value` (pack_view inside, images in
+                # flight), the same with every view's records already built, and one image strictly alone (pack_view inside)
+                'value_views_prepacked': (world * args.steps * len(jobs) * W * H / 1e6 / elapsed_prepacked) if elapsed_prepacked else None,
+                'value_one_image_alone': (W * H / 1e6 / (solo_ms_per_image * 1e-3)) if solo_ms_per_image else None,
+                'ms_one_image_alone': solo_ms_per_image})
+            kernel = ('group_iter_kernel' if group_restos is not None else 'light_grad_kernel' if args.light_model
+                      else 'batch_iter_kernel' if B > 1 else 'fit_closed_kernel' if args.use_closed_form else 'fit_grad_kernel')
+            roof = {'bound': 'hbm', 'kernel': kernel, 'achieved': achieved, 'peak': HBM_PEAK_GBS,
+                    'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS, 'traffic': traffic,
+                    'frac_is': 'ALGORITHMIC work rate: SURVEY 8(d) bytes (7 B/obs at configs 1-4, 5 B at config 5, +12 B light model, + state) '
+                               '/ launch time / 8 TB/s -- not the HBM utilisation, which is stored_bytes_frac',
+                    'store_format': {0: 'f32 words (7 B/obs)', 1: 'u16 mm (5 B/obs)', 2: '24-bit range codes (6 B/obs, lossless)',
+                                     3: '26-bit range codes (6.25 B/obs, lossless)'}[store],
+                    'stored_bytes_per_launch': stored_bytes, 'stored_bytes_rate': moved, 'stored_bytes_frac': moved / HBM_PEAK_GBS,
+                    # (frac_of_achievable is the r01-r04 definition again -- algorithmic bytes against the copy ceiling;
+                    # the stored-bytes variant round 5 had put under that name has its own key)
+                    'frac_of_achievable': achieved / HBM_ACHIEVABLE_GBS, 'stored_bytes_frac_of_achievable': moved / HBM_ACHIEVABLE_GBS,
+                    'achievable_peak': HBM_ACHIEVABLE_GBS,
+                    'algorithmic_bytes_per_launch': algo_bytes, 'ms_per_launch': iter_ms,
+                    'measured': (f'HIP events (on the launch stream) around the {T} launches of each of {len(solo_fit)} image(s) '
+                                 f'restored strictly one at a time after the timed region -- the configuration '
+                                 f'tools/profile.sh runs rocprofv3 in; includes the ~1.5 us launch gaps') if solo_fit else
+                                'HIP events around the lock-step iterations of the timed region',
+                    'timed_region_ms_per_launch': timed_region_iter_ms,
+                    # (a --fit-batch run whose last chunk is short: the timed region's launches hold chunk_fill x B images on average)
+                    'timed_region_frac': chunk_fill * algo_bytes / (timed_region_iter_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                    'timed_region_stored_bytes_frac': chunk_fill * stored_bytes / (timed_region_iter_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                    'obs_passes_per_launch': obs_passes}
+            if prof is not None:
+                name, rec = prof
+                roof['traffic_source'] = f'profiles/{name} (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, separate passes)'
+                if 'rocprofv3_avg_ns' in rec:   # the judge's recomputation: same bytes / the committed profile's average
+                    roof['profile_ms_per_launch'] = rec['rocprofv3_avg_ns'] * 1e-6
+                    roof['profile_frac'] = algo_bytes / (rec['rocprofv3_avg_ns'] * 1e-9) / 1e9 / HBM_PEAK_GBS
+            out['roofline'] = roof
+            if match_ms is not None:
+                out['roofline_match'] = {'bound': 'hbm', 'kernel': 'match_kernel + finalize (view_count, compaction: pixel_count .. scatter_kernel)',
+                                         'achieved': match_bytes / (match_ms * 1e-3) / 1e9, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                                         'frac': match_bytes / (match_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                         'algorithmic_bytes': match_bytes, 'ms': match_ms, 'ms_each_solo_image': match_ms_each,
+                                         'traffic': prof[1].get('match_stage_hbm_bytes') if prof is not None else None,
+                                         'traffic_source': (f'profiles/{prof[0]}: sum over the stage\'s kernels of 2 x FETCH_SIZE + WRITE_SIZE'
+                                                            if prof is not None and 'match_stage_hbm_bytes' in prof[1] else None),
+                                         'measured': 'HIP events around sucre_match_views + sucre_finalize_matches of the same solo images'
+                                                     + (f' (the FIRST image of each chunk of {B}: the others are matched between this pair and the fit)' if B > 1 else '')}
+            if world == 1 and not args.no_cpu_baseline:
+                out['cpu_baseline'] = cpu_baseline(scene, n_obs, n_views, T, args.cpu_views, args.cpu_iters)
         print(json.dumps(out), flush=True)
     note(rank, 'done')
     if world > 1:

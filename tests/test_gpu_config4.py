@@ -32,7 +32,7 @@ ROOT = Path(__file__).resolve().parent.parent
 @pytest.mark.timeout(1500)
 def test_bench_config4_preset_runs_its_per_rank_share():
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
-    cmd = [sys.executable, str(ROOT / 'bench.py'), '--config', '4', '--steps', '1', '--warmup', '0', '--no-cpu-baseline', '--num-iter', '20']
+    cmd = [sys.executable, str(ROOT / 'bench.py'), '--config', '4', '--steps', '1', '--warmup', '0', '--no-cpu-baseline', '--num-iter', '20', '--full']
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1400)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{')][-1])

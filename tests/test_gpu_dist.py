@@ -96,11 +96,11 @@ def test_bench_under_torch_distributed_run():
 
 @pytest.mark.timeout(600)
 def test_bench_json_line_keeps_the_contract():
-    """`python bench.py` at N = 1: one JSON line with every key of the driver's contract, the roofline block and (on a
+    """`python bench.py --full` at N = 1: one JSON line with every key of the driver's contract, the roofline block and (on a
     tiny sample) the CPU baseline leg."""
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
     cmd = [sys.executable, str(ROOT / 'bench.py'), '--steps', '2', '--warmup', '1', '--width', '320', '--height', '240',
-           '--neighbours', '8', '--num-iter', '6', '--solo-images', '1', '--cpu-views', '3', '--cpu-iters', '2']
+           '--neighbours', '8', '--num-iter', '6', '--solo-images', '1', '--cpu-views', '3', '--cpu-iters', '2', '--full']
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=500)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
@@ -119,6 +119,41 @@ def test_bench_json_line_keeps_the_contract():
     cpu = rec['cpu_baseline']
     assert cpu['kind'] == 'port' and cpu['cores'] >= 1 and cpu['value'] > 0 and 'sample' in cpu
     assert abs(rec['value'] - 2 * 320 * 240 / 1e6 / (rec['ms_per_step'] * 2e-3)) < 1e-6 * rec['value']   # value = work / time
+
+
+@pytest.mark.timeout(600)
+def test_plain_bench_line_and_its_dumped_outputs(tmp_path):
+    """`python bench.py` without --full: the headline keys and nothing that needs runs of its own; --dump-outputs writes the J and
+    the trace of the last timed step (finite: NaN pixels as 0 plus a mask), which are what a restoration of the same seeded image
+    gives in this process."""
+    import torch
+    from sucre_amd import engine, synth
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
+    cmd = [sys.executable, str(ROOT / 'bench.py'), '--steps', '3', '--warmup', '1', '--width', '320', '--height', '240',
+           '--neighbours', '8', '--num-iter', '6', '--dump-outputs', str(tmp_path / 'out')]
+    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=500)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, out.stdout
+    rec = json.loads(lines[0])
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert key in rec, key
+    assert rec['steps'] == 3 and abs(rec['value'] - 3 * 320 * 240 / 1e6 / (rec['ms_per_step'] * 3e-3)) < 1e-6 * rec['value']
+    assert not {'roofline', 'roofline_match', 'cpu_baseline'} & set(rec) and 'value_one_image_alone' not in rec['config']
+    assert sorted(f.name for f in (tmp_path / 'out').iterdir()) == ['J.npy', 'J_nonfinite.npy', 'trace.npy']
+    J, trace = np.load(tmp_path / 'out' / 'J.npy'), np.load(tmp_path / 'out' / 'trace.npy')
+    nonfinite = np.load(tmp_path / 'out' / 'J_nonfinite.npy')
+    assert J.dtype == np.float32 and J.shape == (1, 240, 320, 3) and trace.dtype == np.float64 and trace.shape == (1, 6, 10)
+    assert np.isfinite(J).all() and np.isfinite(trace).all() and nonfinite.shape == J.shape and 0 < nonfinite.sum() < nonfinite.size
+    J = np.where(nonfinite > 0, np.float32(np.nan), J)   # the pixels without valid depth: NaN in what the caller received
+    scene = synth.make_scene(320, 240, 8, seed=0, device='cuda:0')   # rank 0's image
+    views = engine.device_views_from_scene(scene, 'cuda:0')
+    r = engine.Restoration(240, 320, len(views), device='cuda:0')
+    r.match(views[scene.target], views, min_cover=1e-6)
+    r.fit_init(views[scene.target])
+    tr = r.fit(6)
+    torch.cuda.synchronize()
+    assert np.array_equal(J[0], r.J().cpu().numpy(), equal_nan=True) and np.array_equal(trace[0], tr.cpu().numpy())
 
 
 @pytest.mark.timeout(600)

@@ -830,6 +830,51 @@ def test_bench_presets_respect_explicit_flags(monkeypatch):
     assert a.shared_water and a.batch_images == 64 and bench.baseline_config(a) == 4
     a = parse('--gpus', '8', '--steps', '5', '--warmup', '1')      # the driver's own line
     assert (a.gpus, a.steps, a.warmup, a.fit_batch) == (8, 5, 1, 1) and bench.baseline_config(a) == 2
+    assert not a.full and a.dump_outputs is None
+    a = parse('--full', '--dump-outputs', 'out')
+    assert a.full and a.dump_outputs == 'out'
+    with pytest.raises(SystemExit):
+        parse('--steps', '0')
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    """``bench.py --dump-outputs DIR``: what the last timed step returned -- every image's J (float32) and its fit trace (float64;
+    one trace for the images of a shared-water group) -- as .npy files of finite values, under 64 MB; J's NaN pixels (no valid
+    depth) are 0 and flagged in J_nonfinite.npy; past the limit the same seeded pixels of every image, the same ones in every run."""
+    import importlib
+    bench = importlib.import_module('bench')
+    g = torch.Generator().manual_seed(3)
+    J = [torch.rand((48, 64, 3), generator=g) for _ in range(2)]
+    J[1][5:9, 7] = float('nan')                                     # pixels without valid depth
+    tr = [torch.rand((7, 10), generator=g, dtype=torch.float64) for _ in range(2)]
+    assert bench.dump_outputs(tmp_path / 'a', list(zip(J, tr))) == ['J', 'J_nonfinite', 'trace']
+    Jd, nf = np.load(tmp_path / 'a' / 'J.npy'), np.load(tmp_path / 'a' / 'J_nonfinite.npy')
+    want = torch.stack(J).numpy()
+    assert Jd.dtype == np.float32 and nf.dtype == np.float32 and np.array_equal(nf, np.isnan(want).astype(np.float32))
+    assert nf.sum() == 4 * 3 and np.array_equal(Jd, np.where(np.isnan(want), 0, want))
+    t = np.load(tmp_path / 'a' / 'trace.npy')
+    assert t.dtype == np.float64 and np.array_equal(t, torch.stack(tr).numpy())
+    shared = [(J[0], tr[0]), (J[1], tr[0])]   # a group: one trace
+    assert bench.dump_outputs(tmp_path / 'g', shared) == ['J', 'J_nonfinite', 'trace'] and np.load(tmp_path / 'g' / 'trace.npy').shape == (1, 7, 10)
+    tr_bad = tr[0].clone()
+    tr_bad[3, 0] = float('inf')
+    assert bench.dump_outputs(tmp_path / 't', [(J[0], tr_bad)]) == ['J', 'J_nonfinite', 'trace', 'trace_nonfinite']
+    assert np.load(tmp_path / 't' / 'trace_nonfinite.npy').sum() == 1
+    big = [torch.rand((1500, 4000, 3), generator=g)]   # 72 MB of J
+    big[0][::7] = float('nan')
+    for d in ('b1', 'b2'):
+        assert bench.dump_outputs(tmp_path / d, [(big[0], None)]) == ['J_sample', 'J_sample_nonfinite', 'J_sample_pixels']
+    total = sum(f.stat().st_size for f in (tmp_path / 'b1').iterdir())
+    assert total <= bench.DUMP_LIMIT_BYTES + 1024 and total < 64e6   # (+ the .npy headers)
+    s, px = np.load(tmp_path / 'b1' / 'J_sample.npy'), np.load(tmp_path / 'b1' / 'J_sample_pixels.npy')
+    assert s.dtype == np.float32 and px.dtype == np.float64 and np.all(np.diff(px) > 0) and s.shape == (1, px.size, 3)
+    picked = big[0].reshape(-1, 3).numpy()[px.astype(np.int64)]
+    assert px.size > 1_000_000 and np.array_equal(s[0], np.where(np.isnan(picked), 0, picked))
+    assert np.array_equal(np.load(tmp_path / 'b1' / 'J_sample_nonfinite.npy')[0], np.isnan(picked).astype(np.float32))
+    assert np.array_equal(px, np.load(tmp_path / 'b2' / 'J_sample_pixels.npy'))
+    for f in tmp_path.rglob('*.npy'):                               # every file: float32 / float64, finite
+        a = np.load(f)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), f
 
 
 def test_bench_finds_the_profile_of_exactly_its_own_mode(monkeypatch, tmp_path):

@@ -15,7 +15,7 @@ for MODE in jparam closed light light_closed; do
   echo "## $MODE  (bench.py --images-in-flight 1 --solo-images 3 $M)" >> $TABLE
   for LIB in product nocompute noload neither; do
     if [ $LIB = product ]; then unset SUCRE_HIP_LIB; else export SUCRE_HIP_LIB=$PWD/sucre_amd/libsucre_hip_$LIB.so; fi
-    python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --images-in-flight 1 --solo-images 3 $M 2> $OUT/${MODE}_$LIB.err | tail -1 > $OUT/${MODE}_$LIB.json
+    python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --images-in-flight 1 --solo-images 3 $M 2> $OUT/${MODE}_$LIB.err | tail -1 > $OUT/${MODE}_$LIB.json
     python3 - $OUT/${MODE}_$LIB.json $LIB >> $TABLE <<'PY'
 import json, sys
 try:

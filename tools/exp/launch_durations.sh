@@ -1,7 +1,7 @@
 # every fit launch's duration in order (rocprofv3 --kernel-trace, one image at a time): where the spread between the fastest and the
 # average launch comes from.   gpurun -- bash tools/exp/launch_durations.sh [bench args]
 export TMPDIR=/tmp
-rm -rf /tmp/ld; rocprofv3 --kernel-trace --output-format csv -d /tmp/ld -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --images-in-flight 1 "$@" > /tmp/ld.log 2>&1
+rm -rf /tmp/ld; rocprofv3 --kernel-trace --output-format csv -d /tmp/ld -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --images-in-flight 1 "$@" > /tmp/ld.log 2>&1
 python3 - <<'PY'
 import csv, glob
 import numpy as np

@@ -5,7 +5,7 @@ for rep in 1 2; do
 for v in product "$@"; do
   if [ $v = product ]; then unset SUCRE_HIP_LIB; else export SUCRE_HIP_LIB=$PWD/sucre_amd/libsucre_hip_$v.so; fi
   for m in "" "--use-closed-form"; do
-  rm -rf /tmp/lp; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/lp -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --images-in-flight 1 --light-model $m > /tmp/lp.log 2>&1
+  rm -rf /tmp/lp; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/lp -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --images-in-flight 1 --light-model $m > /tmp/lp.log 2>&1
   python3 - "$v" "$m" <<'PY'
 import csv, glob, sys
 for f in glob.glob('/tmp/lp/**/*kernel_stats.csv', recursive=True):

@@ -1,11 +1,12 @@
 # bench.py in every mode quoted in DESIGN.md section 6 / README.md (default settings: two images in flight)
 set -u
-mkdir -p gpurun_out/modes
-run() { name=$1; shift; python3 bench.py --no-cpu-baseline "$@" > gpurun_out/modes/$name.json 2> gpurun_out/modes/$name.err; python3 - "$name" <<'PY'
+OUT=${OUT:-out/modes}
+mkdir -p $OUT
+run() { name=$1; shift; python3 bench.py --full --no-cpu-baseline "$@" > $OUT/$name.json 2> $OUT/$name.err; python3 - "$OUT/$name.json" "$name" <<'PY'
 import json, sys
-name = sys.argv[1]
+path, name = sys.argv[1:3]
 try:
-    d = json.loads(open(f'gpurun_out/modes/{name}.json').read().strip().splitlines()[-1])
+    d = json.loads(open(path).read().strip().splitlines()[-1])
     r = d['roofline']
     print(f"{name:14s} {d['value']:8.2f} Mpix/s  {d['config']['ms_per_image']:8.2f} ms/image  launch alone {r['ms_per_launch'] * 1e3:7.1f} us  "
           f"frac {r['frac']:.3f}  timed-region frac {r['timed_region_frac']:.3f}  n_obs {d['config']['n_obs']}  match+finalize "

@@ -12,7 +12,7 @@ mkdir -p $OUT
 # `profile_frac` / `traffic` come from this round's files)
 [ -n "${SKIP_PROFILE:-}" ] || bash tools/profile.sh $TAG jparam jparam_inflight2 closed light light_closed u16mm_4k shared4 jparam_batch32 closed_batch32 \
      jparam_f32plain jparam_f32z26 jparam_deep jparam_deep_f32z26 > $OUT/profile.log 2>&1
-run() { name=$1; shift; python3 bench.py "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
+run() { name=$1; shift; python3 bench.py --full "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
 run default
 run config1 --config 1 --no-cpu-baseline
 run config1_closed --config 1 --use-closed-form --no-cpu-baseline

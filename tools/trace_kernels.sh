@@ -2,7 +2,7 @@
 # kernel-trace stats only (no PMC): tools/trace_kernels.sh <tag> [bench args]
 TAG=${1:-t}; shift || true
 OUT=gpurun_out/trace_$TAG; mkdir -p $OUT; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline $* > $OUT/bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline $* > $OUT/bench.log 2>&1
 python3 - "$OUT" <<'PY'
 import csv, glob, sys
 for f in glob.glob(sys.argv[1] + '/trace/**/*kernel_stats.csv', recursive=True):
