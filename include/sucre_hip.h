@@ -14,7 +14,8 @@
  *     (a hipStream_t passed as void*; NULL = the default stream) and returns.
  *   - Return value: 0 = OK, negative = error; sucre_last_error() gives the message for the calling thread.
  *     No C++ exception crosses the ABI.  All arguments are validated before anything is launched.
- *   - Re-entrant; no global mutable state except the thread-local error string.  One host thread / process
+ *   - Re-entrant; no global mutable state except the thread-local error string and the host copies of the light
+ *     groups' image tables (sucre_light_group_init, behind a lock).  One host thread / process
  *     per GPU; concurrent calls on different streams or devices are safe.
  *   - All state of one restoration lives in ONE caller-allocated workspace of sucre_workspace_bytes() bytes,
  *     256-byte aligned.  Its internal layout (observation store, Adam state, ...) is private; the few regions a
@@ -365,6 +366,37 @@ int sucre_update_J_ext(void *ws, void *lws, int H, int W, int n_views, unsigned 
 int sucre_fit_run_light(void *ws, void *lws, int H, int W, int n_views, int t0, int T, double lr, double beta1,
                         double beta2, double eps, unsigned flags /* SUCRE_FIT_CLOSED_FORM | SUCRE_FIT_KEEP_J | SUCRE_FIT_EXT_COLOUR or SUCRE_FIT_EXT_BOTH */, double *trace_dev,
                         void *stream);
+
+/*
+ * Shared water AND light over several light-model images (the group above for the 19-parameter model; sucre.py:54-61 with
+ * the objective of sucre.py:124-157 summed over the images: one B, beta, gamma, cam2light, sigma, every image its own J, one
+ * n_obs).  `group_dev`: sucre_light_group_bytes(n_images) bytes of device memory, 256-byte aligned; `images` (host array)
+ * names every image's matched, finalised (f32 store, camera points only) and fit_init_light-ed workspaces; images may differ
+ * in size and view count.  sucre_light_group_init sets the shared parameters from params0 (19 host floats; the reference
+ * starts from 0.1 x 9, 0 x 6 and identity) and keeps a host copy of the table, keyed by group_dev, until the next init there.
+ * sucre_light_group_iter(step), step = 1, 2, ... in order (SUCRE_ERR_RANGE otherwise): takes the Adam step the sums left by
+ * the previous call -- all-reduced over the ranks by the host in between -- call for (trace row step-2 of trace_dev, T x 20
+ * float64, nullable: cost, then the 19 parameters after the step), then runs every image's gradient pass on the shared
+ * parameters (J steps and closed-form solves stay per image, scaled by n_obs_total, the observations of all images of all
+ * ranks) and leaves this rank's 19 float64 sums at sucre_light_group_sums_offset(), the images added in table order.
+ * sucre_light_group_finish(step) takes the last step, copies the final parameters into every image's `lws`
+ * (sucre_light_params_offset) and, with SUCRE_FIT_CLOSED_FORM, solves every image's final J (sucre.py:155-156).
+ * flags: SUCRE_FIT_CLOSED_FORM only (float32 colours, SUCRE_FIT_EXT_*, and other stores are refused).
+ */
+typedef struct sucre_light_group_image {
+    void *ws;              /* the image's workspace */
+    void *lws;             /* its light workspace (sucre_light_workspace_bytes) */
+    int32_t H, W, n_views; /* its geometry */
+    int32_t reserved;
+} sucre_light_group_image_t;
+size_t sucre_light_group_bytes(int n_images);
+int64_t sucre_light_group_sums_offset(void);
+int sucre_light_group_init(void *group_dev, int n_images, const sucre_light_group_image_t *images, const float *params0,
+                           void *stream);
+int sucre_light_group_iter(void *group_dev, int n_images, int step, double lr, double beta1, double beta2, double eps,
+                           unsigned flags, uint64_t n_obs_total, double *trace_dev, void *stream);
+int sucre_light_group_finish(void *group_dev, int n_images, int step, double lr, double beta1, double beta2, double eps,
+                             unsigned flags, uint64_t n_obs_total, double *trace_dev, void *stream);
 
 #ifdef __cplusplus
 }

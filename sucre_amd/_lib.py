@@ -39,6 +39,12 @@ class GroupImage(C.Structure):
     """sucre_group_image_t"""
     _fields_ = [('ws', C.c_void_p), ('H', C.c_int32), ('W', C.c_int32), ('n_views', C.c_int32), ('reserved', C.c_int32)]
 
+class LightGroupImage(C.Structure):
+    """sucre_light_group_image_t"""
+    _fields_ = [('ws', C.c_void_p), ('lws', C.c_void_p), ('H', C.c_int32), ('W', C.c_int32), ('n_views', C.c_int32),
+                ('reserved', C.c_int32)]
+
+
 # name -> (restype, argtypes); mirrors include/sucre_hip.h one to one (tests/test_abi.py checks both ways)
 _i, _vp, _d, _u64 = C.c_int, C.c_void_p, C.c_double, C.c_uint64
 SIGNATURES = {
@@ -89,6 +95,11 @@ SIGNATURES = {
     'sucre_update_J_light': (_i, [_vp, _vp, _i, _i, _i, _vp]),
     'sucre_update_J_ext': (_i, [_vp, _vp, _i, _i, _i, C.c_uint, _vp]),
     'sucre_fit_run_light': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _d, _d, _d, _d, C.c_uint, _vp, _vp]),
+    'sucre_light_group_bytes': (C.c_size_t, [_i]),
+    'sucre_light_group_sums_offset': (C.c_int64, []),
+    'sucre_light_group_init': (_i, [_vp, _i, C.POINTER(LightGroupImage), C.POINTER(C.c_float), _vp]),
+    'sucre_light_group_iter': (_i, [_vp, _i, _i, _d, _d, _d, _d, C.c_uint, _u64, _vp, _vp]),
+    'sucre_light_group_finish': (_i, [_vp, _i, _i, _d, _d, _d, _d, C.c_uint, _u64, _vp, _vp]),
 }
 
 _lib = None

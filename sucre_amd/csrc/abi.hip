@@ -2,6 +2,8 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <map>
+#include <mutex>
 #include <vector>
 
 #include "launch.h"
@@ -556,6 +558,111 @@ int sucre_fit_run_light(void *ws, void *lws, int H, int W, int n_views, int t0, 
                                                flags & (SUCRE_FIT_EXT_COLOUR | SUCRE_FIT_EXT_BOTH), static_cast<hipStream_t>(stream)),
                          "sucre_fit_run_light/update_J");
     return SUCRE_OK;
+}
+
+/* ---- shared water and light over the light-model images of a rank (sucre.py:54-61, 124-157) ------------------------ */
+
+}  // extern "C"
+
+namespace sucre {
+
+// What the iterations of a light group need on the host -- every image's layout and buffers, which iteration is next, which
+// mode the gradient launches' deals in the light workspaces were written for -- kept from sucre_light_group_init on,
+// keyed by the group buffer (the device buffer itself is never read back: the loop has no host synchronisation).
+struct LightGroupHost {
+    std::vector<Layout> L;
+    std::vector<uint8_t *> ws, lws;
+    int steps_done = 0;
+    int deal_mode = -1;   // -1: no deal written yet, else the SUCRE_FIT_CLOSED_FORM bit of the launches it was written for
+};
+static std::mutex g_light_groups_lock;
+static std::map<const void *, LightGroupHost> g_light_groups;
+
+static int check_light_group_flags(unsigned flags) {
+    if (flags & (SUCRE_FIT_EXT_COLOUR | SUCRE_FIT_EXT_BOTH))
+        return fail(SUCRE_ERR_ARG, "light groups run on uint8 colours: SUCRE_FIT_EXT_COLOUR / SUCRE_FIT_EXT_BOTH are not supported");
+    if (flags & SUCRE_FIT_OBS_U16MM) return fail(SUCRE_ERR_ARG, "light groups need the f32 store (SUCRE_FIT_OBS_U16MM given)");
+    if (flags & ~SUCRE_FIT_CLOSED_FORM) return fail(SUCRE_ERR_ARG, "unknown light group flags 0x%x", flags);
+    return SUCRE_OK;
+}
+
+// The group's host table (under the lock), after the checks every iter / finish call makes.
+static int light_group_of(void *group_dev, int n_images, LightGroupHost **out) {
+    if (!group_dev || n_images < 1) return fail(SUCRE_ERR_ARG, "light group buffer is NULL / no image");
+    auto it = g_light_groups.find(group_dev);
+    if (it == g_light_groups.end()) return fail(SUCRE_ERR_ARG, "light group buffer was not set up by sucre_light_group_init");
+    if ((int)it->second.L.size() != n_images)
+        return fail(SUCRE_ERR_ARG, "light group holds %d images, not %d", (int)it->second.L.size(), n_images);
+    *out = &it->second;
+    return SUCRE_OK;
+}
+
+}  // namespace sucre
+
+extern "C" {
+
+size_t sucre_light_group_bytes(int n_images) { return n_images > 0 ? light_group_bytes(n_images) : 0; }
+
+int64_t sucre_light_group_sums_offset(void) { return light_group_sums_offset(); }
+
+int sucre_light_group_init(void *group_dev, int n_images, const sucre_light_group_image_t *images, const float *params0, void *stream) {
+    if (!group_dev || !aligned(group_dev, 256)) return fail(SUCRE_ERR_ARG, "light group buffer is NULL or not 256-byte aligned");
+    if (n_images < 1 || !images || !params0) return fail(SUCRE_ERR_ARG, "need at least one image and params0");
+    LightGroupHost h;
+    for (int i = 0; i < n_images; ++i) {
+        Layout L;
+        if (int rc = check_ws(images[i].ws, images[i].H, images[i].W, images[i].n_views, &L)) return rc;
+        if (int rc = check_lws(images[i].lws)) return rc;
+        h.L.push_back(L);
+        h.ws.push_back(static_cast<uint8_t *>(images[i].ws));
+        h.lws.push_back(static_cast<uint8_t *>(images[i].lws));
+    }
+    std::lock_guard<std::mutex> hold(g_light_groups_lock);
+    LightGroupHost &g = g_light_groups[group_dev] = std::move(h);
+    return check_hip(launch_light_group_init(group_dev, n_images, g.L.data(), g.ws.data(), g.lws.data(), params0,
+                                             static_cast<hipStream_t>(stream)), "sucre_light_group_init");
+}
+
+int sucre_light_group_iter(void *group_dev, int n_images, int step, double lr, double beta1, double beta2, double eps,
+                           unsigned flags, uint64_t n_obs_total, double *trace_dev, void *stream) {
+    if (int rc = check_adam(step, lr, beta1, beta2, eps)) return rc;
+    if (int rc = check_light_group_flags(flags)) return rc;
+    if (n_obs_total == 0) return fail(SUCRE_ERR_RANGE, "n_obs_total must be > 0");
+    if (trace_dev && !aligned(trace_dev, 8)) return fail(SUCRE_ERR_ARG, "trace must be 8-byte aligned");
+    std::lock_guard<std::mutex> hold(g_light_groups_lock);
+    LightGroupHost *g;
+    if (int rc = light_group_of(group_dev, n_images, &g)) return rc;
+    if (step != g->steps_done + 1)
+        return fail(SUCRE_ERR_RANGE, "light group: iteration %d asked after %d done -- iterations run in order, once "
+                                     "(sucre_light_group_init starts over)", step, g->steps_done);
+    const int mode = (flags & SUCRE_FIT_CLOSED_FORM) ? 1 : 0;
+    const AdamCoef co_prev = adam_coef(step > 1 ? step - 1 : 1, lr, beta1, beta2, eps);
+    double *row = (trace_dev && step > 1) ? trace_dev + (size_t)(step - 2) * 20 : nullptr;
+    if (int rc = check_hip(launch_light_group_iter(group_dev, n_images, g->L.data(), g->ws.data(), g->lws.data(), step, co_prev,
+                                                   adam_coef(step, lr, beta1, beta2, eps), flags, n_obs_total, row,
+                                                   g->deal_mode != mode, static_cast<hipStream_t>(stream)),
+                           "sucre_light_group_iter")) return rc;
+    g->deal_mode = mode;
+    g->steps_done = step;
+    return SUCRE_OK;
+}
+
+int sucre_light_group_finish(void *group_dev, int n_images, int step, double lr, double beta1, double beta2, double eps,
+                             unsigned flags, uint64_t n_obs_total, double *trace_dev, void *stream) {
+    if (step < 0) return fail(SUCRE_ERR_RANGE, "step=%d must be >= 0", step);
+    if (step >= 1) if (int rc = check_adam(step, lr, beta1, beta2, eps)) return rc;
+    if (int rc = check_light_group_flags(flags)) return rc;
+    if (n_obs_total == 0) return fail(SUCRE_ERR_RANGE, "n_obs_total must be > 0");
+    if (trace_dev && !aligned(trace_dev, 8)) return fail(SUCRE_ERR_ARG, "trace must be 8-byte aligned");
+    std::lock_guard<std::mutex> hold(g_light_groups_lock);
+    LightGroupHost *g;
+    if (int rc = light_group_of(group_dev, n_images, &g)) return rc;
+    if (step != g->steps_done)
+        return fail(SUCRE_ERR_RANGE, "light group: finish after iteration %d, but %d ran -- iterations run in order", step, g->steps_done);
+    double *row = (trace_dev && step >= 1) ? trace_dev + (size_t)(step - 1) * 20 : nullptr;
+    return check_hip(launch_light_group_finish(group_dev, n_images, g->L.data(), g->ws.data(), g->lws.data(), step,
+                                               adam_coef(step >= 1 ? step : 1, lr, beta1, beta2, eps), flags, n_obs_total, row,
+                                               static_cast<hipStream_t>(stream)), "sucre_light_group_finish");
 }
 
 }  // extern "C"

@@ -92,5 +92,15 @@ hipError_t launch_light_deal(const Layout &L, uint8_t *ws, uint8_t *lws, unsigne
 hipError_t launch_light_iter(const Layout &L, uint8_t *ws, uint8_t *lws, const AdamCoef &co, unsigned flags,
                              double *trace_row, hipStream_t s);
 hipError_t launch_light_update_J(const Layout &L, uint8_t *ws, uint8_t *lws, unsigned flags, hipStream_t s);
+// shared parameters over several light-model images (light.hip)
+size_t light_group_bytes(int n_images);
+int64_t light_group_sums_offset();
+hipError_t launch_light_group_init(void *group, int n_images, const Layout *L, uint8_t *const *ws, uint8_t *const *lws,
+                                   const float *params19, hipStream_t s);
+hipError_t launch_light_group_iter(void *group, int n_images, const Layout *L, uint8_t *const *ws, uint8_t *const *lws, int step,
+                                   const AdamCoef &co_prev, const AdamCoef &co, unsigned flags, uint64_t n_obs_total,
+                                   double *trace_prev, bool write_deal, hipStream_t s);
+hipError_t launch_light_group_finish(void *group, int n_images, const Layout *L, uint8_t *const *ws, uint8_t *const *lws, int step,
+                                     const AdamCoef &co_prev, unsigned flags, uint64_t n_obs_total, double *trace_prev, hipStream_t s);
 
 }  // namespace sucre

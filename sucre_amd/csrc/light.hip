@@ -14,6 +14,7 @@
 // workgroup: fixed-order float64 reduction, chain rule through Sigma^-1 and through the matrix exponential -- six 8x8
 // block exponentials evaluated in LDS -- Adam on the 19 parameters, next R, t, Sigma^-1, log row).
 // Plain loads instead of the LDS-DMA ring: the kernel is instruction-limited (~135 instructions per observation).
+#include <cstddef>
 #include <type_traits>
 #include <mutex>
 #include "fit_math.h"
@@ -737,9 +738,10 @@ static LightDeal light_deal_of(K kernel, const Layout &L) {
 }
 
 // kDeal 0: launch with the table light_deal_kernel wrote; 1: write that table; 2: launch without one (plain deal).
+// pstate / geom: the parameters and geometry the pass runs with -- the image's own in `lws` unless given (a light group's).
 template <bool kClosed, bool kJOnly, bool kColour, bool kBoth = false>
 static int launch_light_grad_c(const Layout &L, const LightLayout &X, uint8_t *ws, uint8_t *lws, const AdamCoef &co,
-                               hipStream_t s, int deal_mode) {
+                               hipStream_t s, int deal_mode, const float *pstate = nullptr, const float *geom = nullptr) {
     const LightDeal d = light_deal_of(light_grad_kernel<kClosed, kJOnly, kColour, kBoth>, L);
     uint32_t *count = reinterpret_cast<uint32_t *>(lws + X.off_deal), *strips = count + kLightMaxWaves;
     const bool fits = (uint32_t)d.grid * 4u <= kLightMaxWaves && (size_t)d.grid * 4u * d.kmax <= (size_t)kMaxGen * L.n_strips + kLightMaxWaves;
@@ -753,7 +755,8 @@ static int launch_light_grad_c(const Layout &L, const LightLayout &X, uint8_t *w
     hipLaunchKernelGGL((light_grad_kernel<kClosed, kJOnly, kColour, kBoth>), dim3(d.grid), dim3(256), 0, s, ws + L.off_comp,
                        lws + X.off_ext_comp, kBoth ? light_ext2_comp(L, lws) : nullptr,
                        reinterpret_cast<const StripMeta *>(ws + L.off_strip_meta), L.n_strips,
-                       reinterpret_cast<const float *>(lws + X.off_params), reinterpret_cast<const float *>(lws + X.off_geom),
+                       pstate ? pstate : reinterpret_cast<const float *>(lws + X.off_params),
+                       geom ? geom : reinterpret_cast<const float *>(lws + X.off_geom),
                        reinterpret_cast<const uint64_t *>(ws + L.off_n_obs_total),
                        reinterpret_cast<float *>(ws + L.off_state), reinterpret_cast<float *>(lws + X.off_partials), co,
                        table ? count : nullptr, table ? strips : nullptr, d.kmax);
@@ -796,6 +799,134 @@ hipError_t launch_light_iter(const Layout &L, uint8_t *ws, uint8_t *lws, const A
                        reinterpret_cast<double *>(lws + X.off_sums), reinterpret_cast<float *>(lws + X.off_params),
                        reinterpret_cast<float *>(lws + X.off_geom), reinterpret_cast<double *>(lws + X.off_dexp),
                        reinterpret_cast<const uint64_t *>(ws + L.off_n_obs_total), co, trace_row);
+    return hipGetLastError();
+}
+
+// ---- shared parameters over several images (sucre_light_group_*) -------------------------------------
+// The plain-water group's scheme for the 19-parameter model: one B, beta, gamma, cam2light, sigma for every image of every rank,
+// each image keeping its own J.  An iteration is a step launch (the Adam step the previous iteration's all-reduced sums call for),
+// every image's own light_grad_kernel on the shared parameters and geometry, and ONE tail that reduces all the images' partials.
+// Every image's gradient is linear in its 19 sums with coefficients (R, t, Sigma^-1, the twists, the parameters) that are the
+// same for all images, so the chain rule of light_step applies to the sum of the sums: the step is light_step itself.
+struct LightGroupImage {
+    const float *partials;    // the image's light_grad_kernel partials, [19][grid]
+    uint64_t *n_obs_total;    // its SUCRE_WS_N_OBS_TOTAL (what its gradient launch scales the J step by)
+    float *pstate, *geom;     // its parameters + moments and geometry in `lws` (finish copies the group's there)
+    double *dexp;
+    int grid[2];              // workgroups of its gradient launch: [0] J as a parameter, [1] closed form
+};
+
+struct LightGroupHeader {
+    double dexp[72];
+    double sums[kLightSums + 1];        // this rank's 19 sums of the last pass; all-reduced in place by the host
+    float pstate[3 * kLightParams];     // the 19 shared parameters, exp_avg, exp_avg_sq
+    float geom[16];
+    float staged[kLightParams];         // params0 on their way in (light_init_kernel's input)
+};
+
+static LightGroupImage *light_group_table(void *g) {
+    return reinterpret_cast<LightGroupImage *>(static_cast<uint8_t *>(g) + align_up(sizeof(LightGroupHeader), 256));
+}
+
+__global__ void light_group_set_image_kernel(LightGroupImage *table, int i, const LightGroupImage im) { table[i] = im; }
+
+// The step that the (all-reduced) sums left by the previous pass call for, when `apply`; first hands n_obs_total to every
+// image.  `copy_out` (the group's finish): the final parameters, moments and geometry also go to every image's `lws`.
+__global__ __launch_bounds__(64) void light_group_step_kernel(LightGroupHeader *g, const LightGroupImage *__restrict__ table, int n_images,
+                                                              uint64_t n_obs_total, const AdamCoef co, int apply, int copy_out,
+                                                              double *trace_row) {
+    __shared__ LightLds lds;
+    __shared__ uint64_t n_obs;
+    const int t = threadIdx.x;
+    if (t == 0) n_obs = n_obs_total;
+    for (int i = t; i < n_images; i += blockDim.x) *table[i].n_obs_total = n_obs_total;
+    if (t < kLightSums) lds.sums[t] = g->sums[t];
+    __syncthreads();
+    if (apply) light_step(lds, g->pstate, g->geom, g->dexp, &n_obs, co, trace_row);   // (ends with a barrier)
+    if (!copy_out) return;
+    for (int i = 0; i < n_images; ++i) {
+        const LightGroupImage im = table[i];
+        for (int k = t; k < 3 * kLightParams; k += blockDim.x) im.pstate[k] = g->pstate[k];
+        if (t < 16) im.geom[t] = g->geom[t];
+        for (int k = t; k < 72; k += blockDim.x) im.dexp[k] = g->dexp[k];
+    }
+}
+
+// The rank's sums: every image's partials reduced in light_reduce's fixed order, the images added in table order starting
+// from image 0's sums as they are (a group of one image leaves the very bits of light_tail_kernel).  256 threads.
+__global__ __launch_bounds__(256) void light_group_tail_kernel(LightGroupHeader *g, const LightGroupImage *__restrict__ table,
+                                                               int n_images, int mode) {
+    __shared__ LightLds lds;
+    const int t = threadIdx.x;
+    double total = 0.0;
+    for (int i = 0; i < n_images; ++i) {
+        light_reduce(table[i].partials, table[i].grid[mode], lds.sums, lds.w4);
+        if (t < kLightSums) total = i == 0 ? lds.sums[t] : total + lds.sums[t];
+    }
+    if (t < kLightSums) g->sums[t] = total;
+}
+
+size_t light_group_bytes(int n_images) { return align_up(sizeof(LightGroupHeader), 256) + (size_t)n_images * sizeof(LightGroupImage); }
+
+int64_t light_group_sums_offset() { return (int64_t)offsetof(LightGroupHeader, sums); }
+
+hipError_t launch_light_group_init(void *group, int n_images, const Layout *L, uint8_t *const *ws, uint8_t *const *lws,
+                                   const float *params19, hipStream_t s) {
+    auto *g = static_cast<LightGroupHeader *>(group);
+    LightParams19 p;
+    for (int i = 0; i < kLightParams; ++i) p.v[i] = params19[i];
+    hipLaunchKernelGGL(light_params_upload_kernel, dim3(1), dim3(64), 0, s, g->staged, p);
+    hipLaunchKernelGGL(light_init_kernel, dim3(1), dim3(64), 0, s, g->pstate, g->geom, g->dexp, g->staged);
+    for (int i = 0; i < n_images; ++i) {
+        LightLayout X;
+        make_light_layout(L[i], &X);
+        LightGroupImage im;
+        im.partials = reinterpret_cast<const float *>(lws[i] + X.off_partials);
+        im.n_obs_total = reinterpret_cast<uint64_t *>(ws[i] + L[i].off_n_obs_total);
+        im.pstate = reinterpret_cast<float *>(lws[i] + X.off_params);
+        im.geom = reinterpret_cast<float *>(lws[i] + X.off_geom);
+        im.dexp = reinterpret_cast<double *>(lws[i] + X.off_dexp);
+        im.grid[0] = light_deal_of(light_grad_kernel<false, false, false, false>, L[i]).grid;   // launch_light_grad_c's grids
+        im.grid[1] = light_deal_of(light_grad_kernel<true, false, false, false>, L[i]).grid;
+        hipLaunchKernelGGL(light_group_set_image_kernel, dim3(1), dim3(1), 0, s, light_group_table(group), i, im);
+    }
+    return hipGetLastError();
+}
+
+// Iteration `step` >= 1: the pending step of iteration step - 1 (if any; its row goes to trace_prev), then every image's
+// gradient pass, then the group's tail.  write_deal: the gradient launches' deals are (re)written into every `lws` first.
+hipError_t launch_light_group_iter(void *group, int n_images, const Layout *L, uint8_t *const *ws, uint8_t *const *lws, int step,
+                                   const AdamCoef &co_prev, const AdamCoef &co, unsigned flags, uint64_t n_obs_total,
+                                   double *trace_prev, bool write_deal, hipStream_t s) {
+    auto *g = static_cast<LightGroupHeader *>(group);
+    const LightGroupImage *table = light_group_table(group);
+    const bool closed = (flags & SUCRE_FIT_CLOSED_FORM) != 0;
+    hipLaunchKernelGGL(light_group_step_kernel, dim3(1), dim3(64), 0, s, g, table, n_images, n_obs_total, co_prev, step > 1 ? 1 : 0, 0,
+                       trace_prev);
+    for (int i = 0; i < n_images; ++i) {
+        LightLayout X;
+        make_light_layout(L[i], &X);
+        if (write_deal) {
+            if (closed) launch_light_grad_c<true, false, false>(L[i], X, ws[i], lws[i], AdamCoef{}, s, 1);
+            else launch_light_grad_c<false, false, false>(L[i], X, ws[i], lws[i], AdamCoef{}, s, 1);
+        }
+        if (closed) launch_light_grad_c<true, false, false>(L[i], X, ws[i], lws[i], co, s, 0, g->pstate, g->geom);
+        else launch_light_grad_c<false, false, false>(L[i], X, ws[i], lws[i], co, s, 0, g->pstate, g->geom);
+    }
+    hipLaunchKernelGGL(light_group_tail_kernel, dim3(1), dim3(256), 0, s, g, table, n_images, closed ? 1 : 0);
+    return hipGetLastError();
+}
+
+// After the pass of iteration `step` (and its all-reduce): that last step, the final state into every image, and in closed-form
+// mode every image's final update_J (sucre.py:155-156).
+hipError_t launch_light_group_finish(void *group, int n_images, const Layout *L, uint8_t *const *ws, uint8_t *const *lws, int step,
+                                     const AdamCoef &co_prev, unsigned flags, uint64_t n_obs_total, double *trace_prev, hipStream_t s) {
+    auto *g = static_cast<LightGroupHeader *>(group);
+    hipLaunchKernelGGL(light_group_step_kernel, dim3(1), dim3(64), 0, s, g, light_group_table(group), n_images, n_obs_total, co_prev,
+                       step >= 1 ? 1 : 0, 1, trace_prev);
+    if (flags & SUCRE_FIT_CLOSED_FORM)
+        for (int i = 0; i < n_images; ++i)
+            if (hipError_t e = launch_light_update_J(L[i], ws[i], lws[i], 0u, s)) return e;
     return hipGetLastError();
 }
 

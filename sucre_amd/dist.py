@@ -77,7 +77,8 @@ class WaterBackend:
 def fit_shared_water(backend: WaterBackend, num_iter: int, group=None) -> None:
     """Lock-step fit of one image per rank with shared B, beta, gamma: objective
     sum_ranks sum_obs r^2 / (3 sum_ranks n_obs).  Per iteration: local gradient pass -> all-reduce(sum) of the
-    ten float64 sums -> identical Adam step on every rank (J updates stay local)."""
+    backend's float64 sums (ten for the water model, 19 for the light model) -> identical Adam step on every rank (J updates
+    stay local)."""
     n = torch.tensor([backend.n_obs()], dtype=torch.int64)
     if hasattr(backend, 'grad_device') and dist.is_initialized() and dist.get_backend(group) == 'nccl':
         n = n.to(backend.grad_device())

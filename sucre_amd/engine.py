@@ -655,14 +655,22 @@ class HipWaterGroup:
     GPU, all sharing B, beta, gamma) with one launch and one collective per iteration: ``grad`` runs the gradient pass
     of every image in a single launch (csrc/fit.hip, group_iter_kernel) and returns the rank's ten sums for the
     all-reduce; the Adam step those sums call for is taken in the prologue of the next ``grad`` launch (``step`` only
-    notes it) and ``finish`` takes the last one.  ``trace``: optional (T, 10) float64 device tensor."""
+    notes it) and ``finish`` takes the last one.  ``trace``: optional (T, 10) float64 device tensor.
+
+    Light-model restorations (all of the group, uint8 colours) share the lamp too: one B, beta, gamma, cam2light, sigma
+    (csrc/light.hip, sucre_light_group_*).  ``grad`` then runs every image's own gradient launch and one tail and returns
+    the 19 sums, ``params0`` has 19 values, ``trace`` is (T, 20), and ``finish`` leaves the shared parameters in every
+    image (``Restoration.params()``) and, in closed-form mode, every image's final J."""
 
     def __init__(self, restorations: list, lr: float = 0.05, betas=(0.9, 0.999), eps: float = 1e-8,
                  use_closed_form: bool = False, trace: torch.Tensor | None = None, params0=None):
         rs = [getattr(r, 'r', r) for r in restorations]      # Restoration objects (or HipWaterBackend wrappers)
         assert rs, 'need at least one image'
-        if any(r.light or r.float_colour for r in rs):
-            raise NotImplementedError('shared water parameters run on the plain water model with uint8 colours')
+        if any(r.float_colour for r in rs):
+            raise NotImplementedError('shared water parameters run on uint8 colours (no float32-colour restorations)')
+        self.light = bool(rs[0].light)
+        if any(r.light != self.light for r in rs):
+            raise NotImplementedError('a shared-water group is all light-model restorations or all plain ones, not a mix')
         assert len({(r.obs_format, str(r.device)) for r in rs}) == 1, 'one device and one observation format per group'
         self.rs = rs
         self.lib = rs[0].lib
@@ -674,15 +682,29 @@ class HipWaterGroup:
         self.total = None
         self.steps_done = 0
         n = len(rs)
-        self.buf = torch.empty(self.lib.sucre_group_bytes(n), dtype=torch.uint8, device=self.device)
+        npar = 19 if self.light else 9
+        nbytes = self.lib.sucre_light_group_bytes(n) if self.light else self.lib.sucre_group_bytes(n)
+        self.buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         assert self.buf.data_ptr() % 256 == 0
-        table = (_lib.GroupImage * n)(*[_lib.GroupImage(r.ws.data_ptr(), r.H, r.W, r.n_views, 0) for r in rs])
-        p0 = np.full(9, 0.1, np.float32) if params0 is None else np.asarray(params0, np.float32).reshape(9)
+        if params0 is None:
+            p0 = np.concatenate([np.full(9, 0.1), np.zeros(6), [1.0, 0.0, 0.0, 1.0]])[:npar].astype(np.float32)  # sucre.py:41-46
+        else:
+            p0 = np.asarray(params0, np.float32).reshape(npar)
+        p0c = (C.c_float * npar)(*p0.tolist())
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.sucre_group_init(C.c_void_p(self.buf.data_ptr()), n, table, (C.c_float * 9)(*p0.tolist()),
-                                                 self._sp()))
-        off = self.lib.sucre_group_sums_offset()
-        self._sums = self.buf[off:off + 96].view(torch.float64)
+            if self.light:
+                table = (_lib.LightGroupImage * n)(*[_lib.LightGroupImage(r.ws.data_ptr(), r.lws.data_ptr(), r.H, r.W, r.n_views, 0)
+                                                     for r in rs])
+                _lib.check(self.lib.sucre_light_group_init(C.c_void_p(self.buf.data_ptr()), n, table, p0c, self._sp()))
+            else:
+                table = (_lib.GroupImage * n)(*[_lib.GroupImage(r.ws.data_ptr(), r.H, r.W, r.n_views, 0) for r in rs])
+                _lib.check(self.lib.sucre_group_init(C.c_void_p(self.buf.data_ptr()), n, table, p0c, self._sp()))
+        if self.light:
+            off = self.lib.sucre_light_group_sums_offset()
+            self._sums = self.buf[off:off + 19 * 8].view(torch.float64)
+        else:
+            off = self.lib.sucre_group_sums_offset()
+            self._sums = self.buf[off:off + 96].view(torch.float64)
 
     def grad_device(self):
         return self.device
@@ -710,6 +732,10 @@ class HipWaterGroup:
             raise _lib.SucreError(f'HipWaterGroup: iteration {step} asked after {self.steps_done} done -- iterations run in '
                                   f'order, once; build a new group (after fit_init) to fit again')
         with torch.cuda.device(self.device):
+            if self.light:   # (the light model's closed-form pass solves J itself: no update_J to start from)
+                _lib.check(self.lib.sucre_light_group_iter(C.c_void_p(self.buf.data_ptr()), len(self.rs), int(step), *self.hyper,
+                                                           self.flags, self.total, self._trace_ptr(), self._sp()))
+                return self._sums
             if self.closed and step == 1:   # start the one-pass closed-form kernel from a solved J (see sucre_fit_run)
                 for r in self.rs:
                     r.update_J()
@@ -724,6 +750,10 @@ class HipWaterGroup:
 
     def finish(self) -> None:
         with torch.cuda.device(self.device):
+            if self.light:   # the last step, the parameters into every image, and the final update_J in closed-form mode
+                _lib.check(self.lib.sucre_light_group_finish(C.c_void_p(self.buf.data_ptr()), len(self.rs), self.steps_done,
+                                                             *self.hyper, self.flags, self.total, self._trace_ptr(), self._sp()))
+                return
             _lib.check(self.lib.sucre_group_finish(C.c_void_p(self.buf.data_ptr()), len(self.rs), self.steps_done, *self.hyper,
                                                    self.total, self._trace_ptr(), self._sp()))
             if self.closed:

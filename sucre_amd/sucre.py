@@ -550,6 +550,9 @@ def _restore_pipeline(images, colmap_model, output_dir, in_flight, keep_matches,
 def parse_args(args: argparse.Namespace):
     """Runs the CLI request (sucre.py:222-261); with WORLD_SIZE > 1 each rank restores its shard of the images."""
     rank, local_rank, world = sdist.env_rank_world()
+    shared = bool(getattr(args, 'shared_water', False))
+    if shared:
+        _refuse_shared_flags(args)
     # torch's CPU thread pool follows the machine's CPU count; inside a container with a CPU quota that many spinning
     # threads only get the process throttled (147 CPU-seconds for 64 images on a 256-CPU box with a 16-CPU quota)
     local_world = max(1, int(os.environ.get('LOCAL_WORLD_SIZE', world)))
@@ -572,13 +575,18 @@ def parse_args(args: argparse.Namespace):
     else:
         lo, hi = args.image_ids
         images = [colmap_model.images[i] for i in range(lo, hi) if i in colmap_model.images]
+    if shared and len(images) < world:
+        raise SystemExit(f'--shared-water: {len(images)} image(s) for {world} ranks; every rank needs at least one image')
+    request = [im.name for im in images]
     images = sdist.shard_images(images, rank, world)
 
     skipped = set(args.filter_images_path.read_text().splitlines()) if args.filter_images_path else set()
     image_list = [im for im in colmap_model.images.values() if im.name not in skipped]
+    if shared:
+        _check_shared_memory(images, image_list, args.light_model, device)
     args.output_dir.mkdir(parents=True, exist_ok=True)
     in_flight = int(os.environ.get('SUCRE_IMAGES_IN_FLIGHT', '2'))   # engine knob, not a reference flag
-    survey = len(images) > 1 and in_flight > 1 and args.save_interval is None and str(device).startswith('cuda')
+    survey = not shared and len(images) > 1 and in_flight > 1 and args.save_interval is None and str(device).startswith('cuda')
     if survey:
         # image files are decoded and the result pictures encoded by child processes (_pixelio.WorkerPool: CPU work in
         # the process that drives the GPU slows its launches down, and PIL's decoder does not scale over threads);
@@ -595,7 +603,10 @@ def parse_args(args: argparse.Namespace):
     if host_threads > 0:
         torch.set_num_threads(host_threads)
     try:
-        _run_request(args, images, image_list, colmap_model, device, survey, in_flight)
+        if shared:
+            restore_shared_water(images, colmap_model, args, image_list, device, request, rank, world)
+        else:
+            _run_request(args, images, image_list, colmap_model, device, survey, in_flight)
     finally:
         _pixelio.stop_pool()
         if host_threads > 0:
@@ -619,6 +630,70 @@ def _run_request(args, images, image_list, colmap_model, device, survey: bool, i
                       batch_size=args.batch_size, save_interval=args.save_interval, params_path=args.params_path,
                       force_compute_matches=args.force_compute_matches, keep_matches=args.keep_matches,
                       num_workers=args.num_workers, device=device)
+
+
+def _refuse_shared_flags(args) -> None:
+    """What --shared-water does not combine with, refused before anything is decoded or matched."""
+    if args.image_scale != 1:
+        raise SystemExit(f'--shared-water: --image-scale {args.image_scale} gives float32 colours, which shared fits do not '
+                         f'support; drop --image-scale or --shared-water')
+    if args.save_interval is not None:
+        raise SystemExit('--shared-water: --save-interval snapshots are not supported for a shared fit; drop one of the two flags')
+
+
+def _check_shared_memory(images: list, image_list: list, light_model: bool, device) -> None:
+    """All the images of a rank stay matched on the device at once: their workspaces (sucre_workspace_bytes, plus
+    sucre_light_workspace_bytes with the light model, at the engine's capacity steps) must fit into what is free now."""
+    from . import _lib, engine
+    lib = _lib.load()
+    n = min(len(image_list), engine.MAX_VIEWS)
+    cap = (n + 7) // 8 * 8 if n <= 256 else (n + 31) // 32 * 32    # engine.acquire_restoration's capacity steps
+    cap = min(cap, engine.MAX_VIEWS)
+    need = 0
+    for im in images:
+        H, W = int(im.camera.height), int(im.camera.width)
+        need += int(lib.sucre_workspace_bytes(H, W, cap))
+        if light_model:
+            need += int(lib.sucre_light_workspace_bytes(H, W, cap))
+    free = int(torch.cuda.mem_get_info(device)[0])
+    if need > free:
+        raise SystemExit(f'--shared-water: the {len(images)} image(s) of this rank need {need} bytes of workspaces on {device}, '
+                         f'{free} are free; run more ranks (torchrun --nproc-per-node N) so that each holds fewer images')
+
+
+def restore_shared_water(images: list, colmap_model: sfm.COLMAPModel, args, image_list: list, device, request: list,
+                         rank: int = 0, world: int = 1) -> None:
+    """--shared-water: every image of this rank is matched into its own workspace, then all are fitted jointly with one
+    B, beta, gamma (and, with --light-model, one cam2light, sigma) for the whole request -- every image keeps its own J --
+    through engine.HipWaterGroup under dist.fit_shared_water (one all-reduce of the sums per iteration across the ranks).
+    Per image the outputs of a plain run; rank 0 also writes ``shared_water.pt`` (the shared parameters, ``trace``, ``images``)."""
+    from . import engine
+    if world > 1:
+        sdist.init_process_group()
+    if str(device).startswith('cuda') and images:
+        loader.prefetch_for_targets(images, image_list, device, num_workers=args.num_workers, min_cover=args.min_cover)
+    jobs = []
+    for k, image in enumerate(images):
+        with engine.slot_lane(k):   # every image in its own workspace
+            jobs.append(_restore_submit(image, colmap_model, args.output_dir, args.light_model, args.use_closed_form,
+                                        args.min_cover, image_list, args.learning_rate, args.num_iter, args.params_path,
+                                        args.force_compute_matches, args.num_workers, device))
+    restos = [_adam_begin(j.sucre, j.matches_data, params0=jobs[0].params0) for j in jobs]
+    T = int(args.num_iter)
+    trace = torch.zeros((T, 20 if args.light_model else 10), dtype=torch.float64, device=restos[0].device)
+    print(f'Solve least squares with Adam optimizer ({T} iterations), shared water over {len(request)} images.')
+    group = engine.HipWaterGroup(restos, lr=args.learning_rate, use_closed_form=args.use_closed_form, trace=trace,
+                                 params0=jobs[0].params0)
+    sdist.fit_shared_water(group, T)
+    trace = trace.cpu().numpy()
+    _log_trace(trace, 0)
+    for job, resto in zip(jobs, restos):
+        _pull_results(job.sucre, resto)
+    shared = {k: v.detach().cpu().clone() for k, v in jobs[0].sucre.state_dict().items() if k != 'J'}
+    for job in jobs:
+        _restore_finish(job, args.keep_matches)
+    if rank == 0:
+        torch.save({**shared, 'trace': torch.from_numpy(trace), 'images': list(request)}, Path(args.output_dir) / 'shared_water.pt')
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -652,6 +727,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--keep-matches', action='store_true', help='export the match lists next to the outputs')
     p.add_argument('--num-workers', type=int, default=0, help='threads decoding images (0 = main thread)')
     p.add_argument('--device', type=str, default='cuda', help='GPU to run on')
+    # (off unless given, and then absent from the namespace: the reference's flags and defaults stay exactly what they are)
+    p.add_argument('--shared-water', action='store_true', default=argparse.SUPPRESS,
+                   help='fit all images of the request jointly: one B, beta, gamma (and, with --light-model, one cam2light, '
+                        'sigma) for all of them, a J per image; also writes shared_water.pt')
     return p
 
 
