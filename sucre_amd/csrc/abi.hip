@@ -87,7 +87,7 @@ int64_t sucre_ws_offset(int H, int W, int n_views, int region) {
         case SUCRE_WS_PARAMS: return (int64_t)L.off_params;
         case SUCRE_WS_SUMS: return (int64_t)L.off_sums;
         case SUCRE_WS_N_OBS_TOTAL: return (int64_t)L.off_n_obs_total;
-        case SUCRE_WS_STORE_FORMAT: return (int64_t)L.off_total_chunks + 8;
+        case SUCRE_WS_STORE_FORMAT: return (int64_t)off_store_format(L);
         default: return fail(SUCRE_ERR_RANGE, "unknown workspace region %d", region);
     }
 }

@@ -696,7 +696,7 @@ hipError_t launch_compact(const Layout &L, uint8_t *ws, hipStream_t s, const uin
     // replace -- 139.3 against 135.9 us per launch at 1080p x 65 views, 90.0 against 86.3 us on a scene whose ranges span 0.7-8 m
     // (profiles/r06_jparam_f32z26_*, r06_jparam_deep_*): eight more vector instructions per chunk cost more than 192 fewer bytes return
     const int allow = ext_dense ? 0 : fmt == SUCRE_OBS_F32 ? 1 : fmt == SUCRE_OBS_F32_Z26 ? 2 : 0;
-    const uint32_t *store_fmt = reinterpret_cast<const uint32_t *>(ws + L.off_total_chunks) + 2;
+    const uint32_t *store_fmt = reinterpret_cast<const uint32_t *>(ws + off_store_format(L));
     hipLaunchKernelGGL(pixel_count_kernel, dim3(L.n_tiles), dim3(256), 0, s, reinterpret_cast<const uint64_t *>(ws + L.off_vbits),
                        pmask, L.mask_words, keep, L.n_views, L.n_tiles, pcount, blockhist);
     hipLaunchKernelGGL(bin_scan_kernel, dim3(bins), dim3(256), 0, s, blockhist, L.n_tiles, totals);

@@ -72,34 +72,6 @@ constexpr bool kExactDiv = SUCRE_EXACT_DIV != 0;
 #endif
 constexpr bool kExactJAdam = SUCRE_EXACT_J_ADAM != 0;
 
-// light.hip, --light-model --use-closed-form: I = k/255 folded into I - b of the J pass (1) / into the residual of the gradient
-// pass (2), two instructions per channel each.  Round 6, one box: 479 -> 472 us per iteration each (both: 477 with the build of
-// that hour), but the closed-form trajectories of the fixtures then leave the reference's: parameters 2.7e-4 away within 50
-// iterations where the reference's own two runs differ by 1.7e-5 (tests/test_gpu_parity.py
-// test_light_model_closed_form_vs_reference_golden, four tests red with either fold) -- this mode keeps the reference's exact I.
-#ifdef SUCRE_EXP_LIGHT_VECTOR_BASES   // (A/B: the strip's bases as the compiler holds them, not forced into scalar registers)
-constexpr bool kExpLightVectorBases = true;
-#else
-constexpr bool kExpLightVectorBases = false;
-#endif
-// light.hip: workgroups of a gradient launch (0: as many as are resident).  Round 6, light + closed form, whose second pass re-reads
-// what the first read (a wave's strip is 83 KB at 65 levels; 4096 waves: 340 MB against the 256 MB memory-side cache): see HISTORY 14.
-#ifndef SUCRE_EXP_LIGHT_GRID
-#define SUCRE_EXP_LIGHT_GRID 0
-#endif
-#ifdef SUCRE_EXP_LIGHT_LOAD_Z   // (A/B: the J-parameter light kernel loads the stored ranges, as until round 6, instead of forming ||cP||)
-constexpr bool kExpLightLoadZ = true;
-#else
-constexpr bool kExpLightLoadZ = false;
-#endif
-#ifndef SUCRE_LIGHT_FOLD1
-#define SUCRE_LIGHT_FOLD1 0
-#endif
-#ifndef SUCRE_LIGHT_FOLD2
-#define SUCRE_LIGHT_FOLD2 0
-#endif
-constexpr bool kExpLightFold1 = SUCRE_LIGHT_FOLD1 != 0, kExpLightFold2 = SUCRE_LIGHT_FOLD2 != 0;
-
 // fit.hip, timing only: every wave of a J-parameter launch records when it entered and left its strips (100 MHz wall clock) --
 // how much of a launch is its ragged end (tools/exp/wave_times.py).
 #ifdef SUCRE_EXP_WAVE_TIMES
@@ -109,14 +81,6 @@ constexpr bool kExpWaveTimes = true;
 constexpr bool kExpWaveTimes = false;
 #define SUCRE_EXP_EXPORT [[maybe_unused]] static
 #endif
-
-// fit.hip: s_setprio experiments against the hardware's oldest-wave-first issue order (tools/exp/wave_times.py shows a launch's
-// five resident workgroups per CU finishing one after the other).  0: none; 1: a wave's priority rotates with every strip,
-// offset by the workgroup's generation; 2: static, younger workgroups higher; 3: rotates with every item.
-#ifndef SUCRE_EXP_PRIO
-#define SUCRE_EXP_PRIO 0
-#endif
-constexpr int kExpPrio = SUCRE_EXP_PRIO;
 
 // layout.h: the work a wave of each workgroup generation is dealt, in 64ths of what a wave of generation 0 (the oldest) gets;
 // the first must be 64.  64 everywhere = equal shares.  Measured (tools/exp/wave_times.py, ab_solo.sh, round 4): with
@@ -139,65 +103,5 @@ constexpr int kExpPrio = SUCRE_EXP_PRIO;
 #define SUCRE_DEAL_CLOSED 64, 48, 32, 20
 #endif
 
-// fit.hip batch launches, timing only (results meaningless): where an image's time inside a batch launch of 640x480 images
-// goes.  1: the tail launch reduces the groups but nobody takes the totals or steps; 2: no pass (every wave is told it has no
-// strip: descriptors, wave sums and the hand-in alone).  tools/exp/batch_ablation.sh.
-#ifndef SUCRE_EXP_BATCH
-#define SUCRE_EXP_BATCH 0
-#endif
-constexpr int kExpBatch = SUCRE_EXP_BATCH;
-
-// fit.hip, closed-form kernel: a chunk's 24 exponentials in two batches of twelve (two levels each) instead of one of 24 --
-// twelve registers fewer in flight, which is what the kernel lacks to fit five waves per SIMD (SUCRE_CLOSED_WAVES=5).
-// Measured (round 5, same box, tools/exp/ab_vs.sh, config 2, launch alone): product 146.5-147.9 us; two batches at 4 waves per
-// SIMD 152-153; at 5 waves with the unequal deal 150.5; at 5 waves with equal shares 158-160.  Neither the smaller batches nor
-// the fifth wave pays: the 24 exponentials back to back at four waves stay.
-#ifdef SUCRE_EXP_HALF_EXPS
-constexpr bool kExpHalfExps = true;
-#else
-constexpr bool kExpHalfExps = false;
-#endif
-// ... and for such occupancy experiments the closed-form instantiation of batch_iter_kernel (which needs more registers than
-// five waves leave) compiled to nothing.
-#ifdef SUCRE_EXP_NO_BATCH_CLOSED
-constexpr bool kExpNoBatchClosed = true;
-#else
-constexpr bool kExpNoBatchClosed = false;
-#endif
-
-// match.hip, timing only (the store is then garbage): match_kernel without its dense-chunk stores -- what the first pass of a
-// count-first / write-sorted matching (VERDICT r04 task 7: trade scatter_kernel's read-back for a second matching pass) would
-// cost at least: every projection, gather and ballot, no observation written.  tools/exp/ab_lib.sh countonly match_kernel.
-#ifdef SUCRE_EXP_MATCH_COUNT_ONLY
-constexpr bool kExpMatchCountOnly = true;
-#else
-constexpr bool kExpMatchCountOnly = false;
-#endif
-
-// fit.hip, batch launches: a wave's streams of consecutive images chained into one (StreamChain).  0 = every image's stream on
-// its own (trailing copies, drain, prime), the form of the first batch kernel -- for the same-box A/B.
-#ifndef SUCRE_EXP_BATCH_CHAIN
-#define SUCRE_EXP_BATCH_CHAIN 1
-#endif
-constexpr bool kExpBatchChain = SUCRE_EXP_BATCH_CHAIN != 0;
-
-// J-parameter kernels, timing only: the stepped state of every strip written to ONE place per wave (wrong results): what of
-// the stores' cost is their issue and acknowledgement, and what the write stream to HBM.
-#ifdef SUCRE_EXP_STORE_LOCAL
-constexpr bool kExpStoreLocal = true;
-#else
-constexpr bool kExpStoreLocal = false;
-#endif
-
-// wave_sums through __shfl_down (ds_bpermute) as until round 5, for the same-box A/B of the register-to-register form.
-#ifdef SUCRE_EXP_SHFL_SUMS
-constexpr bool kExpShflSums = true;
-#else
-constexpr bool kExpShflSums = false;
-#endif
-// ... or one register-to-register tree per sum (round 5's form) instead of round 6's several sums to a register: same bits, 80 against 38 instructions.
-#ifdef SUCRE_EXP_PLAIN_WAVE_SUMS
-constexpr bool kExpPlainWaveSums = true;
-#else
-constexpr bool kExpPlainWaveSums = false;
-#endif
+// Knobs whose question is closed are listed, with their measurements and the commit that last held their code, under
+// 'Retired knobs' in tools/exp/README.md.

@@ -26,6 +26,7 @@
 //   dL/dJ[p]  = -2 s sum_k r a          dL/dB     = -2 s sum r (1 - g)
 //   dL/dbeta  = +2 s sum_p J sum_k r a z    dL/dgamma = -2 s B sum r g z        (per channel)
 #include <cstddef>
+#include <type_traits>
 
 #include "experiment.h"
 #include "fit_math.h"
@@ -37,15 +38,19 @@ struct Water {
     float B[3], nb[3], ng[3];  // B, -beta*log2(e), -gamma*log2(e)
 };
 
-__device__ __forceinline__ Water load_water(const float *__restrict__ params) {
+template <class ParamAt>
+__device__ __forceinline__ Water water_from(ParamAt param_at) {   // param_at(i): parameter i of B[3], beta[3], gamma[3]
     Water w;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        w.B[c] = params[c];
-        w.nb[c] = -params[3 + c] * kLog2e;
-        w.ng[c] = -params[6 + c] * kLog2e;
+        w.B[c] = param_at(c);
+        w.nb[c] = -param_at(3 + c) * kLog2e;
+        w.ng[c] = -param_at(6 + c) * kLog2e;
     }
     return w;
+}
+__device__ __forceinline__ Water load_water(const float *__restrict__ params) {
+    return water_from([&](int i) { return params[i]; });
 }
 
 // The same for a caller that keeps other things in vector registers across the pass: every value made wave-uniform
@@ -77,6 +82,13 @@ struct Acc {
     float cost;    // lane's share of sum r^2
 };
 
+// The lane's ten sums in the order of the reduction buffers (kNumSums): sB[3], sGZ[3], sBeta[3], cost.
+__device__ __forceinline__ void pack_sums(float (&s)[kNumSums], const float (&sB)[3], const float (&sGZ)[3], const float (&sBeta)[3], float cost) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { s[c] = sB[c]; s[3 + c] = sGZ[c]; s[6 + c] = sBeta[c]; }
+    s[9] = cost;
+}
+
 struct Exps { float a[kGroupLv][3], g[kGroupLv][3]; };
 
 __device__ __forceinline__ void chunk_exps(const float (&zz)[kGroupLv], const Water &w, Exps &e) {
@@ -90,6 +102,21 @@ __device__ __forceinline__ void chunk_exps(const float (&zz)[kGroupLv], const Wa
 #pragma unroll
         for (int c = 0; c < 3; ++c) { e.a[j][c] = fast_exp2(e.a[j][c]); e.g[j][c] = fast_exp2(e.g[j][c]); }
     __builtin_amdgcn_sched_barrier(0);
+}
+
+// One observation-channel of the J-parameter loop (closed_terms below is its closed-form twin).
+__device__ __forceinline__ void grad_terms(float z, float a, float g, uint32_t k, bool valid, float Bc, float Jc, int c, Acc &acc) {
+    const float omg = 1.0f - g;
+    const float Ihat = __builtin_fmaf(Jc, a, Bc * omg);
+    // I = k/255 folded into the residual: one rounding instead of two, two VALU ops fewer
+    float r = __builtin_fmaf((float)k, kInv255, -Ihat);
+    r = valid ? r : 0.0f;  // select, not multiply: J may be NaN where unobserved
+    const float rz = r * z;
+    acc.cost = __builtin_fmaf(r, r, acc.cost);
+    acc.pa[c] = __builtin_fmaf(r, a, acc.pa[c]);
+    acc.pb[c] = __builtin_fmaf(rz, a, acc.pb[c]);
+    acc.sB[c] = __builtin_fmaf(r, omg, acc.sB[c]);
+    acc.sGZ[c] = __builtin_fmaf(rz, g, acc.sGZ[c]);
 }
 
 // kMasked = false: every level of the chunk is a real observation of every pixel of the strip (chunks wholly below
@@ -108,21 +135,7 @@ __device__ __forceinline__ void accumulate_chunk(const float (&zz)[kGroupLv], co
         const float z = zz[j];
         const bool valid = !kMasked || z > 0.0f;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const uint32_t k = (cc[c] >> (8 * j)) & 255u;
-            const float a = e.a[j][c], g = e.g[j][c];
-            const float omg = 1.0f - g;
-            const float Ihat = __builtin_fmaf(J[c], a, w.B[c] * omg);
-            // I = k/255 folded into the residual: one rounding instead of two, two VALU ops fewer
-            float r = __builtin_fmaf((float)k, kInv255, -Ihat);
-            r = valid ? r : 0.0f;  // select, not multiply: J may be NaN where unobserved
-            const float rz = r * z;
-            acc.cost = __builtin_fmaf(r, r, acc.cost);
-            acc.pa[c] = __builtin_fmaf(r, a, acc.pa[c]);
-            acc.pb[c] = __builtin_fmaf(rz, a, acc.pb[c]);
-            acc.sB[c] = __builtin_fmaf(r, omg, acc.sB[c]);
-            acc.sGZ[c] = __builtin_fmaf(rz, g, acc.sGZ[c]);
-        }
+        for (int c = 0; c < 3; ++c) grad_terms(z, e.a[j][c], e.g[j][c], (cc[c] >> (8 * j)) & 255u, valid, w.B[c], J[c], c, acc);
     }
 }
 
@@ -131,20 +144,7 @@ __device__ __forceinline__ void accumulate_level(float z, const uint32_t (&k)[3]
                                                  Acc &acc) {
     const bool valid = z > 0.0f;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float a = fast_exp2(z * w.nb[c]);
-        const float g = fast_exp2(z * w.ng[c]);
-        const float omg = 1.0f - g;
-        const float Ihat = __builtin_fmaf(J[c], a, w.B[c] * omg);
-        float r = __builtin_fmaf((float)k[c], kInv255, -Ihat);
-        r = valid ? r : 0.0f;
-        const float rz = r * z;
-        acc.cost = __builtin_fmaf(r, r, acc.cost);
-        acc.pa[c] = __builtin_fmaf(r, a, acc.pa[c]);
-        acc.pb[c] = __builtin_fmaf(rz, a, acc.pb[c]);
-        acc.sB[c] = __builtin_fmaf(r, omg, acc.sB[c]);
-        acc.sGZ[c] = __builtin_fmaf(rz, g, acc.sGZ[c]);
-    }
+    for (int c = 0; c < 3; ++c) grad_terms(z, fast_exp2(z * w.nb[c]), fast_exp2(z * w.ng[c]), k[c], valid, w.B[c], J[c], c, acc);
 }
 
 // Closed-form mode in ONE pass over the observations (sucre.py:141 + 142-147 with J a constant of the backward pass).
@@ -191,32 +191,6 @@ __device__ __forceinline__ void accumulate_chunk(const float (&zz)[kGroupLv], co
                                                  const float (&Jp)[3], AccOne &acc) {
     if (kExpNoCompute) {  // ablation build only (experiment.h): touch the data, skip the model
         acc.q[8][0] += (zz[0] + zz[1]) + (zz[2] + zz[3]) + (float)(cc[0] ^ cc[1] ^ cc[2]);
-        return;
-    }
-    if (kExpHalfExps) {   // (experiment.h: the chunk's exponentials in two batches of twelve -- twelve registers fewer in flight)
-#pragma unroll
-        for (int h = 0; h < kGroupLv; h += 2) {
-            float ea[2][3], eg[2][3];
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) { ea[j][c] = zz[h + j] * w.nb[c]; eg[j][c] = zz[h + j] * w.ng[c]; }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) { ea[j][c] = fast_exp2(ea[j][c]); eg[j][c] = fast_exp2(eg[j][c]); }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const float z = zz[h + j];
-                const bool valid = !kMasked || z > 0.0f;
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-                    closed_terms(z, ea[j][c], eg[j][c], (cc[c] >> (8 * (h + j))) & 255u, valid, w.B[c], Jp[c], acc.q[0][c], acc.q[1][c],
-                                 acc.q[2][c], acc.q[3][c], acc.q[4][c], acc.q[5][c], acc.q[6][c], acc.q[7][c], acc.q[8][c]);
-            }
-        }
         return;
     }
     Exps e;
@@ -452,40 +426,30 @@ __device__ __forceinline__ bool store_matches(const uint32_t *__restrict__ store
 // A full chunk in a ring slot -> this lane's four ranges and three colour dwords.  masked: the chunk may hold empty slots.
 template <int kFmt>
 __device__ __forceinline__ void read_chunk(const uint8_t *sp, int lane, float (&zz)[kGroupLv], uint32_t (&cc)[3], const RangeCodes &rc, bool masked) {
-    if (kFmt == 0 && rc.z26) {   // wave-uniform: a kStoreZ24 chunk + one byte per lane with bits 24-25 of its four codes
+    // Range codes: the lane's 24 bytes side by side -- {low 24 bits of the code | red << 24} x 4, G word, B word; a kStoreZ26 chunk adds
+    // one byte per lane with bits 24-25 of its four codes.  One body, compiled once per code width.
+    auto read_codes = [&](auto z26) {
+        constexpr bool kZ26 = decltype(z26)::value;
         const uint2 a = *reinterpret_cast<const uint2 *>(sp + lane * 24), b = *reinterpret_cast<const uint2 *>(sp + lane * 24 + 8),
                     c = *reinterpret_cast<const uint2 *>(sp + lane * 24 + 16);
-        const uint32_t h = sp[kChunk24 + lane];
-        const uint32_t w[4] = {a.x, a.y, b.x, b.y};
-#pragma unroll
-        for (int j = 0; j < kGroupLv; ++j) {
-            uint32_t bits;
-            asm("v_mad_u32_u24 %0, %1, 1, %2" : "=v"(bits) : "v"(w[j]), "s"(rc.zoff));   // low 24 bits of the code + offset
-            bits += ((h >> (2 * j)) & 3u) << 24;                                            // v_bfe_u32 + v_lshl_add_u32
-            zz[j] = __uint_as_float(bits);
-            if (masked) zz[j] = bits != rc.zoff ? zz[j] : 0.0f;   // code 0: an empty slot reads as range 0, like in the float32 store
-        }
-        cc[0] = __builtin_amdgcn_perm(a.y, a.x, 0x0c0c0703u) | __builtin_amdgcn_perm(b.y, b.x, 0x07030c0cu);
-        cc[1] = c.x; cc[2] = c.y;
-        return;
-    }
-    if (kFmt == 0 && rc.z24) {   // wave-uniform: the lane's 24 bytes side by side -- {code | red << 24} x 4, G word, B word
-        const uint2 a = *reinterpret_cast<const uint2 *>(sp + lane * 24), b = *reinterpret_cast<const uint2 *>(sp + lane * 24 + 8),
-                    c = *reinterpret_cast<const uint2 *>(sp + lane * 24 + 16);
+        const uint32_t h = kZ26 ? sp[kChunk24 + lane] : 0u;
         const uint32_t w[4] = {a.x, a.y, b.x, b.y};
 #pragma unroll
         for (int j = 0; j < kGroupLv; ++j) {
             // bits(z) = code + offset in one instruction: v_mad_u32_u24 multiplies the LOW 24 BITS of its operands
             uint32_t bits;
             asm("v_mad_u32_u24 %0, %1, 1, %2" : "=v"(bits) : "v"(w[j]), "s"(rc.zoff));
+            if (kZ26) bits += ((h >> (2 * j)) & 3u) << 24;   // v_bfe_u32 + v_lshl_add_u32
             zz[j] = __uint_as_float(bits);
-            if (masked) zz[j] = (w[j] & 0xffffffu) ? zz[j] : 0.0f;   // an empty slot reads as range 0, like in the float32 store
+            // code 0: an empty slot reads as range 0, like in the float32 store
+            if (masked) zz[j] = (kZ26 ? bits != rc.zoff : (w[j] & 0xffffffu) != 0u) ? zz[j] : 0.0f;
         }
         // the red bytes sit in byte 3 of the four dwords: gathered into one word so that the arithmetic below is format-blind
         cc[0] = __builtin_amdgcn_perm(a.y, a.x, 0x0c0c0703u) | __builtin_amdgcn_perm(b.y, b.x, 0x07030c0cu);
         cc[1] = c.x; cc[2] = c.y;
-        return;
-    }
+    };
+    if (kFmt == 0 && rc.z26) return read_codes(std::true_type{});    // (wave-uniform)
+    if (kFmt == 0 && rc.z24) return read_codes(std::false_type{});
     if (kFmt == 0) {
         const float4 z4 = *reinterpret_cast<const float4 *>(sp + lane * 16);
         zz[0] = z4.x; zz[1] = z4.y; zz[2] = z4.z; zz[3] = z4.w;
@@ -599,16 +563,6 @@ __device__ __forceinline__ void stream_strips(FitLds &lds, const PlanItem *__res
     uint32_t cs = 0u;                  // byte offset of its slot in the wave's ring; item i + kAhead goes to the slot before it
     uint32_t behind = 0u;              // how many of the next items were issued before the previous strip's stores
     if constexpr (kChain) { cs = chain->cs; behind = chain->behind; }
-    const uint32_t gen = blockIdx.x >> 8;   // (experiment) which of a CU's resident workgroups this one is, oldest first
-    constexpr int kPrio = kChain ? 0 : kExpPrio;   // (the priority experiments were on one image's launch; a batch kernel has no register to spare)
-    auto set_prio = [&](uint32_t p) {
-        switch (p & 3u) {
-            case 0: __builtin_amdgcn_s_setprio(0); break;
-            case 1: __builtin_amdgcn_s_setprio(1); break;
-            case 2: __builtin_amdgcn_s_setprio(2); break;
-            default: __builtin_amdgcn_s_setprio(3); break;
-        }
-    };
     auto step = [&]() -> const uint8_t * {
         // The slot that takes item i + kAhead held item i - 1.  Its LDS reads must have RETURNED before the DMA may overwrite
         // it: a chunk's reads have (the arithmetic consumed them), but a J plane is read into registers that are first used
@@ -627,14 +581,11 @@ __device__ __forceinline__ void stream_strips(FitLds &lds, const PlanItem *__res
         const uint8_t *sp = ringp + cs;
         cs = cs == (uint32_t)((kRing - 1) * kSlot) ? 0u : cs + (uint32_t)kSlot;
         ++i;
-        if (kPrio == 3) set_prio(gen + i);
         return sp;
     };
     ItemRegs se;
     if constexpr (kChain) se = chain->se0; else se = strips[0];
-    if (kPrio == 2) set_prio(gen >= 3u ? 3u : gen);
     for (uint32_t k = 0; k < K; ++k) {
-        if (kPrio == 1) set_prio(gen + k);
         const uint32_t strip = se.x, counts = se.y;
         if (k + 1u < K) se = strips[k + 1u];
         const uint32_t nu = counts_unmasked(counts), nm = counts_masked(counts), r = counts_tail(counts);
@@ -664,12 +615,7 @@ __device__ __forceinline__ void stream_strips(FitLds &lds, const PlanItem *__res
 // The same two functions run in the fused tail (group-last / global-last workgroup) and in the split-path
 // kernel, so both paths produce the same bits.  All hand-off data move with agent-scope (sc1) accesses.
 __device__ __forceinline__ double wave_sum_fixed(double x) {  // fixed-shape tree: same bits on every run (lane 0 holds the sum)
-    if (kExpShflSums) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-        return x;
-    }
-    return wave_sum_lane0(x);   // the same additions, register to register (handoff.h)
+    return wave_sum_lane0(x);   // __shfl_down's additions, register to register (handoff.h)
 }
 
 // 256 threads: wave w reduces quantities q = w, w+4, w+8; lane l holds workgroup 32 g + l (lanes >= 32 hold 0).
@@ -711,10 +657,7 @@ __device__ __forceinline__ void water_step(const double *__restrict__ sums, floa
     float p = 0.f, m = 0.f, v = 0.f;
     double g = 0.0;
     if (q < 9) {
-        const int c = q % 3;
-        if (q < 3) g = -2.0 * (double)scale * sums[c];                            // dL/dB
-        else if (q < 6) g = 2.0 * (double)scale * sums[6 + c];                    // dL/dbeta
-        else g = -2.0 * (double)scale * (double)pstate[c] * sums[3 + c];           // dL/dgamma (B before its step)
+        g = water_grad(q, scale, [&](int i) { return sums[i]; }, [&](int c) { return pstate[c]; });
         p = pstate[q];
         m = pstate[9 + q];
         v = pstate[18 + q];
@@ -735,18 +678,6 @@ __device__ __forceinline__ void water_step(const double *__restrict__ sums, floa
 // The lanes' ten sums -> lane 0 holds the wave's: x_l + x_(l+32), then + (l+16), ... + (l+1) -- the additions of the
 // __shfl_down tree that lane 0 depends on, in its association (the other lanes end with values nobody reads).
 __device__ __forceinline__ void wave_sums(float (&s)[kNumSums]) {
-    if (kExpShflSums || kExpPlainWaveSums) {
-#pragma unroll
-        for (int q = 0; q < kNumSums; ++q) {
-            if (kExpShflSums) {
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) s[q] += __shfl_down(s[q], off, 64);
-            } else {
-                s[q] = wave_sum_lane0(s[q]);
-            }
-        }
-        return;
-    }
     // The same ten trees, several to a register (round 6: 38 instructions instead of 80 -- a small image's stream in a batch launch is
     // a few hundred).  v_permlane32_swap a, b leaves [a.lo | b.lo] and [a.hi | b.hi]: their sum holds x_l + x_(l+32) of quantity q in
     // its lower half and of quantity q + 5 in its upper one; v_permlane16_swap of two such registers and one addition leaves the
@@ -776,31 +707,8 @@ __device__ __forceinline__ void wave_sums(float (&s)[kNumSums]) {
     s[4] = at(R[2], 0); s[9] = at(R[2], 32);
 }
 
-template <bool kFused, bool kStep>
-__device__ __forceinline__ void finish_from_wave_sums(FitLds &lds, float *partials, const AdamCoef &co, unsigned *ticket,
-                                                      double *gpart, int n_groups, double *sums, float *pstate,
-                                                      const uint64_t *__restrict__ n_obs_total, double *trace_row);
-
-// End of a fit launch: the lanes' ten sums -> one float32 partial per workgroup -> (fused form) two-level
+// End of a fit launch, from the four waves' sums in lds.wsum on: one float32 partial per workgroup -> (fused form) two-level
 // last-arriver reduction in float64 and the Adam step on B, beta, gamma by the workgroup that arrives last.
-template <bool kFused, bool kStep = kFused>
-__device__ __forceinline__ void finish_launch(FitLds &lds, float (&s)[kNumSums], float *partials, const AdamCoef &co,
-                                              unsigned *ticket, double *gpart, int n_groups, double *sums,
-                                              float *pstate, const uint64_t *__restrict__ n_obs_total,
-                                              double *trace_row) {
-    const int t = threadIdx.x;
-    const int lane = t & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    // ten workgroup sums: wave shuffle tree, then the four waves in fixed order
-    wave_sums(s);
-    if (lane == 0) {
-#pragma unroll
-        for (int q = 0; q < kNumSums; ++q) lds.wsum[wave][q] = s[q];
-    }
-    finish_from_wave_sums<kFused, kStep>(lds, partials, co, ticket, gpart, n_groups, sums, pstate, n_obs_total, trace_row);
-}
-
-// ... from the four waves' sums in lds.wsum on.
 template <bool kFused, bool kStep>
 __device__ __forceinline__ void finish_from_wave_sums(FitLds &lds, float *partials, const AdamCoef &co, unsigned *ticket,
                                                       double *gpart, int n_groups, double *sums, float *pstate,
@@ -832,6 +740,31 @@ __device__ __forceinline__ void finish_from_wave_sums(FitLds &lds, float *partia
             }
         }
     }
+}
+
+// ... from the lanes' ten sums on.
+template <bool kFused, bool kStep = kFused>
+__device__ __forceinline__ void finish_launch(FitLds &lds, float (&s)[kNumSums], float *partials, const AdamCoef &co,
+                                              unsigned *ticket, double *gpart, int n_groups, double *sums,
+                                              float *pstate, const uint64_t *__restrict__ n_obs_total,
+                                              double *trace_row) {
+    const int t = threadIdx.x;
+    const int lane = t & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    // ten workgroup sums: wave shuffle tree, then the four waves in fixed order
+    wave_sums(s);
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < kNumSums; ++q) lds.wsum[wave][q] = s[q];
+    }
+    finish_from_wave_sums<kFused, kStep>(lds, partials, co, ticket, gpart, n_groups, sums, pstate, n_obs_total, trace_row);
+}
+
+// A stepped value -> the strip's state, with the streaming policy where experiment.h's SUCRE_STORE_NT asks for it.
+template <class Chain>
+__device__ __forceinline__ void store_stepped(float *p, float v) {
+    if (kStoreNt == 1 || (kStoreNt == 2 && Chain::kOn)) __builtin_nontemporal_store(v, p);
+    else *p = v;
 }
 
 // One wave's share of a J-parameter iteration on one image (sucre.py:142-148 with J among the parameters): streams
@@ -866,9 +799,7 @@ __device__ __forceinline__ void grad_pass(FitLds &lds, const PlanItem *__restric
         },
         [&](uint32_t strip, const uint8_t *sp) {  // moments landed: torch.optim.Adam on this pixel's J
             const float *f = reinterpret_cast<const float *>(sp);
-            // (kExpStoreLocal, timing only: every wave writes ONE strip's place over and over -- the stores are issued and
-            // acknowledged like the product's, but the lines stay in L2)
-            float *st = state + (size_t)(kExpStoreLocal ? blockIdx.x * 4u + (uint32_t)wave : strip) * kStateFloats;
+            float *st = state + (size_t)strip * kStateFloats;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 float Jc = J[c], m = f[c * kStripPx + lane], v = f[(3 + c) * kStripPx + lane];
@@ -879,15 +810,9 @@ __device__ __forceinline__ void grad_pass(FitLds &lds, const PlanItem *__restric
                     asm volatile("" ::"v"(Jc), "v"(m), "v"(v));
                     continue;
                 }
-                if (kStoreNt == 1 || (kStoreNt == 2 && Chain::kOn)) {
-                    __builtin_nontemporal_store(Jc, &st[c * kStripPx + lane]);
-                    __builtin_nontemporal_store(m, &st[(3 + c) * kStripPx + lane]);
-                    __builtin_nontemporal_store(v, &st[(6 + c) * kStripPx + lane]);
-                    continue;
-                }
-                st[c * kStripPx + lane] = Jc;
-                st[(3 + c) * kStripPx + lane] = m;
-                st[(6 + c) * kStripPx + lane] = v;
+                store_stepped<Chain>(&st[c * kStripPx + lane], Jc);
+                store_stepped<Chain>(&st[(3 + c) * kStripPx + lane], m);
+                store_stepped<Chain>(&st[(6 + c) * kStripPx + lane], v);
             }
         },
         chain);
@@ -941,8 +866,8 @@ __global__ __launch_bounds__(256, kFitWaves) void fit_grad_kernel(const uint8_t 
     grad_pass<kFmt>(lds, plan + (size_t)wid * plan_stride, plan_strips + (size_t)wid * plan_kmax, n_mine, ws, state, wave, lane, w, gscale, co, acc, sBeta, rc);
     if (kExpWaveTimes && lane == 0 && wid < kExpWaveSlots) g_exp_wave_times[1][wid] = wall_clock64();
 
-    float s[kNumSums] = {acc.sB[0], acc.sB[1], acc.sB[2], acc.sGZ[0], acc.sGZ[1], acc.sGZ[2],
-                         sBeta[0], sBeta[1], sBeta[2], acc.cost};
+    float s[kNumSums];
+    pack_sums(s, acc.sB, acc.sGZ, sBeta, acc.cost);
     finish_launch<kFused>(lds, s, partials, co, ticket, gpart, n_groups, sums, pstate, n_obs_total, trace_row);
     if (kExpWaveTimes && lane == 0 && wid < kExpWaveSlots) { g_exp_wave_times[2][wid] = exp_t_in; g_exp_wave_times[3][wid] = wall_clock64(); g_exp_wave_times[4][wid] = clock64() - exp_c_in; }
 }
@@ -994,8 +919,7 @@ __device__ __forceinline__ void closed_pass(FitLds &lds, const PlanItem *__restr
                 const float N = acc.q[0][c], D = acc.q[1][c];
                 const float dJ = N / D;                          // 0/0 = NaN where nothing was observed (sucre.py:77)
                 const float Jc = fmt_ok ? Jp[c] + dJ : __builtin_nanf("");   // = sum y a / sum a^2
-                if (kStoreNt == 1 || (kStoreNt == 2 && Chain::kOn)) __builtin_nontemporal_store(Jc, &st[c * kStripPx + lane]);
-                else st[c * kStripPx + lane] = Jc;
+                store_stepped<Chain>(&st[c * kStripPx + lane], Jc);
                 if (!kJOnly && D != 0.0f) {
                     cs.sB[c] += __builtin_fmaf(-dJ, acc.q[3][c], acc.q[2][c]);
                     cs.sBeta[c] += Jc * __builtin_fmaf(-dJ, acc.q[5][c], acc.q[4][c]);
@@ -1040,11 +964,17 @@ __global__ __launch_bounds__(256, kClosedWaves) void fit_closed_kernel(const uin
     closed_pass<kFmt, kJOnly>(lds, plan + (size_t)wid * plan_stride, plan_strips + (size_t)wid * plan_kmax, n_mine, ws, state, wave, lane, w, fmt_ok, cs, rc);
     if (kExpWaveTimes && !kJOnly && lane == 0 && wid < kExpWaveSlots) g_exp_wave_times[1][wid] = wall_clock64();
     if (kJOnly) return;
-    float s[kNumSums] = {cs.sB[0], cs.sB[1], cs.sB[2], cs.sGZ[0], cs.sGZ[1], cs.sGZ[2], cs.sBeta[0], cs.sBeta[1], cs.sBeta[2], cs.cost};
+    float s[kNumSums];
+    pack_sums(s, cs.sB, cs.sGZ, cs.sBeta, cs.cost);
     finish_launch<kFused>(lds, s, partials, co, ticket, gpart, n_groups, sums, pstate, n_obs_total, trace_row);
 }
 
 struct Params9 { float v[9]; };
+static Params9 params9(const float *p) {
+    Params9 q;
+    for (int i = 0; i < 9; ++i) q.v[i] = p[i];
+    return q;
+}
 
 // The group / batch kernels carry a few registers more than fit_grad_kernel: when an experiment build gives that one six waves per
 // SIMD (SUCRE_FIT_WAVES=6) they keep five (their launches then run their last sixth of workgroups in a second round: timing
@@ -1096,11 +1026,7 @@ __device__ __forceinline__ void group_water_step(const double *__restrict__ sums
         p = ld_agent(in + q); m = ld_agent(in + 9 + q); v = ld_agent(in + 18 + q);
         if (apply) {
             const float scale = (1.0f / 3.0f) / (float)n_obs_total;
-            const int c = q % 3;
-            double g;
-            if (q < 3) g = -2.0 * (double)scale * ld_agent(sums + c);
-            else if (q < 6) g = 2.0 * (double)scale * ld_agent(sums + 6 + c);
-            else g = -2.0 * (double)scale * (double)ld_agent(in + c) * ld_agent(sums + 3 + c);
+            const double g = water_grad(q, scale, [&](int i) { return ld_agent(sums + i); }, [&](int c) { return ld_agent(in + c); });
             adam_update(p, m, v, (float)g, co);
         }
     }
@@ -1159,16 +1085,12 @@ __global__ __launch_bounds__(256, kMode ? kClosedWaves : kGroupFitWaves) void gr
         float s[kNumSums];
         if (kMode == 0) {
             grad_pass<kFmt>(lds, plan, strips, n_mine, ws, state, wave, lane, w, gscale, co, acc, sBeta, rc);
-            const float q[kNumSums] = {acc.sB[0], acc.sB[1], acc.sB[2], acc.sGZ[0], acc.sGZ[1], acc.sGZ[2], sBeta[0], sBeta[1], sBeta[2], acc.cost};
-#pragma unroll
-            for (int j = 0; j < kNumSums; ++j) s[j] = q[j];
+            pack_sums(s, acc.sB, acc.sGZ, sBeta, acc.cost);
             zero_acc(acc);
             sBeta[0] = sBeta[1] = sBeta[2] = 0.f;
         } else {
             closed_pass<kFmt, false>(lds, plan, strips, n_mine, ws, state, wave, lane, w, true, cs, rc);
-            const float q[kNumSums] = {cs.sB[0], cs.sB[1], cs.sB[2], cs.sGZ[0], cs.sGZ[1], cs.sGZ[2], cs.sBeta[0], cs.sBeta[1], cs.sBeta[2], cs.cost};
-#pragma unroll
-            for (int j = 0; j < kNumSums; ++j) s[j] = q[j];
+            pack_sums(s, cs.sB, cs.sGZ, cs.sBeta, cs.cost);
             cs = ClosedSums{{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, 0.f};
         }
         wave_sums(s);
@@ -1237,7 +1159,7 @@ struct BatchEntry { uint8_t *ws; double *trace; BatchOffsets o; };   // trace: t
 // the single-thread forms below add the same numbers in the same association as reduce_group / reduce_total's shuffle
 // trees, so an image's bits are those of its own launch.
 // (Handing every image in by itself, its own arrival chain behind its own pass, cost 5.6 of an image's 14 us at 640x480 --
-// the workgroup has nothing in flight while its stores drain and its arrival returns; tools/exp/batch_ablation.sh.)
+// the workgroup has nothing in flight while its stores drain and its arrival returns; tools/exp/README.md, Retired knobs.)
 constexpr int kBatchMax = 32;   // images per launch (their waves' sums wait in 5 KB of LDS)
 static_assert((kFitGrid + kGroup - 1) / kGroup <= 64 && (kClosedGrid + kGroup - 1) / kGroup <= 64, "reduce_total_thread: one group per lane");
 
@@ -1280,7 +1202,7 @@ __device__ __forceinline__ double reduce_total_thread(const double *gpart, int n
 // What a wave needs to know of one image of the batch.  Everything is read through the constant address space (scalar loads
 // the compiler tracks itself; nothing of it is written during the launch: the parameters are stepped by the tail launch), and
 // the NEXT image's is asked for before this image's pass, so that no wave waits for a chain of dependent loads between two
-// images (measured: 2.2 us per image with nothing else to do, tools/exp/batch_ablation.sh).
+// images (measured: 2.2 us per image with nothing else to do; tools/exp/README.md, Retired knobs).
 template <class T>
 __device__ __forceinline__ T cload(const void *p) {
     return *reinterpret_cast<const __attribute__((address_space(4))) T *>(reinterpret_cast<uintptr_t>(p));
@@ -1312,16 +1234,10 @@ __device__ __forceinline__ BatchView batch_view(const BatchEntry *__restrict__ i
     v.rc = range_codes_of<kFmt>(f0, f1);
     v.fmt_ok = format_readable(kFmt, f0);
     v.n_mine = v.fmt_ok ? cload<uint32_t>(v.ws + o_count + 4ull * wid) : 0u;
-    if (kExpBatch == 2) v.n_mine = 0u;
     v.plan = reinterpret_cast<const PlanItem *>(v.ws + o_plan) + (size_t)wid * stride;
     v.strips = reinterpret_cast<const StripEntry *>(v.ws + o_strips) + (size_t)wid * kmax;
     v.state = reinterpret_cast<float *>(v.ws + o_state);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {   // load_water, from scalar loads
-        v.w.B[c] = cload<float>(v.ws + o_params + 4 * c);
-        v.w.nb[c] = -cload<float>(v.ws + o_params + 4 * (3 + c)) * kLog2e;
-        v.w.ng[c] = -cload<float>(v.ws + o_params + 4 * (6 + c)) * kLog2e;
-    }
+    v.w = water_from([&](int i) { return cload<float>(v.ws + o_params + 4 * i); });   // scalar loads
     v.gscale = -2.0f * ((1.0f / 3.0f) / (float)cload<uint64_t>(v.ws + o_n));
     const ConstItems items = const_items(v.plan);   // (in bounds also for a wave without strips: every wave has its stride)
 #pragma unroll
@@ -1339,7 +1255,6 @@ __device__ __forceinline__ BatchView batch_view(const BatchEntry *__restrict__ i
 template <int kMode, int kFmt>
 __global__ __launch_bounds__(256, kMode ? kClosedWaves : kGroupFitWaves) void batch_iter_kernel(const BatchEntry *__restrict__ images, int n_images,
                                                                                            const AdamCoef co, int row, uint32_t vblocks) {
-    if (kExpNoBatchClosed && kMode == 1) return;   // (experiment.h: occupancy experiments on the closed-form kernel alone)
     __shared__ BatchLds blds;
     FitLds &lds = blds.fit;
     const int t = threadIdx.x;
@@ -1371,7 +1286,7 @@ __global__ __launch_bounds__(256, kMode ? kClosedWaves : kGroupFitWaves) void ba
         // Chained: this wave has strips in both pairs, and this one's stream is long enough to issue ALL of the next one's
         // first kAhead items in place of its trailing ones (a closed-form stream can be ONE item long: a strip of pixels nobody
         // observes -- its second item is already a trailing one).
-        const bool chained = kExpBatchChain && more && v.n_mine != 0u && vn.n_mine != 0u && !(v.head[kAhead - 1].y & kShapeTrail);
+        const bool chained = more && v.n_mine != 0u && vn.n_mine != 0u && !(v.head[kAhead - 1].y & kShapeTrail);
 #pragma unroll
         for (int q = 0; q < kAhead + 1; ++q) ch.head[q] = v.head[q];
         ch.se0 = v.se0;
@@ -1434,7 +1349,6 @@ __global__ __launch_bounds__(kTailThreads) void batch_tail_kernel(const BatchEnt
     uint8_t *ws = mine ? images[i].ws : nullptr;
     if (mine)
         reduce_group_thread(reinterpret_cast<const float *>(ws + images[i].o.partials), n_blocks, g, q, reinterpret_cast<double *>(ws + images[i].o.gpart), n_groups);
-    if (kExpBatch == 1) return;   // (timing experiment, experiment.h)
     // what the step needs besides the totals is asked for before the arrival (every workgroup: one of them will use it)
     float p = 0.f, m = 0.f, v = 0.f, Bc = 0.f, scale = 0.f;
     float *pstate = nullptr;
@@ -1456,11 +1370,7 @@ __global__ __launch_bounds__(kTailThreads) void batch_tail_kernel(const BatchEnt
     // water_step (sucre.py:148-152), thread q of an image in the role of lane q
     double *trace = images[i].trace;
     if (q < 9) {
-        const int c = q % 3;
-        double grad;
-        if (q < 3) grad = -2.0 * (double)scale * stot[i][c];
-        else if (q < 6) grad = 2.0 * (double)scale * stot[i][6 + c];
-        else grad = -2.0 * (double)scale * (double)Bc * stot[i][3 + c];
+        const double grad = water_grad(q, scale, [&](int j) { return stot[i][j]; }, [&](int) { return Bc; });
         adam_update(p, m, v, (float)grad, co);
         pstate[q] = p; pstate[9 + q] = m; pstate[18 + q] = v;
         if (trace) trace[(size_t)row * 10 + 1 + q] = (double)p;
@@ -1468,6 +1378,15 @@ __global__ __launch_bounds__(kTailThreads) void batch_tail_kernel(const BatchEnt
         trace[(size_t)row * 10] = stot[i][9];
     }
 }
+
+// Images per launch.  A workgroup of a launch over n images walks ceil(n vblocks / grid) pairs, grid = min(n vblocks, full), and
+// the waves' sums of every one of them wait in blds.wsum[kBatchMax]: n vblocks <= kBatchMax full.  The product's image grids are
+// no larger than what is resident (vblocks <= full): kBatchMax images; a SUCRE_FIT_WAVES=6 build, whose image grid has a sixth
+// generation that batch_iter_kernel has no registers for (kGroupFitWaves), takes fewer.
+constexpr uint32_t batch_full_grid(int mode) { return (uint32_t)(mode ? kClosedGrid : 256 * kGroupFitWaves); }
+constexpr int batch_images(uint32_t vblocks, uint32_t full) { return vblocks <= full ? kBatchMax : (int)((uint64_t)kBatchMax * full / vblocks); }
+static_assert(batch_images(kClosedGrid, batch_full_grid(1)) == kBatchMax && batch_images(kFitGrid, batch_full_grid(0)) >= 1, "a launch takes at least one image");
+static_assert(SUCRE_FIT_WAVES > 5 || batch_images(kFitGrid, batch_full_grid(0)) == kBatchMax, "the product's launches take kBatchMax images");
 
 constexpr int kBatchSet = 8;
 struct BatchEntries { BatchEntry e[kBatchSet]; };
@@ -1537,12 +1456,10 @@ __global__ void set_n_obs_total_kernel(uint64_t *dst, uint64_t v) { *dst = v; }
 
 hipError_t launch_fit_init(const Layout &L, uint8_t *ws, const uint8_t *rgb1, const float *depth1,
                            const float *params0, const float *J0, hipStream_t s) {
-    Params9 p0;
-    for (int i = 0; i < 9; ++i) p0.v[i] = params0[i];
     hipLaunchKernelGGL(fit_init_kernel, dim3(L.n_tiles), dim3(256), 0, s, rgb1, depth1, J0, L.H, L.W, L.tiles_x,
                        reinterpret_cast<const uint32_t *>(ws + L.off_perm), reinterpret_cast<float *>(ws + L.off_state),
                        reinterpret_cast<float *>(ws + L.off_params),
-                       reinterpret_cast<unsigned *>(ws + L.off_ticket), (1 + L.n_groups) * kTicketStride, p0);  // n_groups = the larger grid's
+                       reinterpret_cast<unsigned *>(ws + L.off_ticket), (1 + L.n_groups) * kTicketStride, params9(params0));  // n_groups = the larger grid's
     return hipGetLastError();
 }
 
@@ -1559,21 +1476,30 @@ static void launch_fit_kernel(Kernel kernel, int mode, const Layout &L, uint8_t 
                        reinterpret_cast<unsigned *>(ws + L.off_ticket),
                        reinterpret_cast<double *>(ws + L.off_gpartials), L.fit_groups[mode],
                        reinterpret_cast<double *>(ws + L.off_sums), trace_row,
-                       reinterpret_cast<const uint32_t *>(ws + L.off_total_chunks + sizeof(uint64_t)));
+                       reinterpret_cast<const uint32_t *>(ws + off_store_format(L)));
 }
+
+// The (J mode, store format) of a call -> the compile-time (kMode, kFmt) of the kernel instantiation that serves it: f is called
+// with two std::integral_constant<int, .>.  kMode 0: J among the parameters, 1: closed form; kFmt 0: float32 ranges (words or
+// range codes), 1: uint16 millimetres.
+template <class F>
+static void dispatch_fit(int mode, bool u16, F f) {
+    using Zero = std::integral_constant<int, 0>;
+    using One = std::integral_constant<int, 1>;
+    if (mode) { if (u16) f(One{}, One{}); else f(One{}, Zero{}); }
+    else { if (u16) f(Zero{}, One{}); else f(Zero{}, Zero{}); }
+}
+static int fit_mode(unsigned flags) { return (flags & SUCRE_FIT_CLOSED_FORM) ? 1 : 0; }
+static bool fit_u16(unsigned flags) { return (flags & SUCRE_FIT_OBS_U16MM) != 0; }
 
 // J-parameter mode: gradient pass + Adam on J; closed-form mode: the one-pass kernel (J re-solved, then constant).
 template <bool kFused>
 static void launch_grad_variant(const Layout &L, uint8_t *ws, const AdamCoef &co, unsigned flags, double *trace_row,
                                 hipStream_t s) {
-    const bool u16 = (flags & SUCRE_FIT_OBS_U16MM) != 0;
-    if (flags & SUCRE_FIT_CLOSED_FORM) {
-        if (u16) launch_fit_kernel(fit_closed_kernel<kFused, 1, false>, 1, L, ws, co, trace_row, s);
-        else launch_fit_kernel(fit_closed_kernel<kFused, 0, false>, 1, L, ws, co, trace_row, s);
-    } else {
-        if (u16) launch_fit_kernel(fit_grad_kernel<kFused, 1>, 0, L, ws, co, trace_row, s);
-        else launch_fit_kernel(fit_grad_kernel<kFused, 0>, 0, L, ws, co, trace_row, s);
-    }
+    dispatch_fit(fit_mode(flags), fit_u16(flags), [&](auto mode, auto fmt) {
+        if constexpr (mode.value) launch_fit_kernel(fit_closed_kernel<kFused, fmt.value, false>, 1, L, ws, co, trace_row, s);
+        else launch_fit_kernel(fit_grad_kernel<kFused, fmt.value>, 0, L, ws, co, trace_row, s);
+    });
 }
 
 // One whole iteration in a single launch (gradient pass + last-arriver reduction + water-parameter step).
@@ -1587,7 +1513,7 @@ hipError_t launch_fit_iter_fused(const Layout &L, uint8_t *ws, const AdamCoef &c
 // all-reduce; launch_fit_step applies them.
 hipError_t launch_fit_grad(const Layout &L, uint8_t *ws, const AdamCoef &co, unsigned flags, hipStream_t s) {
     launch_grad_variant<false>(L, ws, co, flags, nullptr, s);
-    const int mode = (flags & SUCRE_FIT_CLOSED_FORM) ? 1 : 0;
+    const int mode = fit_mode(flags);
     hipLaunchKernelGGL(reduce_groups_kernel, dim3(L.fit_groups[mode]), dim3(256), 0, s,
                        reinterpret_cast<const float *>(ws + L.off_partials), L.fit_blocks[mode],
                        reinterpret_cast<double *>(ws + L.off_gpartials), L.fit_groups[mode]);
@@ -1605,8 +1531,7 @@ hipError_t launch_fit_step(const Layout &L, uint8_t *ws, const AdamCoef &co, dou
 }
 
 hipError_t launch_update_J(const Layout &L, uint8_t *ws, int fmt, hipStream_t s) {
-    if (fmt) launch_fit_kernel(fit_closed_kernel<false, 1, true>, 1, L, ws, AdamCoef{}, nullptr, s);
-    else launch_fit_kernel(fit_closed_kernel<false, 0, true>, 1, L, ws, AdamCoef{}, nullptr, s);
+    dispatch_fit(1, fmt != 0, [&](auto, auto f) { launch_fit_kernel(fit_closed_kernel<false, f.value, true>, 1, L, ws, AdamCoef{}, nullptr, s); });
     return hipGetLastError();
 }
 
@@ -1622,7 +1547,7 @@ hipError_t launch_plan(const Layout &L, uint8_t *ws, hipStream_t s) {
     uint32_t Kmax = (uint32_t)(L.plan_kmax[0] > L.plan_kmax[1] ? L.plan_kmax[0] : L.plan_kmax[1]);   // strips of the busiest wave (of either mode)
     if (Kmax < 32u) Kmax = 32u;   // thread slots per fit wave (k >= the wave's strip count: nothing to do)
     hipLaunchKernelGGL(plan_kernel, dim3((Wmax * Kmax + 255u) / 256u, 2), dim3(256), 0, s, meta, L.n_strips,
-                       reinterpret_cast<const uint32_t *>(ws + L.off_total_chunks) + 2, W0, W1, Kmax,
+                       reinterpret_cast<const uint32_t *>(ws + off_store_format(L)), W0, W1, Kmax,
                        (uint32_t)L.plan_stride[0], (uint32_t)L.plan_stride[1], (uint32_t)L.plan_kmax[0], (uint32_t)L.plan_kmax[1],
                        reinterpret_cast<PlanItem *>(ws + L.off_plan[0]), reinterpret_cast<PlanItem *>(ws + L.off_plan[1]),
                        reinterpret_cast<StripEntry *>(ws + L.off_plan_strips[0]), reinterpret_cast<StripEntry *>(ws + L.off_plan_strips[1]),
@@ -1638,23 +1563,32 @@ hipError_t launch_export_J(const Layout &L, const uint8_t *ws, float *J, hipStre
     return hipGetLastError();
 }
 
+// Where an image keeps what a launch over several images needs of it -- its plan for one J mode, its state, format words and
+// parameters -- as offsets into its workspace: the one reading of a Layout behind the batch and the group tables.
+struct ImageRef {
+    uint64_t plan, strips, count, state, format, params;
+    uint32_t stride, kmax, n_waves;
+};
+static ImageRef image_ref(const Layout &L, int mode) {
+    return ImageRef{L.off_plan[mode], L.off_plan_strips[mode], L.off_plan_count[mode], L.off_state, off_store_format(L), L.off_params,
+                    (uint32_t)L.plan_stride[mode], (uint32_t)L.plan_kmax[mode], (uint32_t)L.fit_blocks[mode] * 4u};
+}
+
 size_t batch_bytes(int n_images) { return align_up((size_t)n_images * sizeof(BatchEntry), 256); }
 
 // The image table of a batch for one J mode (the plans differ between the modes): entry i = image i's workspace, log and
 // the offsets of its own layout.
 hipError_t launch_batch_set(void *batch, int n_images, uint8_t *const *ws, double *const *trace, const Layout *layouts, unsigned flags,
                             hipStream_t s) {
-    const int mode = (flags & SUCRE_FIT_CLOSED_FORM) ? 1 : 0;
+    const int mode = fit_mode(flags);
     for (int i0 = 0; i0 < n_images; i0 += kBatchSet) {
         BatchEntries src;
         const int n = n_images - i0 < kBatchSet ? n_images - i0 : kBatchSet;
         for (int j = 0; j < kBatchSet; ++j) {
             const Layout &L = layouts[j < n ? i0 + j : i0];
-            BatchOffsets o;
-            o.plan = L.off_plan[mode]; o.strips = L.off_plan_strips[mode]; o.count = L.off_plan_count[mode];
-            o.params = L.off_params; o.n_obs_total = L.off_n_obs_total; o.state = L.off_state; o.partials = L.off_partials;
-            o.ticket = L.off_ticket; o.gpart = L.off_gpartials; o.sums = L.off_sums; o.format = L.off_total_chunks + sizeof(uint64_t);
-            o.stride = (uint32_t)L.plan_stride[mode]; o.kmax = (uint32_t)L.plan_kmax[mode]; o.n_groups = L.fit_groups[mode];
+            const ImageRef r = image_ref(L, mode);
+            const BatchOffsets o = {r.plan, r.strips, r.count, r.params, L.off_n_obs_total, r.state, L.off_partials, L.off_ticket,
+                                    L.off_gpartials, L.off_sums, r.format, r.stride, r.kmax, L.fit_groups[mode]};
             src.e[j] = BatchEntry{j < n ? ws[i0 + j] : nullptr, (j < n && trace) ? trace[i0 + j] : nullptr, o};
         }
         hipLaunchKernelGGL(batch_set_kernel, dim3(1), dim3(64), 0, s, static_cast<BatchEntry *>(batch) + i0, src, n);
@@ -1665,23 +1599,18 @@ hipError_t launch_batch_set(void *batch, int n_images, uint8_t *const *ws, doubl
 // One iteration of every image of the batch: one launch (row = the iteration's row in every image's log).  L: any image's
 // layout (the grid is a function of the image size).
 hipError_t launch_batch_iter(const Layout &L, void *batch, int n_images, const AdamCoef &co, unsigned flags, int row, hipStream_t s) {
-    const int mode = (flags & SUCRE_FIT_CLOSED_FORM) ? 1 : 0;
-    const bool u16 = (flags & SUCRE_FIT_OBS_U16MM) != 0;
+    const int mode = fit_mode(flags);
     const uint32_t vblocks = (uint32_t)L.fit_blocks[mode];   // the images' own grid (one size: one grid)
-    const uint32_t full = (uint32_t)(mode ? kClosedGrid : 256 * kGroupFitWaves);   // what is resident at once
-    const dim3 block(256);
-    for (int i0 = 0; i0 < n_images; i0 += kBatchMax) {   // at most kBatchMax images per launch: a workgroup walks at most
-        auto *b = static_cast<const BatchEntry *>(batch) + i0;   // kBatchMax pairs (vblocks <= full), whose sums wait in LDS
-        const int n = n_images - i0 < kBatchMax ? n_images - i0 : kBatchMax;
+    const uint32_t full = batch_full_grid(mode);             // what is resident at once
+    const int per_launch = batch_images(vblocks, full);
+    for (int i0 = 0; i0 < n_images; i0 += per_launch) {
+        auto *b = static_cast<const BatchEntry *>(batch) + i0;
+        const int n = n_images - i0 < per_launch ? n_images - i0 : per_launch;
         const uint32_t pairs = (uint32_t)n * vblocks;
         const dim3 grid(pairs < full ? pairs : full);
-        if (mode) {
-            if (u16) hipLaunchKernelGGL((batch_iter_kernel<1, 1>), grid, block, 0, s, b, n, co, row, vblocks);
-            else hipLaunchKernelGGL((batch_iter_kernel<1, 0>), grid, block, 0, s, b, n, co, row, vblocks);
-        } else {
-            if (u16) hipLaunchKernelGGL((batch_iter_kernel<0, 1>), grid, block, 0, s, b, n, co, row, vblocks);
-            else hipLaunchKernelGGL((batch_iter_kernel<0, 0>), grid, block, 0, s, b, n, co, row, vblocks);
-        }
+        dispatch_fit(mode, fit_u16(flags), [&](auto m, auto f) {
+            hipLaunchKernelGGL((batch_iter_kernel<m.value, f.value>), grid, dim3(256), 0, s, b, n, co, row, vblocks);
+        });
         hipLaunchKernelGGL(batch_tail_kernel, dim3(L.fit_groups[mode]), dim3(kTailThreads), 0, s, b, n, L.fit_blocks[mode], co, row);
     }
     return hipGetLastError();
@@ -1692,9 +1621,7 @@ size_t group_bytes(int n_images) { return align_up(sizeof(GroupHeader), 256) + (
 int64_t group_sums_offset() { return (int64_t)offsetof(GroupHeader, sums); }
 
 hipError_t launch_group_init(void *group, const float *params0, hipStream_t s) {
-    Params9 p0;
-    for (int i = 0; i < 9; ++i) p0.v[i] = params0[i];
-    hipLaunchKernelGGL(group_init_kernel, dim3(1), dim3(64), 0, s, static_cast<GroupHeader *>(group), p0);
+    hipLaunchKernelGGL(group_init_kernel, dim3(1), dim3(64), 0, s, static_cast<GroupHeader *>(group), params9(params0));
     return hipGetLastError();
 }
 
@@ -1702,12 +1629,11 @@ hipError_t launch_group_set_image(void *group, int i, const Layout &L, uint8_t *
     GroupImage im;
     im.ws = ws;
     for (int m = 0; m < 2; ++m) {
-        im.off_plan[m] = L.off_plan[m]; im.off_strips[m] = L.off_plan_strips[m]; im.off_count[m] = L.off_plan_count[m];
-        im.stride[m] = (uint32_t)L.plan_stride[m]; im.kmax[m] = (uint32_t)L.plan_kmax[m]; im.n_waves[m] = (uint32_t)L.fit_blocks[m] * 4u;
+        const ImageRef r = image_ref(L, m);
+        im.off_plan[m] = r.plan; im.off_strips[m] = r.strips; im.off_count[m] = r.count;
+        im.stride[m] = r.stride; im.kmax[m] = r.kmax; im.n_waves[m] = r.n_waves;
+        im.off_state = r.state; im.off_format = r.format; im.off_params = r.params;   // (the same for both modes)
     }
-    im.off_state = L.off_state;
-    im.off_format = L.off_total_chunks + sizeof(uint64_t);
-    im.off_params = L.off_params;
     hipLaunchKernelGGL(group_set_image_kernel, dim3(1), dim3(1), 0, s, static_cast<GroupHeader *>(group), i, im);
     return hipGetLastError();
 }
@@ -1718,16 +1644,11 @@ hipError_t launch_group_iter(void *group, int n_images, int step, const AdamCoef
     auto *g = static_cast<GroupHeader *>(group);
     const int apply = step > 1 ? 1 : 0;
     const int in = apply ? (step - 2) & 1 : 0, out = apply ? (step - 1) & 1 : 0;
-    const bool u16 = (flags & SUCRE_FIT_OBS_U16MM) != 0;
-    if (flags & SUCRE_FIT_CLOSED_FORM) {
-        const int ng = (kClosedGrid + kGroup - 1) / kGroup;
-        if (u16) hipLaunchKernelGGL((group_iter_kernel<1, 1>), dim3(kClosedGrid), dim3(256), 0, s, g, n_images, n_obs_total, co_prev, co, apply, in, out, trace_prev, ng, group_images(g));
-        else hipLaunchKernelGGL((group_iter_kernel<1, 0>), dim3(kClosedGrid), dim3(256), 0, s, g, n_images, n_obs_total, co_prev, co, apply, in, out, trace_prev, ng, group_images(g));
-    } else {
-        const int ng = (kFitGrid + kGroup - 1) / kGroup;
-        if (u16) hipLaunchKernelGGL((group_iter_kernel<0, 1>), dim3(kFitGrid), dim3(256), 0, s, g, n_images, n_obs_total, co_prev, co, apply, in, out, trace_prev, ng, group_images(g));
-        else hipLaunchKernelGGL((group_iter_kernel<0, 0>), dim3(kFitGrid), dim3(256), 0, s, g, n_images, n_obs_total, co_prev, co, apply, in, out, trace_prev, ng, group_images(g));
-    }
+    dispatch_fit(fit_mode(flags), fit_u16(flags), [&](auto m, auto f) {
+        constexpr int grid = m.value ? kClosedGrid : kFitGrid, ng = (grid + kGroup - 1) / kGroup;
+        hipLaunchKernelGGL((group_iter_kernel<m.value, f.value>), dim3(grid), dim3(256), 0, s, g, n_images, n_obs_total, co_prev, co, apply, in, out,
+                           trace_prev, ng, group_images(g));
+    });
     return hipGetLastError();
 }
 

@@ -37,6 +37,17 @@ __device__ __forceinline__ void adam_update(float &p, float &m, float &v, float 
     p = p + (co.step_size_neg * m) / denom;
 }
 
+// dL/dB, dL/dbeta, dL/dgamma of channel q % 3 (q = 0..2, 3..5, 6..8: the parameter's place among the nine) from the ten reduced
+// sums -- sB[3], sGZ[3], sBeta[3], cost -- with scale = (1/3) / n_obs (fit.hip's header).  sum_at(i) and B_at(c) are callables,
+// called inside the branch that needs them: a caller's loads stay conditional.  B is the one BEFORE its own step.
+template <class SumAt, class BAt>
+__device__ __forceinline__ double water_grad(int q, float scale, SumAt sum_at, BAt B_at) {
+    const int c = q % 3;
+    if (q < 3) return -2.0 * (double)scale * sum_at(c);              // dL/dB
+    if (q < 6) return 2.0 * (double)scale * sum_at(6 + c);           // dL/dbeta
+    return -2.0 * (double)scale * (double)B_at(c) * sum_at(3 + c);   // dL/dgamma
+}
+
 // The same step for a pixel's J (three per pixel and iteration: 158 of the J-parameter kernel's ~2000 instructions per
 // pixel were the two IEEE divisions and the IEEE square root of these three steps): hardware square root and reciprocals
 // (1 ulp each) instead of the IEEE sequences, 11 instead of ~42 instructions per channel.  The fit is held to a tolerance,

@@ -194,8 +194,9 @@ struct Layout {
     size_t off_invperm;     // uint32 [n_tiles*256]        dense slot  -> sorted slot
     int n_strips;           // n_tiles * 4 strips of 64 sorted pixels
     size_t off_strip_meta;  // StripMeta [n_strips]
-    size_t off_total_chunks;// uint64 [1] total (padded) levels over all strips, then uint32 [5]: format of the compact store (kStore*), the
-                            // offset of its range codes (kStoreZ24 / kStoreZ26), smallest / largest range bits of the dense store
+    size_t off_total_chunks;// uint64 [1] total (padded) levels over all strips, then four uint32 words: [0] format of the compact store
+                            // (kStore*), [1] offset of its range codes (kStoreZ24 / kStoreZ26) -- off_store_format() --, [2] smallest and
+                            // [3] largest range bits of the dense store -- off_range_span()
     size_t off_zrange;      // uint2  [n_tiles][n_views]   smallest / largest float32 bit pattern of ranges of the tile (0xffffffff / 0: none); an imported
                             // view's entry holds its own, a matched view's the ranges of ALL the views its wave walked (or none)
     size_t off_zpart;       // uint2  [ceil(n_tiles / 32)] the same over 32 tiles and all views
@@ -221,6 +222,11 @@ struct Layout {
 };
 
 __host__ __device__ inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// The words behind the total (Layout.off_total_chunks): the store's format and code offset, uint32 [2], written by the compaction
+// and read by every fit kernel; then the dense store's smallest / largest range bits, uint32 [2], left by the finalize pass.
+inline size_t off_store_format(const Layout &L) { return L.off_total_chunks + sizeof(uint64_t); }
+inline size_t off_range_span(const Layout &L) { return off_store_format(L) + 2 * sizeof(uint32_t); }
 
 inline bool make_layout(int H, int W, int n_views, Layout *L) {
     if (H <= 0 || W <= 0 || n_views <= 0 || n_views > kMaxViews || H > 32767 || W > 32767) return false;

@@ -10,7 +10,7 @@
 // plus the 19 parameters (B, beta, gamma, cam2light[6], sigma[4]), their Adam moments, and the reduction buffers.
 // Everything of the default path (J planes, compact store, perm, levels) is reused from the main workspace.
 //
-// One iteration = light_grad_kernel (persistent waves on strips like fit_grad_kernel; 26 sums) -> light_tail_kernel (one
+// One iteration = light_grad_kernel (persistent waves on strips like fit_grad_kernel; 19 sums) -> light_tail_kernel (one
 // workgroup: fixed-order float64 reduction, chain rule through Sigma^-1 and through the matrix exponential -- six 8x8
 // block exponentials evaluated in LDS -- Adam on the 19 parameters, next R, t, Sigma^-1, log row).
 // Plain loads instead of the LDS-DMA ring: the kernel is instruction-limited (~135 instructions per observation).
@@ -34,8 +34,8 @@ struct LightLayout {
     size_t off_params;                    // float [19] params, [19] exp_avg, [19] exp_avg_sq
     size_t off_geom;                      // float [16]: R[9], t[3], M[4] = Sigma^-1 (row-major)
     size_t off_dexp;                      // double [6][12]: entries 0..5 of row i = the twist v_i = (omega_i, u_i) with D exp(hat xi)[G_i] = hat(v_i) exp(hat xi) (with the geometry)
-    size_t off_partials;                  // float [26][n_blocks]
-    size_t off_sums;                      // double [26]
+    size_t off_partials;                  // float [19][n_blocks]
+    size_t off_sums;                      // double [19]
     size_t off_deal;                      // uint32 [8192] strips per wave, then [8 n_strips] the waves' strip lists (light_deal_kernel)
     size_t off_ext2_dense, off_ext2_comp; // second set of planes (float32 colours next to camera points); only with ext_sets = 2
     size_t total;
@@ -272,7 +272,7 @@ __device__ __forceinline__ float chunk_checksum(const LightChunk &k) {
     return s;
 }
 
-// The 26 sums over the workgroups' partials, float64, fixed order (thread t adds the workgroups t, t + 256, ..., then a
+// The 19 sums over the workgroups' partials, float64, fixed order (thread t adds the workgroups t, t + 256, ..., then a
 // fixed-shape shuffle tree, then the four waves in order); all loads are issued before any is waited for.  256 threads.
 __device__ __forceinline__ void light_reduce(const float *partials, int n_blocks, double *sums, double (*w4)[4]) {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -313,12 +313,9 @@ __device__ __forceinline__ void light_step(LightLds &lds, float *pstate, float *
         for (int r = 0; r < 3; ++r) s += sums[10 + r] * dexp[tid * 12 + r] + sums[13 + r] * dexp[tid * 12 + 3 + r];
         grad[9 + tid] = f * s;
     }
-    if (tid == 6) {  // water parameters (same combinations as water_step of the default path)
-        for (int c = 0; c < 3; ++c) {
-            grad[c] = f * sums[c];
-            grad[3 + c] = -f * sums[6 + c];
-            grad[6 + c] = f * (double)pstate[c] * sums[3 + c];
-        }
+    if (tid == 6) {  // water parameters: the default path's combinations (f = -2 scale)
+        const float scale = (1.0f / 3.0f) / (float)(*n_obs_total);
+        for (int q = 0; q < 9; ++q) grad[q] = water_grad(q, scale, [&](int i) { return sums[i]; }, [&](int c) { return pstate[c]; });
     }
     if (tid == 7) {  // sigma: M = Sigma^-1, Sigma = sigma^T sigma;  dSigma = -M^T dM M^T;  dsigma = sigma (dSigma + dSigma^T)
         const double M[4] = {geom[12], geom[13], geom[14], geom[15]};
@@ -405,10 +402,10 @@ __global__ __launch_bounds__(256) void light_grad_kernel(const uint8_t *__restri
             if (strip >= (uint32_t)n_strips) continue;
         }
         const StripMeta sm = meta[strip];
-        const uint32_t n = kExpLightVectorBases ? sm.levels : __builtin_amdgcn_readfirstlane(sm.levels), nch = (n + 3u) >> 2;
+        const uint32_t n = __builtin_amdgcn_readfirstlane(sm.levels), nch = (n + 3u) >> 2;
         // wave-uniform bases, held in scalar registers: the loads below are base + 32-bit lane offset (with per-lane 64-bit
         // pointers the address arithmetic was 7 vector instructions per observation)
-        const uint64_t lvoff = kExpLightVectorBases ? sm.lvoff : ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(sm.lvoff >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)sm.lvoff);
+        const uint64_t lvoff = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(sm.lvoff >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)sm.lvoff);
         const uint8_t *sobs = comp + lvoff * (uint64_t)level_bytes(0);
         const uint8_t *sext = ext + lvoff * (uint64_t)kExtLevelBytes;
         const uint8_t *sext2 = kBoth ? ext2 + lvoff * (uint64_t)kExtLevelBytes : nullptr;
@@ -441,11 +438,9 @@ __global__ __launch_bounds__(256) void light_grad_kernel(const uint8_t *__restri
                         for (int c = 0; c < 3; ++c) {
                             const float a = o.l * exp2_as<kGradual>(o.z * nb[c]);
                             const float b = o.l * B[c] * (1.0f - exp2_as<kGradual>(o.z * ng[c]));
-                            // uint8 colours: I = k/255 folded into I - b (one rounding instead of two, two instructions fewer), as
-                            // fit.hip's closed_terms does; float32 colours are what they are
-                            const float y = kBoth ? fc.c[c][j] - b : kColour ? cP[c] - b
-                                                  : kExpLightFold1 ? __builtin_fmaf((float)((kk.cc[c] >> (8 * j)) & 255u), kInv255L, -b)
-                                                                   : unit_from_u8((kk.cc[c] >> (8 * j)) & 255u) - b;
+                            // uint8 colours: the reference's exact I = k/255, not folded into I - b as fit.hip's closed_terms does (the
+                            // closed-form trajectories leave the reference's with the fold: tools/exp/README.md, Retired knobs)
+                            const float y = kBoth ? fc.c[c][j] - b : kColour ? cP[c] - b : unit_from_u8((kk.cc[c] >> (8 * j)) & 255u) - b;
                             num[c] = __builtin_fmaf(y, a, num[c]);
                             den[c] = __builtin_fmaf(a, a, den[c]);
                         }
@@ -497,8 +492,8 @@ __global__ __launch_bounds__(256) void light_grad_kernel(const uint8_t *__restri
         auto levels_of = [&](uint32_t g) { return min((uint32_t)kGroupLv, n - g * kGroupLv); };
         // The J-parameter kernel on uint8 colours leaves the ranges in HBM and forms ||cP|| itself (v_sqrt_f32, 1 ulp: this mode is held
         // to a tolerance; the closed-form trajectories are not touched -- they amplify a last-bit change of one range, see the
-        // k/255 fold in experiment.h): 21 % fewer bytes for a kernel that waits for its loads, three FMAs and a square root more.
-        constexpr bool kNoZ = !kClosed && !kColour && !kBoth && !kExpLightLoadZ;
+        // k/255 fold under Retired knobs in tools/exp/README.md): 21 % fewer bytes for a kernel that waits for its loads, three FMAs and a square root more.
+        constexpr bool kNoZ = !kClosed && !kColour && !kBoth;
         auto load_at = [&](uint32_t i) { return load_light_chunk<true, kNoZ>(sobs, sext, chunk_at(i), levels_of(chunk_at(i)), lane); };
         // one chunk: four levels of this lane's pixel
         auto grad_chunk = [&](const LightChunk &kk, uint32_t gi) {
@@ -527,7 +522,7 @@ __global__ __launch_bounds__(256) void light_grad_kernel(const uint8_t *__restri
                     const uint32_t kb = (kk.cc[c] >> (8 * j)) & 255u;
                     const float r = kBoth ? fc.c[c][j] - lE
                                   : kColour ? cP[c] - lE
-                                  : (kClosed && !kExpLightFold2) ? unit_from_u8(kb) - lE : __builtin_fmaf((float)kb, kInv255L, -lE);
+                                  : kClosed ? unit_from_u8(kb) - lE : __builtin_fmaf((float)kb, kInv255L, -lE);
                     const float rl = r * l;
                     const float rlz = rl * z;
                     acc.s[9] = __builtin_fmaf(r, r, acc.s[9]);
@@ -611,7 +606,7 @@ __global__ __launch_bounds__(256) void light_grad_kernel(const uint8_t *__restri
     if (t < kLightSums) partials[(size_t)t * n_blocks + blockIdx.x] = ((wsum[0][t] + wsum[1][t]) + wsum[2][t]) + wsum[3][t];
 }
 
-// The iteration's tail, one workgroup: the 26 sums, the step on the 19 parameters, the next geometry, the log row.
+// The iteration's tail, one workgroup: the 19 sums, the step on the 19 parameters, the next geometry, the log row.
 // (Folding it into the gradient launch as a last-arriver tail, like fit.hip does, was measured: -29 us per iteration with
 // J as a parameter but +9 us in closed-form mode, whose two-pass kernel came out 5 % slower with the tail's code and
 // 14 KB of LDS in it; as its own launch it costs ~20 us + one launch gap in both modes.  Round 2 had two launches here,
@@ -720,7 +715,6 @@ static int resident_grid(K kernel, const Layout &L) {
         }
         grid = per_device[dev];
     }
-    if (SUCRE_EXP_LIGHT_GRID > 0) grid = SUCRE_EXP_LIGHT_GRID;   // (experiment.h: fewer resident workgroups -- a smaller working set)
     return L.n_blocks < grid ? L.n_blocks : grid;
 }
 

@@ -281,7 +281,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))) voi
         } else if (lane == 63) {
             zrange[(size_t)tile * n_views + k] = make_uint2(0xffffffffu, 0u);
         }
-        if (total > 0 && !kExpMatchCountOnly) {  // wave-uniform; chunks of empty (tile, view) pairs are never read
+        if (total > 0) {  // wave-uniform; chunks of empty (tile, view) pairs are never read
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the wave reads back what its own lanes wrote: LDS
             __builtin_amdgcn_wave_barrier();                          // operations of one wave complete in order
             uint8_t *chunk = obs + (size_t)tile * tile_stride + (size_t)k * view_stride;
@@ -747,7 +747,7 @@ hipError_t launch_finalize(const Layout &L, uint8_t *ws, double min_cover, hipSt
     hipLaunchKernelGGL(view_total_kernel, dim3(1), dim3(1024), 0, s, partial, rows, L.n_views, min_cover,
                        (double)L.W * (double)L.H, vc, vk, reinterpret_cast<uint64_t *>(ws + L.off_n_obs),
                        reinterpret_cast<uint64_t *>(ws + L.off_n_obs_total), zpart,
-                       reinterpret_cast<uint32_t *>(ws + L.off_total_chunks) + 4);
+                       reinterpret_cast<uint32_t *>(ws + off_range_span(L)));
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     return launch_compact(L, ws, s, ext_dense, ext_comp, fmt, ext2_dense, ext2_comp);
 }

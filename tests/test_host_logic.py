@@ -619,16 +619,15 @@ def test_experiment_variants_compile(tmp_path):
     header = (csrc / 'experiment.h').read_text()
     # every knob in at least one build; knobs that do not exclude each other share one (a build is ~5 s)
     variants = {
-        'tablate1': '-DSUCRE_EXP_NOCOMPUTE -DSUCRE_EXP_WAVE_TIMES -DSUCRE_EXP_PRIO=3 -DSUCRE_EXACT_J_ADAM=1',
+        'tablate1': '-DSUCRE_EXP_NOCOMPUTE -DSUCRE_EXP_WAVE_TIMES -DSUCRE_EXACT_J_ADAM=1',
         'tablate2': '-DSUCRE_EXP_NOLOAD -DSUCRE_RING=4 -DSUCRE_FIT_WAVES=4 -DSUCRE_DEAL_FIT=64,44,24,14,5 -DSUCRE_DEAL_CLOSED=64,48,32,20',
-        'texactdiv': '-DSUCRE_EXACT_DIV=1 -DSUCRE_EXP_WAVE_TIMES -DSUCRE_EXP_MATCH_COUNT_ONLY',
-        'tlight2': '-DSUCRE_EXP_NOLOAD -DSUCRE_LIGHT_FOLD1=1 -DSUCRE_LIGHT_FOLD2=1 -DSUCRE_EXP_LIGHT_VECTOR_BASES -DSUCRE_EXP_LIGHT_LOAD_Z -DSUCRE_EXP_LIGHT_GRID=512',
+        'texactdiv': '-DSUCRE_EXACT_DIV=1 -DSUCRE_EXP_WAVE_TIMES',
+        'tlight2': '-DSUCRE_EXP_NOLOAD -DSUCRE_EXP_NOCOMPUTE',
         'tscatter': '-DSUCRE_EXP_WAVE_TIMES',
-        'tstorent': '-DSUCRE_STORE_NT=1 -DSUCRE_EXP_STORE_LOCAL -DSUCRE_EXP_SHFL_SUMS',
-        'tbatch': '-DSUCRE_EXP_BATCH=2 -DSUCRE_EXP_NOSTORE -DSUCRE_EXP_BATCH_CHAIN=0 -DSUCRE_MIN_STRIPS=1 -DSUCRE_EXP_PLAIN_WAVE_SUMS',
-        'thalf': '-DSUCRE_EXP_HALF_EXPS -DSUCRE_CLOSED_WAVES=5 -DSUCRE_EXP_NO_BATCH_CLOSED -DSUCRE_DEAL_CLOSED=64,48,32,20,10',
+        'tstorent': '-DSUCRE_STORE_NT=1',
+        'tbatch': '-DSUCRE_EXP_NOSTORE -DSUCRE_MIN_STRIPS=1',
     }
-    objects = {'texactdiv': 'match', 'tlight1': 'light', 'tlight2': 'light', 'tscatter': 'compact'}   # the source a knob lives in (default: fit)
+    objects = {'texactdiv': 'match', 'tlight2': 'light', 'tscatter': 'compact'}   # the source a knob lives in (default: fit)
     for macro in re.findall(r'#\s*if(?:n?def)\s+(SUCRE_[A-Z_0-9]+)', header):   # every knob of the header is exercised here
         assert any(macro in flags for flags in variants.values()) or macro in ('SUCRE_CLOSED_WAVES', 'SUCRE_DMA_POLICY'), macro
     # no other build-time switch hides in the kernel sources
