@@ -368,6 +368,35 @@ int sucre_fit_run_light(void *ws, void *lws, int H, int W, int n_views, int t0, 
                         void *stream);
 
 /*
+ * ---- fit residuals per pixel and per view ------------------------------------------------------------------------------
+ * Where the fitted model can be trusted, and which view hurts it: one streaming pass over the DENSE store of a matched (or
+ * imported), finalised and fitted workspace that evaluates the residual of sucre.adam's objective (sucre.py:144),
+ *     r = I - l (J exp(-beta z) + B (1 - exp(-gamma z)))        SUCRe.forward, sucre.py:79-82; l, z: sucre.py:52-64,
+ * for every observation of every KEPT view (SUCRE_WS_VIEW_KEEP, sfm.py:136) at the workspace's CURRENT parameters and CURRENT
+ * J (the J sucre_export_J would return), and keeps two kinds of sums -- what a caller otherwise rebuilds on the host from
+ * MatchesData.iter (loader.py:120-130) to write a --filter-images-path list (sucre.py:227-232):
+ *   count_dev       int32   (H,W)        observations of the pixel over the kept views
+ *   ssr_dev         float32 (H,W,3)      sum of r^2 per channel over those observations (0 where count is 0)
+ *   view_stats_dev  float64 (n_views,4)  per view: observations, then sum of r^2 for R, G, B; zeros for a view that is not kept
+ * The workspaces are only read.  scratch_dev: sucre_residual_scratch_bytes() bytes of caller-owned device memory, 16-byte
+ * aligned, that must stay untouched until the pass has run; every sum is formed in a fixed order (no atomics), so two calls
+ * give the same bits.  obs_format: the format the store was finalised with -- with SUCRE_OBS_U16MM the range of an observation
+ * is the one that store's fit reads, 0.001f * clamp(rint(1000 z), 1, 65535); the three float32 forms read the same number.
+ * sucre_fit_residuals_ext: the same for a workspace with extension planes.  flags = SUCRE_FIT_EXT_COLOUR: float32 colours from
+ * the dense extension planes, plain water model (its nine parameters are the first nine of `lws`); flags = 0: the light model
+ * (SUCRE_EXT_POINTS), flags = SUCRE_FIT_EXT_BOTH: the light model on float32 colours.  With the light model l and z come from
+ * the camera point cP and R, t, Sigma^-1 of the parameters as they stand in `lws` (derived anew, as sucre_update_J_ext does, so a
+ * caller may have written them); the range that enters z = range + ||lP|| is the STORED one of the dense store -- ||cP|| as the
+ * match kernel wrote it, or an imported list's own z -- as in the closed-form kernel, not the ||cP|| the J-parameter kernel
+ * re-forms from the point.
+ */
+size_t sucre_residual_scratch_bytes(int H, int W, int n_views);
+int sucre_fit_residuals(const void *ws, int H, int W, int n_views, int obs_format, int32_t *count_dev, float *ssr_dev,
+                        double *view_stats_dev, void *scratch_dev, void *stream);
+int sucre_fit_residuals_ext(const void *ws, const void *lws, int H, int W, int n_views, unsigned flags /* 0 | SUCRE_FIT_EXT_COLOUR | SUCRE_FIT_EXT_BOTH */,
+                            int32_t *count_dev, float *ssr_dev, double *view_stats_dev, void *scratch_dev, void *stream);
+
+/*
  * Shared water AND light over several light-model images (the group above for the 19-parameter model; sucre.py:54-61 with
  * the objective of sucre.py:124-157 summed over the images: one B, beta, gamma, cam2light, sigma, every image its own J, one
  * n_obs).  `group_dev`: sucre_light_group_bytes(n_images) bytes of device memory, 256-byte aligned; `images` (host array)

@@ -95,6 +95,9 @@ SIGNATURES = {
     'sucre_update_J_light': (_i, [_vp, _vp, _i, _i, _i, _vp]),
     'sucre_update_J_ext': (_i, [_vp, _vp, _i, _i, _i, C.c_uint, _vp]),
     'sucre_fit_run_light': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _d, _d, _d, _d, C.c_uint, _vp, _vp]),
+    'sucre_residual_scratch_bytes': (C.c_size_t, [_i, _i, _i]),
+    'sucre_fit_residuals': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'sucre_fit_residuals_ext': (_i, [_vp, _vp, _i, _i, _i, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
     'sucre_light_group_bytes': (C.c_size_t, [_i]),
     'sucre_light_group_sums_offset': (C.c_int64, []),
     'sucre_light_group_init': (_i, [_vp, _i, C.POINTER(LightGroupImage), C.POINTER(C.c_float), _vp]),

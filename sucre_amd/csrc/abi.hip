@@ -560,6 +560,55 @@ int sucre_fit_run_light(void *ws, void *lws, int H, int W, int n_views, int t0, 
     return SUCRE_OK;
 }
 
+/* ---- fit residuals per pixel and per view ------------------------------------------------------------------------ */
+
+size_t sucre_residual_scratch_bytes(int H, int W, int n_views) {
+    Layout L;
+    if (!make_layout(H, W, n_views, &L)) {
+        fail(SUCRE_ERR_ARG, "invalid geometry H=%d W=%d n_views=%d", H, W, n_views);
+        return 0;
+    }
+    return residual_scratch_bytes(L);
+}
+
+}  // extern "C"
+
+namespace sucre {
+static int check_residual_outputs(const int32_t *count_dev, const float *ssr_dev, const double *view_stats_dev, const void *scratch_dev) {
+    if (!count_dev || !ssr_dev || !view_stats_dev || !scratch_dev) return fail(SUCRE_ERR_ARG, "count_dev / ssr_dev / view_stats_dev / scratch_dev is NULL");
+    if (!aligned(count_dev, 4) || !aligned(ssr_dev, 4) || !aligned(view_stats_dev, 8)) return fail(SUCRE_ERR_ARG, "outputs must be 4 / 4 / 8-byte aligned");
+    if (!aligned(scratch_dev, 16)) return fail(SUCRE_ERR_ARG, "scratch_dev must be 16-byte aligned");
+    return SUCRE_OK;
+}
+}  // namespace sucre
+
+extern "C" {
+
+int sucre_fit_residuals(const void *ws, int H, int W, int n_views, int obs_format, int32_t *count_dev, float *ssr_dev,
+                        double *view_stats_dev, void *scratch_dev, void *stream) {
+    Layout L;
+    if (int rc = check_ws(ws, H, W, n_views, &L)) return rc;
+    if (obs_format != SUCRE_OBS_F32 && obs_format != SUCRE_OBS_U16MM && obs_format != SUCRE_OBS_F32_PLAIN && obs_format != SUCRE_OBS_F32_Z26)
+        return fail(SUCRE_ERR_ARG, "unknown observation format %d", obs_format);
+    if (int rc = check_residual_outputs(count_dev, ssr_dev, view_stats_dev, scratch_dev)) return rc;
+    return check_hip(launch_residuals(L, static_cast<const uint8_t *>(ws), obs_format == SUCRE_OBS_U16MM ? SUCRE_OBS_U16MM : SUCRE_OBS_F32,
+                                      count_dev, ssr_dev, view_stats_dev, scratch_dev, static_cast<hipStream_t>(stream)),
+                     "sucre_fit_residuals");
+}
+
+int sucre_fit_residuals_ext(const void *ws, const void *lws, int H, int W, int n_views, unsigned flags, int32_t *count_dev,
+                            float *ssr_dev, double *view_stats_dev, void *scratch_dev, void *stream) {
+    Layout L;
+    if (int rc = check_ws(ws, H, W, n_views, &L)) return rc;
+    if (int rc = check_lws(lws)) return rc;
+    if (flags & ~(SUCRE_FIT_EXT_COLOUR | SUCRE_FIT_EXT_BOTH)) return fail(SUCRE_ERR_ARG, "unknown flags 0x%x", flags);
+    if ((flags & SUCRE_FIT_EXT_COLOUR) && (flags & SUCRE_FIT_EXT_BOTH)) return fail(SUCRE_ERR_ARG, "SUCRE_FIT_EXT_COLOUR and SUCRE_FIT_EXT_BOTH exclude each other");
+    if (int rc = check_residual_outputs(count_dev, ssr_dev, view_stats_dev, scratch_dev)) return rc;
+    return check_hip(launch_residuals_ext(L, static_cast<const uint8_t *>(ws), static_cast<const uint8_t *>(lws), flags, count_dev,
+                                          ssr_dev, view_stats_dev, scratch_dev, static_cast<hipStream_t>(stream)),
+                     "sucre_fit_residuals_ext");
+}
+
 /* ---- shared water and light over the light-model images of a rank (sucre.py:54-61, 124-157) ------------------------ */
 
 }  // extern "C"

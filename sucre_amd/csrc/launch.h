@@ -73,6 +73,13 @@ hipError_t launch_batch_set(void *batch, int n_images, uint8_t *const *ws, doubl
                             hipStream_t s);
 hipError_t launch_batch_iter(const Layout &L, void *batch, int n_images, const AdamCoef &co, unsigned flags, int row, hipStream_t s);
 
+// fit residuals per pixel and per view (residual.h; residual.hip, the variants with camera points in light.hip)
+size_t residual_scratch_bytes(const Layout &L);
+hipError_t launch_residuals(const Layout &L, const uint8_t *ws, int fmt, int32_t *count, float *ssr, double *view_stats,
+                            void *scratch, hipStream_t s);
+hipError_t launch_residuals_ext(const Layout &L, const uint8_t *ws, const uint8_t *lws, unsigned flags, int32_t *count, float *ssr,
+                                double *view_stats, void *scratch, hipStream_t s);
+
 // output stage (plot.hip)
 size_t select_scratch_bytes();
 hipError_t launch_select_ranks(const float *J, int H, int W, int n_ranks, const uint64_t *ranks, float *out, void *scratch,

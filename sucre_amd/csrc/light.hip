@@ -19,6 +19,7 @@
 #include <mutex>
 #include "fit_math.h"
 #include "handoff.h"
+#include "residual.h"
 
 namespace sucre {
 
@@ -780,6 +781,50 @@ hipError_t launch_light_update_J(const Layout &L, uint8_t *ws, uint8_t *lws, uns
     hipLaunchKernelGGL(light_geometry_kernel, dim3(1), dim3(64), 0, s, reinterpret_cast<const float *>(lws + X.off_params),
                        reinterpret_cast<float *>(lws + X.off_geom), reinterpret_cast<double *>(lws + X.off_dexp));
     launch_light_grad<true, true>(L, X, ws, lws, AdamCoef{}, flags, s, 2);
+    return hipGetLastError();
+}
+
+// ---- fit residuals per pixel and per view with extension planes (residual.h) -----------------------------------------
+// The light variants of the one skeleton: l and z of an observation from its camera point through light_obs.  The range that
+// enters z = zc + ||lP|| is the STORED one of the dense chunk (||cP|| as the match kernel wrote it, or the list's own range of
+// an imported view) -- the closed-form kernel's choice, not the ||cP|| the J-parameter kernel re-forms from the point.
+struct LightModel {
+    float R[9], tl[3], M[4];
+    __device__ __forceinline__ explicit LightModel(const float *geom) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) R[i] = geom[i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) tl[i] = geom[9 + i];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) M[i] = geom[12 + i];
+    }
+    __device__ __forceinline__ void lz(const float (&cP)[3], float zc, float &l, float &z) const {
+        const LightObs o = light_obs(cP, zc, R, tl, M);
+        l = o.l; z = o.z;
+    }
+};
+
+hipError_t launch_residuals_ext(const Layout &L, const uint8_t *ws, const uint8_t *lws, unsigned flags, int32_t *count, float *ssr,
+                                double *view_stats, void *scratch, hipStream_t s) {
+    LightLayout X;
+    make_light_layout(L, &X, (flags & SUCRE_FIT_EXT_BOTH) ? 2 : 1);
+    ResidualArgs A = residual_args(L, ws, count, ssr, view_stats, scratch);
+    A.params = reinterpret_cast<const float *>(lws + X.off_params);
+    A.ext = lws + X.off_ext_dense;
+    A.ext2 = (flags & SUCRE_FIT_EXT_BOTH) ? lws + X.off_ext2_dense : nullptr;
+    if (flags & SUCRE_FIT_EXT_COLOUR) {
+        launch_residual_colour(A, s);
+    } else {
+        // the geometry of the parameters as they stand (the caller may have written them since the last step), as
+        // launch_light_update_J derives it -- into the head of the scratch buffer: the workspaces are only read
+        float *geom = static_cast<float *>(scratch);
+        static_assert(16 * sizeof(float) + 72 * sizeof(double) <= kResidualGeomBytes, "geometry and twists fit the scratch head");
+        hipLaunchKernelGGL(light_geometry_kernel, dim3(1), dim3(64), 0, s, A.params, geom, reinterpret_cast<double *>(geom + 16));
+        A.geom = geom;
+        if (flags & SUCRE_FIT_EXT_BOTH) launch_residual_kernel(residual_kernel<false, SUCRE_EXT_POINTS_COLOUR, LightModel>, A, s);
+        else launch_residual_kernel(residual_kernel<false, SUCRE_EXT_POINTS, LightModel>, A, s);
+    }
+    launch_residual_view_sums(A, s);
     return hipGetLastError();
 }
 

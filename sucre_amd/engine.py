@@ -499,6 +499,30 @@ class Restoration:
             else:
                 _lib.check(self.lib.sucre_update_J_fmt(ws, H, W, n, self._fmt, self._sp()))
 
+    def residuals(self):
+        """Per-pixel and per-view residuals of the fit as it stands (``sucre_fit_residuals``): ``(count, ssr, view_stats)`` on
+        the device -- int32 (H,W) observations per pixel over the kept views, float32 (H,W,3) sum of r^2 per channel, float64
+        (n_views,4) per view {observations, sum r^2 R, G, B}, zeros for a view that is not kept -- with
+        r = I - l (J e^(-beta z) + B (1 - e^(-gamma z))) (sucre.py:79-82, 144) at the current parameters and J.  One pass over
+        the dense store, enqueued on the current stream without a host wait; the workspace is only read, so the call may sit
+        anywhere between fits.  Works on a matched and on an imported store."""
+        count = torch.empty((self.H, self.W), dtype=torch.int32, device=self.device)
+        ssr = torch.empty((self.H, self.W, 3), dtype=torch.float32, device=self.device)
+        stats = torch.empty((self.n_views, 4), dtype=torch.float64, device=self.device)
+        nbytes = self.lib.sucre_residual_scratch_bytes(self.H, self.W, self.n_views)
+        if nbytes == 0:
+            raise _lib.SucreError(self.lib.sucre_last_error().decode())
+        # torch's caching allocator keeps the block for this stream until the launches queued here have run
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        ws, H, W, n = self._geom
+        outs = (C.c_void_p(count.data_ptr()), C.c_void_p(ssr.data_ptr()), C.c_void_p(stats.data_ptr()), C.c_void_p(scratch.data_ptr()))
+        with torch.cuda.device(self.device):
+            if self.light or self.float_colour:
+                _lib.check(self.lib.sucre_fit_residuals_ext(ws, C.c_void_p(self.lws.data_ptr()), H, W, n, self._ext_flag, *outs, self._sp()))
+            else:
+                _lib.check(self.lib.sucre_fit_residuals(ws, H, W, n, self._fmt, *outs, self._sp()))
+        return count, ssr, stats
+
     def params(self) -> torch.Tensor:
         """B[3], beta[3], gamma[3] (+ cam2light[6], sigma[4] with the light model) on the device."""
         if self.light or self.float_colour:

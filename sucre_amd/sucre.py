@@ -88,6 +88,15 @@ class SUCRe(torch.nn.Module):
         resto.update_J()
         self.J = resto.J().to(self.B.device)
 
+    @torch.no_grad()
+    def residuals(self, matches_data: loader.MatchesData):
+        """Per-pixel and per-view residuals of this model on ``matches_data`` (``engine.Restoration.residuals``): the
+        module's water (and light) parameters go to the engine first, as in ``update_J``; J is the engine's own.  Returns
+        the device tensors ``(count, ssr, view_stats)``; the Adam state and the step count are left alone."""
+        resto = _restoration_of(matches_data, self)
+        resto.params().copy_(self.water_vector().to(resto.device))
+        return resto.residuals()
+
     def forward(self, u: Tensor, v: Tensor, cP: Tensor) -> Tensor:
         l, z = self.compute_l_z(cP)
         direct = self.J[v, u].T * torch.exp(-self.beta * z)
@@ -298,6 +307,8 @@ def adam(sucre: SUCRe, matches_data: loader.MatchesData, lr: float = 0.05, num_i
             sucre.save_plots(save_dir=save_dir, iteration=done - 1)
             if sucre.use_closed_form and done == num_iter:
                 resto.update_J()   # the final update_J of sucre.py:156, held back for the snapshot
+    if getattr(sucre, '_quality_wanted', False):   # --save-quality: the pass right behind the fit, read with the results
+        sucre._quality = _enqueue_residuals(resto)
     _pull_results(sucre, resto)
     return sucre
 
@@ -319,6 +330,59 @@ def _adam_begin(sucre: SUCRe, matches_data: loader.MatchesData, params0: np.ndar
     return resto
 
 
+# ---- --save-quality: where J can be trusted, and which view hurts the fit -----------------------------------------------
+QUALITY_RMS_FULL_SCALE = 0.25   # RMS residual (intensities are in [0, 1]) that maps to white in <stem>_residual.png
+
+
+def coverage_image(count: np.ndarray, n_kept: int) -> np.ndarray:
+    """8-bit grey: ``255 * count // n_kept`` -- the share of the kept views that observe the pixel."""
+    count = np.asarray(count, np.int64)
+    return np.uint8(255 * count // max(1, int(n_kept)))
+
+
+def residual_image(count: np.ndarray, ssr: np.ndarray) -> np.ndarray:
+    """8-bit grey: ``uint8(255 * min(1, rms / QUALITY_RMS_FULL_SCALE))`` with ``rms = sqrt(sum_c ssr_c / (3 count))``, 0 where
+    the pixel has no observation."""
+    count = np.asarray(count, np.float64)
+    total = np.asarray(ssr, np.float64).sum(axis=-1)
+    rms = np.sqrt(np.divide(total, 3.0 * count, out=np.zeros_like(total), where=count > 0))
+    return np.uint8(255.0 * np.minimum(1.0, rms / QUALITY_RMS_FULL_SCALE))
+
+
+def _enqueue_residuals(resto) -> tuple:
+    """The residual pass on the current stream, no host wait: (count, ssr, view_stats, view_keep) on the device."""
+    return resto.residuals() + (resto.view_keep().clone(),)
+
+
+def _enqueue_quality(job, resto=None) -> None:
+    if getattr(job, 'save_quality', False):
+        job.quality = _enqueue_residuals(resto if resto is not None else _restoration_of(job.matches_data))
+
+
+def _write_quality(job) -> None:
+    """``<stem>_quality.pt``, ``<stem>_coverage.png``, ``<stem>_residual.png`` and one printed line."""
+    count, ssr, stats, keep = job.quality   # host tensors (_restore_finish)
+    stem = Path(job.image.name).stem
+    image_list = getattr(job.matches_data, 'image_list', None)
+    views = [im.name for im in image_list] if image_list else [str(k) for k in range(stats.shape[0])]
+    view_kept = keep != 0
+    view_n = stats[:, 0].round().to(torch.int64)
+    view_ssr = stats[:, 1:].clone()
+    torch.save({'count': count, 'ssr': ssr, 'views': views, 'view_kept': view_kept, 'view_n': view_n, 'view_ssr': view_ssr},
+               job.output_dir / f'{stem}_quality.pt')
+    _save_png(PILImage.fromarray(coverage_image(count.numpy(), int(view_kept.sum()))), job.output_dir / f'{stem}_coverage.png')
+    _save_png(PILImage.fromarray(residual_image(count.numpy(), ssr.numpy())), job.output_dir / f'{stem}_residual.png')
+    n = int(view_n.sum())
+    rms = np.sqrt(view_ssr.sum(dim=0).numpy() / max(1, n))
+    per_view = np.sqrt(view_ssr.sum(dim=1).numpy() / np.maximum(1, 3 * view_n.numpy()))
+    per_view[~(view_kept.numpy() & (view_n.numpy() > 0))] = -1.0
+    line = f'{job.image.name}: residual RMS R {rms[0]:.4f} G {rms[1]:.4f} B {rms[2]:.4f} over {n} observations'
+    if (per_view >= 0).any():
+        worst = int(per_view.argmax())
+        line += f'; worst kept view {views[worst]} (RMS {per_view[worst]:.4f})'
+    print(line)
+
+
 class _Job:
     """One image between ``_restore_submit`` (everything enqueued, nothing waited for) and ``_restore_finish``."""
 
@@ -329,7 +393,7 @@ class _Job:
 def _restore_submit(image: sfm.Image, colmap_model: sfm.COLMAPModel, output_dir: Path, light_model: bool,
                     use_closed_form: bool, min_cover: float, image_list: list[sfm.Image], lr: float, num_iter: int,
                     params_path: Path, force_compute_matches: bool, num_workers: int, device: str,
-                    defer_checks: bool = False) -> _Job:
+                    defer_checks: bool = False, save_quality: bool = False) -> _Job:
     """Stages of sucre.py:160-210 up to and including the enqueued fit; the trace and J stay on the device.
     ``defer_checks``: the integrity verdicts and the observation count stay on the device until ``_restore_finish``
     reads them with the results -- waiting for them here would make the host wait for the matching, which shares the
@@ -375,7 +439,7 @@ def _restore_submit(image: sfm.Image, colmap_model: sfm.COLMAPModel, output_dir:
 
     return _Job(image=image, sucre=sucre, matches_file=matches_file, matches_data=matches_data,
                 matches_path=matches_path, output_dir=output_dir, lr=lr, num_iter=num_iter, trace=None,
-                deferred_checks=defer_checks, params0=params0)
+                deferred_checks=defer_checks, params0=params0, save_quality=bool(save_quality), quality=None)
 
 
 def _report_observations(image: sfm.Image, n_obs: int) -> None:
@@ -389,6 +453,7 @@ def _restore_enqueue_fit(job: _Job) -> None:
     print(f'Solve least squares with Adam optimizer ({job.num_iter} iterations).')
     resto = _adam_begin(job.sucre, job.matches_data, params0=job.params0)
     job.trace = resto.fit(job.num_iter, lr=job.lr, use_closed_form=job.sucre.use_closed_form)
+    _enqueue_quality(job, resto)
 
 
 def _restore_enqueue_fits(jobs: list) -> None:
@@ -414,9 +479,11 @@ def _restore_enqueue_fits(jobs: list) -> None:
         traces = engine.fit_batch([j.resto for j in members], key[3], lr=key[4], use_closed_form=key[5])
         for j, t in zip(members, traces):
             j.trace = t
+            _enqueue_quality(j, j.resto)
     for job in singles:
         print(f'Solve least squares with Adam optimizer ({job.num_iter} iterations).')
         job.trace = job.resto.fit(job.num_iter, lr=job.lr, use_closed_form=job.sucre.use_closed_form)
+        _enqueue_quality(job, job.resto)
 
 
 def fit_batch_size(images: list, light_model: bool = False, in_flight: int = 2, n_views: int | None = None, device='cuda') -> int:
@@ -460,6 +527,8 @@ def _restore_finish(job: _Job, keep_matches: bool, writers: ThreadPoolExecutor |
         if writers is None:
             _log_trace(job.trace, 0)
         _pull_results(sucre, _restoration_of(job.matches_data))
+    if job.quality is not None:
+        job.quality = tuple(t.cpu() for t in job.quality)
     if keep_matches and job.matches_file.restoration._views_dev is not None:   # freshly matched (not loaded from this
         print(f'Keep {job.matches_file.save()}.')                              # very file); needs the live workspace
     if writers is None:
@@ -475,6 +544,8 @@ def _write_outputs(job: _Job, keep_matches: bool, log: bool = False) -> None:
     if log and job.trace is not None:   # formatted off the main thread, printed as one block
         print(f'{job.image.name}:\n' + _format_trace(job.trace, 0))
     sucre.save_plots(save_dir=job.output_dir)
+    if job.quality is not None:
+        _write_quality(job)
     torch.save({**sucre.cpu().state_dict(), 'J': sucre.J.detach().cpu()},
                (job.output_dir / job.image.name).with_suffix('.pt'))
     if not keep_matches and job.matches_path.exists():
@@ -489,11 +560,21 @@ def restore_image(image: sfm.Image, colmap_model: sfm.COLMAPModel, output_dir: P
                   num_workers: int = 0, device: str = 'cpu'):
     """Per-image pipeline (sucre.py:160-219): match -> prepare -> check -> load -> fit -> save.  The signature is the
     reference's, default ``device='cpu'`` included -- which this engine refuses (``sfm.require_gpu``): pass a GPU."""
+    return _restore_one(image, colmap_model, output_dir, light_model, use_closed_form, min_cover, image_list, lr, num_iter,
+                        batch_size, save_interval, params_path, force_compute_matches, keep_matches, num_workers, device)
+
+
+def _restore_one(image, colmap_model, output_dir, light_model, use_closed_form, min_cover, image_list, lr, num_iter, batch_size,
+                 save_interval, params_path, force_compute_matches, keep_matches, num_workers, device, save_quality: bool = False):
+    """``restore_image`` plus what its pinned signature has no room for (``save_quality``: --save-quality)."""
     sfm.require_gpu(device, 'restore_image')
     job = _restore_submit(image, colmap_model, output_dir, light_model, use_closed_form, min_cover, image_list, lr,
-                          num_iter, params_path, force_compute_matches, num_workers, device)
+                          num_iter, params_path, force_compute_matches, num_workers, device, save_quality=save_quality)
+    if save_quality:
+        job.sucre._quality_wanted = True   # adam enqueues the pass behind its last fit
     adam(sucre=job.sucre, matches_data=job.matches_data, lr=lr, num_iter=num_iter, batch_size=batch_size,
          save_dir=job.output_dir, save_interval=save_interval, device=device)
+    job.quality = job.sucre.__dict__.pop('_quality', None)
     return _restore_finish(job, keep_matches)
 
 
@@ -616,14 +697,20 @@ def parse_args(args: argparse.Namespace):
 def _run_request(args, images, image_list, colmap_model, device, survey: bool, in_flight: int) -> None:
     if str(device).startswith('cuda') and images:   # start decoding + uploading the scene now, in the background
         loader.prefetch_for_targets(images, image_list, device, num_workers=args.num_workers, min_cover=args.min_cover)
+    quality = {'save_quality': True} if getattr(args, 'save_quality', False) else {}
     if survey:
         restore_images(images, colmap_model, args.output_dir, in_flight=in_flight, keep_matches=args.keep_matches,
                        device=device, light_model=args.light_model, use_closed_form=args.use_closed_form,
                        min_cover=args.min_cover, image_list=image_list, lr=args.learning_rate, num_iter=args.num_iter,
                        params_path=args.params_path, force_compute_matches=args.force_compute_matches,
-                       num_workers=args.num_workers)
+                       num_workers=args.num_workers, **quality)
         return
     for image in images:
+        if quality:
+            _restore_one(image, colmap_model, args.output_dir, args.light_model, args.use_closed_form, args.min_cover, image_list,
+                         args.learning_rate, args.num_iter, args.batch_size, args.save_interval, args.params_path,
+                         args.force_compute_matches, args.keep_matches, args.num_workers, device, save_quality=True)
+            continue
         restore_image(image=image, colmap_model=colmap_model, output_dir=args.output_dir,
                       light_model=args.light_model, use_closed_form=args.use_closed_form, min_cover=args.min_cover,
                       image_list=image_list, lr=args.learning_rate, num_iter=args.num_iter,
@@ -677,7 +764,8 @@ def restore_shared_water(images: list, colmap_model: sfm.COLMAPModel, args, imag
         with engine.slot_lane(k):   # every image in its own workspace
             jobs.append(_restore_submit(image, colmap_model, args.output_dir, args.light_model, args.use_closed_form,
                                         args.min_cover, image_list, args.learning_rate, args.num_iter, args.params_path,
-                                        args.force_compute_matches, args.num_workers, device))
+                                        args.force_compute_matches, args.num_workers, device,
+                                        save_quality=bool(getattr(args, 'save_quality', False))))
     restos = [_adam_begin(j.sucre, j.matches_data, params0=jobs[0].params0) for j in jobs]
     T = int(args.num_iter)
     trace = torch.zeros((T, 20 if args.light_model else 10), dtype=torch.float64, device=restos[0].device)
@@ -685,6 +773,8 @@ def restore_shared_water(images: list, colmap_model: sfm.COLMAPModel, args, imag
     group = engine.HipWaterGroup(restos, lr=args.learning_rate, use_closed_form=args.use_closed_form, trace=trace,
                                  params0=jobs[0].params0)
     sdist.fit_shared_water(group, T)
+    for job, resto in zip(jobs, restos):   # --save-quality: behind the group's finish, per image, before anything is read
+        _enqueue_quality(job, resto)
     trace = trace.cpu().numpy()
     _log_trace(trace, 0)
     for job, resto in zip(jobs, restos):
@@ -696,9 +786,31 @@ def restore_shared_water(images: list, colmap_model: sfm.COLMAPModel, args, imag
         torch.save({**shared, 'trace': torch.from_numpy(trace), 'images': list(request)}, Path(args.output_dir) / 'shared_water.pt')
 
 
+class _Parser(argparse.ArgumentParser):
+    """The reference's parser plus ``extras``: flags of this engine's own that stay out of the reference-pinned table of
+    actions and defaults (tests/test_shared_water_cli.py lists it action by action).  They are parsed first, from the same
+    command line, and whatever they set is added to the namespace; absent, they leave no trace in it."""
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.extras = argparse.ArgumentParser(add_help=False, allow_abbrev=False, formatter_class=self.formatter_class,
+                                              usage=argparse.SUPPRESS)
+
+    def parse_known_args(self, args=None, namespace=None):
+        own, rest = self.extras.parse_known_args(args)
+        namespace, rest = super().parse_known_args(rest, namespace)
+        for k, v in vars(own).items():
+            setattr(namespace, k, v)
+        return namespace, rest
+
+    def format_help(self):
+        own = self.extras.format_help()
+        return super().format_help() + '\nfurther outputs:\n' + own[own.index('  --'):]
+
+
 def build_parser() -> argparse.ArgumentParser:
     """Same flags, defaults and exclusivity group as the reference CLI (sucre.py:264-305)."""
-    p = argparse.ArgumentParser(description='SUCRe (MI355X engine).', formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p = _Parser(description='SUCRe (MI355X engine).', formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument('--image-dir', required=True, type=Path, help='directory holding the colour images')
     p.add_argument('--depth-dir', required=True, type=Path, help='directory holding the depth_<stem>.png maps')
     p.add_argument('--model-dir', required=True, type=Path, help='undistorted COLMAP model (cameras/images .bin or .txt)')
@@ -731,6 +843,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--shared-water', action='store_true', default=argparse.SUPPRESS,
                    help='fit all images of the request jointly: one B, beta, gamma (and, with --light-model, one cam2light, '
                         'sigma) for all of them, a J per image; also writes shared_water.pt')
+    p.extras.add_argument('--save-quality', action='store_true', default=argparse.SUPPRESS,
+                          help='also write, per image, <stem>_quality.pt (observations and squared residuals of the fit per pixel and '
+                        'per neighbour view), <stem>_coverage.png and <stem>_residual.png, and print the RMS residual and the '
+                        'worst-fitting view')
     return p
 
 
