@@ -20,6 +20,9 @@
  *   - All state of one restoration lives in ONE caller-allocated workspace of sucre_workspace_bytes() bytes,
  *     256-byte aligned.  Its internal layout (observation store, Adam state, ...) is private; the few regions a
  *     host needs to read back are located with sucre_ws_offset().
+ *   - A workspace, an extension workspace (`lws`), a group buffer, a batch table and a scratch buffer may hold anything when
+ *     they are handed in -- the library clears nothing wholesale, every region is written by the call that owns it before
+ *     another reads it -- and the same bytes may be laid out again for another `n_views` (or mode) between images.
  *
  * Data layout in HBM: the target image is cut into 16x16-pixel tiles.  Matching writes,
  * for every (tile, view) pair, one 1792-byte chunk = 256 float32 ranges z=||cP|| (0 = no observation) + 256 x 3

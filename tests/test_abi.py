@@ -52,6 +52,25 @@ def test_geometry_queries_and_errors():
     assert lib.sucre_ws_offset(1080, 1920, 65, 99) < 0 and b'unknown workspace region' in lib.sucre_last_error()
 
 
+@pytest.mark.parametrize('H,W', [(52, 75), (32, 48), (48, 80), (1, 1), (250, 272), (1080, 1920)])
+def test_buffer_sizes_never_shrink_with_the_view_count(H, W):
+    """A buffer sized for a capacity holds every layout of fewer views (engine.acquire_restoration rounds the view count up and
+    lays the same bytes out again for each target's own count): all four size queries are non-decreasing in n_views, across
+    both capacity steps (8 below 256 views, 32 above) and the 255-view switch of the compaction's path."""
+    lib = _lib.load()
+    queries = {
+        'sucre_workspace_bytes': lambda n: lib.sucre_workspace_bytes(H, W, n),
+        'sucre_light_workspace_bytes': lambda n: lib.sucre_light_workspace_bytes(H, W, n),
+        'sucre_light_workspace_bytes_ext(POINTS_COLOUR)': lambda n: lib.sucre_light_workspace_bytes_ext(H, W, n, _lib.EXT_POINTS_COLOUR),
+        'sucre_residual_scratch_bytes': lambda n: lib.sucre_residual_scratch_bytes(H, W, n),
+    }
+    for name, q in queries.items():
+        sizes = [q(n) for n in range(1, 330)]
+        assert sizes[0] > 0, name
+        shrinks = [(n + 1, a, b) for n, (a, b) in enumerate(zip(sizes, sizes[1:]), 1) if b < a]
+        assert not shrinks, (name, H, W, shrinks[:3])
+
+
 def test_argument_validation_happens_before_any_launch():
     """NULL / misaligned / out-of-range arguments are rejected on the host (no GPU needed to see that)."""
     lib = _lib.load()

@@ -143,6 +143,16 @@ def test_plain_71_views(scene71):
     assert kept.all() and count.max() > 64
 
 
+def test_plain_more_tiles_than_threads_of_the_view_sums():
+    """272 x 250 pixels = 17 x 16 = 272 tiles: residual_view_sum_kernel's threads take tiles t, t + 256, ... -- sixteen of them go
+    round twice --, and the scratch index view * n_tiles + tile runs past 256 tiles per view."""
+    scene = synth.make_scene(272, 250, 3, seed=4)
+    r = fitted(scene, 5)
+    assert (scene.width + 15) // 16 * ((scene.height + 15) // 16) == 272
+    count, _, stats, (rc, _, _, kept) = check_against_reference('plain 272x250 x 4 views, 272 tiles', r, scene_observations(scene))
+    assert kept.all() and (rc == 0).sum() > 0
+
+
 # ---- 2. the sum of the residuals is the next logged cost --------------------------------------------------------------------
 @pytest.mark.parametrize('light', [False, True], ids=['plain', 'light'])
 def test_sum_equals_the_next_logged_cost(scene75, light):
