@@ -465,9 +465,13 @@ class Restoration:
             eps: float = 1e-8, record_trace: bool = True, keep_J: bool = False) -> torch.Tensor | None:
         """Enqueues ``num_iter`` Adam iterations without any host sync; returns the (num_iter,10) float64
         device trace (cost, B, beta, gamma per iteration) or None.  In closed-form mode the C ABI appends the
-        final ``update_J`` of sucre.py:156 to a ``sucre_fit_run`` call (idempotent, so a fit split into several
-        calls ends in the same state) unless ``keep_J``: then J stays the J(theta_k) the last iteration k solved,
-        next to theta_{k+1} -- what the reference holds when it plots at a --save-interval stop (sucre.py:141,153)."""
+        final ``update_J`` of sucre.py:156 to a ``sucre_fit_run`` call unless ``keep_J``: then J stays the J(theta_k)
+        the last iteration k solved, next to theta_{k+1} -- what the reference holds when it plots at a --save-interval
+        stop (sucre.py:141,153).  A fit split into several calls: with ``keep_J`` in every call and one ``update_J()``
+        behind the last, the launches are those of the unsplit fit and so are the bits.  Without it the appended
+        ``update_J`` leaves J(theta_{k+1}) where the unsplit fit has J(theta_k); the light-model kernel re-solves J from
+        zero and does not notice, the plain one-pass kernel (fit.hip, AccOne) measures its sums from the J it finds, so
+        the split fit ends in the same state up to rounding only (tests/test_gpu_snapshots.py)."""
         ext = self.light or self.float_colour
         width = 20 if ext else 10
         trace = torch.zeros((num_iter, width), dtype=torch.float64, device=self.device) if record_trace else None

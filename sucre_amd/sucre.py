@@ -280,6 +280,18 @@ def _log_trace(trace: np.ndarray, first_iteration: int) -> None:
     print(_format_trace(trace, first_iteration))
 
 
+def snapshot_stops(num_iter: int, save_interval: int | None) -> list[tuple[int, bool]]:
+    """Where ``adam`` cuts its ``num_iter`` iterations into engine calls: ``(stop, snapshot)`` pairs in ascending order, a call
+    running the iterations from the previous stop (0 at first) up to ``stop``, exclusive, and ``snapshot`` telling whether the
+    plots are saved behind it.  The reference saves them after iteration i when ``i % save_interval == 0`` (sucre.py:153), so
+    every such i < num_iter ends a call (stop = i + 1); the last pair always ends at ``num_iter``.  ``save_interval`` None: one
+    call, no snapshot."""
+    if save_interval is None:
+        return [(num_iter, False)]
+    stops = sorted({k + 1 for k in range(0, num_iter, save_interval)} | {num_iter})
+    return [(stop, stop >= 1 and (stop - 1) % save_interval == 0) for stop in stops]
+
+
 def adam(sucre: SUCRe, matches_data: loader.MatchesData, lr: float = 0.05, num_iter: int = 200, batch_size: int = 1,
          save_dir: Path = None, save_interval: int = None, device: str = 'cpu', verbose: bool = True) -> SUCRe:
     """``num_iter`` steps of ``torch.optim.Adam(lr)`` on the least-squares cost (sucre.py:124-157).
@@ -288,13 +300,8 @@ def adam(sucre: SUCRe, matches_data: loader.MatchesData, lr: float = 0.05, num_i
     what the reference's accumulated mini-batch gradients add up to."""
     print(f'Solve least squares with Adam optimizer ({num_iter} iterations).')
     resto = _adam_begin(sucre, matches_data)
-    if save_dir is not None and save_interval is not None:
-        stops = sorted({min(k + 1, num_iter) for k in range(0, num_iter, save_interval)} | {num_iter})
-    else:
-        stops = [num_iter]
     done = 0
-    for stop in stops:
-        snapshot = save_dir is not None and save_interval is not None and (stop - 1) % save_interval == 0
+    for stop, snapshot in snapshot_stops(num_iter, save_interval if save_dir is not None else None):
         if stop > done:
             # at a snapshot stop closed-form J stays J(theta_k) of the last iteration k: the pair
             # (J(theta_k), theta_{k+1}) is what the reference plots (sucre.py:141,153-154)

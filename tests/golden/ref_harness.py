@@ -1,7 +1,7 @@
 """Drive the *real* reference (clementinboittiaux/sucre, mounted read-only at /root/reference) on synthetic
 scenes.  Only usable in the dev container: the reference never travels to the GPU box, so this module is
 imported exclusively by the fixture generators next to it (``gen_golden.py``, ``gen_golden_extras.py``,
-``gen_golden_baseline.py``) and by ``tools/time_reference.py`` (the CPU-baseline calibration); no test imports it.
+``gen_golden_baseline.py``, ``gen_golden_snapshots.py``) and by ``tools/time_reference.py`` (the CPU-baseline calibration); no test imports it.
 
 The reference's hot path imports fine once its three I/O-only dependencies (cv2, h5py, pycolmap — all absent
 here and never called by the functions we exercise) are registered as empty modules.  Synthetic pixels are
@@ -102,16 +102,24 @@ def reference_matches(scene, min_cover: float = 1e-6):
 
 
 def reference_fit(scene, matches_data, target, num_iter: int, use_closed_form: bool = False,
-                  light_model: bool = False, batch_size: int = 5, lr: float = 0.05, snapshots=()):
+                  light_model: bool = False, batch_size: int = 5, lr: float = 0.05, snapshots=(),
+                  save_dir: Path | None = None, save_interval: int | None = None):
     """Runs sucre.adam (sucre.py:124-157) and records the exact per-iteration trace through public hooks.
 
-    trace[i] = (cost_i, B, beta, gamma *after* step i).  ``snapshots`` = iteration counts after which J is
-    captured (J-parameter mode only).
+    trace[i] = (cost_i, B, beta, gamma *after* step i).  ``snapshots`` = iteration counts n after whose n-th step the J
+    the module holds is captured, in every mode: with J as a parameter that is J after n steps; in closed form it is the
+    J(theta_{n-1}) the n-th iteration solved before its step (sucre.py:141), next to theta_n.
+
+    ``save_dir`` / ``save_interval``: handed to sucre.adam, which then calls ``save_plots`` after every iteration i with
+    ``i % save_interval == 0`` (sucre.py:153-154).  ``save_plots`` is wrapped to record, per such stop,
+    ``stops[i] = dict(J, params, files)``: the J and the parameters (all 19 with the light model) the module holds while it
+    plots, and the 8-bit arrays of the PNG files that call wrote, by file name.
     """
     _, loader, _, sucre_mod = import_reference()
     model = sucre_mod.SUCRe(image=target, light_model=light_model, use_closed_form=use_closed_form)
     trace = []
     snaps = {}
+    stops = {}
     state = dict(cost=0.0, batches=None, bi=0, it=0)
 
     batches_I = [I for (_, _, _, I) in matches_data.iter(batch_size=batch_size)]
@@ -132,19 +140,36 @@ def reference_fit(scene, matches_data, target, num_iter: int, use_closed_form: b
                     [float(x) for x in model.sigma.detach().flatten()]
         trace.append(row + extra)
         state['cost'] = 0.0
-        if state['it'] in snapshots and not use_closed_form:
+        if state['it'] in snapshots:
             snaps[state['it']] = model.J.detach().clone().numpy()
+
+    def all_params():
+        parts = [model.B, model.beta, model.gamma] + ([model.cam2light, model.sigma] if light_model else [])
+        return np.concatenate([p.detach().numpy().ravel() for p in parts]).astype(np.float32)
+
+    if save_dir is not None:
+        from PIL import Image as PILImage
+        save_plots = model.save_plots
+
+        def recording_save_plots(save_dir, iteration=None):
+            before = {f.name for f in Path(save_dir).iterdir()}
+            save_plots(save_dir=save_dir, iteration=iteration)
+            written = sorted(f.name for f in Path(save_dir).iterdir() if f.name not in before)
+            stops[iteration] = dict(J=model.J.detach().clone().numpy(), params=all_params(),
+                                    files={n: np.asarray(PILImage.open(Path(save_dir) / n)).copy() for n in written})
+        model.save_plots = recording_save_plots
 
     h1 = model.register_forward_hook(fwd_hook)
     from torch.optim.optimizer import register_optimizer_step_post_hook
     h2 = register_optimizer_step_post_hook(step_hook)
     try:
-        sucre_mod.adam(model, matches_data, lr=lr, num_iter=num_iter, batch_size=batch_size, device='cpu')
+        sucre_mod.adam(model, matches_data, lr=lr, num_iter=num_iter, batch_size=batch_size, device='cpu',
+                       save_dir=save_dir, save_interval=save_interval)
     finally:
         h1.remove()
         h2.remove()
     J = model.J.detach().numpy().copy()
-    return dict(J=J, trace=np.asarray(trace, dtype=np.float64), snaps=snaps, model=model)
+    return dict(J=J, trace=np.asarray(trace, dtype=np.float64), snaps=snaps, stops=stops, params=all_params(), model=model)
 
 
 def reference_shared_water(scenes, num_iter: int, batch_size: int = 5, lr: float = 0.05, use_closed_form: bool = False):

@@ -101,6 +101,67 @@ def load_fixture(name: str) -> Fixture:
     return _FIXTURES[name]
 
 
+# ---- what the reference holds and plots at its --save-interval stops (tests/golden/gen_golden_snapshots.py) ---------------
+
+SNAPSHOT_MODES = {'param': (False, False), 'closed': (True, False), 'light': (False, True), 'light_closed': (True, True)}
+
+
+class Snapshots:
+    """The reference's ``sucre.adam(num_iter=9, save_dir=..., save_interval=4)`` on the scene of ``Fixture(name)``, per mode of
+    SNAPSHOT_MODES (mode -> (use_closed_form, light_model)): the state it held at every stop, the pictures it wrote there,
+    what it returned and its trace.  At stop k it holds theta_{k+1}, next to J after k+1 steps (J as a parameter) or
+    J(theta_k) (closed form: sucre.py:141 solves J before the step, sucre.py:153 plots after it)."""
+
+    def __init__(self, name: str):
+        self.name = name
+        self.z = np.load(GOLDEN_DIR / f'snapshots_{name}.npz')
+        self.pictures = np.load(GOLDEN_DIR / f'snapshots_{name}_pictures.npz')
+        self.stops = [int(k) for k in self.z['stops']]
+        self.num_iter, self.save_interval = int(self.z['num_iter']), int(self.z['save_interval'])
+
+    def J(self, mode: str, k: int) -> np.ndarray:
+        return self.z[f'{mode}_stop{k}_J']
+
+    def params(self, mode: str, k: int) -> np.ndarray:
+        return self.z[f'{mode}_stop{k}_params']
+
+    def rms_to_next(self, mode: str, k: int) -> np.ndarray:
+        """Closed form: per-channel RMS between the stop's J(theta_k) and the reference's J(theta_{k+1})."""
+        return self.z[f'{mode}_stop{k}_rms_to_next']
+
+    def picture(self, mode: str, k: int, kind: str) -> np.ndarray:
+        """``kind``: rgb, reconstruction or (light model) vignetting -- the (H,W,3) uint8 array of the PNG of stop k."""
+        return self.pictures[f'{mode}_stop{k}_{kind}']
+
+    def files(self, mode: str) -> list:
+        return [str(n) for n in self.z[f'{mode}_files']]
+
+    def trace(self, mode: str) -> np.ndarray:
+        return self.z[f'{mode}_trace']
+
+    def final(self, mode: str):
+        """(J, parameters) ``sucre.adam`` returned.  With J as a parameter that J is the last stop's (the generator checked it)."""
+        closed, _ = SNAPSHOT_MODES[mode]
+        J = self.z[f'{mode}_J_final'] if closed else self.J(mode, self.num_iter - 1)
+        return J, self.z[f'{mode}_params_final']
+
+
+_SNAPSHOTS = {}
+
+
+def load_snapshots(name: str) -> Snapshots:
+    if name not in _SNAPSHOTS:
+        _SNAPSHOTS[name] = Snapshots(name)
+    return _SNAPSHOTS[name]
+
+
+def picture_distance(got, ref):
+    """(share of the 8-bit values that differ, largest difference in levels) of two pictures of one shape."""
+    got, ref = np.asarray(got).astype(np.int16), np.asarray(ref).astype(np.int16)
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    return float((got != ref).mean()), int(np.abs(got - ref).max())
+
+
 # ---- closed-form "knee" scenes (tests/golden/gen_golden_extras.py) --------------------------------------------------------
 
 KNEE_FIXTURES = ['knee_190x51_n1', 'knee_215x74_n1', 'knee_225x87_n1', 'knee_115x67_n5']

@@ -5,6 +5,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 import torch
+from PIL import Image as PILImage
 
 import helpers
 from oracle import oracle
@@ -70,6 +71,15 @@ def test_cli_end_to_end(disk_scene, tmp_path, capsys):
     tgt = loaded.views[loaded.target]
     J0 = oracle.init_J(tgt.rgb_u8.numpy(), tgt.depth_f32().numpy())
     Jo, po, to = oracle.fit(64, 96, samples, J0, num_iter=30)
+    # the snapshot after iteration 20 shows J after 21 steps (sucre.py:148, 153): the picture of the oracle's 21-iteration J,
+    # at the picture bar of tests/test_gpu_snapshots.py (at most 1e-2 of the values differ, by at most one level)
+    J21 = oracle.fit(64, 96, samples, J0, num_iter=21)[0]
+    shown = sucre.SUCRe(helpers.synth_image(1, tgt, loaded.K, 96, 64))
+    with torch.no_grad():
+        shown.J.copy_(torch.tensor(J21))
+    share, step = helpers.picture_distance(PILImage.open(tmp_path / f'{stem}_rgb_0020.png'), shown.plot_J())
+    print(f'_rgb_0020.png vs plot_J of the oracle after 21 iterations: {share:.1e} of the values differ, by at most {step}')
+    assert share <= 1e-2 and step <= 1, (share, step)
     J = state['J'].numpy()
     assert np.array_equal(np.isnan(J), np.isnan(Jo))
     assert helpers.rms_per_channel(J, Jo).max() < 1e-5
@@ -253,6 +263,32 @@ def test_survey_of_images_reuses_one_workspace():
         assert helpers.rms_per_channel(J, Jo).max() < 1e-5
         assert np.abs(trace.cpu().numpy()[:, 1:] - to[:, 1:]).max() < 1e-5
     assert engine.acquire_restoration(48, 80, 5, 'cuda') is resto
+
+
+@pytest.mark.parametrize('light', [False, True], ids=['plain', 'light-model'])
+def test_cli_closed_form_snapshots_change_nothing_but_the_files(disk_scene, tmp_path, light):
+    """--use-closed-form --save-interval 4 --num-iter 9 (the last iteration is a snapshot: the final update_J is held back for
+    it), without and with --light-model: the run writes the snapshot set of the reference's rule (after iteration i when
+    i % 4 == 0, sucre.py:153; ``_vignetting_*`` only with the light model) next to the final pictures, and its .pt is, bit for
+    bit, the .pt of the same command without --save-interval."""
+    root, scene, model, loaded = disk_scene
+    name = scene.names[scene.target]
+    stem = Path(name).stem
+    flags = ['--image-name', name, '--use-closed-form', '--num-iter', 9] + (['--light-model'] if light else [])
+    (tmp_path / 'snap').mkdir(); (tmp_path / 'plain').mkdir()
+    _cli(root, tmp_path / 'snap', *flags, '--save-interval', 4)
+    _cli(root, tmp_path / 'plain', *flags)
+    kinds = ['rgb', 'reconstruction'] + (['vignetting'] if light else [])
+    final = {f'{stem}_{kind}.png' for kind in kinds}
+    snapshots = {f'{stem}_{kind}_{i:04d}.png' for kind in kinds for i in range(9) if i % 4 == 0}
+    assert {f.name for f in (tmp_path / 'snap').glob('*.png')} == final | snapshots
+    assert {f.name for f in (tmp_path / 'plain').glob('*.png')} == final
+    a, b = torch.load(tmp_path / 'snap' / f'{stem}.pt'), torch.load(tmp_path / 'plain' / f'{stem}.pt')
+    assert set(a) == set(b) == {'B', 'beta', 'gamma', 'J'} | ({'cam2light', 'sigma'} if light else set())
+    for key in a:
+        assert a[key].dtype == b[key].dtype and np.array_equal(a[key].numpy(), b[key].numpy(), equal_nan=True), key
+    for f in final:   # and so are the final pictures
+        assert np.array_equal(np.asarray(PILImage.open(tmp_path / 'snap' / f)), np.asarray(PILImage.open(tmp_path / 'plain' / f))), f
 
 
 def test_cli_light_model(disk_scene, tmp_path, capsys):
