@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define SUCRE_ABI_VERSION 1
+#define SUCRE_ABI_VERSION 2
 
 /* error codes */
 #define SUCRE_OK 0
@@ -398,6 +398,45 @@ int sucre_fit_residuals(const void *ws, int H, int W, int n_views, int obs_forma
                         double *view_stats_dev, void *scratch_dev, void *stream);
 int sucre_fit_residuals_ext(const void *ws, const void *lws, int H, int W, int n_views, unsigned flags /* 0 | SUCRE_FIT_EXT_COLOUR | SUCRE_FIT_EXT_BOTH */,
                             int32_t *count_dev, float *ssr_dev, double *view_stats_dev, void *scratch_dev, void *stream);
+
+/*
+ * ---- outlier-trimmed refit: sigma-clip observations out of the dense store -------------------------------------------------
+ * The fit is a least-squares mean over every view that sees a pixel, so one fish or diver in one view is averaged into J.  These
+ * calls drop the offending OBSERVATIONS (not whole views, as a --filter-images-path list does) from the dense store of a matched
+ * (or imported), finalised and fitted workspace.  One round, for a multiple k_sigma > 0:
+ *  1 Scale.  view_stats_dev is the table sucre_fit_residuals* has just left (the caller runs that pass; it is only read).  Over
+ *    the KEPT views, in view order, in float64: N = sum view_stats[v][0], S_c = sum view_stats[v][1+c]; per channel
+ *    tau^2_c = float32(k_sigma^2 S_c / N), formed on the device.  N = 0: nothing is dropped (tau^2 = +inf).
+ *  2 Decision.  For every stored observation (match count > 0, z > 0) of every kept view the residual r_c of sucre.adam's
+ *    objective (sucre.py:144) is evaluated exactly as sucre_fit_residuals* evaluates it -- one device function serves both: the
+ *    SUCRE_OBS_U16MM range, float32 colours, the light model's l, z from the parameters as they stand with the stored range.
+ *    The observation is an OUTLIER iff r_c^2 > tau^2_c for any channel, compared in float32; a NaN compares false and stays.
+ *  3 Guard.  A pixel whose observations over the kept views would all be outliers keeps all of them.
+ *  4 Drop.  A dropped observation's range in the dense store becomes 0; colours and extension planes stay as they are, behind
+ *    z > 0.  For every (tile, kept view) pair the match count, the four pixel-bit words and the range pair end up as a recount
+ *    of the chunk would leave them (sucre_import_view's last step), the neutral pair where nothing is left.  Views that are
+ *    not kept keep their observations, counts and bits; their range pairs are restated as their chunks' own (a matched store
+ *    keeps the ranges of several views in the pair of one of them, through which a dropped range could stay in the span).
+ *  5 Outputs, on the device, every sum in a fixed order without atomics (two calls give the same bits):
+ *      dropped_dev       int32   (H,W)      observations dropped from the pixel
+ *      view_dropped_dev  int64   (n_views)  observations dropped from the view (0 for a view that is not kept)
+ *      thresholds_dev    float32 [3]        tau^2_c
+ *  6 Re-finalise.  The CALLER then runs sucre_finalize_matches_fmt / _ext with the min_cover and format of the first time: view
+ *    totals, the min_cover rule (a view that falls below it drops out, as in a plain run on the survivors), n_obs, the range
+ *    span, the store format, the compaction and the plans are redone; then sucre_fit_init* and the fit start over, and the
+ *    result is bit for bit that of a plain run on a store into which only the survivors were imported.  sucre_match_map is
+ *    geometry and keeps returning the untrimmed matches.
+ * Nothing in 1-6 waits on the host.  scratch_dev: sucre_trim_scratch_bytes() bytes of caller-owned device memory, 16-byte
+ * aligned, untouched until the launches have run.  obs_format / flags: as for sucre_fit_residuals / sucre_fit_residuals_ext.
+ * Arguments are checked before anything is launched: k_sigma not finite or <= 0, NULL or misaligned pointers and a bad geometry
+ * give SUCRE_ERR_ARG.
+ */
+size_t sucre_trim_scratch_bytes(int H, int W, int n_views);
+int sucre_trim_outliers(void *ws, int H, int W, int n_views, int obs_format, double k_sigma, const double *view_stats_dev,
+                        int32_t *dropped_dev, int64_t *view_dropped_dev, float *thresholds_dev, void *scratch_dev, void *stream);
+int sucre_trim_outliers_ext(void *ws, const void *lws, int H, int W, int n_views, unsigned flags /* 0 | SUCRE_FIT_EXT_COLOUR | SUCRE_FIT_EXT_BOTH */,
+                            double k_sigma, const double *view_stats_dev, int32_t *dropped_dev, int64_t *view_dropped_dev,
+                            float *thresholds_dev, void *scratch_dev, void *stream);
 
 /*
  * Shared water AND light over several light-model images (the group above for the 19-parameter model; sucre.py:54-61 with

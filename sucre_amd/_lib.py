@@ -9,7 +9,7 @@ import ctypes as C
 import os
 from pathlib import Path
 
-ABI_VERSION = 1
+ABI_VERSION = 2
 # SUCRE_HIP_LIB selects another build of the same ABI (experiment builds, tools/exp/build_variants.sh); default = the product
 LIB_PATH = Path(os.environ.get('SUCRE_HIP_LIB', Path(__file__).resolve().parent / 'libsucre_hip.so'))
 
@@ -98,6 +98,9 @@ SIGNATURES = {
     'sucre_residual_scratch_bytes': (C.c_size_t, [_i, _i, _i]),
     'sucre_fit_residuals': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'sucre_fit_residuals_ext': (_i, [_vp, _vp, _i, _i, _i, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
+    'sucre_trim_scratch_bytes': (C.c_size_t, [_i, _i, _i]),
+    'sucre_trim_outliers': (_i, [_vp, _i, _i, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sucre_trim_outliers_ext': (_i, [_vp, _vp, _i, _i, _i, C.c_uint, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
     'sucre_light_group_bytes': (C.c_size_t, [_i]),
     'sucre_light_group_sums_offset': (C.c_int64, []),
     'sucre_light_group_init': (_i, [_vp, _i, C.POINTER(LightGroupImage), C.POINTER(C.c_float), _vp]),

@@ -609,6 +609,60 @@ int sucre_fit_residuals_ext(const void *ws, const void *lws, int H, int W, int n
                      "sucre_fit_residuals_ext");
 }
 
+/* ---- outlier-trimmed refit: sigma-clip observations out of the dense store ---------------------------------------------- */
+
+size_t sucre_trim_scratch_bytes(int H, int W, int n_views) {
+    Layout L;
+    if (!make_layout(H, W, n_views, &L)) {
+        fail(SUCRE_ERR_ARG, "invalid geometry H=%d W=%d n_views=%d", H, W, n_views);
+        return 0;
+    }
+    return trim_scratch_bytes(L);
+}
+
+}  // extern "C"
+
+namespace sucre {
+static int check_trim_args(double k_sigma, const double *view_stats_dev, const int32_t *dropped_dev, const int64_t *view_dropped_dev,
+                           const float *thresholds_dev, const void *scratch_dev) {
+    if (!std::isfinite(k_sigma) || !(k_sigma > 0.0)) return fail(SUCRE_ERR_ARG, "k_sigma must be finite and > 0 (got %g)", k_sigma);
+    if (!view_stats_dev || !dropped_dev || !view_dropped_dev || !thresholds_dev || !scratch_dev)
+        return fail(SUCRE_ERR_ARG, "view_stats_dev / dropped_dev / view_dropped_dev / thresholds_dev / scratch_dev is NULL");
+    if (!aligned(view_stats_dev, 8) || !aligned(dropped_dev, 4) || !aligned(view_dropped_dev, 8) || !aligned(thresholds_dev, 4))
+        return fail(SUCRE_ERR_ARG, "view_stats_dev / dropped_dev / view_dropped_dev / thresholds_dev must be 8 / 4 / 8 / 4-byte aligned");
+    if (!aligned(scratch_dev, 16)) return fail(SUCRE_ERR_ARG, "scratch_dev must be 16-byte aligned");
+    return SUCRE_OK;
+}
+}  // namespace sucre
+
+extern "C" {
+
+int sucre_trim_outliers(void *ws, int H, int W, int n_views, int obs_format, double k_sigma, const double *view_stats_dev,
+                        int32_t *dropped_dev, int64_t *view_dropped_dev, float *thresholds_dev, void *scratch_dev, void *stream) {
+    Layout L;
+    if (int rc = check_ws(ws, H, W, n_views, &L)) return rc;
+    if (obs_format != SUCRE_OBS_F32 && obs_format != SUCRE_OBS_U16MM && obs_format != SUCRE_OBS_F32_PLAIN && obs_format != SUCRE_OBS_F32_Z26)
+        return fail(SUCRE_ERR_ARG, "unknown observation format %d", obs_format);
+    if (int rc = check_trim_args(k_sigma, view_stats_dev, dropped_dev, view_dropped_dev, thresholds_dev, scratch_dev)) return rc;
+    return check_hip(launch_trim(L, static_cast<uint8_t *>(ws), obs_format == SUCRE_OBS_U16MM ? SUCRE_OBS_U16MM : SUCRE_OBS_F32, k_sigma,
+                                 view_stats_dev, dropped_dev, view_dropped_dev, thresholds_dev, scratch_dev,
+                                 static_cast<hipStream_t>(stream)), "sucre_trim_outliers");
+}
+
+int sucre_trim_outliers_ext(void *ws, const void *lws, int H, int W, int n_views, unsigned flags, double k_sigma,
+                            const double *view_stats_dev, int32_t *dropped_dev, int64_t *view_dropped_dev, float *thresholds_dev,
+                            void *scratch_dev, void *stream) {
+    Layout L;
+    if (int rc = check_ws(ws, H, W, n_views, &L)) return rc;
+    if (int rc = check_lws(lws)) return rc;
+    if (flags & ~(SUCRE_FIT_EXT_COLOUR | SUCRE_FIT_EXT_BOTH)) return fail(SUCRE_ERR_ARG, "unknown flags 0x%x", flags);
+    if ((flags & SUCRE_FIT_EXT_COLOUR) && (flags & SUCRE_FIT_EXT_BOTH)) return fail(SUCRE_ERR_ARG, "SUCRE_FIT_EXT_COLOUR and SUCRE_FIT_EXT_BOTH exclude each other");
+    if (int rc = check_trim_args(k_sigma, view_stats_dev, dropped_dev, view_dropped_dev, thresholds_dev, scratch_dev)) return rc;
+    return check_hip(launch_trim_ext(L, static_cast<uint8_t *>(ws), static_cast<const uint8_t *>(lws), flags, k_sigma, view_stats_dev,
+                                     dropped_dev, view_dropped_dev, thresholds_dev, scratch_dev, static_cast<hipStream_t>(stream)),
+                     "sucre_trim_outliers_ext");
+}
+
 /* ---- shared water and light over the light-model images of a rank (sucre.py:54-61, 124-157) ------------------------ */
 
 }  // extern "C"

@@ -80,6 +80,13 @@ hipError_t launch_residuals(const Layout &L, const uint8_t *ws, int fmt, int32_t
 hipError_t launch_residuals_ext(const Layout &L, const uint8_t *ws, const uint8_t *lws, unsigned flags, int32_t *count, float *ssr,
                                 double *view_stats, void *scratch, hipStream_t s);
 
+// outlier trim of the dense store (trim.h; trim.hip, the variants with camera points in light.hip)
+size_t trim_scratch_bytes(const Layout &L);
+hipError_t launch_trim(const Layout &L, uint8_t *ws, int fmt, double k_sigma, const double *view_stats, int32_t *dropped,
+                       int64_t *view_dropped, float *tau2, void *scratch, hipStream_t s);
+hipError_t launch_trim_ext(const Layout &L, uint8_t *ws, const uint8_t *lws, unsigned flags, double k_sigma, const double *view_stats,
+                           int32_t *dropped, int64_t *view_dropped, float *tau2, void *scratch, hipStream_t s);
+
 // output stage (plot.hip)
 size_t select_scratch_bytes();
 hipError_t launch_select_ranks(const float *J, int H, int W, int n_ranks, const uint64_t *ranks, float *out, void *scratch,

@@ -20,6 +20,7 @@
 #include "fit_math.h"
 #include "handoff.h"
 #include "residual.h"
+#include "trim.h"
 
 namespace sucre {
 
@@ -825,6 +826,29 @@ hipError_t launch_residuals_ext(const Layout &L, const uint8_t *ws, const uint8_
         else launch_residual_kernel(residual_kernel<false, SUCRE_EXT_POINTS, LightModel>, A, s);
     }
     launch_residual_view_sums(A, s);
+    return hipGetLastError();
+}
+
+// ---- outlier trim with extension planes (trim.h): the same variants, the same geometry of the parameters as they stand ----
+hipError_t launch_trim_ext(const Layout &L, uint8_t *ws, const uint8_t *lws, unsigned flags, double k_sigma, const double *view_stats,
+                           int32_t *dropped, int64_t *view_dropped, float *tau2, void *scratch, hipStream_t s) {
+    LightLayout X;
+    make_light_layout(L, &X, (flags & SUCRE_FIT_EXT_BOTH) ? 2 : 1);
+    TrimArgs T = trim_args(L, ws, tau2, dropped, view_dropped, scratch);
+    T.R.params = reinterpret_cast<const float *>(lws + X.off_params);
+    T.R.ext = lws + X.off_ext_dense;
+    T.R.ext2 = (flags & SUCRE_FIT_EXT_BOTH) ? lws + X.off_ext2_dense : nullptr;
+    launch_trim_thresholds(T, view_stats, k_sigma * k_sigma, tau2, s);
+    if (flags & SUCRE_FIT_EXT_COLOUR) {
+        launch_trim_colour(T, s);
+    } else {
+        float *geom = static_cast<float *>(scratch);   // as launch_residuals_ext: into the head of the scratch buffer
+        hipLaunchKernelGGL(light_geometry_kernel, dim3(1), dim3(64), 0, s, T.R.params, geom, reinterpret_cast<double *>(geom + 16));
+        T.R.geom = geom;
+        if (flags & SUCRE_FIT_EXT_BOTH) launch_trim_kernel(trim_kernel<false, SUCRE_EXT_POINTS_COLOUR, LightModel>, T, s);
+        else launch_trim_kernel(trim_kernel<false, SUCRE_EXT_POINTS, LightModel>, T, s);
+    }
+    launch_trim_view_sums(T, s);
     return hipGetLastError();
 }
 

@@ -51,63 +51,99 @@ struct NoLight {
 
 struct ResidualChunk { float zz[4]; uint32_t cc[3]; float p[3][4], f[3][4]; };   // ranges, colour words, extension planes (sets 1, 2)
 
+// The pieces of the walk that the outlier trim (trim.h) shares with the residual pass, so that its decisions are made from the
+// very numbers the residuals are: the lane's J, the lane's share of a chunk, one observation's residual.
+
+// the current J of the lane's four pixels, where the fit keeps it
+__device__ __forceinline__ void residual_load_J(const ResidualArgs &A, int tile, int lane, float (&J)[4][3]) {
+    const uint4 d4 = *reinterpret_cast<const uint4 *>(A.invperm + (size_t)tile * kTilePx + lane * 4);
+    const uint32_t d[4] = {d4.x, d4.y, d4.z, d4.w};
+    const uint32_t last = (uint32_t)A.n_tiles * kTilePx - 1u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t dst = min(d[j], last);   // (a workspace that was never finalised holds anything here)
+        const float *st = A.state + (size_t)(dst / kStripPx) * kStateFloats + dst % kStripPx;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) J[j][c] = st[c * kStripPx];
+    }
+}
+
+// the lane's slots 4 lane .. 4 lane + 3 of chunk (tile, k)
+template <int kExt>
+__device__ __forceinline__ ResidualChunk residual_load_chunk(const ResidualArgs &A, int tile, int k, int lane) {
+    constexpr bool kPoints = (kExt & 1) != 0, kFloatColour = (kExt & 2) != 0;
+    ResidualChunk q;
+    const uint8_t *ch = A.obs + (size_t)tile * A.tile_stride + (size_t)k * A.view_stride;
+    const float4 z4 = *reinterpret_cast<const float4 *>(ch + lane * 16);
+    q.zz[0] = z4.x; q.zz[1] = z4.y; q.zz[2] = z4.z; q.zz[3] = z4.w;
+    if (!kFloatColour) {
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl) q.cc[pl] = *reinterpret_cast<const uint32_t *>(ch + kChunkZ + pl * kTilePx + lane * 4);
+    }
+    if (kExt) {
+        const size_t eo = ((size_t)tile * A.n_views + k) * kExtChunk;
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl) {
+            const float4 v = *reinterpret_cast<const float4 *>(A.ext + eo + (size_t)(pl * kTilePx + lane * 4) * sizeof(float));
+            q.p[pl][0] = v.x; q.p[pl][1] = v.y; q.p[pl][2] = v.z; q.p[pl][3] = v.w;
+        }
+        if (kPoints && kFloatColour) {
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) {
+                const float4 v = *reinterpret_cast<const float4 *>(A.ext2 + eo + (size_t)(pl * kTilePx + lane * 4) * sizeof(float));
+                q.f[pl][0] = v.x; q.f[pl][1] = v.y; q.f[pl][2] = v.z; q.f[pl][3] = v.w;
+            }
+        }
+    }
+    return q;
+}
+
+// water parameters as the evaluation reads them: B, -beta log2 e, -gamma log2 e
+struct ResidualWater {
+    float B[3], nb[3], ng[3];
+    __device__ __forceinline__ explicit ResidualWater(const float *params) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { B[c] = params[c]; nb[c] = -params[3 + c] * kLog2e; ng[c] = -params[6 + c] * kLog2e; }
+    }
+};
+
+// r[c] of the lane's slot j of the chunk (0 for an empty slot); returns whether the slot holds an observation
+template <bool kU16, int kExt, class Light>
+__device__ __forceinline__ bool residual_obs(const ResidualChunk &cur, int j, const Light &light, const ResidualWater &w,
+                                             const float (&J)[3], float (&r)[3]) {
+    constexpr bool kPoints = (kExt & 1) != 0, kFloatColour = (kExt & 2) != 0;
+    const bool valid = cur.zz[j] > 0.0f;   // an empty slot holds range 0
+    float zc = cur.zz[j];
+    if (kU16) zc = kMPerMm * fminf(fmaxf(rintf(zc * kMmPerM), 1.0f), 65535.0f);
+    const float cP[3] = {kPoints ? cur.p[0][j] : 0.0f, kPoints ? cur.p[1][j] : 0.0f, kPoints ? cur.p[2][j] : 0.0f};
+    float l, z;
+    light.lz(cP, zc, l, z);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float a = fast_exp2(z * w.nb[c]), g = fast_exp2(z * w.ng[c]);
+        float Ihat = __builtin_fmaf(J[c], a, w.B[c] * (1.0f - g));
+        if (kPoints) Ihat = l * Ihat;
+        const float I = kFloatColour ? (kPoints ? cur.f[c][j] : cur.p[c][j]) : unit_from_u8((cur.cc[c] >> (8 * j)) & 255u);
+        r[c] = valid ? I - Ihat : 0.0f;   // select, not multiply: J may be NaN where nothing is observed
+    }
+    return valid;
+}
+
 template <bool kU16, int kExt, class Light>
 __global__ __launch_bounds__(256) void residual_kernel(const ResidualArgs A) {
-    constexpr bool kPoints = (kExt & 1) != 0, kFloatColour = (kExt & 2) != 0;
     static_assert(kExt >= 0 && kExt <= 3 && !(kU16 && kExt), "extension planes ride with the f32 store only");
     const int lane = threadIdx.x & 63;
     const int tile = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (tile >= A.n_tiles) return;   // (no barrier below: the wave is on its own)
     const int n_views = A.n_views;
-    float B[3], nb[3], ng[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { B[c] = A.params[c]; nb[c] = -A.params[3 + c] * kLog2e; ng[c] = -A.params[6 + c] * kLog2e; }
+    const ResidualWater water(A.params);
     const Light light(A.geom);
 
-    // the current J of the lane's four pixels, where the fit keeps it
     float J[4][3];
-    {
-        const uint4 d4 = *reinterpret_cast<const uint4 *>(A.invperm + (size_t)tile * kTilePx + lane * 4);
-        const uint32_t d[4] = {d4.x, d4.y, d4.z, d4.w};
-        const uint32_t last = (uint32_t)A.n_tiles * kTilePx - 1u;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t dst = min(d[j], last);   // (a workspace that was never finalised holds anything here)
-            const float *st = A.state + (size_t)(dst / kStripPx) * kStateFloats + dst % kStripPx;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) J[j][c] = st[c * kStripPx];
-        }
-    }
+    residual_load_J(A, tile, lane, J);
 
-    const uint8_t *tbase = A.obs + (size_t)tile * A.tile_stride;
     const uint16_t *tcnt = A.cnt + (size_t)tile * n_views;
     auto next_view = [&](int k) { while (k < n_views && !(tcnt[k] > 0 && A.view_keep[k] != 0u)) ++k; return k; };   // wave-uniform
-    auto load = [&](int k) {
-        ResidualChunk q;
-        const uint8_t *ch = tbase + (size_t)k * A.view_stride;
-        const float4 z4 = *reinterpret_cast<const float4 *>(ch + lane * 16);
-        q.zz[0] = z4.x; q.zz[1] = z4.y; q.zz[2] = z4.z; q.zz[3] = z4.w;
-        if (!kFloatColour) {
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl) q.cc[pl] = *reinterpret_cast<const uint32_t *>(ch + kChunkZ + pl * kTilePx + lane * 4);
-        }
-        if (kExt) {
-            const size_t eo = ((size_t)tile * n_views + k) * kExtChunk;
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl) {
-                const float4 v = *reinterpret_cast<const float4 *>(A.ext + eo + (size_t)(pl * kTilePx + lane * 4) * sizeof(float));
-                q.p[pl][0] = v.x; q.p[pl][1] = v.y; q.p[pl][2] = v.z; q.p[pl][3] = v.w;
-            }
-            if (kPoints && kFloatColour) {
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) {
-                    const float4 v = *reinterpret_cast<const float4 *>(A.ext2 + eo + (size_t)(pl * kTilePx + lane * 4) * sizeof(float));
-                    q.f[pl][0] = v.x; q.f[pl][1] = v.y; q.f[pl][2] = v.z; q.f[pl][3] = v.w;
-                }
-            }
-        }
-        return q;
-    };
 
     float ssr[4][3], pn[4];
 #pragma unroll
@@ -115,32 +151,23 @@ __global__ __launch_bounds__(256) void residual_kernel(const ResidualArgs A) {
 
     int k = next_view(0);
     ResidualChunk cur = {};
-    if (k < n_views) cur = load(k);
+    if (k < n_views) cur = residual_load_chunk<kExt>(A, tile, k, lane);
     while (k < n_views) {
         const int kn = next_view(k + 1);
         ResidualChunk nx = {};
-        if (kn < n_views) nx = load(kn);
+        if (kn < n_views) nx = residual_load_chunk<kExt>(A, tile, kn, lane);
         float vn = 0.0f, vs[3] = {0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const bool valid = cur.zz[j] > 0.0f;   // an empty slot holds range 0
-            float zc = cur.zz[j];
-            if (kU16) zc = kMPerMm * fminf(fmaxf(rintf(zc * kMmPerM), 1.0f), 65535.0f);
-            const float cP[3] = {kPoints ? cur.p[0][j] : 0.0f, kPoints ? cur.p[1][j] : 0.0f, kPoints ? cur.p[2][j] : 0.0f};
-            float l, z;
-            light.lz(cP, zc, l, z);
+            float r[3];
+            const bool valid = residual_obs<kU16, kExt>(cur, j, light, water, J[j], r);
             const float one = valid ? 1.0f : 0.0f;
             pn[j] += one;
             vn += one;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const float a = fast_exp2(z * nb[c]), g = fast_exp2(z * ng[c]);
-                float Ihat = __builtin_fmaf(J[j][c], a, B[c] * (1.0f - g));
-                if (kPoints) Ihat = l * Ihat;
-                const float I = kFloatColour ? (kPoints ? cur.f[c][j] : cur.p[c][j]) : unit_from_u8((cur.cc[c] >> (8 * j)) & 255u);
-                const float r = valid ? I - Ihat : 0.0f;   // select, not multiply: J may be NaN where nothing is observed
-                ssr[j][c] = __builtin_fmaf(r, r, ssr[j][c]);
-                vs[c] = __builtin_fmaf(r, r, vs[c]);
+                ssr[j][c] = __builtin_fmaf(r[c], r[c], ssr[j][c]);
+                vs[c] = __builtin_fmaf(r[c], r[c], vs[c]);
             }
         }
         const float t0 = wave_sum_lane0(vn), t1 = wave_sum_lane0(vs[0]), t2 = wave_sum_lane0(vs[1]), t3 = wave_sum_lane0(vs[2]);

@@ -251,6 +251,7 @@ class Restoration:
         self._batch_table = None
         self.trace = None
         self.steps_done = 0
+        self.min_cover = None   # of the last match / import_matches: trim_outliers finalises again with it
 
     # -- plumbing -----------------------------------------------------------------------------------------
     def _sp(self) -> C.c_void_p:
@@ -295,6 +296,7 @@ class Restoration:
         ``PACKED_VIEWS``.  Records pay off for a survey, whose targets share views; for ONE target, building them (0.36 ms for 65
         views at 1080p) costs eight times what they save (45 us).  Same match sets, ranges and colours either way."""
         assert 1 <= len(views) <= self.capacity, (len(views), self.capacity)
+        self.min_cover = float(min_cover)
         self.n_views = len(views)   # the workspace layout is a function of (H, W, n_views) and grows with n_views
         tgt = target.to_struct()
         packed = (PACKED_VIEWS if packed is None else bool(packed)) and not self.float_colour   # (float32 colour images keep the two-gather form)
@@ -335,6 +337,7 @@ class Restoration:
         float32 (3, n) tensor, fills the extension planes of a ``light`` restoration (the camera points cP) or of a
         ``float_colour`` one (the colours I; ``rgb_u8`` may then be None); a restoration that is both takes (6, n): cP, then I."""
         assert 1 <= len(lists) <= self.capacity, (len(lists), self.capacity)
+        self.min_cover = float(min_cover)
         self.n_views = len(lists)
         self._keepalive = [target, lists]
         self._views_dev = None
@@ -526,6 +529,45 @@ class Restoration:
             else:
                 _lib.check(self.lib.sucre_fit_residuals(ws, H, W, n, self._fmt, *outs, self._sp()))
         return count, ssr, stats
+
+    def trim_outliers(self, k_sigma: float, residuals=None):
+        """One round of the outlier trim (``sucre_trim_outliers``): drops from the store every observation of a kept view whose
+        residual at the fit as it stands has r_c^2 > tau^2_c = float32(k_sigma^2 S_c / N) in any channel (N, S_c: observations
+        and sums of r^2 over the kept views) -- except at a pixel that would lose all its observations, which keeps them all --
+        and finalises the store again with the ``min_cover`` of the last ``match`` / ``import_matches``: view totals, kept views
+        (a view may now fall below ``min_cover``), ``n_obs``, the store's format, the compaction and the plans are what a plain
+        run on the survivors would have.  ``residuals``: what ``residuals()`` returned for this very state (run here if None).
+        Returns ``(dropped, view_dropped, thresholds)`` on the device: int32 (H,W), int64 (n_views), float32 [3] = tau^2.
+        Everything is enqueued on the current stream without a host wait.  The fit must start over: ``steps_done`` is 0 and the
+        caller calls ``fit_init`` again -- with the same initial values the refit is bit for bit a plain run on a store into
+        which only the survivors were imported.  ``match_map`` keeps returning the untrimmed matches (it is geometry)."""
+        k_sigma = float(k_sigma)
+        if not (np.isfinite(k_sigma) and k_sigma > 0.0):
+            raise ValueError(f'trim_outliers: k_sigma must be finite and > 0, not {k_sigma!r}')
+        if self.min_cover is None:
+            raise _lib.SucreError('trim_outliers: call match() or import_matches() first')
+        stats = (self.residuals() if residuals is None else residuals)[2]
+        assert stats.is_cuda and stats.dtype == torch.float64 and stats.is_contiguous() and stats.shape == (self.n_views, 4)
+        dropped = torch.empty((self.H, self.W), dtype=torch.int32, device=self.device)
+        view_dropped = torch.empty(self.n_views, dtype=torch.int64, device=self.device)
+        thresholds = torch.empty(3, dtype=torch.float32, device=self.device)
+        nbytes = self.lib.sucre_trim_scratch_bytes(self.H, self.W, self.n_views)
+        if nbytes == 0:
+            raise _lib.SucreError(self.lib.sucre_last_error().decode())
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        ws, H, W, n = self._geom
+        args = (k_sigma, C.c_void_p(stats.data_ptr()), C.c_void_p(dropped.data_ptr()), C.c_void_p(view_dropped.data_ptr()),
+                C.c_void_p(thresholds.data_ptr()), C.c_void_p(scratch.data_ptr()))
+        with torch.cuda.device(self.device):
+            if self.lws is not None:
+                lws = C.c_void_p(self.lws.data_ptr())
+                _lib.check(self.lib.sucre_trim_outliers_ext(ws, lws, H, W, n, self._ext_flag, *args, self._sp()))
+                _lib.check(self.lib.sucre_finalize_matches_ext(ws, lws, H, W, n, self.min_cover, self._ext_mode, self._sp()))
+            else:
+                _lib.check(self.lib.sucre_trim_outliers(ws, H, W, n, self._fmt, *args, self._sp()))
+                _lib.check(self.lib.sucre_finalize_matches_fmt(ws, H, W, n, self.min_cover, self._fmt, self._sp()))
+        self.steps_done = 0
+        return dropped, view_dropped, thresholds
 
     def params(self) -> torch.Tensor:
         """B[3], beta[3], gamma[3] (+ cam2light[6], sigma[4] with the light model) on the device."""

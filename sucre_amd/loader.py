@@ -559,8 +559,10 @@ class MatchesFile:
             return md
         return MatchesData(restoration=self._need(), image_list=self.image_list)
 
-    def save(self) -> Path:
-        """Persists the explicit match lists in the reference's layout (used by --keep-matches)."""
+    def save(self, survivors: bool = False) -> Path:
+        """Persists the explicit match lists in the reference's layout (used by --keep-matches).  ``survivors``: only the
+        matches whose observation is still in the store (after ``Restoration.trim_outliers``; the match map is geometry and
+        keeps the dropped ones)."""
         r = self._need()
         keep = r.view_keep().cpu().numpy().astype(bool)
         groups = {}
@@ -568,6 +570,8 @@ class MatchesFile:
             if not keep[k]:
                 continue
             q = r.match_map(k)
+            if survivors:
+                q = torch.where(r.export_view(k)[0] > 0, q, torch.full_like(q, -1))
             v1, u1 = torch.where(q >= 0)
             p2 = q[v1, u1].long()
             W2 = im.camera.width

@@ -293,11 +293,19 @@ def snapshot_stops(num_iter: int, save_interval: int | None) -> list[tuple[int, 
 
 
 def adam(sucre: SUCRe, matches_data: loader.MatchesData, lr: float = 0.05, num_iter: int = 200, batch_size: int = 1,
-         save_dir: Path = None, save_interval: int = None, device: str = 'cpu', verbose: bool = True) -> SUCRe:
+         save_dir: Path = None, save_interval: int = None, device: str = 'cpu', verbose: bool = True,
+         trim_outliers: float = None, trim_rounds: int = 1) -> SUCRe:
     """``num_iter`` steps of ``torch.optim.Adam(lr)`` on the least-squares cost (sucre.py:124-157).
 
     ``batch_size`` is accepted for compatibility: the engine always uses the full batch in one pass, which is
-    what the reference's accumulated mini-batch gradients add up to."""
+    what the reference's accumulated mini-batch gradients add up to.
+
+    ``trim_outliers`` (not a reference argument): after the fit, ``trim_rounds`` rounds of trim -> fit anew from the same
+    initial values with the same ``num_iter`` (``_enqueue_trim``); the model ends with the last fit, and ``sucre._trim`` holds
+    every round's record."""
+    _check_trim(trim_outliers, trim_rounds)
+    if trim_outliers is not None and save_dir is not None and save_interval is not None:
+        raise ValueError('trim_outliers does not combine with save_interval snapshots')
     print(f'Solve least squares with Adam optimizer ({num_iter} iterations).')
     resto = _adam_begin(sucre, matches_data)
     done = 0
@@ -314,6 +322,15 @@ def adam(sucre: SUCRe, matches_data: loader.MatchesData, lr: float = 0.05, num_i
             sucre.save_plots(save_dir=save_dir, iteration=done - 1)
             if sucre.use_closed_form and done == num_iter:
                 resto.update_J()   # the final update_J of sucre.py:156, held back for the snapshot
+    if trim_outliers is not None:
+        sucre._trim = []
+        for i in range(int(trim_rounds)):   # (no snapshot stops here: nothing has been pulled into the model yet, so
+            sucre._trim.append(_enqueue_trim(resto, trim_outliers))   # _adam_begin starts from the same values again)
+            print(f'Solve least squares with Adam optimizer ({num_iter} iterations) after trim round {i + 1}.')
+            _adam_begin(sucre, matches_data)
+            trace = resto.fit(num_iter, lr=lr, use_closed_form=sucre.use_closed_form)
+            if verbose:
+                _log_trace(trace.cpu().numpy(), 0)
     if getattr(sucre, '_quality_wanted', False):   # --save-quality: the pass right behind the fit, read with the results
         sucre._quality = _enqueue_residuals(resto)
     _pull_results(sucre, resto)
@@ -390,6 +407,65 @@ def _write_quality(job) -> None:
     print(line)
 
 
+# ---- --trim-outliers: sigma-clip single observations on the device, fit again ------------------------------------------
+def _check_trim(trim_outliers, trim_rounds) -> None:
+    if trim_outliers is None:
+        return
+    if not (np.isfinite(float(trim_outliers)) and float(trim_outliers) > 0):
+        raise ValueError(f'trim_outliers must be a finite multiple > 0, not {trim_outliers!r}')
+    if int(trim_rounds) < 1:
+        raise ValueError(f'trim_rounds must be >= 1, not {trim_rounds!r}')
+
+
+def _enqueue_trim(resto, k_sigma: float) -> dict:
+    """One round on the current stream, no host wait (``Restoration.trim_outliers`` behind the residual pass it takes its scale
+    from); the fit must be started over.  The round's record, on the device."""
+    n_obs, kept = resto.n_obs_device().clone(), resto.view_keep().clone()
+    dropped, view_dropped, thresholds = resto.trim_outliers(k_sigma, resto.residuals())
+    return {'dropped': dropped, 'view_dropped': view_dropped, 'thresholds': thresholds, 'n_obs': n_obs, 'view_kept': kept,
+            'k': float(k_sigma)}
+
+
+def _enqueue_trim_refits(jobs: list, fit) -> None:
+    """The rounds of ``--trim-outliers`` for images whose first fit is enqueued: trim, ``fit_init`` with the initial values of
+    the first fit, and ``fit(jobs)`` -- the caller's way of fitting them, alone or in a batch launch -- again."""
+    for job in jobs:
+        job.trim = [] if job.trim_outliers is not None else None
+    for i in range(max((int(j.trim_rounds) for j in jobs if j.trim_outliers is not None), default=0)):
+        again = [j for j in jobs if j.trim_outliers is not None and i < int(j.trim_rounds)]
+        for job in again:
+            job.trim.append(_enqueue_trim(job.resto, job.trim_outliers))
+            _adam_begin(job.sucre, job.matches_data, params0=job.params0)
+        fit(again)
+
+
+def trimmed_image(dropped_rounds, n_kept: int) -> np.ndarray:
+    """``<stem>_trimmed.png``: ``coverage_image`` of the observations dropped from every pixel, summed over the rounds, against
+    the number of views kept before the first round."""
+    total = np.asarray(dropped_rounds, np.int64)
+    return coverage_image(total.reshape((-1,) + total.shape[-2:]).sum(axis=0), n_kept)
+
+
+def _write_trim(job) -> None:
+    """``<stem>_trim.pt``, ``<stem>_trimmed.png`` and one printed line per round."""
+    rounds = job.trim   # host tensors (_restore_finish)
+    stem = Path(job.image.name).stem
+    image_list = getattr(job.matches_data, 'image_list', None)
+    n_views = int(rounds[0]['view_dropped'].shape[0])
+    views = [im.name for im in image_list] if image_list else [str(k) for k in range(n_views)]
+    dropped = torch.stack([r['dropped'] for r in rounds])
+    torch.save({'dropped': dropped, 'views': views, 'view_dropped': torch.stack([r['view_dropped'] for r in rounds]),
+                'thresholds': torch.stack([r['thresholds'] for r in rounds]), 'k': rounds[0]['k'],
+                'n_obs': torch.cat([r['n_obs'] for r in rounds]), 'view_kept': torch.stack([r['view_kept'] != 0 for r in rounds])},
+               job.output_dir / f'{stem}_trim.pt')
+    _save_png(PILImage.fromarray(trimmed_image(dropped.numpy(), int((rounds[0]['view_kept'] != 0).sum()))),
+              job.output_dir / f'{stem}_trimmed.png')
+    for i, r in enumerate(rounds):
+        t = np.sqrt(r['thresholds'].numpy().astype(np.float64))
+        print(f'{job.image.name}: trim round {i + 1} dropped {int(r["view_dropped"].sum())} of {int(r["n_obs"])} observations '
+              f'(threshold R {t[0]:.4f} G {t[1]:.4f} B {t[2]:.4f})')
+
+
 class _Job:
     """One image between ``_restore_submit`` (everything enqueued, nothing waited for) and ``_restore_finish``."""
 
@@ -400,7 +476,8 @@ class _Job:
 def _restore_submit(image: sfm.Image, colmap_model: sfm.COLMAPModel, output_dir: Path, light_model: bool,
                     use_closed_form: bool, min_cover: float, image_list: list[sfm.Image], lr: float, num_iter: int,
                     params_path: Path, force_compute_matches: bool, num_workers: int, device: str,
-                    defer_checks: bool = False, save_quality: bool = False) -> _Job:
+                    defer_checks: bool = False, save_quality: bool = False, trim_outliers: float = None,
+                    trim_rounds: int = 1) -> _Job:
     """Stages of sucre.py:160-210 up to and including the enqueued fit; the trace and J stay on the device.
     ``defer_checks``: the integrity verdicts and the observation count stay on the device until ``_restore_finish``
     reads them with the results -- waiting for them here would make the host wait for the matching, which shares the
@@ -446,7 +523,8 @@ def _restore_submit(image: sfm.Image, colmap_model: sfm.COLMAPModel, output_dir:
 
     return _Job(image=image, sucre=sucre, matches_file=matches_file, matches_data=matches_data,
                 matches_path=matches_path, output_dir=output_dir, lr=lr, num_iter=num_iter, trace=None,
-                deferred_checks=defer_checks, params0=params0, save_quality=bool(save_quality), quality=None)
+                deferred_checks=defer_checks, params0=params0, save_quality=bool(save_quality), quality=None,
+                trim_outliers=trim_outliers, trim_rounds=int(trim_rounds), trim=None)
 
 
 def _report_observations(image: sfm.Image, n_obs: int) -> None:
@@ -458,8 +536,13 @@ def _report_observations(image: sfm.Image, n_obs: int) -> None:
 def _restore_enqueue_fit(job: _Job) -> None:
     """The whole fit of sucre.py:138-156 enqueued in one go (no intermediate plots): no host synchronisation."""
     print(f'Solve least squares with Adam optimizer ({job.num_iter} iterations).')
-    resto = _adam_begin(job.sucre, job.matches_data, params0=job.params0)
-    job.trace = resto.fit(job.num_iter, lr=job.lr, use_closed_form=job.sucre.use_closed_form)
+    job.resto = resto = _adam_begin(job.sucre, job.matches_data, params0=job.params0)
+
+    def fit(jobs):
+        for j in jobs:
+            j.trace = j.resto.fit(j.num_iter, lr=j.lr, use_closed_form=j.sucre.use_closed_form)
+    fit([job])
+    _enqueue_trim_refits([job], fit)
     _enqueue_quality(job, resto)
 
 
@@ -478,18 +561,31 @@ def _restore_enqueue_fits(jobs: list) -> None:
             singles.append(job)
         else:
             groups.setdefault((resto.H, resto.W, resto.obs_format, job.num_iter, job.lr, job.sucre.use_closed_form), []).append(job)
+
+    def fit_alone(members):
+        for job in members:
+            print(f'Solve least squares with Adam optimizer ({job.num_iter} iterations).')
+            job.trace = job.resto.fit(job.num_iter, lr=job.lr, use_closed_form=job.sucre.use_closed_form)
+
     for key, members in groups.items():
         if len(members) == 1:
             singles.extend(members)
             continue
-        print(f'Solve least squares with Adam optimizer ({key[3]} iterations), {len(members)} images per launch.')
-        traces = engine.fit_batch([j.resto for j in members], key[3], lr=key[4], use_closed_form=key[5])
-        for j, t in zip(members, traces):
-            j.trace = t
+
+        def fit_together(members, key=key):   # (the refits after a trim too: a batch launch gives every image its own bits)
+            if len(members) == 1:
+                return fit_alone(members)
+            print(f'Solve least squares with Adam optimizer ({key[3]} iterations), {len(members)} images per launch.')
+            traces = engine.fit_batch([j.resto for j in members], key[3], lr=key[4], use_closed_form=key[5])
+            for j, t in zip(members, traces):
+                j.trace = t
+        fit_together(members)
+        _enqueue_trim_refits(members, fit_together)
+        for j in members:
             _enqueue_quality(j, j.resto)
+    fit_alone(singles)
+    _enqueue_trim_refits(singles, fit_alone)
     for job in singles:
-        print(f'Solve least squares with Adam optimizer ({job.num_iter} iterations).')
-        job.trace = job.resto.fit(job.num_iter, lr=job.lr, use_closed_form=job.sucre.use_closed_form)
         _enqueue_quality(job, job.resto)
 
 
@@ -536,8 +632,13 @@ def _restore_finish(job: _Job, keep_matches: bool, writers: ThreadPoolExecutor |
         _pull_results(sucre, _restoration_of(job.matches_data))
     if job.quality is not None:
         job.quality = tuple(t.cpu() for t in job.quality)
+    if job.trim is not None:
+        job.trim = [{k: (v.cpu() if torch.is_tensor(v) else v) for k, v in r.items()} for r in job.trim]
     if keep_matches and job.matches_file.restoration._views_dev is not None:   # freshly matched (not loaded from this
-        print(f'Keep {job.matches_file.save()}.')                              # very file); needs the live workspace
+        if job.trim is not None:                                               # very file); needs the live workspace
+            print(f'Keep {job.matches_file.save(survivors=True)} (the observations that survived the trim).')
+        else:
+            print(f'Keep {job.matches_file.save()}.')
     if writers is None:
         _write_outputs(job, keep_matches)
         return sucre
@@ -553,6 +654,8 @@ def _write_outputs(job: _Job, keep_matches: bool, log: bool = False) -> None:
     sucre.save_plots(save_dir=job.output_dir)
     if job.quality is not None:
         _write_quality(job)
+    if job.trim is not None:
+        _write_trim(job)
     torch.save({**sucre.cpu().state_dict(), 'J': sucre.J.detach().cpu()},
                (job.output_dir / job.image.name).with_suffix('.pt'))
     if not keep_matches and job.matches_path.exists():
@@ -572,16 +675,23 @@ def restore_image(image: sfm.Image, colmap_model: sfm.COLMAPModel, output_dir: P
 
 
 def _restore_one(image, colmap_model, output_dir, light_model, use_closed_form, min_cover, image_list, lr, num_iter, batch_size,
-                 save_interval, params_path, force_compute_matches, keep_matches, num_workers, device, save_quality: bool = False):
-    """``restore_image`` plus what its pinned signature has no room for (``save_quality``: --save-quality)."""
+                 save_interval, params_path, force_compute_matches, keep_matches, num_workers, device, save_quality: bool = False,
+                 trim_outliers: float = None, trim_rounds: int = 1):
+    """``restore_image`` plus what its pinned signature has no room for (``save_quality``: --save-quality; ``trim_outliers``,
+    ``trim_rounds``: --trim-outliers, --trim-rounds)."""
     sfm.require_gpu(device, 'restore_image')
+    _check_trim(trim_outliers, trim_rounds)
+    if trim_outliers is not None and save_interval is not None:
+        raise ValueError('trim_outliers does not combine with save_interval snapshots')
     job = _restore_submit(image, colmap_model, output_dir, light_model, use_closed_form, min_cover, image_list, lr,
-                          num_iter, params_path, force_compute_matches, num_workers, device, save_quality=save_quality)
+                          num_iter, params_path, force_compute_matches, num_workers, device, save_quality=save_quality,
+                          trim_outliers=trim_outliers, trim_rounds=trim_rounds)
     if save_quality:
         job.sucre._quality_wanted = True   # adam enqueues the pass behind its last fit
     adam(sucre=job.sucre, matches_data=job.matches_data, lr=lr, num_iter=num_iter, batch_size=batch_size,
-         save_dir=job.output_dir, save_interval=save_interval, device=device)
+         save_dir=job.output_dir, save_interval=save_interval, device=device, trim_outliers=trim_outliers, trim_rounds=trim_rounds)
     job.quality = job.sucre.__dict__.pop('_quality', None)
+    job.trim = job.sucre.__dict__.pop('_trim', None)
     return _restore_finish(job, keep_matches)
 
 
@@ -592,7 +702,9 @@ def restore_images(images: list[sfm.Image], colmap_model: sfm.COLMAPModel, outpu
     image i+1 is matched and submitted and the plots of images < i are encoded, so neither the tails of the fit
     launches nor the PNG encoding leave the GPU idle.  Per-image results are the same bits as ``restore_image``
     (each image has its own workspace and stream; nothing is shared).  ``fit_batch`` consecutive images share a slot and
-    their fits one launch per iteration (``fit_batch_size``; same bits again)."""
+    their fits one launch per iteration (``fit_batch_size``; same bits again).  ``trim_outliers=None, trim_rounds=1`` (in
+    ``kw``): the rounds of --trim-outliers, enqueued with the image behind its first fit, no host wait added."""
+    _check_trim(kw.get('trim_outliers'), kw.get('trim_rounds', 1))
     pending: list[tuple[int, list]] = []
     written = []
     if fit_batch is None:
@@ -639,6 +751,7 @@ def parse_args(args: argparse.Namespace):
     """Runs the CLI request (sucre.py:222-261); with WORLD_SIZE > 1 each rank restores its shard of the images."""
     rank, local_rank, world = sdist.env_rank_world()
     shared = bool(getattr(args, 'shared_water', False))
+    _refuse_trim_flags(args)
     if shared:
         _refuse_shared_flags(args)
     # torch's CPU thread pool follows the machine's CPU count; inside a container with a CPU quota that many spinning
@@ -705,6 +818,9 @@ def _run_request(args, images, image_list, colmap_model, device, survey: bool, i
     if str(device).startswith('cuda') and images:   # start decoding + uploading the scene now, in the background
         loader.prefetch_for_targets(images, image_list, device, num_workers=args.num_workers, min_cover=args.min_cover)
     quality = {'save_quality': True} if getattr(args, 'save_quality', False) else {}
+    trim = getattr(args, 'trim_outliers', None)
+    if trim is not None:
+        quality.update(trim_outliers=float(trim), trim_rounds=int(getattr(args, 'trim_rounds', 1)))
     if survey:
         restore_images(images, colmap_model, args.output_dir, in_flight=in_flight, keep_matches=args.keep_matches,
                        device=device, light_model=args.light_model, use_closed_form=args.use_closed_form,
@@ -716,7 +832,7 @@ def _run_request(args, images, image_list, colmap_model, device, survey: bool, i
         if quality:
             _restore_one(image, colmap_model, args.output_dir, args.light_model, args.use_closed_form, args.min_cover, image_list,
                          args.learning_rate, args.num_iter, args.batch_size, args.save_interval, args.params_path,
-                         args.force_compute_matches, args.keep_matches, args.num_workers, device, save_quality=True)
+                         args.force_compute_matches, args.keep_matches, args.num_workers, device, **quality)
             continue
         restore_image(image=image, colmap_model=colmap_model, output_dir=args.output_dir,
                       light_model=args.light_model, use_closed_form=args.use_closed_form, min_cover=args.min_cover,
@@ -724,6 +840,23 @@ def _run_request(args, images, image_list, colmap_model, device, survey: bool, i
                       batch_size=args.batch_size, save_interval=args.save_interval, params_path=args.params_path,
                       force_compute_matches=args.force_compute_matches, keep_matches=args.keep_matches,
                       num_workers=args.num_workers, device=device)
+
+
+def _refuse_trim_flags(args) -> None:
+    """What --trim-outliers does not combine with (and what it takes), refused before anything is decoded or matched."""
+    trim, rounds = getattr(args, 'trim_outliers', None), getattr(args, 'trim_rounds', None)
+    if trim is None:
+        if rounds is not None:
+            raise SystemExit('--trim-rounds: only with --trim-outliers K')
+        return
+    if not (np.isfinite(trim) and trim > 0):
+        raise SystemExit(f'--trim-outliers: K must be a finite multiple > 0, not {trim}')
+    if rounds is not None and rounds < 1:
+        raise SystemExit(f'--trim-rounds: N must be >= 1, not {rounds}')
+    if getattr(args, 'shared_water', False):
+        raise SystemExit('--trim-outliers: a shared fit (--shared-water) is not trimmed; drop one of the two flags')
+    if args.save_interval is not None:
+        raise SystemExit('--trim-outliers: --save-interval snapshots are not supported for a trimmed refit; drop one of the two flags')
 
 
 def _refuse_shared_flags(args) -> None:
@@ -854,6 +987,12 @@ def build_parser() -> argparse.ArgumentParser:
                           help='also write, per image, <stem>_quality.pt (observations and squared residuals of the fit per pixel and '
                         'per neighbour view), <stem>_coverage.png and <stem>_residual.png, and print the RMS residual and the '
                         'worst-fitting view')
+    p.extras.add_argument('--trim-outliers', type=float, metavar='K', default=argparse.SUPPRESS,
+                          help='after the fit, drop every observation whose residual exceeds K times the RMS residual of its '
+                               'channel (never a pixel\'s last ones) and fit again from the same start; also writes, per image, '
+                               '<stem>_trim.pt and <stem>_trimmed.png and prints what each round dropped')
+    p.extras.add_argument('--trim-rounds', type=int, metavar='N', default=argparse.SUPPRESS,
+                          help='rounds of --trim-outliers (1 unless given)')
     return p
 
 
