@@ -46,14 +46,35 @@ def plant(scene, patch=PATCH, view=0):
     return bad
 
 
-def scene_observations(scene):
-    """Per view, in engine order (= scene order): (u1, v1, cP (3,n) float32, I (3,n) float32, u2, v2) from the oracle."""
+def float_images(scene, seed=75):
+    """Per view a float32 (H,W,3) colour image that is NOT k/255: float32(u8 / 255) + (rand - 0.5) 0.003, clamped to [0, 1] (what
+    tools/parity_sweep.py feeds its float-colour stores).  A kernel that rounded a colour through uint8 is off by up to 1.5e-3."""
+    gen = torch.Generator().manual_seed(seed)
+    out = []
+    for v in scene.views:
+        f = (v.rgb_u8.to(torch.float64) / 255).to(torch.float32)
+        out.append((f + (torch.rand(f.shape, generator=gen) - 0.5) * 0.003).clamp(0, 1).contiguous())
+    return out
+
+
+def device_views(scene, frgb=None):
+    """The scene's views on the device: uint8 colours as stored, or the float32 images ``frgb`` in their place."""
+    if frgb is None:
+        return engine.device_views_from_scene(scene, DEV)
+    return [engine.DeviceView(depth=v.depth_f32().to(DEV).contiguous(), rgb=f.to(DEV), K=scene.K, R=v.R, t=v.t, name=v.name)
+            for v, f in zip(scene.views, frgb)]
+
+
+def scene_observations(scene, frgb=None):
+    """Per view, in engine order (= scene order): (u1, v1, cP (3,n) float32, I (3,n) float32, u2, v2) from the oracle.  With
+    ``frgb`` the colours are gathered from those float32 images, I = frgb[view][v2, u2] (copies: bit-exact)."""
     per_view, _ = helpers.oracle_scene_samples(scene)
     obs = []
-    for (name, _, m), view in zip(per_view, scene.views):
+    for k, ((name, _, m), view) in enumerate(zip(per_view, scene.views)):
         cP = oracle.unproject(helpers.oracle_cam(scene, view), m.u2, m.v2, m.d)
-        I = oracle.gather_rgb(view.rgb_u8.numpy(), m.u2, m.v2)
-        obs.append((m.u1.astype(np.int64), m.v1.astype(np.int64), cP, I, m.u2.astype(np.int64), m.v2.astype(np.int64)))
+        u2, v2 = m.u2.astype(np.int64), m.v2.astype(np.int64)
+        I = oracle.gather_rgb(view.rgb_u8.numpy(), m.u2, m.v2) if frgb is None else np.ascontiguousarray(frgb[k].numpy()[v2, u2].T)
+        obs.append((m.u1.astype(np.int64), m.v1.astype(np.int64), cP, I, u2, v2))
     return obs
 
 
@@ -75,8 +96,20 @@ def scene_of(key):
     return _SCENES[key]
 
 
-def fitted(scene, T, min_cover=1e-6, closed=False, **kw):
-    views = engine.device_views_from_scene(scene, DEV)
+_FLOAT_SCENES = {}
+
+
+def float_scene_of(key):
+    """(scene, observations, float32 images) of ``scene_of(key)``'s scene with colours off the 1/255 grid, made once."""
+    if key not in _FLOAT_SCENES:
+        scene, _ = scene_of(key)
+        frgb = float_images(scene)
+        _FLOAT_SCENES[key] = (scene, scene_observations(scene, frgb), frgb)
+    return _FLOAT_SCENES[key]
+
+
+def fitted(scene, T, min_cover=1e-6, closed=False, frgb=None, **kw):
+    views = device_views(scene, frgb)
     r = engine.Restoration(scene.height, scene.width, len(views), device=DEV, **kw)
     r.match(views[scene.target], views, min_cover=min_cover)
     r.fit_init(views[scene.target])
@@ -250,25 +283,35 @@ def _same_bits(a, b):
     return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.cpu().view(torch.uint8), b.cpu().view(torch.uint8))
 
 
-def surviving_lists(r):
-    """The per-view lists import_matches takes, from the store as it stands (camera points along with the light model)."""
+def surviving_lists(r, obs=None):
+    """The per-view lists import_matches takes, from the store as it stands: camera points along with the light model, float32
+    colours in place of the uint8 ones with ``float_colour``.  export_view_ext returns ONE set of planes -- the camera points
+    of a store that holds both --, so there the colours are the test's own, ``obs[k]``'s I at the surviving pixels."""
     lists = []
     for k in range(r.n_views):
         z, rgb = r.export_view(k)
         v1, u1 = torch.where(z > 0)
-        item = (u1.to(torch.int16), v1.to(torch.int16), z[v1, u1], rgb[v1, u1])
-        if r.light:
+        item = (u1.to(torch.int16), v1.to(torch.int16), z[v1, u1], None if r.float_colour else rgb[v1, u1])
+        if r.both:
+            I = torch.zeros((3, r.H, r.W), dtype=torch.float32)
+            I[:, torch.from_numpy(obs[k][1]), torch.from_numpy(obs[k][0])] = torch.from_numpy(obs[k][3])
+            item += (torch.cat([r.export_view_ext(k)[:, v1, u1], I.to(r.device)[:, v1, u1]]).contiguous(),)
+        elif r.lws is not None:
             item += (r.export_view_ext(k)[:, v1, u1].contiguous(),)
         lists.append(item)
     return lists
 
 
-def refit_contract(label, scene, T, rounds=1, min_cover=1e-6, closed=False, **kw):
-    a, views = fitted(scene, T, min_cover=min_cover, closed=closed, **kw)
+def refit_contract(label, scene, T, rounds=1, min_cover=1e-6, closed=False, frgb=None, obs=None, start=None, **kw):
+    """``start``: how the fitted workspace comes about, () -> (restoration, views); ``fitted`` (a matched store) unless given.
+    The views kept before every round are left in ``a.kept_before_round``."""
+    a, views = (fitted(scene, T, min_cover=min_cover, closed=closed, frgb=frgb, **kw) if start is None else start())
     target = views[scene.target]
+    a.kept_before_round = []
     for _ in range(rounds):
+        a.kept_before_round.append(a.view_keep().cpu().numpy() != 0)
         a.trim_outliers(K_SIGMA)
-        lists = surviving_lists(a)
+        lists = surviving_lists(a, obs)
         a.fit_init(target)
         ta = a.fit(T, use_closed_form=closed)
     b = engine.Restoration(scene.height, scene.width, len(views), device=DEV, **kw)
@@ -367,8 +410,8 @@ def test_trim_removes_the_planted_patch_and_restores_the_fit():
 
 
 # ---- 5. determinism and hygiene ---------------------------------------------------------------------------------------------
-def _trimmed_run(scene, T, fill=None, **kw):
-    views = engine.device_views_from_scene(scene, DEV)
+def _trimmed_run(scene, T, fill=None, frgb=None, **kw):
+    views = device_views(scene, frgb)
     r = engine.Restoration(scene.height, scene.width, len(views), device=DEV, **kw)
     if fill is not None:
         r.ws.fill_(fill)
@@ -383,12 +426,14 @@ def _trimmed_run(scene, T, fill=None, **kw):
     return r, outs + (trace, r.J(), r.params(), r.view_counts().clone(), r.store_format().clone())
 
 
-@pytest.mark.parametrize('light', [False, True], ids=['plain', 'light'])
-def test_two_runs_and_a_dirty_workspace_give_the_same_bits(light):
+@pytest.mark.parametrize('kw', [dict(light=False), dict(light=True), dict(float_colour=True), dict(light=True, float_colour=True)],
+                         ids=['plain', 'light', 'float-colour', 'light-float-colour'])
+def test_two_runs_and_a_dirty_workspace_give_the_same_bits(kw):
     scene, _ = scene_of('planted75')
-    _, first = _trimmed_run(scene, 20, light=light)
-    _, second = _trimmed_run(scene, 20, light=light)
-    _, dirty = _trimmed_run(scene, 20, fill=0xFF, light=light)
+    frgb = float_scene_of('planted75')[2] if kw.get('float_colour') else None
+    _, first = _trimmed_run(scene, 20, frgb=frgb, **kw)
+    _, second = _trimmed_run(scene, 20, frgb=frgb, **kw)
+    _, dirty = _trimmed_run(scene, 20, fill=0xFF, frgb=frgb, **kw)
     for x, y, z in zip(first, second, dirty):
         assert _same_bits(x, y) and _same_bits(x, z)
     assert int(first[1].sum()) > 0
