@@ -439,6 +439,39 @@ int sucre_trim_outliers_ext(void *ws, const void *lws, int H, int W, int n_views
                             float *thresholds_dev, void *scratch_dev, void *stream);
 
 /*
+ * ---- single-view inversion: a fitted water (and light) model applied to any image -------------------------------------------
+ * With ONE observation per pixel -- the image itself, through its own depth map -- SUCRe.update_J (sucre.py:66-77) is
+ *     J = (I - l B (1 - exp(-gamma z))) a / a^2,   a = l exp(-beta z),   cP = Kinv d [u+.5, v+.5, 1] (loader.py:113),
+ *     z = ||cP|| (sucre.py:53), l = 1 -- or l, z = ||cP|| + ||lP|| of SUCRe.compute_l_z (sucre.py:54-61) with SUCRE_INVERT_LIGHT,
+ * per pixel, and NaN in all three channels where depth <= 0 (sucre.py:48).  This is what update_J returns on a matches file
+ * that holds only the image matched against itself, and the call gives the very bits sucre_update_J / sucre_update_J_ext leave
+ * for such a store -- wherever the two-way match of the image with itself keeps every pixel with depth > 0, which a depth map
+ * consistent with its camera does -- without matching, without a workspace and without a neighbour view: the way to restore
+ * the images of a survey that were not part of the fit with the parameters of those that were.
+ * `images`: HOST array of n_images entries, 1 <= n_images <= 4096 (SUCRE_ERR_RANGE otherwise); the images of one call may differ
+ * in size.  depth: device, (H,W) float32, 16-byte aligned; rgb: device, (H,W,3) uint8, 4-byte aligned -- or float32, 16-byte
+ * aligned, with SUCRE_INVERT_FLOAT_COLOUR (all images of a call alike); J: device, (H,W,3) float32, 16-byte aligned, caller-owned,
+ * written in full; Kinv: row-major K.inverse() (sfm.py:92), as in sucre_view_t; reserved: ignored.  1 <= H, W <= 32767.
+ * `params`: HOST, B[3], beta[3], gamma[3], and with SUCRE_INVERT_LIGHT cam2light[6], sigma[4] behind them (the geometry is
+ * derived anew from them, as sucre_update_J_ext does).  `table_dev`: sucre_invert_bytes(n_images) bytes of device memory (0 on an
+ * invalid count), 256-byte aligned, that the call fills -- by value through small kernels, no host-to-device copy -- and that must
+ * stay untouched until the launches have run; it may hold anything before.  The call only enqueues, all images in one launch.
+ */
+#define SUCRE_INVERT_LIGHT 1u          /* params: 19 floats, else 9 */
+#define SUCRE_INVERT_FLOAT_COLOUR 2u   /* rgb: (H,W,3) float32, else uint8 */
+typedef struct sucre_invert_image {
+    const float *depth;
+    const void *rgb;
+    float *J;
+    int32_t H, W;
+    float Kinv[9];
+    int32_t reserved;
+} sucre_invert_image_t;
+size_t sucre_invert_bytes(int n_images);
+int sucre_invert_images(void *table_dev, int n_images, const sucre_invert_image_t *images, const float *params, unsigned flags,
+                        void *stream);
+
+/*
  * Shared water AND light over several light-model images (the group above for the 19-parameter model; sucre.py:54-61 with
  * the objective of sucre.py:124-157 summed over the images: one B, beta, gamma, cam2light, sigma, every image its own J, one
  * n_obs).  `group_dev`: sucre_light_group_bytes(n_images) bytes of device memory, 256-byte aligned; `images` (host array)

@@ -22,6 +22,8 @@ OBS_F32, OBS_U16MM, OBS_F32_PLAIN, OBS_F32_Z26 = 0, 1, 2, 3
 EXT_POINTS, EXT_COLOUR, EXT_POINTS_COLOUR = 1, 2, 3
 OBS_FORMATS = {'f32': OBS_F32, 'u16mm': OBS_U16MM, 'f32plain': OBS_F32_PLAIN, 'f32z26': OBS_F32_Z26}
 WS_VIEW_COUNT, WS_VIEW_KEEP, WS_N_OBS, WS_PARAMS, WS_SUMS, WS_N_OBS_TOTAL, WS_STORE_FORMAT = range(7)
+INVERT_LIGHT, INVERT_FLOAT_COLOUR = 1, 2
+INVERT_MAX_IMAGES = 4096   # kInvertMaxImages of csrc/invert.h: images per sucre_invert_images call
 STORE_F32, STORE_U16MM, STORE_Z24, STORE_Z26 = 0, 1, 2, 3   # what the compaction chose (SUCRE_WS_STORE_FORMAT)
 
 
@@ -43,6 +45,15 @@ class LightGroupImage(C.Structure):
     """sucre_light_group_image_t"""
     _fields_ = [('ws', C.c_void_p), ('lws', C.c_void_p), ('H', C.c_int32), ('W', C.c_int32), ('n_views', C.c_int32),
                 ('reserved', C.c_int32)]
+
+
+class InvertImage(C.Structure):
+    """sucre_invert_image_t"""
+    _fields_ = [('depth', C.c_void_p), ('rgb', C.c_void_p), ('J', C.c_void_p), ('H', C.c_int32), ('W', C.c_int32),
+                ('Kinv', C.c_float * 9), ('reserved', C.c_int32)]
+
+
+assert C.sizeof(InvertImage) == 72
 
 
 # name -> (restype, argtypes); mirrors include/sucre_hip.h one to one (tests/test_abi.py checks both ways)
@@ -101,6 +112,8 @@ SIGNATURES = {
     'sucre_trim_scratch_bytes': (C.c_size_t, [_i, _i, _i]),
     'sucre_trim_outliers': (_i, [_vp, _i, _i, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
     'sucre_trim_outliers_ext': (_i, [_vp, _vp, _i, _i, _i, C.c_uint, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sucre_invert_bytes': (C.c_size_t, [_i]),
+    'sucre_invert_images': (_i, [_vp, _i, C.POINTER(InvertImage), C.POINTER(C.c_float), C.c_uint, _vp]),
     'sucre_light_group_bytes': (C.c_size_t, [_i]),
     'sucre_light_group_sums_offset': (C.c_int64, []),
     'sucre_light_group_init': (_i, [_vp, _i, C.POINTER(LightGroupImage), C.POINTER(C.c_float), _vp]),

@@ -6,6 +6,7 @@
 #include <mutex>
 #include <vector>
 
+#include "invert.h"
 #include "launch.h"
 
 namespace sucre {
@@ -661,6 +662,36 @@ int sucre_trim_outliers_ext(void *ws, const void *lws, int H, int W, int n_views
     return check_hip(launch_trim_ext(L, static_cast<uint8_t *>(ws), static_cast<const uint8_t *>(lws), flags, k_sigma, view_stats_dev,
                                      dropped_dev, view_dropped_dev, thresholds_dev, scratch_dev, static_cast<hipStream_t>(stream)),
                      "sucre_trim_outliers_ext");
+}
+
+/* ---- single-view inversion (sucre.py:66-77 with one observation per pixel: the image itself) ---------------------------- */
+
+size_t sucre_invert_bytes(int n_images) {
+    if (n_images < 1 || n_images > kInvertMaxImages) {
+        fail(SUCRE_ERR_RANGE, "n_images=%d outside [1,%d]", n_images, kInvertMaxImages);
+        return 0;
+    }
+    return invert_bytes(n_images);
+}
+
+int sucre_invert_images(void *table_dev, int n_images, const sucre_invert_image_t *images, const float *params, unsigned flags,
+                        void *stream) {
+    if (!table_dev || !aligned(table_dev, 256)) return fail(SUCRE_ERR_ARG, "invert table is NULL or not 256-byte aligned");
+    if (n_images < 1 || n_images > kInvertMaxImages) return fail(SUCRE_ERR_RANGE, "n_images=%d outside [1,%d]", n_images, kInvertMaxImages);
+    if (!images || !params) return fail(SUCRE_ERR_ARG, "images / params is NULL");
+    if (flags & ~(SUCRE_INVERT_LIGHT | SUCRE_INVERT_FLOAT_COLOUR)) return fail(SUCRE_ERR_ARG, "unknown invert flags 0x%x", flags);
+    const size_t rgb_align = (flags & SUCRE_INVERT_FLOAT_COLOUR) ? 16 : 4;
+    uint64_t blocks = 0;
+    for (int i = 0; i < n_images; ++i) {
+        const sucre_invert_image_t &im = images[i];
+        if (im.H < 1 || im.W < 1 || im.H > 32767 || im.W > 32767) return fail(SUCRE_ERR_ARG, "image %d: invalid size %dx%d (need 1..32767)", i, im.W, im.H);
+        if (!im.depth || !im.rgb || !im.J) return fail(SUCRE_ERR_ARG, "image %d: depth / rgb / J is NULL", i);
+        if (!aligned(im.depth, 16) || !aligned(im.J, 16) || !aligned(im.rgb, rgb_align))
+            return fail(SUCRE_ERR_ARG, "image %d: depth / J must be 16-byte aligned, rgb %d-byte aligned", i, (int)rgb_align);
+        blocks += invert_blocks(im.H, im.W);
+    }
+    if (blocks > 0x7fffffffull) return fail(SUCRE_ERR_RANGE, "%llu workgroups: the images of one call may hold 2^41 pixels together", (unsigned long long)blocks);
+    return check_hip(launch_invert(table_dev, n_images, images, params, flags, static_cast<hipStream_t>(stream)), "sucre_invert_images");
 }
 
 /* ---- shared water and light over the light-model images of a rank (sucre.py:54-61, 124-157) ------------------------ */

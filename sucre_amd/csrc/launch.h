@@ -87,6 +87,13 @@ hipError_t launch_trim(const Layout &L, uint8_t *ws, int fmt, double k_sigma, co
 hipError_t launch_trim_ext(const Layout &L, uint8_t *ws, const uint8_t *lws, unsigned flags, double k_sigma, const double *view_stats,
                            int32_t *dropped, int64_t *view_dropped, float *tau2, void *scratch, hipStream_t s);
 
+// single-view inversion (invert.h; invert.hip, the light variants in light.hip)
+size_t invert_bytes(int n_images);
+uint64_t invert_blocks(int H, int W);   // workgroups an HxW image takes in the launch grid
+hipError_t launch_invert(void *table, int n_images, const sucre_invert_image_t *images, const float *params, unsigned flags,
+                         hipStream_t s);
+hipError_t launch_invert_light(void *table, int n_images, uint32_t n_blocks, bool float_colour, hipStream_t s);
+
 // output stage (plot.hip)
 size_t select_scratch_bytes();
 hipError_t launch_select_ranks(const float *J, int H, int W, int n_ranks, const uint64_t *ranks, float *out, void *scratch,

@@ -19,6 +19,7 @@
 #include <mutex>
 #include "fit_math.h"
 #include "handoff.h"
+#include "invert.h"
 #include "residual.h"
 #include "trim.h"
 
@@ -849,6 +850,32 @@ hipError_t launch_trim_ext(const Layout &L, uint8_t *ws, const uint8_t *lws, uns
         else launch_trim_kernel(trim_kernel<false, SUCRE_EXT_POINTS, LightModel>, T, s);
     }
     launch_trim_view_sums(T, s);
+    return hipGetLastError();
+}
+
+// ---- single-view inversion with the light model (invert.h): l and z of the pixel's own camera point through light_obs, with the
+// range ||cP|| the match kernel would store -- the closed-form kernel's z = range + ||lP||.  The geometry is derived anew from the
+// 19 parameters the call left in the table's head, as launch_light_update_J derives it.
+struct InvertLight : LightModel {
+    static constexpr bool kLight = true;
+    __device__ __forceinline__ explicit InvertLight(const float *geom) : LightModel(geom) {}
+    template <bool kGradual>
+    __device__ __forceinline__ void lz(const float (&cP)[3], float zc, float &l, float &z) const {
+        const LightObs o = light_obs<kGradual>(cP, zc, R, tl, M);
+        l = o.l; z = o.z;
+    }
+};
+
+hipError_t launch_invert_light(void *table, int n_images, uint32_t n_blocks, bool float_colour, hipStream_t s) {
+    auto *base = static_cast<uint8_t *>(table);
+    const float *params = reinterpret_cast<const float *>(base + kInvertOffParams);
+    float *geom = reinterpret_cast<float *>(base + kInvertOffGeom);
+    static_assert(kInvertOffParams + kLightParams * sizeof(float) <= kInvertOffGeom && kInvertOffGeom + 16 * sizeof(float) <= kInvertOffDexp &&
+                  kInvertOffDexp + 72 * sizeof(double) <= kInvertOffTable, "parameters, geometry and twists fit the table's head");
+    hipLaunchKernelGGL(light_geometry_kernel, dim3(1), dim3(64), 0, s, params, geom, reinterpret_cast<double *>(base + kInvertOffDexp));
+    const auto *entries = reinterpret_cast<const InvertImage *>(base + kInvertOffTable);
+    if (float_colour) hipLaunchKernelGGL((invert_kernel<InvertLight, true>), dim3(n_blocks), dim3(256), 0, s, entries, n_images, params, geom);
+    else hipLaunchKernelGGL((invert_kernel<InvertLight, false>), dim3(n_blocks), dim3(256), 0, s, entries, n_images, params, geom);
     return hipGetLastError();
 }
 

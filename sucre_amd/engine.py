@@ -672,6 +672,57 @@ def plot_stretch(J: torch.Tensor, lo, hi) -> torch.Tensor:
     return out
 
 
+def invert_images(views: list, params, light: bool = False) -> list:
+    """Single-view inversion (``sucre_invert_images``): J of every view of ``views`` from its OWN depth map and colours at the
+    given water parameters -- ``SUCRe.update_J`` (sucre.py:66-77) with one observation per pixel, the image itself:
+    ``J = (I - l B (1 - e^(-gamma z))) a / a^2``, ``a = l e^(-beta z)``, ``z = ||K^-1 d [u+.5, v+.5, 1]||``, NaN where ``depth <= 0``;
+    bit for bit what ``Restoration.update_J`` leaves after ``match(view, [view])`` wherever the image matches itself in full.
+    No ``Restoration``, no matching, no neighbour.  ``params``: 9 host floats B, beta, gamma -- 19 with ``light`` (+ cam2light,
+    sigma) -- as an array or a CPU tensor.  The views may differ in size; their colours are all uint8 or all float32
+    (``ValueError`` otherwise).  One launch per 4096 views on the current stream, no host wait.  Returns one (H,W,3) float32
+    device tensor per view."""
+    views = list(views)
+    if not views:
+        raise ValueError('invert_images: no view')
+    dtypes = {v.rgb.dtype for v in views}
+    if len(dtypes) != 1 or not dtypes <= {torch.uint8, torch.float32}:
+        raise ValueError(f'invert_images: the views\' colours must be all uint8 or all float32, not {sorted(str(d) for d in dtypes)}')
+    if torch.is_tensor(params):
+        params = params.detach().cpu().numpy()
+    p = np.asarray(params, np.float64).reshape(-1)
+    need = 19 if light else 9
+    if p.size != need:
+        raise ValueError(f'invert_images: {need} parameters expected ({"B, beta, gamma, cam2light, sigma" if light else "B, beta, gamma"}), got {p.size}')
+    dev = views[0].depth.device
+    if dev.type != 'cuda' or any(v.depth.device != dev or v.rgb.device != dev for v in views):
+        raise _lib.SucreError('invert_images: the views must sit on one GPU device (there is no CPU fallback)')
+    lib = _lib.load()
+    pc = (C.c_float * need)(*p.astype(np.float32).tolist())
+    flags = (_lib.INVERT_LIGHT if light else 0) | (_lib.INVERT_FLOAT_COLOUR if torch.float32 in dtypes else 0)
+    outs = []
+    with torch.cuda.device(dev):
+        for i0 in range(0, len(views), _lib.INVERT_MAX_IMAGES):
+            chunk = views[i0:i0 + _lib.INVERT_MAX_IMAGES]
+            n = len(chunk)
+            arr = (_lib.InvertImage * n)()
+            keep = []
+            for e, v in zip(arr, chunk):
+                s = v.to_struct()   # (checks shapes and dtypes; Kinv derived the way the reference derives it, cached)
+                depth, rgb = v.depth, v.rgb
+                if depth.data_ptr() % 16 or rgb.data_ptr() % 16:   # views into larger buffers: the kernel loads 16 bytes at once
+                    depth, rgb = depth.clone(), rgb.clone()
+                    keep += [depth, rgb]
+                H, W = depth.shape
+                J = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+                e.depth, e.rgb, e.J, e.H, e.W, e.Kinv = depth.data_ptr(), rgb.data_ptr(), J.data_ptr(), H, W, s.Kinv
+                outs.append(J)
+            # (the table, like `keep`: torch's caching allocator keeps a freed block for this stream until the launches queued
+            # here have run)
+            table = torch.empty(lib.sucre_invert_bytes(n), dtype=torch.uint8, device=dev)
+            _lib.check(lib.sucre_invert_images(C.c_void_p(table.data_ptr()), n, arr, pc, flags, _stream_ptr()))
+    return outs
+
+
 def device_views_from_scene(scene, device='cuda') -> list[DeviceView]:
     """Uploads a synthetic scene (sucre_amd.synth) the way the loaders would: float32 depth, uint8 colour."""
     out = []

@@ -89,6 +89,24 @@ class SUCRe(torch.nn.Module):
         self.J = resto.J().to(self.B.device)
 
     @torch.no_grad()
+    def invert(self) -> 'SUCRe':
+        """Single-view ``update_J``: J from the module's OWN image -- its depth map and colours, no matches -- at the module's
+        current parameters (``engine.invert_images``; sucre.py:66-77 with the image as its only observation).  Sets the
+        attribute of a closed-form model, copies into the parameter of a J-parameter one.  Reads the parameters to the host
+        (one small device-to-host copy)."""
+        from . import engine
+        dev = self.B.device
+        if dev.type != 'cuda':
+            raise RuntimeError('invert runs on the GPU engine: move the model to a cuda device (SUCRe(...).to("cuda"))')
+        J = engine.invert_images([self.image.device_view(dev)], self.water_vector().cpu(), light=self.light_model)[0]
+        if self.use_closed_form:
+            self.J = J
+        else:
+            self.J.copy_(J)
+            self._J_unset = False
+        return self
+
+    @torch.no_grad()
     def residuals(self, matches_data: loader.MatchesData):
         """Per-pixel and per-view residuals of this model on ``matches_data`` (``engine.Restoration.residuals``): the
         module's water (and light) parameters go to the engine first, as in ``update_J``; J is the engine's own.  Returns
@@ -747,10 +765,136 @@ def _restore_pipeline(images, colmap_model, output_dir, in_flight, keep_matches,
             f.result()   # re-raises anything a writer thread hit
 
 
+# ---- --apply-water: a fitted water model applied to any image (single-view inversion) ------------------------------------
+APPLY_IMAGES_PER_LAUNCH = 32
+
+
+def water_shapes(light_model: bool) -> dict:
+    """Key -> shape of what a water file must hold (sucre.py:41-46)."""
+    shapes = {'B': (3, 1), 'beta': (3, 1), 'gamma': (3, 1)}
+    if light_model:
+        shapes.update(cam2light=(6,), sigma=(2, 2))
+    return shapes
+
+
+def check_water(water, light_model: bool = False, where: str = 'water') -> dict:
+    """The float32 CPU tensors ``B, beta, gamma`` (3,1) -- and ``cam2light`` (6), ``sigma`` (2,2) with the light model -- of a
+    mapping such as a loaded ``shared_water.pt`` or per-image ``<name>.pt``; other keys are ignored.  ``ValueError`` naming the
+    first key that is missing or mis-shaped."""
+    if not hasattr(water, 'keys'):
+        raise ValueError(f'{where} holds no parameters (a mapping with the keys {", ".join(water_shapes(light_model))} is expected)')
+    out = {}
+    for key, shape in water_shapes(light_model).items():
+        if key not in water:
+            raise ValueError(f"{where} holds no '{key}'" + (' (--light-model needs the light parameters too)' if key in ('cam2light', 'sigma') else ''))
+        t = water[key]
+        if not torch.is_tensor(t) or tuple(t.shape) != shape:
+            got = tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
+            raise ValueError(f"'{key}' in {where} is {got}, expected a tensor of shape {shape}")
+        out[key] = t.detach().to('cpu', torch.float32)
+    return out
+
+
+def read_water_file(path: Path, light_model: bool = False) -> dict:
+    """``check_water`` of a ``.pt`` file, for the command line: ``SystemExit`` naming the file and the key."""
+    try:
+        data = torch.load(path, map_location='cpu')
+    except Exception as e:
+        raise SystemExit(f'--apply-water: cannot read {path}: {e}')
+    try:
+        return check_water(data, light_model, where=str(path))
+    except ValueError as e:
+        raise SystemExit(f'--apply-water: {e}')
+
+
+def _write_applied(image: sfm.Image, J: Tensor, water: dict, light_model: bool, output_dir: Path, device) -> None:
+    """``<stem>_rgb.png``, ``<name>.pt`` and, with the light model, ``<stem>_vignetting.png`` of one inverted image.  No
+    ``_reconstruction.png``: the reconstruction of a single-view inversion is the input image."""
+    sucre = SUCRe(image=image, light_model=light_model, use_closed_form=True)
+    sucre.load_state_dict(water, strict=True)
+    sucre.J = J
+    stem = Path(image.name).stem
+    _save_png(sucre.plot_J(), output_dir / f'{stem}_rgb.png')
+    if light_model:
+        _save_png(sucre.to(device).plot_l(), output_dir / f'{stem}_vignetting.png')
+    torch.save({**sucre.cpu().state_dict(), 'J': J.detach().cpu()}, (output_dir / image.name).with_suffix('.pt'))
+
+
+def apply_water(images: list, colmap_model: sfm.COLMAPModel, output_dir: Path, water, light_model: bool = False,
+                device: str = 'cuda', in_flight: int = 2) -> None:
+    """Restores ``images`` (``sfm.Image`` objects or names of ``colmap_model``) with GIVEN water parameters instead of fitting
+    them: per image ``J = (I - l B (1 - e^(-gamma z))) a / a^2``, ``a = l e^(-beta z)``, from the image's own depth map
+    (``engine.invert_images``: ``update_J`` with the image as its only observation).  ``water``: a mapping with ``B, beta,
+    gamma`` (3,1) -- and ``cam2light`` (6), ``sigma`` (2,2) with ``light_model`` -- e.g. a loaded ``shared_water.pt`` or
+    ``<name>.pt``, or the path of one.  Only the target images are decoded (the next launch's while this one's run); nothing is
+    matched and no workspace is allocated.  Up to 32 images go into one launch on one of ``in_flight`` slots, and the
+    output files -- ``<stem>_rgb.png``, ``<name>.pt`` (the parameters and J), ``<stem>_vignetting.png`` with the light model --
+    are written by background threads."""
+    from . import engine
+    sfm.require_gpu(device, 'apply_water')
+    if isinstance(water, (str, Path)):
+        water = torch.load(water, map_location='cpu')
+    water = check_water(water, light_model)
+    params = torch.cat([water[k].flatten() for k in water_shapes(light_model)]).numpy()
+    images = [colmap_model[im] if isinstance(im, str) else im for im in images]
+    output_dir = Path(output_dir)
+    output_dir.mkdir(parents=True, exist_ok=True)
+    in_flight = max(1, int(in_flight))
+    chunks = [images[i:i + APPLY_IMAGES_PER_LAUNCH] for i in range(0, len(images), APPLY_IMAGES_PER_LAUNCH)]
+    if chunks:
+        loader.prefetch_device_views(chunks[0], device, background=True)
+    pending: list = []
+    written = []
+    with ThreadPoolExecutor(max_workers=max(1, int(os.environ.get('SUCRE_WRITER_THREADS', min(32, loader.effective_cpus() - 2)))),
+                            thread_name_prefix='sucre-write') as writers:
+        def finish(slot, chunk, Js):
+            with engine.in_flight_slot(slot, device, wait_for_caller=False):
+                torch.cuda.current_stream().synchronize()   # the writer threads work on another stream
+            for image, J in zip(chunk, Js):
+                written.append(writers.submit(_write_applied, image, J, water, light_model, output_dir, device))
+            while len(written) > 64:   # bound the memory held by queued outputs
+                written.pop(0).result()
+
+        for c, chunk in enumerate(chunks):
+            slot = c % in_flight
+            while pending and (len(pending) >= in_flight or pending[0][0] == slot):
+                finish(*pending.pop(0))
+            if c + 1 < len(chunks):
+                loader.prefetch_device_views(chunks[c + 1], device, background=True)
+            for image in chunk:
+                print(f'Restore {image.name} (given water parameters).')
+            views = [image.device_view(device) for image in chunk]   # waits only for an image that is still being decoded
+            with engine.in_flight_slot(slot, device, wait_for_caller=False):   # inputs: Image.device_view, complete
+                Js = engine.invert_images(views, params, light=light_model)
+            pending.append((slot, chunk, Js))
+        for item in pending:
+            finish(*item)
+        for f in written:
+            f.result()   # re-raises anything a writer thread hit
+
+
+def _refuse_apply_flags(args) -> None:
+    """What --apply-water does not combine with, refused before any file is opened."""
+    refused = [('--shared-water', bool(getattr(args, 'shared_water', False)), 'nothing is fitted, so nothing is shared'),
+               ('--trim-outliers', getattr(args, 'trim_outliers', None) is not None or getattr(args, 'trim_rounds', None) is not None,
+                'there is no fit to trim'),
+               ('--save-quality', bool(getattr(args, 'save_quality', False)), 'a single-view inversion has no residuals'),
+               ('--save-interval', args.save_interval is not None, 'there are no iterations to snapshot'),
+               ('--params-path', args.params_path is not None, 'the parameters come from the --apply-water file'),
+               ('--keep-matches', bool(args.keep_matches), 'nothing is matched')]
+    for flag, given, why in refused:
+        if given:
+            raise SystemExit(f'--apply-water: {flag} does not combine with it ({why}); drop one of the two flags')
+
+
 def parse_args(args: argparse.Namespace):
     """Runs the CLI request (sucre.py:222-261); with WORLD_SIZE > 1 each rank restores its shard of the images."""
     rank, local_rank, world = sdist.env_rank_world()
     shared = bool(getattr(args, 'shared_water', False))
+    apply = getattr(args, 'apply_water', None)
+    if apply is not None:
+        _refuse_apply_flags(args)
+        water = read_water_file(apply, args.light_model)
     _refuse_trim_flags(args)
     if shared:
         _refuse_shared_flags(args)
@@ -788,6 +932,10 @@ def parse_args(args: argparse.Namespace):
     args.output_dir.mkdir(parents=True, exist_ok=True)
     in_flight = int(os.environ.get('SUCRE_IMAGES_IN_FLIGHT', '2'))   # engine knob, not a reference flag
     survey = not shared and len(images) > 1 and in_flight > 1 and args.save_interval is None and str(device).startswith('cuda')
+    if apply is not None:
+        survey = len(images) > 1 and str(device).startswith('cuda')   # (the worker processes: decoding and PNG encoding)
+        print(f'--apply-water: single-view inversion at the parameters of {apply}; nothing is fitted or matched, so --num-iter, '
+              f'--learning-rate, --batch-size, --use-closed-form, --min-cover, --filter-images-path and --force-compute-matches are ignored.')
     if survey:
         # image files are decoded and the result pictures encoded by child processes (_pixelio.WorkerPool: CPU work in
         # the process that drives the GPU slows its launches down, and PIL's decoder does not scale over threads);
@@ -804,7 +952,9 @@ def parse_args(args: argparse.Namespace):
     if host_threads > 0:
         torch.set_num_threads(host_threads)
     try:
-        if shared:
+        if apply is not None:
+            apply_water(images, colmap_model, args.output_dir, water, light_model=args.light_model, device=device, in_flight=in_flight)
+        elif shared:
             restore_shared_water(images, colmap_model, args, image_list, device, request, rank, world)
         else:
             _run_request(args, images, image_list, colmap_model, device, survey, in_flight)
@@ -991,6 +1141,10 @@ def build_parser() -> argparse.ArgumentParser:
                           help='after the fit, drop every observation whose residual exceeds K times the RMS residual of its '
                                'channel (never a pixel\'s last ones) and fit again from the same start; also writes, per image, '
                                '<stem>_trim.pt and <stem>_trimmed.png and prints what each round dropped')
+    p.extras.add_argument('--apply-water', type=Path, metavar='PATH', default=argparse.SUPPRESS,
+                          help='do not fit: restore every image of the request from its own depth map with the B, beta, gamma (and, '
+                               'with --light-model, cam2light, sigma) of this .pt file -- a shared_water.pt or a <name>.pt of an '
+                               'earlier run; writes <stem>_rgb.png and <name>.pt (and <stem>_vignetting.png) per image')
     p.extras.add_argument('--trim-rounds', type=int, metavar='N', default=argparse.SUPPRESS,
                           help='rounds of --trim-outliers (1 unless given)')
     return p
