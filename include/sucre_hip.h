@@ -439,6 +439,53 @@ int sucre_trim_outliers_ext(void *ws, const void *lws, int H, int W, int n_views
                             float *thresholds_dev, void *scratch_dev, void *stream);
 
 /*
+ * ---- per-view gain compensation: estimate, divide out of the dense store ---------------------------------------------------
+ * The fit assumes that every view saw the scene with one camera response; auto-exposure, a strobe that has not recharged or a
+ * white-balance step makes ONE view brighter or darker than the rest in every pixel.  These calls estimate one multiplicative
+ * gain per kept view and channel at the fit as it stands, and divide it out of the dense store of a matched (or imported),
+ * finalised and fitted workspace.  One round:
+ *  1 Estimate (sucre_view_gains*; the workspaces are only read).  With the modelled intensity of sucre.adam's objective,
+ *        Ihat = l (J exp(-beta z) + B (1 - exp(-gamma z)))        SUCRe.forward, sucre.py:79-82, 144 (l, z: sucre.py:52-64),
+ *    evaluated exactly as sucre_fit_residuals* evaluates it (one device function serves both: the SUCRE_OBS_U16MM range, float32
+ *    colours, the light model's l, z from the parameters as they stand with the stored range), the gain of view k in channel c
+ *    is the least-squares answer to I = g Ihat over the view's observations at the CURRENT J and parameters:
+ *        g = S_IIhat / S_IhatIhat,   S_IIhat = sum I_c Ihat_c,   S_IhatIhat = sum Ihat_c^2.
+ *    The sums are float32 FMAs per (tile, view), then float64 over the view's tiles, all in a fixed order without atomics (two
+ *    calls give the same bits); a term whose Ihat is not finite contributes to neither sum.
+ *      sums_dev   float64 (n_views,7)  per view: observations, S_IIhat R, G, B, S_IhatIhat R, G, B; zeros for a view not kept
+ *      gains_dev  float64 (n_views,3)  g
+ *      inv_dev    float32 (n_views,3)  float32(1 / g)
+ *    g = 1 and inv = 1 exactly where there is nothing to estimate from: the view is not kept (SUCRE_WS_VIEW_KEEP), it has no
+ *    observation, or S_IhatIhat or the quotient is not finite and positive.  Otherwise g is clamped to [1 / limit, limit].
+ *    Gains are not normalised: at a converged fit the pooled gain is 1 by the optimality condition.
+ *  2 Apply (sucre_apply_view_gains*).  In every slot with z > 0 of every kept view with a match count, the three colours are
+ *    multiplied by the view's inv_c (positive and finite, as step 1 leaves them):
+ *      uint8 colours    k' = min(255, rintf(float(k) * inv_c)) -- one correctly rounded float32 multiply, then round half to even;
+ *      float32 colours  I' = I * inv_c, one float32 multiply, no clamp (SUCRE_FIT_EXT_COLOUR / SUCRE_FIT_EXT_BOTH: the planes of
+ *                       `lws` the colours live in; the uint8 colours of such a store are not read by anything and stay).
+ *    Empty slots, ranges, match counts, pixel bits, range pairs and views that are not kept are not touched.
+ *      view_clipped_dev  int64 (n_views)  uint8 values of the view that met the 255 clamp (0 for a view not kept, and for
+ *                                          float32 colours)
+ *  3 Re-finalise.  The CALLER then runs sucre_finalize_matches_fmt / _ext with the min_cover and format of the first time -- the
+ *    compacted store the fit reads is rebuilt from the dense one; nothing else changes, no view is gained or lost -- and then
+ *    sucre_fit_init* and the fit start over: the result is bit for bit that of a plain run on a store into which the corrected
+ *    colours were imported.  A uint8 store is re-rounded once per round; a float32-colour store is not rounded at all.
+ * Nothing in 1-3 waits on the host.  scratch_dev: sucre_gain_scratch_bytes() bytes of caller-owned device memory (one size for
+ * both calls), 16-byte aligned, untouched until the launches have run.  obs_format / flags: as for sucre_fit_residuals /
+ * sucre_fit_residuals_ext (the apply needs no range format).  Arguments are checked before anything is launched: NULL or
+ * misaligned pointers, a bad geometry and a limit that is not finite or is < 1 give SUCRE_ERR_ARG.
+ */
+size_t sucre_gain_scratch_bytes(int H, int W, int n_views);
+int sucre_view_gains(const void *ws, int H, int W, int n_views, int obs_format, double limit, double *gains_dev, float *inv_dev,
+                     double *sums_dev, void *scratch_dev, void *stream);
+int sucre_view_gains_ext(const void *ws, const void *lws, int H, int W, int n_views, unsigned flags /* 0 | SUCRE_FIT_EXT_COLOUR | SUCRE_FIT_EXT_BOTH */,
+                         double limit, double *gains_dev, float *inv_dev, double *sums_dev, void *scratch_dev, void *stream);
+int sucre_apply_view_gains(void *ws, int H, int W, int n_views, const float *inv_dev, int64_t *view_clipped_dev, void *scratch_dev,
+                           void *stream);
+int sucre_apply_view_gains_ext(void *ws, void *lws, int H, int W, int n_views, unsigned flags /* 0 | SUCRE_FIT_EXT_COLOUR | SUCRE_FIT_EXT_BOTH */,
+                               const float *inv_dev, int64_t *view_clipped_dev, void *scratch_dev, void *stream);
+
+/*
  * ---- single-view inversion: a fitted water (and light) model applied to any image -------------------------------------------
  * With ONE observation per pixel -- the image itself, through its own depth map -- SUCRe.update_J (sucre.py:66-77) is
  *     J = (I - l B (1 - exp(-gamma z))) a / a^2,   a = l exp(-beta z),   cP = Kinv d [u+.5, v+.5, 1] (loader.py:113),

@@ -112,6 +112,11 @@ SIGNATURES = {
     'sucre_trim_scratch_bytes': (C.c_size_t, [_i, _i, _i]),
     'sucre_trim_outliers': (_i, [_vp, _i, _i, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
     'sucre_trim_outliers_ext': (_i, [_vp, _vp, _i, _i, _i, C.c_uint, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sucre_gain_scratch_bytes': (C.c_size_t, [_i, _i, _i]),
+    'sucre_view_gains': (_i, [_vp, _i, _i, _i, _i, _d, _vp, _vp, _vp, _vp, _vp]),
+    'sucre_view_gains_ext': (_i, [_vp, _vp, _i, _i, _i, C.c_uint, _d, _vp, _vp, _vp, _vp, _vp]),
+    'sucre_apply_view_gains': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'sucre_apply_view_gains_ext': (_i, [_vp, _vp, _i, _i, _i, C.c_uint, _vp, _vp, _vp, _vp]),
     'sucre_invert_bytes': (C.c_size_t, [_i]),
     'sucre_invert_images': (_i, [_vp, _i, C.POINTER(InvertImage), C.POINTER(C.c_float), C.c_uint, _vp]),
     'sucre_light_group_bytes': (C.c_size_t, [_i]),

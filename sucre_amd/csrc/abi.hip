@@ -664,6 +664,90 @@ int sucre_trim_outliers_ext(void *ws, const void *lws, int H, int W, int n_views
                      "sucre_trim_outliers_ext");
 }
 
+/* ---- per-view gain compensation: estimate at the fit as it stands, divide out of the dense store ------------------------- */
+
+size_t sucre_gain_scratch_bytes(int H, int W, int n_views) {
+    Layout L;
+    if (!make_layout(H, W, n_views, &L)) {
+        fail(SUCRE_ERR_ARG, "invalid geometry H=%d W=%d n_views=%d", H, W, n_views);
+        return 0;
+    }
+    return gain_scratch_bytes(L);
+}
+
+}  // extern "C"
+
+namespace sucre {
+static int check_gain_args(double limit, const double *gains_dev, const float *inv_dev, const double *sums_dev, const void *scratch_dev) {
+    if (!std::isfinite(limit) || !(limit >= 1.0)) return fail(SUCRE_ERR_ARG, "limit must be finite and >= 1 (got %g)", limit);
+    if (!gains_dev || !inv_dev || !sums_dev || !scratch_dev) return fail(SUCRE_ERR_ARG, "gains_dev / inv_dev / sums_dev / scratch_dev is NULL");
+    if (!aligned(gains_dev, 8) || !aligned(inv_dev, 4) || !aligned(sums_dev, 8))
+        return fail(SUCRE_ERR_ARG, "gains_dev / inv_dev / sums_dev must be 8 / 4 / 8-byte aligned");
+    if (!aligned(scratch_dev, 16)) return fail(SUCRE_ERR_ARG, "scratch_dev must be 16-byte aligned");
+    return SUCRE_OK;
+}
+
+static int check_gain_apply_args(const float *inv_dev, const int64_t *view_clipped_dev, const void *scratch_dev) {
+    if (!inv_dev || !view_clipped_dev || !scratch_dev) return fail(SUCRE_ERR_ARG, "inv_dev / view_clipped_dev / scratch_dev is NULL");
+    if (!aligned(inv_dev, 4) || !aligned(view_clipped_dev, 8)) return fail(SUCRE_ERR_ARG, "inv_dev / view_clipped_dev must be 4 / 8-byte aligned");
+    if (!aligned(scratch_dev, 16)) return fail(SUCRE_ERR_ARG, "scratch_dev must be 16-byte aligned");
+    return SUCRE_OK;
+}
+
+static int check_ext_flags(unsigned flags) {
+    if (flags & ~(SUCRE_FIT_EXT_COLOUR | SUCRE_FIT_EXT_BOTH)) return fail(SUCRE_ERR_ARG, "unknown flags 0x%x", flags);
+    if ((flags & SUCRE_FIT_EXT_COLOUR) && (flags & SUCRE_FIT_EXT_BOTH)) return fail(SUCRE_ERR_ARG, "SUCRE_FIT_EXT_COLOUR and SUCRE_FIT_EXT_BOTH exclude each other");
+    return SUCRE_OK;
+}
+}  // namespace sucre
+
+extern "C" {
+
+int sucre_view_gains(const void *ws, int H, int W, int n_views, int obs_format, double limit, double *gains_dev, float *inv_dev,
+                     double *sums_dev, void *scratch_dev, void *stream) {
+    Layout L;
+    if (int rc = check_ws(ws, H, W, n_views, &L)) return rc;
+    if (obs_format != SUCRE_OBS_F32 && obs_format != SUCRE_OBS_U16MM && obs_format != SUCRE_OBS_F32_PLAIN && obs_format != SUCRE_OBS_F32_Z26)
+        return fail(SUCRE_ERR_ARG, "unknown observation format %d", obs_format);
+    if (int rc = check_gain_args(limit, gains_dev, inv_dev, sums_dev, scratch_dev)) return rc;
+    return check_hip(launch_view_gains(L, static_cast<const uint8_t *>(ws), obs_format == SUCRE_OBS_U16MM ? SUCRE_OBS_U16MM : SUCRE_OBS_F32,
+                                       limit, gains_dev, inv_dev, sums_dev, scratch_dev, static_cast<hipStream_t>(stream)),
+                     "sucre_view_gains");
+}
+
+int sucre_view_gains_ext(const void *ws, const void *lws, int H, int W, int n_views, unsigned flags, double limit, double *gains_dev,
+                         float *inv_dev, double *sums_dev, void *scratch_dev, void *stream) {
+    Layout L;
+    if (int rc = check_ws(ws, H, W, n_views, &L)) return rc;
+    if (int rc = check_lws(lws)) return rc;
+    if (int rc = check_ext_flags(flags)) return rc;
+    if (int rc = check_gain_args(limit, gains_dev, inv_dev, sums_dev, scratch_dev)) return rc;
+    return check_hip(launch_view_gains_ext(L, static_cast<const uint8_t *>(ws), static_cast<const uint8_t *>(lws), flags, limit, gains_dev,
+                                           inv_dev, sums_dev, scratch_dev, static_cast<hipStream_t>(stream)),
+                     "sucre_view_gains_ext");
+}
+
+int sucre_apply_view_gains(void *ws, int H, int W, int n_views, const float *inv_dev, int64_t *view_clipped_dev, void *scratch_dev,
+                           void *stream) {
+    Layout L;
+    if (int rc = check_ws(ws, H, W, n_views, &L)) return rc;
+    if (int rc = check_gain_apply_args(inv_dev, view_clipped_dev, scratch_dev)) return rc;
+    return check_hip(launch_apply_view_gains(L, static_cast<uint8_t *>(ws), inv_dev, view_clipped_dev, scratch_dev,
+                                             static_cast<hipStream_t>(stream)), "sucre_apply_view_gains");
+}
+
+int sucre_apply_view_gains_ext(void *ws, void *lws, int H, int W, int n_views, unsigned flags, const float *inv_dev,
+                               int64_t *view_clipped_dev, void *scratch_dev, void *stream) {
+    Layout L;
+    if (int rc = check_ws(ws, H, W, n_views, &L)) return rc;
+    if (int rc = check_lws(lws)) return rc;
+    if (int rc = check_ext_flags(flags)) return rc;
+    if (int rc = check_gain_apply_args(inv_dev, view_clipped_dev, scratch_dev)) return rc;
+    return check_hip(launch_apply_view_gains_ext(L, static_cast<uint8_t *>(ws), static_cast<uint8_t *>(lws), flags, inv_dev,
+                                                 view_clipped_dev, scratch_dev, static_cast<hipStream_t>(stream)),
+                     "sucre_apply_view_gains_ext");
+}
+
 /* ---- single-view inversion (sucre.py:66-77 with one observation per pixel: the image itself) ---------------------------- */
 
 size_t sucre_invert_bytes(int n_images) {

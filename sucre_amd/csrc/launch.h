@@ -87,6 +87,16 @@ hipError_t launch_trim(const Layout &L, uint8_t *ws, int fmt, double k_sigma, co
 hipError_t launch_trim_ext(const Layout &L, uint8_t *ws, const uint8_t *lws, unsigned flags, double k_sigma, const double *view_stats,
                            int32_t *dropped, int64_t *view_dropped, float *tau2, void *scratch, hipStream_t s);
 
+// per-view gains (gain.h; gain.hip, the estimate's variants with camera points in light.hip)
+size_t gain_scratch_bytes(const Layout &L);
+hipError_t launch_view_gains(const Layout &L, const uint8_t *ws, int fmt, double limit, double *gains, float *inv, double *sums,
+                             void *scratch, hipStream_t s);
+hipError_t launch_view_gains_ext(const Layout &L, const uint8_t *ws, const uint8_t *lws, unsigned flags, double limit, double *gains,
+                                 float *inv, double *sums, void *scratch, hipStream_t s);
+hipError_t launch_apply_view_gains(const Layout &L, uint8_t *ws, const float *inv, int64_t *view_clipped, void *scratch, hipStream_t s);
+hipError_t launch_apply_view_gains_ext(const Layout &L, uint8_t *ws, uint8_t *lws, unsigned flags, const float *inv,
+                                       int64_t *view_clipped, void *scratch, hipStream_t s);
+
 // single-view inversion (invert.h; invert.hip, the light variants in light.hip)
 size_t invert_bytes(int n_images);
 uint64_t invert_blocks(int H, int W);   // workgroups an HxW image takes in the launch grid

@@ -22,6 +22,7 @@
 #include "invert.h"
 #include "residual.h"
 #include "trim.h"
+#include "gain.h"
 
 namespace sucre {
 
@@ -851,6 +852,37 @@ hipError_t launch_trim_ext(const Layout &L, uint8_t *ws, const uint8_t *lws, uns
     }
     launch_trim_view_sums(T, s);
     return hipGetLastError();
+}
+
+// ---- per-view gains with extension planes (gain.h): the estimate's variants, the same geometry of the parameters as they stand;
+// the apply needs no model, only the planes the float32 colours live in ----
+hipError_t launch_view_gains_ext(const Layout &L, const uint8_t *ws, const uint8_t *lws, unsigned flags, double limit, double *gains,
+                                 float *inv, double *sums, void *scratch, hipStream_t s) {
+    LightLayout X;
+    make_light_layout(L, &X, (flags & SUCRE_FIT_EXT_BOTH) ? 2 : 1);
+    GainArgs G = gain_args(L, ws, limit, gains, inv, sums, scratch);
+    G.R.params = reinterpret_cast<const float *>(lws + X.off_params);
+    G.R.ext = lws + X.off_ext_dense;
+    G.R.ext2 = (flags & SUCRE_FIT_EXT_BOTH) ? lws + X.off_ext2_dense : nullptr;
+    if (flags & SUCRE_FIT_EXT_COLOUR) {
+        launch_gain_colour(G, s);
+    } else {
+        float *geom = static_cast<float *>(scratch);   // as launch_residuals_ext: into the head of the scratch buffer
+        hipLaunchKernelGGL(light_geometry_kernel, dim3(1), dim3(64), 0, s, G.R.params, geom, reinterpret_cast<double *>(geom + 16));
+        G.R.geom = geom;
+        if (flags & SUCRE_FIT_EXT_BOTH) launch_gain_kernel(gain_sum_kernel<false, SUCRE_EXT_POINTS_COLOUR, LightModel>, G, s);
+        else launch_gain_kernel(gain_sum_kernel<false, SUCRE_EXT_POINTS, LightModel>, G, s);
+    }
+    launch_gain_view_sums(G, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_apply_view_gains_ext(const Layout &L, uint8_t *ws, uint8_t *lws, unsigned flags, const float *inv,
+                                       int64_t *view_clipped, void *scratch, hipStream_t s) {
+    LightLayout X;
+    make_light_layout(L, &X, (flags & SUCRE_FIT_EXT_BOTH) ? 2 : 1);
+    uint8_t *colour = (flags & SUCRE_FIT_EXT_BOTH) ? lws + X.off_ext2_dense : (flags & SUCRE_FIT_EXT_COLOUR) ? lws + X.off_ext_dense : nullptr;
+    return launch_gain_apply(gain_apply_args(L, ws, colour, inv, view_clipped, scratch), s);
 }
 
 // ---- single-view inversion with the light model (invert.h): l and z of the pixel's own camera point through light_obs, with the

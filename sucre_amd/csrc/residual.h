@@ -107,10 +107,12 @@ struct ResidualWater {
     }
 };
 
-// r[c] of the lane's slot j of the chunk (0 for an empty slot); returns whether the slot holds an observation
+// The two numbers a residual is the difference of, for the lane's slot j of the chunk: the observed I[c] and the modelled
+// Ihat[c] -- whatever the slot holds, also where it is empty (the callers select).  Returns whether the slot holds an
+// observation.  residual_obs subtracts the two; the gain pass (gain.h) sums their products, from the very same numbers.
 template <bool kU16, int kExt, class Light>
-__device__ __forceinline__ bool residual_obs(const ResidualChunk &cur, int j, const Light &light, const ResidualWater &w,
-                                             const float (&J)[3], float (&r)[3]) {
+__device__ __forceinline__ bool residual_model(const ResidualChunk &cur, int j, const Light &light, const ResidualWater &w,
+                                               const float (&J)[3], float (&I)[3], float (&Ihat)[3]) {
     constexpr bool kPoints = (kExt & 1) != 0, kFloatColour = (kExt & 2) != 0;
     const bool valid = cur.zz[j] > 0.0f;   // an empty slot holds range 0
     float zc = cur.zz[j];
@@ -121,11 +123,22 @@ __device__ __forceinline__ bool residual_obs(const ResidualChunk &cur, int j, co
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float a = fast_exp2(z * w.nb[c]), g = fast_exp2(z * w.ng[c]);
-        float Ihat = __builtin_fmaf(J[c], a, w.B[c] * (1.0f - g));
-        if (kPoints) Ihat = l * Ihat;
-        const float I = kFloatColour ? (kPoints ? cur.f[c][j] : cur.p[c][j]) : unit_from_u8((cur.cc[c] >> (8 * j)) & 255u);
-        r[c] = valid ? I - Ihat : 0.0f;   // select, not multiply: J may be NaN where nothing is observed
+        float m = __builtin_fmaf(J[c], a, w.B[c] * (1.0f - g));
+        if (kPoints) m = l * m;
+        Ihat[c] = m;
+        I[c] = kFloatColour ? (kPoints ? cur.f[c][j] : cur.p[c][j]) : unit_from_u8((cur.cc[c] >> (8 * j)) & 255u);
     }
+    return valid;
+}
+
+// r[c] of the lane's slot j of the chunk (0 for an empty slot); returns whether the slot holds an observation
+template <bool kU16, int kExt, class Light>
+__device__ __forceinline__ bool residual_obs(const ResidualChunk &cur, int j, const Light &light, const ResidualWater &w,
+                                             const float (&J)[3], float (&r)[3]) {
+    float I[3], Ihat[3];
+    const bool valid = residual_model<kU16, kExt>(cur, j, light, w, J, I, Ihat);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) r[c] = valid ? I[c] - Ihat[c] : 0.0f;   // select, not multiply: J may be NaN where nothing is observed
     return valid;
 }
 

@@ -569,6 +569,64 @@ class Restoration:
         self.steps_done = 0
         return dropped, view_dropped, thresholds
 
+    def _gain_scratch(self) -> torch.Tensor:
+        nbytes = self.lib.sucre_gain_scratch_bytes(self.H, self.W, self.n_views)
+        if nbytes == 0:
+            raise _lib.SucreError(self.lib.sucre_last_error().decode())
+        # torch's caching allocator keeps the block for this stream until the launches queued here have run
+        return torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+
+    def view_gains(self, limit: float = 2.0):
+        """One multiplicative gain per kept view and channel at the fit as it stands (``sucre_view_gains``): the least-squares
+        answer ``g = sum I Ihat / sum Ihat^2`` to ``I = g Ihat`` over the view's observations, with
+        Ihat = l (J e^(-beta z) + B (1 - e^(-gamma z))) (sucre.py:79-82, 144) at the current parameters and J -- the number the
+        residual pass evaluates.  Returns ``(gains, inv, sums)`` on the device: float64 (n_views,3) clamped to
+        [1 / limit, limit], float32 (n_views,3) = float32(1 / g), float64 (n_views,7) per view {observations, sum I Ihat R, G, B,
+        sum Ihat^2 R, G, B}.  g = 1 and inv = 1 exactly for a view that is not kept or has nothing to estimate from.  A pure
+        read, enqueued on the current stream without a host wait; two calls give the same bits."""
+        limit = float(limit)
+        if not (np.isfinite(limit) and limit >= 1.0):
+            raise ValueError(f'view_gains: limit must be finite and >= 1, not {limit!r}')
+        gains = torch.empty((self.n_views, 3), dtype=torch.float64, device=self.device)
+        inv = torch.empty((self.n_views, 3), dtype=torch.float32, device=self.device)
+        sums = torch.empty((self.n_views, 7), dtype=torch.float64, device=self.device)
+        scratch = self._gain_scratch()
+        ws, H, W, n = self._geom
+        outs = (limit, C.c_void_p(gains.data_ptr()), C.c_void_p(inv.data_ptr()), C.c_void_p(sums.data_ptr()), C.c_void_p(scratch.data_ptr()))
+        with torch.cuda.device(self.device):
+            if self.lws is not None:
+                _lib.check(self.lib.sucre_view_gains_ext(ws, C.c_void_p(self.lws.data_ptr()), H, W, n, self._ext_flag, *outs, self._sp()))
+            else:
+                _lib.check(self.lib.sucre_view_gains(ws, H, W, n, self._fmt, *outs, self._sp()))
+        return gains, inv, sums
+
+    def apply_view_gains(self, inv: torch.Tensor) -> torch.Tensor:
+        """Divides per-view gains out of the store (``sucre_apply_view_gains``): every observation of a kept view k has its
+        colours multiplied by ``inv[k]`` (float32 (n_views,3) on the device, what ``view_gains`` returned) -- uint8 colours
+        become min(255, rintf(float(k) inv_c)), float32 colours I inv_c -- and the store is finalised again with the
+        ``min_cover`` of the last ``match`` / ``import_matches``, which rebuilds what the fit reads; ranges, counts and the set of
+        kept views stay.  Returns ``view_clipped`` on the device: int64 (n_views), the uint8 values per view that met the 255
+        clamp.  Everything is enqueued on the current stream without a host wait.  The fit must start over: ``steps_done`` is 0
+        and the caller calls ``fit_init`` again -- with the same initial values the refit is bit for bit a plain run on a store
+        into which the corrected colours were imported."""
+        if self.min_cover is None:
+            raise _lib.SucreError('apply_view_gains: call match() or import_matches() first')
+        assert inv.is_cuda and inv.dtype == torch.float32 and inv.is_contiguous() and inv.shape == (self.n_views, 3)
+        view_clipped = torch.empty(self.n_views, dtype=torch.int64, device=self.device)
+        scratch = self._gain_scratch()
+        ws, H, W, n = self._geom
+        args = (C.c_void_p(inv.data_ptr()), C.c_void_p(view_clipped.data_ptr()), C.c_void_p(scratch.data_ptr()))
+        with torch.cuda.device(self.device):
+            if self.lws is not None:
+                lws = C.c_void_p(self.lws.data_ptr())
+                _lib.check(self.lib.sucre_apply_view_gains_ext(ws, lws, H, W, n, self._ext_flag, *args, self._sp()))
+                _lib.check(self.lib.sucre_finalize_matches_ext(ws, lws, H, W, n, self.min_cover, self._ext_mode, self._sp()))
+            else:
+                _lib.check(self.lib.sucre_apply_view_gains(ws, H, W, n, *args, self._sp()))
+                _lib.check(self.lib.sucre_finalize_matches_fmt(ws, H, W, n, self.min_cover, self._fmt, self._sp()))
+        self.steps_done = 0
+        return view_clipped
+
     def params(self) -> torch.Tensor:
         """B[3], beta[3], gamma[3] (+ cam2light[6], sigma[4] with the light model) on the device."""
         if self.light or self.float_colour:

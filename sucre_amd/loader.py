@@ -559,10 +559,12 @@ class MatchesFile:
             return md
         return MatchesData(restoration=self._need(), image_list=self.image_list)
 
-    def save(self, survivors: bool = False) -> Path:
+    def save(self, survivors: bool = False, colour_scales: list = ()) -> Path:
         """Persists the explicit match lists in the reference's layout (used by --keep-matches).  ``survivors``: only the
         matches whose observation is still in the store (after ``Restoration.trim_outliers``; the match map is geometry and
-        keeps the dropped ones)."""
+        keeps the dropped ones).  ``colour_scales``: float32 (n_views, 3) per round of ``Restoration.apply_view_gains``, in
+        order -- the colours are taken through the store's own rule (uint8: min(255, rint(float32(k) * inv)) per round;
+        float32: one multiply per round), so the file holds what the corrected store holds."""
         r = self._need()
         keep = r.view_keep().cpu().numpy().astype(bool)
         groups = {}
@@ -578,6 +580,10 @@ class MatchesFile:
             u2, v2 = p2 % W2, torch.div(p2, W2, rounding_mode='floor')
             view = im.device_view(r.device)
             I = view.rgb[v2, u2]
+            for scale in colour_scales:
+                inv = scale[k].to(I.device, torch.float32)
+                I = (I * inv if I.dtype == torch.float32 else
+                     torch.clamp(torch.round(I.to(torch.float32) * inv), max=255.0).to(torch.uint8))
             I = (I if I.dtype == torch.float32 else (I.to(torch.float64) / 255).to(torch.float32)).T
             groups[im.name] = dict(u1=u1.short().cpu().numpy(), v1=v1.short().cpu().numpy(),
                                    u2=u2.short().cpu().numpy(), v2=v2.short().cpu().numpy(),

@@ -312,7 +312,8 @@ def snapshot_stops(num_iter: int, save_interval: int | None) -> list[tuple[int, 
 
 def adam(sucre: SUCRe, matches_data: loader.MatchesData, lr: float = 0.05, num_iter: int = 200, batch_size: int = 1,
          save_dir: Path = None, save_interval: int = None, device: str = 'cpu', verbose: bool = True,
-         trim_outliers: float = None, trim_rounds: int = 1) -> SUCRe:
+         trim_outliers: float = None, trim_rounds: int = 1, view_gains: bool = False, gain_rounds: int = 1,
+         gain_limit: float = 2.0) -> SUCRe:
     """``num_iter`` steps of ``torch.optim.Adam(lr)`` on the least-squares cost (sucre.py:124-157).
 
     ``batch_size`` is accepted for compatibility: the engine always uses the full batch in one pass, which is
@@ -320,10 +321,17 @@ def adam(sucre: SUCRe, matches_data: loader.MatchesData, lr: float = 0.05, num_i
 
     ``trim_outliers`` (not a reference argument): after the fit, ``trim_rounds`` rounds of trim -> fit anew from the same
     initial values with the same ``num_iter`` (``_enqueue_trim``); the model ends with the last fit, and ``sucre._trim`` holds
-    every round's record."""
+    every round's record.
+
+    ``view_gains`` (not a reference argument): after the fit, ``gain_rounds`` rounds of estimate the per-view gains -> divide
+    them out of the store -> fit anew from the same initial values with the same ``num_iter`` (``_enqueue_gains``);
+    ``sucre._gains`` holds every round's record.  Not together with ``trim_outliers``."""
     _check_trim(trim_outliers, trim_rounds)
+    _check_gains(view_gains, gain_rounds, gain_limit, trim_outliers)
     if trim_outliers is not None and save_dir is not None and save_interval is not None:
         raise ValueError('trim_outliers does not combine with save_interval snapshots')
+    if view_gains and save_dir is not None and save_interval is not None:
+        raise ValueError('view_gains does not combine with save_interval snapshots')
     print(f'Solve least squares with Adam optimizer ({num_iter} iterations).')
     resto = _adam_begin(sucre, matches_data)
     done = 0
@@ -345,6 +353,15 @@ def adam(sucre: SUCRe, matches_data: loader.MatchesData, lr: float = 0.05, num_i
         for i in range(int(trim_rounds)):   # (no snapshot stops here: nothing has been pulled into the model yet, so
             sucre._trim.append(_enqueue_trim(resto, trim_outliers))   # _adam_begin starts from the same values again)
             print(f'Solve least squares with Adam optimizer ({num_iter} iterations) after trim round {i + 1}.')
+            _adam_begin(sucre, matches_data)
+            trace = resto.fit(num_iter, lr=lr, use_closed_form=sucre.use_closed_form)
+            if verbose:
+                _log_trace(trace.cpu().numpy(), 0)
+    if view_gains:
+        sucre._gains = []
+        for i in range(int(gain_rounds)):
+            sucre._gains.append(_enqueue_gains(resto, gain_limit))
+            print(f'Solve least squares with Adam optimizer ({num_iter} iterations) after gain round {i + 1}.')
             _adam_begin(sucre, matches_data)
             trace = resto.fit(num_iter, lr=lr, use_closed_form=sucre.use_closed_form)
             if verbose:
@@ -484,6 +501,61 @@ def _write_trim(job) -> None:
               f'(threshold R {t[0]:.4f} G {t[1]:.4f} B {t[2]:.4f})')
 
 
+# ---- --view-gains: one multiplicative gain per view and channel, estimated on the device and divided out; fit again ------
+def _check_gains(view_gains, gain_rounds, gain_limit, trim_outliers=None) -> None:
+    if not view_gains:
+        return
+    if int(gain_rounds) < 1:
+        raise ValueError(f'gain_rounds must be >= 1, not {gain_rounds!r}')
+    if not (np.isfinite(float(gain_limit)) and float(gain_limit) >= 1):
+        raise ValueError(f'gain_limit must be finite and >= 1, not {gain_limit!r}')
+    if trim_outliers is not None:
+        raise ValueError('view_gains does not combine with trim_outliers')
+
+
+def _enqueue_gains(resto, limit: float) -> dict:
+    """One round on the current stream, no host wait (``Restoration.view_gains``, then ``apply_view_gains`` with what it
+    estimated); the fit must be started over.  The round's record, on the device."""
+    kept = resto.view_keep().clone()
+    gains, inv, sums = resto.view_gains(limit)
+    view_clipped = resto.apply_view_gains(inv)
+    return {'gains': gains, 'inv': inv, 'sums': sums, 'view_clipped': view_clipped, 'view_kept': kept, 'limit': float(limit)}
+
+
+def _enqueue_gain_refits(jobs: list, fit) -> None:
+    """The rounds of ``--view-gains`` for images whose first fit is enqueued: estimate and apply, ``fit_init`` with the initial
+    values of the first fit, and ``fit(jobs)`` -- the caller's way of fitting them, alone or in a batch launch -- again."""
+    for job in jobs:
+        job.gains = [] if job.view_gains else None
+    for i in range(max((int(j.gain_rounds) for j in jobs if j.view_gains), default=0)):
+        again = [j for j in jobs if j.view_gains and i < int(j.gain_rounds)]
+        for job in again:
+            job.gains.append(_enqueue_gains(job.resto, job.gain_limit))
+            _adam_begin(job.sucre, job.matches_data, params0=job.params0)
+        fit(again)
+
+
+def _write_gains(job) -> None:
+    """``<stem>_gains.pt`` and one printed line per round."""
+    rounds = job.gains   # host tensors (_restore_finish)
+    stem = Path(job.image.name).stem
+    image_list = getattr(job.matches_data, 'image_list', None)
+    n_views = int(rounds[0]['gains'].shape[0])
+    views = [im.name for im in image_list] if image_list else [str(k) for k in range(n_views)]
+    gain = torch.ones((n_views, 3), dtype=torch.float64)
+    for r in rounds:
+        gain = gain * r['gains']
+    torch.save({'views': views, 'gains': torch.stack([r['gains'] for r in rounds]), 'sums': torch.stack([r['sums'] for r in rounds]),
+                'view_clipped': torch.stack([r['view_clipped'] for r in rounds]),
+                'view_kept': torch.stack([r['view_kept'] != 0 for r in rounds]), 'gain': gain, 'limit': rounds[0]['limit']},
+               job.output_dir / f'{stem}_gains.pt')
+    for i, r in enumerate(rounds):
+        g = r['gains'].numpy()
+        worst = int(np.abs(np.log(g)).max(axis=1).argmax())
+        print(f'{job.image.name}: gain round {i + 1}: largest correction in view {views[worst]} '
+              f'(gain R {g[worst, 0]:.4f} G {g[worst, 1]:.4f} B {g[worst, 2]:.4f}; {int(r["view_clipped"].sum())} values clipped)')
+
+
 class _Job:
     """One image between ``_restore_submit`` (everything enqueued, nothing waited for) and ``_restore_finish``."""
 
@@ -495,7 +567,7 @@ def _restore_submit(image: sfm.Image, colmap_model: sfm.COLMAPModel, output_dir:
                     use_closed_form: bool, min_cover: float, image_list: list[sfm.Image], lr: float, num_iter: int,
                     params_path: Path, force_compute_matches: bool, num_workers: int, device: str,
                     defer_checks: bool = False, save_quality: bool = False, trim_outliers: float = None,
-                    trim_rounds: int = 1) -> _Job:
+                    trim_rounds: int = 1, view_gains: bool = False, gain_rounds: int = 1, gain_limit: float = 2.0) -> _Job:
     """Stages of sucre.py:160-210 up to and including the enqueued fit; the trace and J stay on the device.
     ``defer_checks``: the integrity verdicts and the observation count stay on the device until ``_restore_finish``
     reads them with the results -- waiting for them here would make the host wait for the matching, which shares the
@@ -542,7 +614,8 @@ def _restore_submit(image: sfm.Image, colmap_model: sfm.COLMAPModel, output_dir:
     return _Job(image=image, sucre=sucre, matches_file=matches_file, matches_data=matches_data,
                 matches_path=matches_path, output_dir=output_dir, lr=lr, num_iter=num_iter, trace=None,
                 deferred_checks=defer_checks, params0=params0, save_quality=bool(save_quality), quality=None,
-                trim_outliers=trim_outliers, trim_rounds=int(trim_rounds), trim=None)
+                trim_outliers=trim_outliers, trim_rounds=int(trim_rounds), trim=None,
+                view_gains=bool(view_gains), gain_rounds=int(gain_rounds), gain_limit=float(gain_limit), gains=None)
 
 
 def _report_observations(image: sfm.Image, n_obs: int) -> None:
@@ -561,6 +634,7 @@ def _restore_enqueue_fit(job: _Job) -> None:
             j.trace = j.resto.fit(j.num_iter, lr=j.lr, use_closed_form=j.sucre.use_closed_form)
     fit([job])
     _enqueue_trim_refits([job], fit)
+    _enqueue_gain_refits([job], fit)
     _enqueue_quality(job, resto)
 
 
@@ -599,10 +673,12 @@ def _restore_enqueue_fits(jobs: list) -> None:
                 j.trace = t
         fit_together(members)
         _enqueue_trim_refits(members, fit_together)
+        _enqueue_gain_refits(members, fit_together)
         for j in members:
             _enqueue_quality(j, j.resto)
     fit_alone(singles)
     _enqueue_trim_refits(singles, fit_alone)
+    _enqueue_gain_refits(singles, fit_alone)
     for job in singles:
         _enqueue_quality(job, job.resto)
 
@@ -652,9 +728,13 @@ def _restore_finish(job: _Job, keep_matches: bool, writers: ThreadPoolExecutor |
         job.quality = tuple(t.cpu() for t in job.quality)
     if job.trim is not None:
         job.trim = [{k: (v.cpu() if torch.is_tensor(v) else v) for k, v in r.items()} for r in job.trim]
+    if job.gains is not None:
+        job.gains = [{k: (v.cpu() if torch.is_tensor(v) else v) for k, v in r.items()} for r in job.gains]
     if keep_matches and job.matches_file.restoration._views_dev is not None:   # freshly matched (not loaded from this
         if job.trim is not None:                                               # very file); needs the live workspace
             print(f'Keep {job.matches_file.save(survivors=True)} (the observations that survived the trim).')
+        elif job.gains is not None:
+            print(f'Keep {job.matches_file.save(colour_scales=[r["inv"] for r in job.gains])} (colours with the view gains divided out).')
         else:
             print(f'Keep {job.matches_file.save()}.')
     if writers is None:
@@ -674,6 +754,8 @@ def _write_outputs(job: _Job, keep_matches: bool, log: bool = False) -> None:
         _write_quality(job)
     if job.trim is not None:
         _write_trim(job)
+    if job.gains is not None:
+        _write_gains(job)
     torch.save({**sucre.cpu().state_dict(), 'J': sucre.J.detach().cpu()},
                (job.output_dir / job.image.name).with_suffix('.pt'))
     if not keep_matches and job.matches_path.exists():
@@ -694,22 +776,30 @@ def restore_image(image: sfm.Image, colmap_model: sfm.COLMAPModel, output_dir: P
 
 def _restore_one(image, colmap_model, output_dir, light_model, use_closed_form, min_cover, image_list, lr, num_iter, batch_size,
                  save_interval, params_path, force_compute_matches, keep_matches, num_workers, device, save_quality: bool = False,
-                 trim_outliers: float = None, trim_rounds: int = 1):
+                 trim_outliers: float = None, trim_rounds: int = 1, view_gains: bool = False, gain_rounds: int = 1,
+                 gain_limit: float = 2.0):
     """``restore_image`` plus what its pinned signature has no room for (``save_quality``: --save-quality; ``trim_outliers``,
-    ``trim_rounds``: --trim-outliers, --trim-rounds)."""
+    ``trim_rounds``: --trim-outliers, --trim-rounds; ``view_gains``, ``gain_rounds``, ``gain_limit``: --view-gains, --gain-rounds,
+    --gain-limit)."""
     sfm.require_gpu(device, 'restore_image')
     _check_trim(trim_outliers, trim_rounds)
+    _check_gains(view_gains, gain_rounds, gain_limit, trim_outliers)
     if trim_outliers is not None and save_interval is not None:
         raise ValueError('trim_outliers does not combine with save_interval snapshots')
+    if view_gains and save_interval is not None:
+        raise ValueError('view_gains does not combine with save_interval snapshots')
     job = _restore_submit(image, colmap_model, output_dir, light_model, use_closed_form, min_cover, image_list, lr,
                           num_iter, params_path, force_compute_matches, num_workers, device, save_quality=save_quality,
-                          trim_outliers=trim_outliers, trim_rounds=trim_rounds)
+                          trim_outliers=trim_outliers, trim_rounds=trim_rounds, view_gains=view_gains, gain_rounds=gain_rounds,
+                          gain_limit=gain_limit)
     if save_quality:
         job.sucre._quality_wanted = True   # adam enqueues the pass behind its last fit
     adam(sucre=job.sucre, matches_data=job.matches_data, lr=lr, num_iter=num_iter, batch_size=batch_size,
-         save_dir=job.output_dir, save_interval=save_interval, device=device, trim_outliers=trim_outliers, trim_rounds=trim_rounds)
+         save_dir=job.output_dir, save_interval=save_interval, device=device, trim_outliers=trim_outliers, trim_rounds=trim_rounds,
+         view_gains=view_gains, gain_rounds=gain_rounds, gain_limit=gain_limit)
     job.quality = job.sucre.__dict__.pop('_quality', None)
     job.trim = job.sucre.__dict__.pop('_trim', None)
+    job.gains = job.sucre.__dict__.pop('_gains', None)
     return _restore_finish(job, keep_matches)
 
 
@@ -721,8 +811,10 @@ def restore_images(images: list[sfm.Image], colmap_model: sfm.COLMAPModel, outpu
     launches nor the PNG encoding leave the GPU idle.  Per-image results are the same bits as ``restore_image``
     (each image has its own workspace and stream; nothing is shared).  ``fit_batch`` consecutive images share a slot and
     their fits one launch per iteration (``fit_batch_size``; same bits again).  ``trim_outliers=None, trim_rounds=1`` (in
-    ``kw``): the rounds of --trim-outliers, enqueued with the image behind its first fit, no host wait added."""
+    ``kw``): the rounds of --trim-outliers, enqueued with the image behind its first fit, no host wait added; ``view_gains=False,
+    gain_rounds=1, gain_limit=2.0``: those of --view-gains, likewise."""
     _check_trim(kw.get('trim_outliers'), kw.get('trim_rounds', 1))
+    _check_gains(kw.get('view_gains', False), kw.get('gain_rounds', 1), kw.get('gain_limit', 2.0), kw.get('trim_outliers'))
     pending: list[tuple[int, list]] = []
     written = []
     if fit_batch is None:
@@ -878,6 +970,8 @@ def _refuse_apply_flags(args) -> None:
     refused = [('--shared-water', bool(getattr(args, 'shared_water', False)), 'nothing is fitted, so nothing is shared'),
                ('--trim-outliers', getattr(args, 'trim_outliers', None) is not None or getattr(args, 'trim_rounds', None) is not None,
                 'there is no fit to trim'),
+               ('--view-gains', bool(getattr(args, 'view_gains', False)) or getattr(args, 'gain_rounds', None) is not None
+                or getattr(args, 'gain_limit', None) is not None, 'there is no fit to estimate gains from'),
                ('--save-quality', bool(getattr(args, 'save_quality', False)), 'a single-view inversion has no residuals'),
                ('--save-interval', args.save_interval is not None, 'there are no iterations to snapshot'),
                ('--params-path', args.params_path is not None, 'the parameters come from the --apply-water file'),
@@ -896,6 +990,7 @@ def parse_args(args: argparse.Namespace):
         _refuse_apply_flags(args)
         water = read_water_file(apply, args.light_model)
     _refuse_trim_flags(args)
+    _refuse_gain_flags(args)
     if shared:
         _refuse_shared_flags(args)
     # torch's CPU thread pool follows the machine's CPU count; inside a container with a CPU quota that many spinning
@@ -971,6 +1066,8 @@ def _run_request(args, images, image_list, colmap_model, device, survey: bool, i
     trim = getattr(args, 'trim_outliers', None)
     if trim is not None:
         quality.update(trim_outliers=float(trim), trim_rounds=int(getattr(args, 'trim_rounds', 1)))
+    if getattr(args, 'view_gains', False):
+        quality.update(view_gains=True, gain_rounds=int(getattr(args, 'gain_rounds', 1)), gain_limit=float(getattr(args, 'gain_limit', 2.0)))
     if survey:
         restore_images(images, colmap_model, args.output_dir, in_flight=in_flight, keep_matches=args.keep_matches,
                        device=device, light_model=args.light_model, use_closed_form=args.use_closed_form,
@@ -1007,6 +1104,27 @@ def _refuse_trim_flags(args) -> None:
         raise SystemExit('--trim-outliers: a shared fit (--shared-water) is not trimmed; drop one of the two flags')
     if args.save_interval is not None:
         raise SystemExit('--trim-outliers: --save-interval snapshots are not supported for a trimmed refit; drop one of the two flags')
+
+
+def _refuse_gain_flags(args) -> None:
+    """What --view-gains does not combine with (and what it takes), refused before anything is decoded or matched."""
+    rounds, limit = getattr(args, 'gain_rounds', None), getattr(args, 'gain_limit', None)
+    if not getattr(args, 'view_gains', False):
+        if rounds is not None:
+            raise SystemExit('--gain-rounds: only with --view-gains')
+        if limit is not None:
+            raise SystemExit('--gain-limit: only with --view-gains')
+        return
+    if rounds is not None and rounds < 1:
+        raise SystemExit(f'--gain-rounds: N must be >= 1, not {rounds}')
+    if limit is not None and not (np.isfinite(limit) and limit >= 1):
+        raise SystemExit(f'--gain-limit: L must be finite and >= 1, not {limit}')
+    if getattr(args, 'shared_water', False):
+        raise SystemExit('--view-gains: a shared fit (--shared-water) is not compensated; drop one of the two flags')
+    if args.save_interval is not None:
+        raise SystemExit('--view-gains: --save-interval snapshots are not supported for a compensated refit; drop one of the two flags')
+    if getattr(args, 'trim_outliers', None) is not None:
+        raise SystemExit('--view-gains: --trim-outliers is not supported together with it yet; drop one of the two flags')
 
 
 def _refuse_shared_flags(args) -> None:
@@ -1147,6 +1265,15 @@ def build_parser() -> argparse.ArgumentParser:
                                'earlier run; writes <stem>_rgb.png and <name>.pt (and <stem>_vignetting.png) per image')
     p.extras.add_argument('--trim-rounds', type=int, metavar='N', default=argparse.SUPPRESS,
                           help='rounds of --trim-outliers (1 unless given)')
+    p.extras.add_argument('--view-gains', action='store_true', default=argparse.SUPPRESS,
+                          help='after the fit, estimate one brightness gain per neighbour view and channel (exposure, strobe or '
+                               'white-balance differences between views), divide it out of that view\'s observations and fit again '
+                               'from the same start; also writes, per image, <stem>_gains.pt and prints the largest correction of '
+                               'each round')
+    p.extras.add_argument('--gain-rounds', type=int, metavar='N', default=argparse.SUPPRESS,
+                          help='rounds of --view-gains (1 unless given)')
+    p.extras.add_argument('--gain-limit', type=float, metavar='L', default=argparse.SUPPRESS,
+                          help='gains of --view-gains are kept within [1/L, L] (2 unless given)')
     return p
 
 
