@@ -356,10 +356,14 @@ int sucre_finalize_matches_ext(void *ws, void *lws, int H, int W, int n_views, d
  * With the light model the range of an observation IS the norm of its camera point (sucre.py:53, compute_l_z): the
  * J-parameter light kernel forms it from the point instead of reading the stored range, and takes a non-zero cP.z (the
  * depth) as the mark of a real observation.
+ * sucre_export_view_ext2 returns the SECOND set of planes of view k the same way: the float32 colours of a store that keeps
+ * both sets.  It is valid only for an `lws` of sucre_light_workspace_bytes_ext(.., SUCRE_EXT_POINTS_COLOUR) bytes: a smaller
+ * extension workspace has no second set, and the call would read past its end.
  */
 int sucre_import_view_ext(void *ws, void *lws, int H, int W, int n_views, int k, const int16_t *u1_dev, const int16_t *v1_dev,
                           const float *z_dev, const uint8_t *rgb_dev, const float *ext_dev, int64_t n, int ext_mode, void *stream);
 int sucre_export_view_ext(const void *ws, const void *lws, int H, int W, int n_views, int k, float *planes_dev, void *stream);
+int sucre_export_view_ext2(const void *ws, const void *lws, int H, int W, int n_views, int k, float *planes_dev, void *stream);
 int sucre_finalize_matches_light(void *ws, void *lws, int H, int W, int n_views, double min_cover, void *stream);
 int sucre_fit_init_light(void *ws, void *lws, int H, int W, int n_views, const uint8_t *rgb1_dev, const float *depth1_dev,
                          const float *params0, const float *J0_dev, void *stream);

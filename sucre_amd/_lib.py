@@ -101,6 +101,7 @@ SIGNATURES = {
     'sucre_finalize_matches_ext': (_i, [_vp, _vp, _i, _i, _i, _d, _i, _vp]),
     'sucre_import_view_ext': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _vp]),
     'sucre_export_view_ext': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'sucre_export_view_ext2': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     'sucre_finalize_matches_light': (_i, [_vp, _vp, _i, _i, _i, _d, _vp]),
     'sucre_fit_init_light': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, C.POINTER(C.c_float), _vp, _vp]),
     'sucre_update_J_light': (_i, [_vp, _vp, _i, _i, _i, _vp]),

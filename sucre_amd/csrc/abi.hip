@@ -498,6 +498,17 @@ int sucre_export_view_ext(const void *ws, const void *lws, int H, int W, int n_v
                                             planes_dev, static_cast<hipStream_t>(stream)), "sucre_export_view_ext");
 }
 
+int sucre_export_view_ext2(const void *ws, const void *lws, int H, int W, int n_views, int k, float *planes_dev, void *stream) {
+    Layout L;
+    if (int rc = check_ws(ws, H, W, n_views, &L)) return rc;
+    if (int rc = check_lws(lws)) return rc;
+    if (k < 0 || k >= n_views) return fail(SUCRE_ERR_RANGE, "view %d outside [0,%d)", k, n_views);
+    if (!planes_dev) return fail(SUCRE_ERR_ARG, "planes_dev is NULL");
+    return check_hip(launch_export_view_ext(L, static_cast<const uint8_t *>(ws),
+                                            light_ext2_dense(L, const_cast<uint8_t *>(static_cast<const uint8_t *>(lws))), k,
+                                            planes_dev, static_cast<hipStream_t>(stream)), "sucre_export_view_ext2");
+}
+
 int sucre_finalize_matches_light(void *ws, void *lws, int H, int W, int n_views, double min_cover, void *stream) {
     Layout L;
     if (int rc = check_ws(ws, H, W, n_views, &L)) return rc;

@@ -425,6 +425,18 @@ class Restoration:
                                                       C.c_void_p(out.data_ptr()), self._sp()))
         return out
 
+    def export_view_colour(self, k: int) -> torch.Tensor:
+        """(3, H, W) float32: the float32 colours of view k of a restoration that is both ``light`` and ``float_colour`` (its
+        second set of extension planes; ``export_view_ext`` returns the first, the camera points), zero where the view has no
+        observation."""
+        assert self.both, 'only a light restoration on float32 colours keeps a second set of extension planes'
+        out = torch.empty((3, self.H, self.W), dtype=torch.float32, device=self.device)
+        ws, H, W, n = self._geom
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.sucre_export_view_ext2(ws, C.c_void_p(self.lws.data_ptr()), H, W, n, int(k),
+                                                       C.c_void_p(out.data_ptr()), self._sp()))
+        return out
+
     def check_store(self) -> torch.Tensor:
         """uint32 per view: 0 = sound, bit 0 = non-finite range, bit 1 = negative range, bit 2 = the number of stored
         ranges differs from the view's match count (the checks of loader.py:89-101, one launch for all views)."""

@@ -360,7 +360,9 @@ class MatchesData:
         extension planes when the restoration keeps them (light model), else recomputed exactly as the reference
         does, ``unproject_depth(u2, v2, depth2[v2, u2])``, from the explicit correspondences (``match_map``) while the
         matched views are at hand; for a store filled from lists that carried no points, ``(0, 0, ||cP||)`` -- all
-        that ``SUCRe.forward`` reads without the light model (sucre.py:53)."""
+        that ``SUCRe.forward`` reads without the light model (sucre.py:53).  ``I`` is always what the store holds (uint8 words,
+        or the float32 planes of ``export_view_ext`` / ``export_view_colour``): after ``apply_view_gains`` the corrected colours,
+        also for a store that was imported and has no views to gather from."""
         r = self.restoration
         keep = r.view_keep().cpu().numpy().astype(bool)
         order = sorted(range(r.n_views), key=lambda k: self.image_list[k].name if self.image_list else k)
@@ -381,12 +383,8 @@ class MatchesData:
                 cP = other.unproject_depth(u=u2, v=v2, d=other.device_view(r.device).depth[v2, u2])
             else:
                 cP = torch.stack([torch.zeros_like(zz), torch.zeros_like(zz), zz])
-            if r.float_colour and r.light:   # the colours sit in the second extension set: gathered from the view itself
-                other = self.image_list[k]
-                p2 = r.match_map(k)[v, u].long()
-                W2 = other.camera.width
-                rgbf = other.device_view(r.device).as_float_colour().rgb
-                I = rgbf[torch.div(p2, W2, rounding_mode='floor'), p2 % W2].T.contiguous()
+            if r.both:   # the colours sit in the second extension set
+                I = r.export_view_colour(k)[:, v, u].contiguous()
             elif r.float_colour:
                 I = r.export_view_ext(k)[:, v, u].contiguous()
             else:

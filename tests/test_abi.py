@@ -84,6 +84,14 @@ def test_argument_validation_happens_before_any_launch():
     assert lib.sucre_fit_grad(ws, 48, 64, 3, 0, 0.05, 0.9, 0.999, 1e-8, 0, None) == -2
     assert lib.sucre_export_view(ws, 48, 64, 3, 3, ws, None, None) == -2
     assert lib.sucre_export_J(ws, 48, 64, 3, None, None) == -1
+    lws = C.c_void_p(512)
+    for export_ext in (lib.sucre_export_view_ext, lib.sucre_export_view_ext2):      # the same validation for both plane sets
+        assert export_ext(None, lws, 48, 64, 3, 0, ws, None) == -1 and b'NULL' in lib.sucre_last_error()
+        assert export_ext(ws, None, 48, 64, 3, 0, ws, None) == -1 and b'light workspace' in lib.sucre_last_error()
+        assert export_ext(ws, C.c_void_p(516), 48, 64, 3, 0, ws, None) == -1 and b'aligned' in lib.sucre_last_error()
+        assert export_ext(ws, lws, 0, 64, 3, 0, ws, None) == -1 and b'invalid geometry' in lib.sucre_last_error()
+        assert export_ext(ws, lws, 48, 64, 3, 3, ws, None) == -2 and export_ext(ws, lws, 48, 64, 3, -1, ws, None) == -2
+        assert export_ext(ws, lws, 48, 64, 3, 0, None, None) == -1 and b'planes_dev is NULL' in lib.sucre_last_error()
     assert lib.sucre_set_n_obs_total(ws, 48, 64, 3, 0, None) == -2
     tgt = _lib.SucreView()
     assert lib.sucre_match_views(ws, 48, 64, 3, C.byref(tgt), ws, 0, 3, None) == -1  # NULL depth
