@@ -72,6 +72,15 @@ constexpr bool kExactDiv = SUCRE_EXACT_DIV != 0;
 #endif
 constexpr bool kExactJAdam = SUCRE_EXACT_J_ADAM != 0;
 
+// fit.hip: the backscatter term of a chunk as bo = fma(-B, g, B) with the sums of r (1 - g) accumulated B-scaled and divided by
+// B once per launch (1, the product: one instruction per observation-channel fewer; fit_math.h scaled_b_ok says for which B) or
+// as B * (1 - g) everywhere, the form until round 10 (0; tools/exp/ab_vs.sh / ab_bench.sh unscaledb).
+// (tests/test_scaled_b_host.py builds the 0 form, so that it cannot rot.)
+#if !defined(SUCRE_SCALED_B)
+#define SUCRE_SCALED_B 1
+#endif
+constexpr bool kScaledBBuilt = SUCRE_SCALED_B != 0;
+
 // fit.hip, timing only: every wave of a J-parameter launch records when it entered and left its strips (100 MHz wall clock) --
 // how much of a launch is its ragged end (tools/exp/wave_times.py).
 #ifdef SUCRE_EXP_WAVE_TIMES

@@ -25,6 +25,11 @@
 // With L = sum r^2 / (3 n_obs) and s = (1/3)/n_obs (sucre.py:145):
 //   dL/dJ[p]  = -2 s sum_k r a          dL/dB     = -2 s sum r (1 - g)
 //   dL/dbeta  = +2 s sum_p J sum_k r a z    dL/dgamma = -2 s B sum r g z        (per channel)
+// The backscatter term is formed as bo = B (1 - g) = fma(-B, g, B), one instruction, and the launch accumulates
+// sum r bo = B sum r (1 - g); the workgroup that finishes the sums divides it by B, in float64, once per launch and channel,
+// so that the published sums -- and dL/dB = -2 s (sum r bo) / B -- keep the meaning above.  A launch whose B has a channel that
+// is 0, not finite or outside [2^-24, 8] in absolute value (fit_math.h scaled_b_ok) runs the form with 1 - g on its own
+// instead, one instruction per observation-channel more: the pass is compiled twice and every wave takes one branch per pass.
 #include <cstddef>
 #include <type_traits>
 
@@ -68,8 +73,9 @@ constexpr float kInv255 = (float)(1.0 / 255.0);
 // ---------------------------------------------------------------------------------------------------------------
 // Arithmetic of one chunk: four levels of this lane's pixel.
 //
-// The loop's arithmetic is what the launch waits for next to the stream: 13 plain instructions and 2 v_exp_f32 per
-// observation-channel (an exponential issues at 1.7x the cost of a plain instruction and overlaps with nothing:
+// The loop's arithmetic is what the launch waits for next to the stream: 12 plain instructions and 2 v_exp_f32 per
+// observation-channel in the scaled form, 13 + 2 in the fallback (grad_terms; an exponential issues at 1.7x the cost of a
+// plain instruction and overlaps with nothing:
 // tools/probes/exp_probe.hip; a three-register v_fma_f32 every 2.4-2.6 shader cycles per SIMD at 5-8 waves:
 // tools/probes/fma3_probe.hip -- the loop as it runs reaches about half of that).  The 24 exponentials of a chunk are issued back to back, their arguments before them and their
 // uses after them: interleaved with their dependent arithmetic the loop was 14 % slower (337 -> 296 ns per chunk per SIMD).
@@ -77,7 +83,7 @@ constexpr float kInv255 = (float)(1.0 / 255.0);
 struct Acc {
     float pa[3];   // this pixel: sum r a
     float pb[3];   // this pixel: sum r a z
-    float sB[3];   // lane's share of sum r (1 - g)
+    float sB[3];   // lane's share of sum r (1 - g) -- of B sum r (1 - g) in the scaled form (grad_terms)
     float sGZ[3];  // lane's share of sum r g z
     float cost;    // lane's share of sum r^2
 };
@@ -105,9 +111,13 @@ __device__ __forceinline__ void chunk_exps(const float (&zz)[kGroupLv], const Wa
 }
 
 // One observation-channel of the J-parameter loop (closed_terms below is its closed-form twin).
+// kScaledB: the backscatter term B (1 - g) in ONE instruction, bo = fma(-B, g, B) (one rounding instead of two), and acc.sB takes
+// r bo: B sum r (1 - g), which the launch's finisher divides by B (unscale_sum).  Otherwise the form until round 10, 1 - g on its
+// own: one instruction more, and legal for every B (fit_math.h scaled_b_ok picks per launch).
+template <bool kScaledB>
 __device__ __forceinline__ void grad_terms(float z, float a, float g, uint32_t k, bool valid, float Bc, float Jc, int c, Acc &acc) {
-    const float omg = 1.0f - g;
-    const float Ihat = __builtin_fmaf(Jc, a, Bc * omg);
+    const float omg = kScaledB ? __builtin_fmaf(-Bc, g, Bc) : 1.0f - g;   // scaled: bo = B (1 - g)
+    const float Ihat = __builtin_fmaf(Jc, a, kScaledB ? omg : Bc * omg);
     // I = k/255 folded into the residual: one rounding instead of two, two VALU ops fewer
     float r = __builtin_fmaf((float)k, kInv255, -Ihat);
     r = valid ? r : 0.0f;  // select, not multiply: J may be NaN where unobserved
@@ -121,7 +131,7 @@ __device__ __forceinline__ void grad_terms(float z, float a, float g, uint32_t k
 
 // kMasked = false: every level of the chunk is a real observation of every pixel of the strip (chunks wholly below
 // the strip's smallest pixel count), so the z > 0 test and the selects are compiled out.
-template <bool kMasked>
+template <bool kMasked, bool kScaledB>
 __device__ __forceinline__ void accumulate_chunk(const float (&zz)[kGroupLv], const uint32_t (&cc)[3], const Water &w,
                                                  const float (&J)[3], Acc &acc) {
     if (kExpNoCompute) {  // ablation build only (experiment.h): touch the data, skip the model
@@ -135,16 +145,17 @@ __device__ __forceinline__ void accumulate_chunk(const float (&zz)[kGroupLv], co
         const float z = zz[j];
         const bool valid = !kMasked || z > 0.0f;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) grad_terms(z, e.a[j][c], e.g[j][c], (cc[c] >> (8 * j)) & 255u, valid, w.B[c], J[c], c, acc);
+        for (int c = 0; c < 3; ++c) grad_terms<kScaledB>(z, e.a[j][c], e.g[j][c], (cc[c] >> (8 * j)) & 255u, valid, w.B[c], J[c], c, acc);
     }
 }
 
 // One level (a strip's last, short chunk): same arithmetic, always masked.
+template <bool kScaledB>
 __device__ __forceinline__ void accumulate_level(float z, const uint32_t (&k)[3], const Water &w, const float (&J)[3],
                                                  Acc &acc) {
     const bool valid = z > 0.0f;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) grad_terms(z, fast_exp2(z * w.nb[c]), fast_exp2(z * w.ng[c]), k[c], valid, w.B[c], J[c], c, acc);
+    for (int c = 0; c < 3; ++c) grad_terms<kScaledB>(z, fast_exp2(z * w.nb[c]), fast_exp2(z * w.ng[c]), k[c], valid, w.B[c], J[c], c, acc);
 }
 
 // Closed-form mode in ONE pass over the observations (sucre.py:141 + 142-147 with J a constant of the backward pass).
@@ -165,13 +176,16 @@ struct AccOne {
     float q[9][3];  // N, D, S1..S7 of this pixel, per channel
 };
 
+// kScaledB (see grad_terms): bo = fma(-B, g, B) takes the place of 1 - g, so S1 and S2 -- and the strip end's S1 - dJ S2 -- are
+// B-scaled; everything else is as before.
+template <bool kScaledB>
 __device__ __forceinline__ void closed_terms(float z, float a, float g, uint32_t k, bool valid, float Bc, float Jp,
                                              float &q0, float &q1, float &q2, float &q3, float &q4, float &q5,
                                              float &q6, float &q7, float &q8) {
-    const float omg = 1.0f - g;
+    const float omg = kScaledB ? __builtin_fmaf(-Bc, g, Bc) : 1.0f - g;   // scaled: bo = B (1 - g)
     // I = k/255 folded into y: one rounding instead of two and two VALU operations fewer, like the J-parameter loop (the
     // kernel is instruction-limited: 79 instructions per observation, profiles/r03_closed_summary.txt)
-    const float y = __builtin_fmaf((float)k, kInv255, -(Bc * omg));
+    const float y = __builtin_fmaf((float)k, kInv255, -(kScaledB ? omg : Bc * omg));
     float p = __builtin_fmaf(-Jp, a, y);
     p = valid ? p : 0.0f;  // a padding slot contributes nothing (its Jp a is not zero)
     const float za = z * a, zg = z * g;  // a padding slot has z = 0, g = 1: it only touches D (masked below)
@@ -186,7 +200,7 @@ __device__ __forceinline__ void closed_terms(float z, float a, float g, uint32_t
     q8 = __builtin_fmaf(p, p, q8);
 }
 
-template <bool kMasked>
+template <bool kMasked, bool kScaledB>
 __device__ __forceinline__ void accumulate_chunk(const float (&zz)[kGroupLv], const uint32_t (&cc)[3], const Water &w,
                                                  const float (&Jp)[3], AccOne &acc) {
     if (kExpNoCompute) {  // ablation build only (experiment.h): touch the data, skip the model
@@ -201,11 +215,12 @@ __device__ __forceinline__ void accumulate_chunk(const float (&zz)[kGroupLv], co
         const bool valid = !kMasked || z > 0.0f;
 #pragma unroll
         for (int c = 0; c < 3; ++c)
-            closed_terms(z, e.a[j][c], e.g[j][c], (cc[c] >> (8 * j)) & 255u, valid, w.B[c], Jp[c], acc.q[0][c], acc.q[1][c],
-                         acc.q[2][c], acc.q[3][c], acc.q[4][c], acc.q[5][c], acc.q[6][c], acc.q[7][c], acc.q[8][c]);
+            closed_terms<kScaledB>(z, e.a[j][c], e.g[j][c], (cc[c] >> (8 * j)) & 255u, valid, w.B[c], Jp[c], acc.q[0][c], acc.q[1][c],
+                                   acc.q[2][c], acc.q[3][c], acc.q[4][c], acc.q[5][c], acc.q[6][c], acc.q[7][c], acc.q[8][c]);
     }
 }
 
+template <bool kScaledB>
 __device__ __forceinline__ void accumulate_level(float z, const uint32_t (&k)[3], const Water &w, const float (&Jp)[3],
                                                  AccOne &acc) {
     if (kExpNoCompute) {
@@ -215,8 +230,8 @@ __device__ __forceinline__ void accumulate_level(float z, const uint32_t (&k)[3]
     const bool valid = z > 0.0f;
 #pragma unroll
     for (int c = 0; c < 3; ++c)
-        closed_terms(z, fast_exp2(z * w.nb[c]), fast_exp2(z * w.ng[c]), k[c], valid, w.B[c], Jp[c], acc.q[0][c], acc.q[1][c],
-                     acc.q[2][c], acc.q[3][c], acc.q[4][c], acc.q[5][c], acc.q[6][c], acc.q[7][c], acc.q[8][c]);
+        closed_terms<kScaledB>(z, fast_exp2(z * w.nb[c]), fast_exp2(z * w.ng[c]), k[c], valid, w.B[c], Jp[c], acc.q[0][c], acc.q[1][c],
+                               acc.q[2][c], acc.q[3][c], acc.q[4][c], acc.q[5][c], acc.q[6][c], acc.q[7][c], acc.q[8][c]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -631,14 +646,23 @@ __device__ __forceinline__ void reduce_group(const float *partials, int n_blocks
     }
 }
 
+// The finisher's half of the scaled form (grad_terms): sums 0-2 of a launch that ran it hold B_c sum r (1 - g); divided, in
+// float64, by the B_c the pass used they are sum r (1 - g) -- what water_grad, the host's all-reduce and the split step have always
+// read.  `scaled` is scaled_b_ok of the same three words the waves of the pass evaluated it on.
+__device__ __forceinline__ double unscale_sum(double x, int q, bool scaled, float Bq) {
+    return (kScaledBBuilt && scaled && q < 3) ? x / (double)Bq : x;
+}
+
 // 256 threads: wave w reduces quantities q = w, w+4, w+8 over all groups (lane l takes groups l, l+64, ...).
-__device__ __forceinline__ void reduce_total(const double *gpart, int n_groups, double *stot, double *__restrict__ sums) {
+// Bpass: the three B the pass computed with (the image's parameters before their step; a group launch's stepped copy).
+__device__ __forceinline__ void reduce_total(const double *gpart, int n_groups, double *stot, double *__restrict__ sums, const float *Bpass) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool scaled = scaled_b_ok(Bpass[0], Bpass[1], Bpass[2]);
     for (int q = wave; q < kNumSums; q += 4) {
         double x = 0.0;
         for (int g = lane; g < n_groups; g += 64)
             x += __hip_atomic_load(gpart + (size_t)q * n_groups + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        x = wave_sum_fixed(x);
+        x = unscale_sum(wave_sum_fixed(x), q, scaled, Bpass[q < 3 ? q : 0]);
         if (lane == 0) {
             __hip_atomic_store(sums + q, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // global copy: read by the host all-reduce
             stot[q] = x;  // LDS copy: read by water_step of the same workgroup
@@ -709,10 +733,11 @@ __device__ __forceinline__ void wave_sums(float (&s)[kNumSums]) {
 
 // End of a fit launch, from the four waves' sums in lds.wsum on: one float32 partial per workgroup -> (fused form) two-level
 // last-arriver reduction in float64 and the Adam step on B, beta, gamma by the workgroup that arrives last.
+// Bpass: the three B the launch's passes computed with (reduce_total; read by the fused form only).
 template <bool kFused, bool kStep>
 __device__ __forceinline__ void finish_from_wave_sums(FitLds &lds, float *partials, const AdamCoef &co, unsigned *ticket,
                                                       double *gpart, int n_groups, double *sums, float *pstate,
-                                                      const uint64_t *__restrict__ n_obs_total, double *trace_row) {
+                                                      const uint64_t *__restrict__ n_obs_total, double *trace_row, const float *Bpass) {
     const int n_blocks = gridDim.x;
     const int t = threadIdx.x;
     __syncthreads();
@@ -734,7 +759,7 @@ __device__ __forceinline__ void finish_from_wave_sums(FitLds &lds, float *partia
         if (arrive_last(ticket + (size_t)(1 + g) * kTicketStride, gsize, &lds.is_last)) {  // workgroup-uniform
             reduce_group(partials, n_blocks, g, gpart, n_groups);
             if (arrive_last(ticket, (unsigned)n_groups, &lds.is_last_total)) {
-                reduce_total(gpart, n_groups, lds.stot, sums);
+                reduce_total(gpart, n_groups, lds.stot, sums, Bpass);
                 // every other workgroup has finished (it arrived after its last use of the parameters)
                 if (kStep && t < 64) water_step(lds.stot, pstate, n_obs_total, co, trace_row);
             }
@@ -757,7 +782,7 @@ __device__ __forceinline__ void finish_launch(FitLds &lds, float (&s)[kNumSums],
 #pragma unroll
         for (int q = 0; q < kNumSums; ++q) lds.wsum[wave][q] = s[q];
     }
-    finish_from_wave_sums<kFused, kStep>(lds, partials, co, ticket, gpart, n_groups, sums, pstate, n_obs_total, trace_row);
+    finish_from_wave_sums<kFused, kStep>(lds, partials, co, ticket, gpart, n_groups, sums, pstate, n_obs_total, trace_row, pstate);   // B before its step
 }
 
 // A stepped value -> the strip's state, with the streaming policy where experiment.h's SUCRE_STORE_NT asks for it.
@@ -769,7 +794,9 @@ __device__ __forceinline__ void store_stepped(float *p, float v) {
 
 // One wave's share of a J-parameter iteration on one image (sucre.py:142-148 with J among the parameters): streams
 // the wave's items, steps J of every strip, and keeps adding the lane's shares of the global sums to acc / sBeta.
-template <int kFmt, bool kPrimed = false, class Chain = NoChain>
+// kScaledB: the pass's chunk arithmetic in the B-scaled form (grad_terms); acc.sB then holds B sum r (1 - g).  The caller picks it
+// with ONE wave-uniform branch per pass (run_grad_pass) from scaled_b_ok of the pass's own B.
+template <int kFmt, bool kScaledB, bool kPrimed = false, class Chain = NoChain>
 __device__ __forceinline__ void grad_pass(FitLds &lds, const PlanItem *__restrict__ plan, const StripEntry *__restrict__ strips, uint32_t n_strips_wave,
                                           const uint8_t *__restrict__ ws, float *__restrict__ state, int wave, int lane,
                                           const Water &w, float gscale, const AdamCoef &co, Acc &acc, float (&sBeta)[3], const RangeCodes &rc,
@@ -786,15 +813,15 @@ __device__ __forceinline__ void grad_pass(FitLds &lds, const PlanItem *__restric
             float zz[kGroupLv];
             uint32_t cc[3];
             read_chunk<kFmt>(sp, lane, zz, cc, rc, masked);
-            if (masked) accumulate_chunk<true>(zz, cc, w, J, acc);
-            else accumulate_chunk<false>(zz, cc, w, J, acc);
+            if (masked) accumulate_chunk<true, kScaledB>(zz, cc, w, J, acc);
+            else accumulate_chunk<false, kScaledB>(zz, cc, w, J, acc);
         },
         [&](const uint8_t *sp, uint32_t r) {  // the strip's short last chunk
             for (uint32_t j = 0; j < r; ++j) {
                 float z;
                 uint32_t k[3];
                 read_level<kFmt>(sp, lane, r, j, z, k, rc);
-                accumulate_level(z, k, w, J, acc);
+                accumulate_level<kScaledB>(z, k, w, J, acc);
             }
         },
         [&](uint32_t strip, const uint8_t *sp) {  // moments landed: torch.optim.Adam on this pixel's J
@@ -816,6 +843,21 @@ __device__ __forceinline__ void grad_pass(FitLds &lds, const PlanItem *__restric
             }
         },
         chain);
+}
+
+// Which form a pass over one image runs: scaled_b_ok (fit_math.h) of the B the pass computes with, as a scalar -- the pass is
+// compiled twice and a wave takes ONE branch per pass.  The finisher of the sums asks the same question of the same words.
+__device__ __forceinline__ bool pass_scaled_b(const Water &w) {
+    return kScaledBBuilt && __builtin_amdgcn_readfirstlane((int)scaled_b_ok(w.B[0], w.B[1], w.B[2])) != 0;
+}
+
+template <int kFmt, bool kPrimed = false, class Chain = NoChain>
+__device__ __forceinline__ void run_grad_pass(bool scaled, FitLds &lds, const PlanItem *__restrict__ plan, const StripEntry *__restrict__ strips,
+                                              uint32_t n_strips_wave, const uint8_t *__restrict__ ws, float *__restrict__ state, int wave, int lane,
+                                              const Water &w, float gscale, const AdamCoef &co, Acc &acc, float (&sBeta)[3], const RangeCodes &rc,
+                                              Chain *chain = nullptr) {
+    if (kScaledBBuilt && scaled) grad_pass<kFmt, true, kPrimed, Chain>(lds, plan, strips, n_strips_wave, ws, state, wave, lane, w, gscale, co, acc, sBeta, rc, chain);
+    else grad_pass<kFmt, false, kPrimed, Chain>(lds, plan, strips, n_strips_wave, ws, state, wave, lane, w, gscale, co, acc, sBeta, rc, chain);
 }
 
 __device__ __forceinline__ void zero_acc(Acc &acc) {
@@ -863,7 +905,7 @@ __global__ __launch_bounds__(256, kFitWaves) void fit_grad_kernel(const uint8_t 
     if (!fmt_ok) acc.cost = __builtin_nanf("");
     float sBeta[3] = {0.f, 0.f, 0.f};
     if (kExpWaveTimes && lane == 0 && wid < kExpWaveSlots) g_exp_wave_times[0][wid] = wall_clock64();
-    grad_pass<kFmt>(lds, plan + (size_t)wid * plan_stride, plan_strips + (size_t)wid * plan_kmax, n_mine, ws, state, wave, lane, w, gscale, co, acc, sBeta, rc);
+    run_grad_pass<kFmt>(pass_scaled_b(w), lds, plan + (size_t)wid * plan_stride, plan_strips + (size_t)wid * plan_kmax, n_mine, ws, state, wave, lane, w, gscale, co, acc, sBeta, rc);
     if (kExpWaveTimes && lane == 0 && wid < kExpWaveSlots) g_exp_wave_times[1][wid] = wall_clock64();
 
     float s[kNumSums];
@@ -876,7 +918,8 @@ __global__ __launch_bounds__(256, kFitWaves) void fit_grad_kernel(const uint8_t 
 // SUCRe.update_J alone (sucre.py:66-77, 156): J = sum (I - b) a / sum a^2 from the current parameters, nothing else.
 struct ClosedSums { float sB[3], sGZ[3], sBeta[3], cost; };
 
-template <int kFmt, bool kJOnly, bool kPrimed = false, class Chain = NoChain>
+// kScaledB: closed_terms' B-scaled form; cs.sB then takes B sum r (1 - g) (run_closed_pass picks, like run_grad_pass).
+template <int kFmt, bool kJOnly, bool kScaledB, bool kPrimed = false, class Chain = NoChain>
 __device__ __forceinline__ void closed_pass(FitLds &lds, const PlanItem *__restrict__ plan, const StripEntry *__restrict__ strips, uint32_t n_strips_wave,
                                             const uint8_t *__restrict__ ws, float *__restrict__ state, int wave, int lane,
                                             const Water &w, bool fmt_ok, ClosedSums &cs, const RangeCodes &rc, Chain *chain = nullptr) {
@@ -901,15 +944,15 @@ __device__ __forceinline__ void closed_pass(FitLds &lds, const PlanItem *__restr
             float zz[kGroupLv];
             uint32_t cc[3];
             read_chunk<kFmt>(sp, lane, zz, cc, rc, masked);
-            if (masked) accumulate_chunk<true>(zz, cc, w, Jp, acc);
-            else accumulate_chunk<false>(zz, cc, w, Jp, acc);
+            if (masked) accumulate_chunk<true, kScaledB>(zz, cc, w, Jp, acc);
+            else accumulate_chunk<false, kScaledB>(zz, cc, w, Jp, acc);
         },
         [&](const uint8_t *sp, uint32_t r) {
             for (uint32_t j = 0; j < r; ++j) {
                 float z;
                 uint32_t k[3];
                 read_level<kFmt>(sp, lane, r, j, z, k, rc);
-                accumulate_level(z, k, w, Jp, acc);
+                accumulate_level<kScaledB>(z, k, w, Jp, acc);
             }
         },
         [&](uint32_t strip, const uint8_t *) {  // all levels seen: re-solve J, form the pixel's share of the sums
@@ -930,7 +973,7 @@ __device__ __forceinline__ void closed_pass(FitLds &lds, const PlanItem *__restr
                     // +-inf there (sucre.py:77), its residuals with it, the cost of the iteration is inf and the channel's
                     // three parameters are NaN from the next step on (seen with the reference itself on a scene of
                     // tools/parity_sweep.py).  The sums that factor J out would skip the pixel: hand them the infinity.
-                    cs.sB[c] += dJ;
+                    cs.sB[c] += kScaledB ? dJ * w.B[c] : dJ;   // scaled: the finisher's division by B hands over dJ's own infinity
                     cs.sBeta[c] += dJ;
                     cs.sGZ[c] += dJ;
                     cs.cost += __builtin_inff();
@@ -938,6 +981,14 @@ __device__ __forceinline__ void closed_pass(FitLds &lds, const PlanItem *__restr
             }
         },
         chain);
+}
+
+template <int kFmt, bool kPrimed = false, class Chain = NoChain>
+__device__ __forceinline__ void run_closed_pass(bool scaled, FitLds &lds, const PlanItem *__restrict__ plan, const StripEntry *__restrict__ strips,
+                                                uint32_t n_strips_wave, const uint8_t *__restrict__ ws, float *__restrict__ state, int wave, int lane,
+                                                const Water &w, bool fmt_ok, ClosedSums &cs, const RangeCodes &rc, Chain *chain = nullptr) {
+    if (kScaledBBuilt && scaled) closed_pass<kFmt, false, true, kPrimed, Chain>(lds, plan, strips, n_strips_wave, ws, state, wave, lane, w, fmt_ok, cs, rc, chain);
+    else closed_pass<kFmt, false, false, kPrimed, Chain>(lds, plan, strips, n_strips_wave, ws, state, wave, lane, w, fmt_ok, cs, rc, chain);
 }
 
 template <bool kFused, int kFmt, bool kJOnly>
@@ -961,7 +1012,9 @@ __global__ __launch_bounds__(256, kClosedWaves) void fit_closed_kernel(const uin
     const uint32_t n_mine = (fmt_ok || kJOnly) ? plan_count[wid] : 0u;   // strips of this wave
     ClosedSums cs = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, fmt_ok ? 0.f : __builtin_nanf("")};
     if (kExpWaveTimes && !kJOnly && lane == 0 && wid < kExpWaveSlots) g_exp_wave_times[0][wid] = wall_clock64();
-    closed_pass<kFmt, kJOnly>(lds, plan + (size_t)wid * plan_stride, plan_strips + (size_t)wid * plan_kmax, n_mine, ws, state, wave, lane, w, fmt_ok, cs, rc);
+    // update_J keeps the unscaled form: it has no sum to scale, and its J = N / D stays the bits it has always been
+    if (kJOnly) closed_pass<kFmt, true, false>(lds, plan + (size_t)wid * plan_stride, plan_strips + (size_t)wid * plan_kmax, n_mine, ws, state, wave, lane, w, fmt_ok, cs, rc);
+    else run_closed_pass<kFmt>(pass_scaled_b(w), lds, plan + (size_t)wid * plan_stride, plan_strips + (size_t)wid * plan_kmax, n_mine, ws, state, wave, lane, w, fmt_ok, cs, rc);
     if (kExpWaveTimes && !kJOnly && lane == 0 && wid < kExpWaveSlots) g_exp_wave_times[1][wid] = wall_clock64();
     if (kJOnly) return;
     float s[kNumSums];
@@ -1056,6 +1109,7 @@ __global__ __launch_bounds__(256, kMode ? kClosedWaves : kGroupFitWaves) void gr
     }
     __syncthreads();
     const Water w = load_water_uniform(wpar);
+    const bool scaled = pass_scaled_b(w);   // one B for all the rank's images: one form for the whole launch
     const float gscale = -2.0f * ((1.0f / 3.0f) / (float)n_obs_total);
     const uint32_t wid = blockIdx.x * 4u + (uint32_t)wave;
     Acc acc;
@@ -1084,12 +1138,12 @@ __global__ __launch_bounds__(256, kMode ? kClosedWaves : kGroupFitWaves) void gr
         float *state = reinterpret_cast<float *>(ws + im.off_state);
         float s[kNumSums];
         if (kMode == 0) {
-            grad_pass<kFmt>(lds, plan, strips, n_mine, ws, state, wave, lane, w, gscale, co, acc, sBeta, rc);
+            run_grad_pass<kFmt>(scaled, lds, plan, strips, n_mine, ws, state, wave, lane, w, gscale, co, acc, sBeta, rc);
             pack_sums(s, acc.sB, acc.sGZ, sBeta, acc.cost);
             zero_acc(acc);
             sBeta[0] = sBeta[1] = sBeta[2] = 0.f;
         } else {
-            closed_pass<kFmt, false>(lds, plan, strips, n_mine, ws, state, wave, lane, w, true, cs, rc);
+            run_closed_pass<kFmt>(scaled, lds, plan, strips, n_mine, ws, state, wave, lane, w, true, cs, rc);
             pack_sums(s, cs.sB, cs.sGZ, cs.sBeta, cs.cost);
             cs = ClosedSums{{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, 0.f};
         }
@@ -1104,7 +1158,7 @@ __global__ __launch_bounds__(256, kMode ? kClosedWaves : kGroupFitWaves) void gr
         for (int j = 0; j < kNumSums; ++j) lds.wsum[wave][j] = (float)lds.wtotal[wave][j];
         if (poisoned) lds.wsum[wave][kNumSums - 1] = __builtin_nanf("");   // an image compacted in the other format: the logged cost turns NaN
     }
-    finish_from_wave_sums<true, false>(lds, g->partials, co, g->ticket, g->gpart, n_groups, g->sums, nullptr, nullptr, nullptr);
+    finish_from_wave_sums<true, false>(lds, g->partials, co, g->ticket, g->gpart, n_groups, g->sums, nullptr, nullptr, nullptr, wpar);   // the B every workgroup stepped to
 }
 
 // The last pending step; the final parameters also go to every image's own workspace (Restoration.params()).
@@ -1301,13 +1355,13 @@ __global__ __launch_bounds__(256, kMode ? kClosedWaves : kGroupFitWaves) void ba
             zero_acc(acc);
             if (!v.fmt_ok) acc.cost = __builtin_nanf("");
             float sBeta[3] = {0.f, 0.f, 0.f};
-            grad_pass<kFmt, true, StreamChain>(lds, v.plan, v.strips, v.n_mine, v.ws, v.state, wave, lane, v.w, v.gscale, co, acc, sBeta, v.rc, &ch);
+            run_grad_pass<kFmt, true, StreamChain>(pass_scaled_b(v.w), lds, v.plan, v.strips, v.n_mine, v.ws, v.state, wave, lane, v.w, v.gscale, co, acc, sBeta, v.rc, &ch);   // the form: per image
             const float q[kNumSums] = {acc.sB[0], acc.sB[1], acc.sB[2], acc.sGZ[0], acc.sGZ[1], acc.sGZ[2], sBeta[0], sBeta[1], sBeta[2], acc.cost};
 #pragma unroll
             for (int j = 0; j < kNumSums; ++j) s[j] = q[j];
         } else {
             ClosedSums cs = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, v.fmt_ok ? 0.f : __builtin_nanf("")};
-            closed_pass<kFmt, false, true, StreamChain>(lds, v.plan, v.strips, v.n_mine, v.ws, v.state, wave, lane, v.w, v.fmt_ok, cs, v.rc, &ch);
+            run_closed_pass<kFmt, true, StreamChain>(pass_scaled_b(v.w), lds, v.plan, v.strips, v.n_mine, v.ws, v.state, wave, lane, v.w, v.fmt_ok, cs, v.rc, &ch);
             const float q[kNumSums] = {cs.sB[0], cs.sB[1], cs.sB[2], cs.sGZ[0], cs.sGZ[1], cs.sGZ[2], cs.sBeta[0], cs.sBeta[1], cs.sBeta[2], cs.cost};
 #pragma unroll
             for (int j = 0; j < kNumSums; ++j) s[j] = q[j];
@@ -1352,16 +1406,19 @@ __global__ __launch_bounds__(kTailThreads) void batch_tail_kernel(const BatchEnt
     // what the step needs besides the totals is asked for before the arrival (every workgroup: one of them will use it)
     float p = 0.f, m = 0.f, v = 0.f, Bc = 0.f, scale = 0.f;
     float *pstate = nullptr;
+    bool scaled = false;   // did this image's stream run the scaled form (batch_iter_kernel asked the same of the same words)?
     if (mine && q < 9) {
         pstate = reinterpret_cast<float *>(ws + images[i].o.params);
         scale = (1.0f / 3.0f) / (float)(*reinterpret_cast<const uint64_t *>(ws + images[i].o.n_obs_total));
         p = pstate[q]; m = pstate[9 + q]; v = pstate[18 + q];
         Bc = pstate[q % 3];   // B before its step
+        scaled = scaled_b_ok(pstate[0], pstate[1], pstate[2]);
     }
     unsigned *ticket = reinterpret_cast<unsigned *>(images[0].ws + images[0].o.ticket);   // the batch's arrival counter: the first image's
     if (!arrive_last(ticket, (unsigned)n_groups, &is_last)) return;
     if (mine) {
-        const double y = reduce_total_thread(reinterpret_cast<const double *>(ws + images[i].o.gpart), n_groups, q);
+        // reduce_total's bits: the image's own B_q undoes the scale of its sums 0-2 (Bc = B_q for q < 3)
+        const double y = unscale_sum(reduce_total_thread(reinterpret_cast<const double *>(ws + images[i].o.gpart), n_groups, q), q, scaled, Bc);
         __hip_atomic_store(reinterpret_cast<double *>(ws + images[i].o.sums) + q, y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         stot[i][q] = y;
     }
@@ -1399,9 +1456,9 @@ __global__ __launch_bounds__(256) void reduce_groups_kernel(const float *partial
     reduce_group(partials, n_blocks, blockIdx.x, gpart, n_groups);
 }
 
-__global__ __launch_bounds__(256) void reduce_sums_kernel(const double *gpart, int n_groups, double *__restrict__ sums) {
+__global__ __launch_bounds__(256) void reduce_sums_kernel(const double *gpart, int n_groups, double *__restrict__ sums, const float *__restrict__ pstate) {
     __shared__ double stot[kSumsPad];
-    reduce_total(gpart, n_groups, stot, sums);
+    reduce_total(gpart, n_groups, stot, sums, pstate);   // launch_fit_step has not run yet: the B of the pass
 }
 
 __global__ __launch_bounds__(64) void param_step_kernel(const double *__restrict__ sums, float *__restrict__ pstate,
@@ -1519,7 +1576,7 @@ hipError_t launch_fit_grad(const Layout &L, uint8_t *ws, const AdamCoef &co, uns
                        reinterpret_cast<double *>(ws + L.off_gpartials), L.fit_groups[mode]);
     hipLaunchKernelGGL(reduce_sums_kernel, dim3(1), dim3(256), 0, s,
                        reinterpret_cast<const double *>(ws + L.off_gpartials), L.fit_groups[mode],
-                       reinterpret_cast<double *>(ws + L.off_sums));
+                       reinterpret_cast<double *>(ws + L.off_sums), reinterpret_cast<const float *>(ws + L.off_params));
     return hipGetLastError();
 }
 

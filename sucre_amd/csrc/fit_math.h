@@ -48,6 +48,26 @@ __device__ __forceinline__ double water_grad(int q, float scale, SumAt sum_at, B
     return -2.0 * (double)scale * (double)B_at(c) * sum_at(3 + c);   // dL/dgamma
 }
 
+// May a fit launch run the B-scaled form of its chunk arithmetic (fit.hip, grad_terms / closed_terms: bo = fma(-B, g, B) in
+// one instruction, the sums of r (1 - g) accumulated as sum r bo = B sum r (1 - g) and divided by B, in float64, where the
+// launch's sums become final)?  Only when all three |B_c| are finite and inside [kScaledBMin, kScaledBMax]: with B_c = 0 the
+// scaled sum is identically 0 and dL/dB would be lost, and a NaN or infinite B must keep poisoning what it poisons today.
+// Below 2^-24 nothing is claimed for the scaled sums (B (1 - g) of a short range nears the denormals); above 8 the model
+// itself leaves the range the fit is held in -- the colours are in [0, 1], the fixtures' B in 0.001 .. 0.53, while the
+// absolute bars on the parameters (1e-5) and on a closed-form J, which is of B's size (1e-4), are a few float32 roundings
+// wide from |B| = 16 on in either form (tests/test_gpu_scaled_b.py) -- so such a launch keeps the arithmetic it has always
+// had.  One channel outside: the WHOLE launch -- all three -- runs the unscaled form.  The waves of a launch evaluate it on
+// the parameters they load, and the workgroup that finishes the sums on the same words again (nothing writes them in
+// between): the two cannot disagree.
+// SUCRE_SCALED_B=0 (experiment.h) builds the unscaled form everywhere.
+constexpr float kScaledBMin = 0x1p-24f, kScaledBMax = 0x1p+3f;
+__host__ __device__ inline bool scaled_b_ok(float B0, float B1, float B2) {
+    if (!kScaledBBuilt) return false;
+    const float a0 = __builtin_fabsf(B0), a1 = __builtin_fabsf(B1), a2 = __builtin_fabsf(B2);
+    // (comparisons with a NaN are false; infinity is above the window)
+    return a0 >= kScaledBMin && a0 <= kScaledBMax && a1 >= kScaledBMin && a1 <= kScaledBMax && a2 >= kScaledBMin && a2 <= kScaledBMax;
+}
+
 // The same step for a pixel's J (three per pixel and iteration: 158 of the J-parameter kernel's ~2000 instructions per
 // pixel were the two IEEE divisions and the IEEE square root of these three steps): hardware square root and reciprocals
 // (1 ulp each) instead of the IEEE sequences, 11 instead of ~42 instructions per channel.  The fit is held to a tolerance,
