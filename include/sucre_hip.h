@@ -303,6 +303,42 @@ int sucre_count_valid(const float *J_dev, int H, int W, uint64_t *count_dev, voi
 int sucre_plot_stretch(const float *J_dev, int H, int W, const float *lo, const float *hi, uint8_t *out_dev, void *stream);
 
 /*
+ * ---- pooled radix select: order statistics of the valid pixels of MANY images ------------------------------------------
+ * The select above for a POOL of images -- of any sizes, in any number of chunks, possibly on several ranks -- without
+ * concatenating or moving them: for every channel the values at given 0-based ranks among the valid pixels (no NaN in any
+ * channel) of all the images together.  It is split into its phases so that the caller can add histograms between them:
+ *     begin;  for pass = 0..3: { pass (once per chunk of images) ...;  [all-reduce the histograms over the ranks];  locate }
+ * `state_dev`: sucre_pool_select_bytes() bytes of device memory, 8-byte aligned.  It BEGINS with uint64_t hist[3][8][256]
+ * ([channel][rank][byte]; this placement is part of the contract: the caller may sum these 6144 words over processes between
+ * the pass calls and locate); what follows (prefix, remaining rank per channel and rank) is private.
+ * sucre_pool_select_begin zeroes the state.
+ * sucre_pool_select_pass ADDS to hist the histogram of key byte 3 - pass over the valid pixels of the chunk's images whose
+ * higher key bytes equal the rank's prefix (the key is the order-preserving integer image of the float32 bits); it may be
+ * called any number of times per pass.  Pass 0 has no prefix, does not depend on the ranks and fills hist[c][0] only: the sum
+ * of hist[0][0][0..255] after the pass-0 calls IS the number of valid pixels of the pool, from which the caller forms the
+ * ranks -- there is no separate counting pass.  `images`: HOST array of n_images entries, 0 <= n_images <= 4096; J: device,
+ * (n_px, 3) float32, 16-byte aligned; n_px >= 0 (an image with n_px == 0, whose J may be NULL, or with NaN in every pixel is
+ * legal and contributes nothing); the images of one call may hold 2^45 pixels together.  `table_dev`:
+ * sucre_pool_table_bytes(n_images) bytes of device memory (0 on an invalid count), 8-byte aligned, that the call fills -- by
+ * value through small kernels -- and that must stay untouched until the launch has run; it may be NULL when n_images == 0.
+ * sucre_pool_select_locate consumes hist: finds the byte under which each rank falls, updates prefix and remaining rank and
+ * zeroes hist.  `ranks`: HOST array of n_ranks 0-based pooled ranks, each below the pooled valid count, read at pass 0 only
+ * (may be NULL later).  After pass 3 it writes out_dev[c * n_ranks + r] (device, 3 * n_ranks float32; may be NULL before).
+ * 1 <= n_ranks <= 8, the same in every call of a select; pass = 0..3; anything else, a NULL or misaligned pointer and a
+ * negative count give SUCRE_ERR_ARG without a launch.  The calls only enqueue.
+ */
+typedef struct sucre_pool_image {
+    const float *J;
+    int64_t n_px;
+} sucre_pool_image_t;
+size_t sucre_pool_select_bytes(void);
+size_t sucre_pool_table_bytes(int n_images);
+int sucre_pool_select_begin(void *state_dev, void *stream);
+int sucre_pool_select_pass(void *state_dev, int pass, void *table_dev, int n_images, const sucre_pool_image_t *images, int n_ranks,
+                           void *stream);
+int sucre_pool_select_locate(void *state_dev, int pass, int n_ranks, const uint64_t *ranks, float *out_dev, void *stream);
+
+/*
  * MatchesFile.check_integrity (loader.py:89-101) over the whole store in one launch: verdict_dev[k] (uint32, one per
  * view) gets bit 0 if a stored range of view k is not finite, bit 1 if one is negative, bit 2 if the number of
  * stored ranges > 0 differs from the view's match count; 0 = sound.  scratch_dev: n_views uint64 of scratch.

@@ -24,6 +24,9 @@ OBS_FORMATS = {'f32': OBS_F32, 'u16mm': OBS_U16MM, 'f32plain': OBS_F32_PLAIN, 'f
 WS_VIEW_COUNT, WS_VIEW_KEEP, WS_N_OBS, WS_PARAMS, WS_SUMS, WS_N_OBS_TOTAL, WS_STORE_FORMAT = range(7)
 INVERT_LIGHT, INVERT_FLOAT_COLOUR = 1, 2
 INVERT_MAX_IMAGES = 4096   # kInvertMaxImages of csrc/invert.h: images per sucre_invert_images call
+POOL_MAX_IMAGES = 4096     # kPoolMaxImages of csrc/pool.h: images per sucre_pool_select_pass call
+POOL_MAX_RANKS = 8
+POOL_HIST_WORDS = 3 * 8 * 256   # uint64 hist[3][8][256] at the head of the pooled select's state
 STORE_F32, STORE_U16MM, STORE_Z24, STORE_Z26 = 0, 1, 2, 3   # what the compaction chose (SUCRE_WS_STORE_FORMAT)
 
 
@@ -54,6 +57,14 @@ class InvertImage(C.Structure):
 
 
 assert C.sizeof(InvertImage) == 72
+
+
+class PoolImage(C.Structure):
+    """sucre_pool_image_t"""
+    _fields_ = [('J', C.c_void_p), ('n_px', C.c_int64)]
+
+
+assert C.sizeof(PoolImage) == 16
 
 
 # name -> (restype, argtypes); mirrors include/sucre_hip.h one to one (tests/test_abi.py checks both ways)
@@ -90,6 +101,11 @@ SIGNATURES = {
     'sucre_select_ranks': (_i, [_vp, _i, _i, _i, C.POINTER(C.c_uint64), _vp, _vp, _vp]),
     'sucre_count_valid': (_i, [_vp, _i, _i, _vp, _vp]),
     'sucre_plot_stretch': (_i, [_vp, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _vp]),
+    'sucre_pool_select_bytes': (C.c_size_t, []),
+    'sucre_pool_table_bytes': (C.c_size_t, [_i]),
+    'sucre_pool_select_begin': (_i, [_vp, _vp]),
+    'sucre_pool_select_pass': (_i, [_vp, _i, _vp, _i, C.POINTER(PoolImage), _i, _vp]),
+    'sucre_pool_select_locate': (_i, [_vp, _i, _i, C.POINTER(C.c_uint64), _vp, _vp]),
     'sucre_check_store': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     'sucre_export_view': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'sucre_light_workspace_bytes': (C.c_size_t, [_i, _i, _i]),

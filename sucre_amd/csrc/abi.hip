@@ -8,6 +8,7 @@
 
 #include "invert.h"
 #include "launch.h"
+#include "pool.h"
 
 namespace sucre {
 
@@ -389,6 +390,54 @@ int sucre_plot_stretch(const float *J_dev, int H, int W, const float *lo, const 
     if (!J_dev || !lo || !hi || !out_dev) return fail(SUCRE_ERR_ARG, "J_dev / lo / hi / out_dev is NULL");
     if (!aligned(J_dev, 4)) return fail(SUCRE_ERR_ARG, "misaligned pointer");
     return check_hip(launch_plot_stretch(J_dev, H, W, lo, hi, out_dev, static_cast<hipStream_t>(stream)), "sucre_plot_stretch");
+}
+
+/* ---- pooled radix select: order statistics of the valid pixels of many images ---------------------------------------- */
+
+size_t sucre_pool_select_bytes(void) { return pool_state_bytes(); }
+
+size_t sucre_pool_table_bytes(int n_images) {
+    if (n_images < 0 || n_images > kPoolMaxImages) {
+        fail(SUCRE_ERR_ARG, "n_images=%d outside [0,%d]", n_images, kPoolMaxImages);
+        return 0;
+    }
+    return pool_table_bytes(n_images);
+}
+
+int sucre_pool_select_begin(void *state_dev, void *stream) {
+    if (!state_dev || !aligned(state_dev, 8)) return fail(SUCRE_ERR_ARG, "pool select state is NULL or not 8-byte aligned");
+    return check_hip(launch_pool_begin(state_dev, static_cast<hipStream_t>(stream)), "sucre_pool_select_begin");
+}
+
+int sucre_pool_select_pass(void *state_dev, int pass, void *table_dev, int n_images, const sucre_pool_image_t *images, int n_ranks,
+                           void *stream) {
+    if (!state_dev || !aligned(state_dev, 8)) return fail(SUCRE_ERR_ARG, "pool select state is NULL or not 8-byte aligned");
+    if (pass < 0 || pass > 3) return fail(SUCRE_ERR_ARG, "pass=%d outside [0,3]", pass);
+    if (n_ranks < 1 || n_ranks > kPoolMaxRanks) return fail(SUCRE_ERR_ARG, "n_ranks=%d outside [1,%d]", n_ranks, kPoolMaxRanks);
+    if (n_images < 0 || n_images > kPoolMaxImages) return fail(SUCRE_ERR_ARG, "n_images=%d outside [0,%d]", n_images, kPoolMaxImages);
+    if (n_images == 0) return SUCRE_OK;   // nothing to add, nothing launched
+    if (!images) return fail(SUCRE_ERR_ARG, "images is NULL");
+    if (!table_dev || !aligned(table_dev, 8)) return fail(SUCRE_ERR_ARG, "pool table is NULL or not 8-byte aligned");
+    uint64_t blocks = 0;
+    for (int i = 0; i < n_images; ++i) {
+        if (images[i].n_px < 0) return fail(SUCRE_ERR_ARG, "image %d: negative pixel count %lld", i, (long long)images[i].n_px);
+        if (images[i].n_px > 0 && (!images[i].J || !aligned(images[i].J, 16)))
+            return fail(SUCRE_ERR_ARG, "image %d: J is NULL or not 16-byte aligned", i);
+        blocks += pool_blocks(images[i].n_px);
+        if (blocks > 0x7fffffffull) return fail(SUCRE_ERR_ARG, "the images of one call may hold 2^45 pixels together (image %d passes that)", i);
+    }
+    return check_hip(launch_pool_pass(state_dev, pass, table_dev, n_images, images, n_ranks, static_cast<hipStream_t>(stream)),
+                     "sucre_pool_select_pass");
+}
+
+int sucre_pool_select_locate(void *state_dev, int pass, int n_ranks, const uint64_t *ranks, float *out_dev, void *stream) {
+    if (!state_dev || !aligned(state_dev, 8)) return fail(SUCRE_ERR_ARG, "pool select state is NULL or not 8-byte aligned");
+    if (pass < 0 || pass > 3) return fail(SUCRE_ERR_ARG, "pass=%d outside [0,3]", pass);
+    if (n_ranks < 1 || n_ranks > kPoolMaxRanks) return fail(SUCRE_ERR_ARG, "n_ranks=%d outside [1,%d]", n_ranks, kPoolMaxRanks);
+    if (pass == 0 && !ranks) return fail(SUCRE_ERR_ARG, "ranks is NULL at pass 0");
+    if (pass == 3 && (!out_dev || !aligned(out_dev, 4))) return fail(SUCRE_ERR_ARG, "out_dev is NULL or misaligned at pass 3");
+    return check_hip(launch_pool_locate(state_dev, pass, n_ranks, ranks, out_dev, static_cast<hipStream_t>(stream)),
+                     "sucre_pool_select_locate");
 }
 
 /* ---- artificial-light model (--light-model) ------------------------------------------------------------------ */

@@ -111,6 +111,14 @@ hipError_t launch_select_ranks(const float *J, int H, int W, int n_ranks, const 
 hipError_t launch_plot_stretch(const float *J, int H, int W, const float *lo, const float *hi, uint8_t *out, hipStream_t s);
 hipError_t launch_count_valid(const float *J, int H, int W, uint64_t *count, hipStream_t s);
 
+// pooled radix select over many images (pool.h; pool.hip)
+size_t pool_state_bytes();
+size_t pool_table_bytes(int n_images);
+hipError_t launch_pool_begin(void *state, hipStream_t s);
+hipError_t launch_pool_pass(void *state, int pass, void *table, int n_images, const sucre_pool_image_t *images, int n_ranks,
+                            hipStream_t s);
+hipError_t launch_pool_locate(void *state, int pass, int n_ranks, const uint64_t *ranks, float *out, hipStream_t s);
+
 // artificial-light model (light.hip)
 size_t light_workspace_bytes(const Layout &L, int ext_sets = 1);
 uint8_t *light_ext2_dense(const Layout &L, uint8_t *lws);   // second extension set (float32 colours next to camera points);

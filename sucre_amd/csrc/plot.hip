@@ -7,6 +7,7 @@
 // the float32 bit pattern, four passes of 256-bin histograms.  The interpolation itself stays on the host
 // (sucre_amd/sucre.py), so the result is numpy's number bit for bit.
 #include "launch.h"
+#include "order_key.h"
 
 namespace sucre {
 
@@ -17,15 +18,6 @@ struct SelectState {
     uint32_t prefix[3][kMaxRanks];      // key bytes fixed so far, right-aligned
     uint64_t remaining[3][kMaxRanks];   // rank among the keys that share the prefix
 };
-
-__device__ __forceinline__ uint32_t order_key(float x) {
-    const uint32_t u = __float_as_uint(x);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // monotone: a < b  <=>  key(a) < key(b)
-}
-
-__device__ __forceinline__ float key_value(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 
 // One pass: histogram of byte (3 - kPass) of every valid pixel's key whose higher bytes equal the rank's prefix.
 template <int kPass>

@@ -742,6 +742,125 @@ def plot_stretch(J: torch.Tensor, lo, hi) -> torch.Tensor:
     return out
 
 
+class PoolSelect:
+    """The pooled radix select (``sucre_pool_select_*``, csrc/pool.hip) phase by phase: exact order statistics of the valid
+    pixels of many device images without concatenating or moving them.  ``begin()``; then for ``pass_`` 0..3: ``add(Js, pass_)``
+    any number of times, the histograms ``hist`` summed over the ranks by the caller, ``locate(pass_, ranks)``; ``values()``.
+    Pass 0 does not depend on the ranks: ``hist[0, 0].sum()`` after its ``add`` calls is the pooled number of valid pixels, and
+    ``ranks`` (0-based, at most 8, each below that number) are given to ``locate(0, ranks)`` only."""
+
+    def __init__(self, device):
+        lib = _lib.load()
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise _lib.SucreError('PoolSelect runs on a GPU device (there is no CPU fallback)')
+        n = int(lib.sucre_pool_select_bytes())
+        self.state = torch.empty((n + 7) // 8, dtype=torch.int64, device=self.device)
+        # a VIEW of the state's head, uint64 hist[3][8][256] (counts stay far below 2^63): what dist.all_reduce_sum sums
+        self.hist = self.state[:_lib.POOL_HIST_WORDS].view(3, _lib.POOL_MAX_RANKS, 256)
+        self.n_ranks = None
+        self._out = None
+        self._keep = []
+
+    def _sp(self) -> C.c_void_p:
+        return C.c_void_p(self.state.data_ptr())
+
+    def begin(self) -> None:
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().sucre_pool_select_begin(self._sp(), _stream_ptr()))
+        self.n_ranks = None
+        self._out = None
+        self._keep = []
+
+    def add(self, Js: list, pass_: int, n_ranks: int | None = None) -> None:
+        """Adds the histograms of pass ``pass_`` over the (H,W,3) float32 contiguous device images ``Js`` (any sizes, empty ones
+        and an empty list included), in chunks of the table limit.  ``n_ranks``: what ``locate(0, ranks)`` fixed, unless given."""
+        lib = _lib.load()
+        n_ranks = int(n_ranks if n_ranks is not None else (self.n_ranks or 1))
+        Js = list(Js)
+        for J in Js:
+            if not (J.is_cuda and J.device == self.device and J.dtype == torch.float32 and J.is_contiguous() and J.dim() == 3 and J.shape[2] == 3):
+                raise ValueError('PoolSelect.add: every image must be an (H,W,3) float32 contiguous tensor on the select\'s device')
+        with torch.cuda.device(self.device):
+            if not Js:   # (the argument checks still run)
+                _lib.check(lib.sucre_pool_select_pass(self._sp(), int(pass_), None, 0, None, n_ranks, _stream_ptr()))
+            for i0 in range(0, len(Js), _lib.POOL_MAX_IMAGES):
+                chunk = Js[i0:i0 + _lib.POOL_MAX_IMAGES]
+                arr = (_lib.PoolImage * len(chunk))()
+                for e, J in zip(arr, chunk):
+                    if J.numel() and J.data_ptr() % 16:   # a view into a larger buffer: the kernel loads 16 bytes at once
+                        J = J.clone()
+                        self._keep.append(J)
+                    e.J, e.n_px = (J.data_ptr() if J.numel() else None), J.shape[0] * J.shape[1]
+                # (torch's caching allocator keeps a freed block for this stream until the launches queued here have run)
+                table = torch.empty(lib.sucre_pool_table_bytes(len(chunk)), dtype=torch.uint8, device=self.device)
+                _lib.check(lib.sucre_pool_select_pass(self._sp(), int(pass_), C.c_void_p(table.data_ptr()), len(chunk), arr, n_ranks,
+                                                      _stream_ptr()))
+
+    def locate(self, pass_: int, ranks=None) -> None:
+        lib = _lib.load()
+        arr = None
+        if int(pass_) == 0:
+            if ranks is None or not 1 <= len(ranks) <= _lib.POOL_MAX_RANKS:
+                raise ValueError(f'PoolSelect.locate: pass 0 takes 1..{_lib.POOL_MAX_RANKS} ranks')
+            self.n_ranks = len(ranks)
+            arr = (C.c_uint64 * len(ranks))(*[int(r) for r in ranks])
+            self._out = torch.empty((3, self.n_ranks), dtype=torch.float32, device=self.device)
+        elif self.n_ranks is None:
+            raise ValueError('PoolSelect.locate: pass 0 comes first (it takes the ranks)')
+        with torch.cuda.device(self.device):
+            _lib.check(lib.sucre_pool_select_locate(self._sp(), int(pass_), self.n_ranks, arr, C.c_void_p(self._out.data_ptr()),
+                                                    _stream_ptr()))
+
+    def values(self) -> torch.Tensor:
+        """(3, n_ranks) float32 device tensor: per channel the values at the ranks, once ``locate(3)`` has been called."""
+        return self._out
+
+
+def pooled_percentiles(Js: list, q=(1.0, 99.0), group=None):
+    """``(P, n)``: ``P[c, i] = float32(np.percentile(pool_c.astype(float64), q[i]))`` over the pool of the valid pixels (no NaN in
+    any channel) of all the (H,W,3) float32 device images ``Js`` -- of any sizes, on one device -- of ALL ranks of ``group``, as
+    a (3, len(q)) float32 numpy array, and ``n``, the pooled number of valid pixels.  Exact: the order statistics come from the
+    pooled radix select (``PoolSelect``; the histograms of every pass are summed over the ranks by ``dist.all_reduce_sum``, so
+    every rank obtains the same numbers), the ranks and the interpolation are numpy's 'linear' method in float64
+    (``sucre.percentile_plan64``), rounded once.  At most 4 percentiles.  ``Js`` may be empty on a rank whose group has other
+    members (the device is then the current one); ``ValueError`` if the pool holds no valid pixel."""
+    from . import dist as sdist
+    from .sucre import percentile_plan64
+    q = [float(x) for x in q]
+    if not 1 <= len(q) <= _lib.POOL_MAX_RANKS // 2:
+        raise ValueError(f'pooled_percentiles: 1..{_lib.POOL_MAX_RANKS // 2} percentiles, got {len(q)}')
+    Js = list(Js)
+    dev = Js[0].device if Js else torch.device('cuda', torch.cuda.current_device())
+    sel = PoolSelect(dev)
+    sel.begin()
+    n, plans = 0, None
+    for pass_ in range(4):
+        sel.add(Js, pass_, n_ranks=2 * len(q))
+        sdist.all_reduce_sum(sel.hist, group)
+        if pass_ == 0:
+            n = int(sel.hist[0, 0].sum().item())
+            if n == 0:
+                raise ValueError('pooled_percentiles: the pool holds no valid pixel')
+            plans = [percentile_plan64(n, x) for x in q]
+            sel.locate(0, [r for below, above, _ in plans for r in (below, above)])
+        else:
+            sel.locate(pass_)
+    stats = sel.values().cpu().numpy().astype(np.float64)   # (3, 2 len(q))
+    P = np.empty((3, len(q)), np.float32)
+    for c in range(3):
+        for i, (_, _, t) in enumerate(plans):
+            P[c, i] = np.float32(_lerp64(stats[c, 2 * i], stats[c, 2 * i + 1], t))
+    return P, n
+
+
+def _lerp64(a: float, b: float, t: float) -> float:
+    """numpy's ``_lerp`` in float64: ``a + (b - a) t``, formed from the upper end when ``t >= 0.5``."""
+    a, b, t = np.float64(a), np.float64(b), np.float64(t)
+    diff = b - a
+    return b - diff * (1 - t) if t >= 0.5 else a + diff * t
+
+
 def invert_images(views: list, params, light: bool = False) -> list:
     """Single-view inversion (``sucre_invert_images``): J of every view of ``views`` from its OWN depth map and colours at the
     given water parameters -- ``SUCRe.update_J`` (sucre.py:66-77) with one observation per pixel, the image itself:

@@ -34,6 +34,8 @@ class SUCRe(torch.nn.Module):
     image itself with NaN where the depth map is invalid, or -- with ``use_closed_form`` -- a plain attribute
     recomputed from the observations."""
 
+    stretch = None   # None: plot_J stretches every image by its own percentiles (the reference); (lo, hi): a fixed stretch
+
     def __init__(self, image: sfm.Image, light_model: bool = False, use_closed_form: bool = False,
                  _J_by_engine: bool = False):
         """``_J_by_engine`` (engine-internal): leave ``J`` uninitialised on the device -- the fit's first kernel
@@ -129,7 +131,16 @@ class SUCRe(torch.nn.Module):
     # -- output stage (sucre.py:84-121) -----------------------------------------------------------------------------
     @torch.no_grad()
     def plot_J(self) -> PILImage.Image:
-        """Restored image: per-channel 1-99 percentile stretch of the valid pixels, invalid pixels black."""
+        """Restored image: per-channel 1-99 percentile stretch of the valid pixels, invalid pixels black.  With
+        ``self.stretch = (lo, hi)`` set (--common-stretch, --stretch-from) the percentiles, the minimum and the maximum of the
+        image are replaced by the given numbers: ``uint8(((min(max(J, lo), hi) - lo) / (hi - lo)) * 255)`` in float32, the same
+        for every image that shares the stretch."""
+        if self.stretch is not None:
+            lo, hi = self.stretch
+            if self.J.is_cuda:
+                from . import engine
+                return PILImage.fromarray(engine.plot_stretch(self.J.detach().contiguous(), lo, hi).cpu().numpy())
+            return PILImage.fromarray(stretch_picture(self.J.detach().cpu().numpy(), lo, hi))
         if self.J.is_cuda and _NUMPY_2:
             return PILImage.fromarray(self._plot_J_device().cpu().numpy())
         J = self.J.detach().cpu().numpy().copy()
@@ -251,6 +262,94 @@ def percentile_lerp(a, b, t):
     if t >= 0.5:
         out = np.subtract(b, diff * (1 - t))
     return out
+
+
+def percentile_plan64(n: int, q: float) -> tuple[int, int, float]:
+    """(rank below, rank above, weight) of ``np.percentile(a.astype(np.float64), q)`` (method 'linear') for ``n`` values, in
+    float64: ``virtual = (n - 1) (q / 100)``, ``below = floor(virtual)``, ``above = min(below + 1, n - 1)``, ``t = virtual -
+    below``.  The plan of a POOL of images (``engine.pooled_percentiles``): a pool passes 2^24 pixels with nine 1080p images,
+    where the float32 index arithmetic of ``percentile_plan`` -- numpy's own for a float32 array, kept for the per-image path
+    that mirrors the reference -- would round the ranks."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f'percentile_plan64: n must be >= 1, not {n}')
+    q = float(q)
+    if not 0.0 <= q <= 100.0:
+        raise ValueError(f'percentile_plan64: q must lie in [0, 100], not {q}')
+    virtual = float(n - 1) * (q / 100.0)
+    below = int(np.floor(virtual))
+    if below >= n - 1:
+        return n - 1, n - 1, 0.0
+    return below, below + 1, virtual - below
+
+
+def stretch_picture(J: np.ndarray, lo, hi) -> np.ndarray:
+    """(H,W,3) uint8: the fixed stretch of a host image, ``uint8(((min(max(J, lo), hi) - lo) / (hi - lo)) * 255)`` in float32,
+    invalid pixels (a NaN in any channel) black -- ``plot_J`` with the per-image percentiles, minimum and maximum replaced by
+    ``lo``, ``lo`` and ``hi - lo``; the arithmetic of ``sucre_plot_stretch``."""
+    J = np.asarray(J, np.float32)
+    lo, hi = np.asarray(lo, np.float32).reshape(3), np.asarray(hi, np.float32).reshape(3)
+    ok = ~np.isnan(J).any(axis=2)
+    out = np.zeros(J.shape, np.uint8)
+    vals = np.minimum(np.maximum(J[ok], lo), hi)
+    out[ok] = (((vals - lo) / (hi - lo)) * np.float32(255)).astype(np.uint8)
+    return out
+
+
+def check_stretch(obj, where: str = 'stretch') -> tuple[np.ndarray, np.ndarray]:
+    """``(lo, hi)``, two (3,) float32 arrays, of a mapping such as a loaded ``stretch.pt`` (tensors or arrays of any float dtype;
+    other keys are ignored) or of a ``(lo, hi)`` pair.  A stretch is usable only if all six numbers are finite and ``hi > lo``
+    in every channel: ``ValueError`` naming the key or the channel that is missing, mis-shaped, non-finite or non-increasing."""
+    if hasattr(obj, 'keys'):
+        for key in ('lo', 'hi'):
+            if key not in obj:
+                raise ValueError(f"{where} holds no '{key}'")
+        pair = {'lo': obj['lo'], 'hi': obj['hi']}
+    else:
+        try:
+            lo, hi = obj
+        except (TypeError, ValueError):
+            raise ValueError(f"{where} holds no stretch (a mapping with the keys lo, hi or a (lo, hi) pair is expected)") from None
+        pair = {'lo': lo, 'hi': hi}
+    out = {}
+    for key, v in pair.items():
+        if torch.is_tensor(v):
+            v = v.detach().cpu().numpy()
+        v = np.asarray(v)
+        if v.shape != (3,) or v.dtype.kind != 'f':
+            raise ValueError(f"'{key}' in {where} is {v.dtype} {v.shape}, expected three floats, shape (3,)")
+        out[key] = v.astype(np.float32)
+    for c, name in enumerate('RGB'):
+        l, h = out['lo'][c], out['hi'][c]
+        if not np.isfinite(l):
+            raise ValueError(f"'lo' in {where} is not finite in channel {name} ({l})")
+        if not np.isfinite(h):
+            raise ValueError(f"'hi' in {where} is not finite in channel {name} ({h})")
+        if not h > l:
+            raise ValueError(f"{where}: hi must exceed lo in every channel, but channel {name} has lo {l} and hi {h}")
+    return out['lo'], out['hi']
+
+
+def read_stretch_file(path: Path) -> tuple[np.ndarray, np.ndarray]:
+    """``check_stretch`` of a ``.pt`` file, for the command line: ``SystemExit`` naming the file and the key or channel."""
+    try:
+        data = torch.load(path, map_location='cpu')
+    except Exception as e:
+        raise SystemExit(f'--stretch-from: cannot read {path}: {e}')
+    try:
+        return check_stretch(data, where=str(path))
+    except ValueError as e:
+        raise SystemExit(f'--stretch-from: {e}')
+
+
+def common_stretch(Js: list, q=(1, 99), group=None) -> tuple[np.ndarray, np.ndarray, int]:
+    """``(lo, hi, n)``: the per-channel ``q[0]``-th and ``q[1]``-th percentile, (3,) float32 each, of the POOL of the valid
+    pixels of the device images ``Js`` of all ranks of ``group`` (``engine.pooled_percentiles``), and the pooled number of valid
+    pixels.  ``ValueError`` when the pool is empty or the two do not make a stretch (``check_stretch``)."""
+    from . import engine
+    P, n = engine.pooled_percentiles(Js, q=(float(q[0]), float(q[1])), group=group)
+    lo, hi = check_stretch((P[:, 0].copy(), P[:, 1].copy()), where=f'the common stretch over {n} valid pixels')
+    return lo, hi, n
 
 
 def _restoration_of(matches_data: loader.MatchesData, sucre: 'SUCRe | None' = None):
@@ -567,7 +666,8 @@ def _restore_submit(image: sfm.Image, colmap_model: sfm.COLMAPModel, output_dir:
                     use_closed_form: bool, min_cover: float, image_list: list[sfm.Image], lr: float, num_iter: int,
                     params_path: Path, force_compute_matches: bool, num_workers: int, device: str,
                     defer_checks: bool = False, save_quality: bool = False, trim_outliers: float = None,
-                    trim_rounds: int = 1, view_gains: bool = False, gain_rounds: int = 1, gain_limit: float = 2.0) -> _Job:
+                    trim_rounds: int = 1, view_gains: bool = False, gain_rounds: int = 1, gain_limit: float = 2.0,
+                    stretch=None) -> _Job:
     """Stages of sucre.py:160-210 up to and including the enqueued fit; the trace and J stay on the device.
     ``defer_checks``: the integrity verdicts and the observation count stay on the device until ``_restore_finish``
     reads them with the results -- waiting for them here would make the host wait for the matching, which shares the
@@ -589,6 +689,7 @@ def _restore_submit(image: sfm.Image, colmap_model: sfm.COLMAPModel, output_dir:
     if params_path is not None:
         sucre.load_state_dict(torch.load(params_path), strict=False)
     params0 = sucre.water_vector().detach().cpu().numpy()   # still on the host: no wait
+    sucre.stretch = stretch   # (lo, hi): every _rgb*.png of this model, snapshots included (plot_J)
     sucre = sucre.to(device)
 
     reuse = not force_compute_matches and matches_file.on_disk()
@@ -777,11 +878,13 @@ def restore_image(image: sfm.Image, colmap_model: sfm.COLMAPModel, output_dir: P
 def _restore_one(image, colmap_model, output_dir, light_model, use_closed_form, min_cover, image_list, lr, num_iter, batch_size,
                  save_interval, params_path, force_compute_matches, keep_matches, num_workers, device, save_quality: bool = False,
                  trim_outliers: float = None, trim_rounds: int = 1, view_gains: bool = False, gain_rounds: int = 1,
-                 gain_limit: float = 2.0):
+                 gain_limit: float = 2.0, stretch=None):
     """``restore_image`` plus what its pinned signature has no room for (``save_quality``: --save-quality; ``trim_outliers``,
     ``trim_rounds``: --trim-outliers, --trim-rounds; ``view_gains``, ``gain_rounds``, ``gain_limit``: --view-gains, --gain-rounds,
-    --gain-limit)."""
+    --gain-limit; ``stretch``: the ``(lo, hi)`` of --stretch-from)."""
     sfm.require_gpu(device, 'restore_image')
+    if stretch is not None:
+        stretch = check_stretch(stretch)
     _check_trim(trim_outliers, trim_rounds)
     _check_gains(view_gains, gain_rounds, gain_limit, trim_outliers)
     if trim_outliers is not None and save_interval is not None:
@@ -791,7 +894,7 @@ def _restore_one(image, colmap_model, output_dir, light_model, use_closed_form, 
     job = _restore_submit(image, colmap_model, output_dir, light_model, use_closed_form, min_cover, image_list, lr,
                           num_iter, params_path, force_compute_matches, num_workers, device, save_quality=save_quality,
                           trim_outliers=trim_outliers, trim_rounds=trim_rounds, view_gains=view_gains, gain_rounds=gain_rounds,
-                          gain_limit=gain_limit)
+                          gain_limit=gain_limit, stretch=stretch)
     if save_quality:
         job.sucre._quality_wanted = True   # adam enqueues the pass behind its last fit
     adam(sucre=job.sucre, matches_data=job.matches_data, lr=lr, num_iter=num_iter, batch_size=batch_size,
@@ -812,7 +915,10 @@ def restore_images(images: list[sfm.Image], colmap_model: sfm.COLMAPModel, outpu
     (each image has its own workspace and stream; nothing is shared).  ``fit_batch`` consecutive images share a slot and
     their fits one launch per iteration (``fit_batch_size``; same bits again).  ``trim_outliers=None, trim_rounds=1`` (in
     ``kw``): the rounds of --trim-outliers, enqueued with the image behind its first fit, no host wait added; ``view_gains=False,
-    gain_rounds=1, gain_limit=2.0``: those of --view-gains, likewise."""
+    gain_rounds=1, gain_limit=2.0``: those of --view-gains, likewise; ``stretch=(lo, hi)``: every ``_rgb.png`` by this fixed
+    stretch (``check_stretch``) instead of the image's own percentiles (--stretch-from)."""
+    if kw.get('stretch') is not None:
+        kw['stretch'] = check_stretch(kw['stretch'])
     _check_trim(kw.get('trim_outliers'), kw.get('trim_rounds', 1))
     _check_gains(kw.get('view_gains', False), kw.get('gain_rounds', 1), kw.get('gain_limit', 2.0), kw.get('trim_outliers'))
     pending: list[tuple[int, list]] = []
@@ -899,12 +1005,38 @@ def read_water_file(path: Path, light_model: bool = False) -> dict:
         raise SystemExit(f'--apply-water: {e}')
 
 
-def _write_applied(image: sfm.Image, J: Tensor, water: dict, light_model: bool, output_dir: Path, device) -> None:
+def _free_device_memory(device) -> int:
+    return int(torch.cuda.mem_get_info(device)[0])
+
+
+def _check_stretch_memory(images: list, device) -> None:
+    """--apply-water --common-stretch keeps the J of every image of this rank on the device until the pool is complete: their
+    H W 12 bytes must fit into 0.8 of what is free now.  Checked before any image is decoded."""
+    need = sum(int(im.camera.height) * int(im.camera.width) * 12 for im in images)
+    free = _free_device_memory(device)
+    if need > 0.8 * free:
+        raise SystemExit(f'--common-stretch: the restored images of this rank ({len(images)} image(s), {need} bytes) stay on {device} '
+                         f'until the pool is complete, and {free} bytes are free; run more ranks (torchrun --nproc-per-node N), or '
+                         f'measure the stretch on fewer images and give its stretch.pt to the others with --stretch-from')
+
+
+def _write_common_stretch(output_dir: Path, lo, hi, n_valid: int, request: list, rank: int) -> None:
+    """Rank 0: ``stretch.pt`` and the line that reports the common stretch."""
+    if rank != 0:
+        return
+    torch.save({'lo': torch.from_numpy(np.asarray(lo, np.float32).copy()), 'hi': torch.from_numpy(np.asarray(hi, np.float32).copy()),
+                'q': torch.tensor([1.0, 99.0]), 'n_valid': int(n_valid), 'images': list(request)}, Path(output_dir) / 'stretch.pt')
+    print(f'common stretch over {len(request)} images, {int(n_valid)} valid pixels: '
+          + ', '.join(f'{name} lo {lo[c]:.6g} hi {hi[c]:.6g}' for c, name in enumerate('RGB')))
+
+
+def _write_applied(image: sfm.Image, J: Tensor, water: dict, light_model: bool, output_dir: Path, device, stretch=None) -> None:
     """``<stem>_rgb.png``, ``<name>.pt`` and, with the light model, ``<stem>_vignetting.png`` of one inverted image.  No
     ``_reconstruction.png``: the reconstruction of a single-view inversion is the input image."""
     sucre = SUCRe(image=image, light_model=light_model, use_closed_form=True)
     sucre.load_state_dict(water, strict=True)
     sucre.J = J
+    sucre.stretch = stretch
     stem = Path(image.name).stem
     _save_png(sucre.plot_J(), output_dir / f'{stem}_rgb.png')
     if light_model:
@@ -913,7 +1045,7 @@ def _write_applied(image: sfm.Image, J: Tensor, water: dict, light_model: bool, 
 
 
 def apply_water(images: list, colmap_model: sfm.COLMAPModel, output_dir: Path, water, light_model: bool = False,
-                device: str = 'cuda', in_flight: int = 2) -> None:
+                device: str = 'cuda', in_flight: int = 2, stretch=None, request: list | None = None, rank: int = 0) -> None:
     """Restores ``images`` (``sfm.Image`` objects or names of ``colmap_model``) with GIVEN water parameters instead of fitting
     them: per image ``J = (I - l B (1 - e^(-gamma z))) a / a^2``, ``a = l e^(-beta z)``, from the image's own depth map
     (``engine.invert_images``: ``update_J`` with the image as its only observation).  ``water``: a mapping with ``B, beta,
@@ -921,9 +1053,18 @@ def apply_water(images: list, colmap_model: sfm.COLMAPModel, output_dir: Path, w
     ``<name>.pt``, or the path of one.  Only the target images are decoded (the next launch's while this one's run); nothing is
     matched and no workspace is allocated.  Up to 32 images go into one launch on one of ``in_flight`` slots, and the
     output files -- ``<stem>_rgb.png``, ``<name>.pt`` (the parameters and J), ``<stem>_vignetting.png`` with the light model --
-    are written by background threads."""
+    are written by background threads.  ``stretch``: ``None`` -- every ``_rgb.png`` by its own percentiles, as the reference
+    does; ``(lo, hi)`` -- by this fixed stretch (``check_stretch``; --stretch-from); ``'common'`` -- by the 1st and 99th percentile
+    of the pool of the valid pixels of ALL images (of all ranks, when a process group is up: ``common_stretch``): the J of this
+    rank's images then stay on the device and the files are written once the pool is complete; rank 0 (``rank``) also writes
+    ``stretch.pt`` (``lo, hi, q, n_valid, images``: ``request``, the names of all ranks' images) for --stretch-from."""
     from . import engine
     sfm.require_gpu(device, 'apply_water')
+    common = isinstance(stretch, str)
+    if common and stretch != 'common':
+        raise ValueError(f"apply_water: stretch is None, 'common' or a (lo, hi) pair, not {stretch!r}")
+    if stretch is not None and not common:
+        stretch = check_stretch(stretch)
     if isinstance(water, (str, Path)):
         water = torch.load(water, map_location='cpu')
     water = check_water(water, light_model)
@@ -932,6 +1073,9 @@ def apply_water(images: list, colmap_model: sfm.COLMAPModel, output_dir: Path, w
     output_dir = Path(output_dir)
     output_dir.mkdir(parents=True, exist_ok=True)
     in_flight = max(1, int(in_flight))
+    if common:
+        _check_stretch_memory(images, device)
+    held: list = []   # 'common': (image, J) of this rank until the pool is complete
     chunks = [images[i:i + APPLY_IMAGES_PER_LAUNCH] for i in range(0, len(images), APPLY_IMAGES_PER_LAUNCH)]
     if chunks:
         loader.prefetch_device_views(chunks[0], device, background=True)
@@ -942,8 +1086,11 @@ def apply_water(images: list, colmap_model: sfm.COLMAPModel, output_dir: Path, w
         def finish(slot, chunk, Js):
             with engine.in_flight_slot(slot, device, wait_for_caller=False):
                 torch.cuda.current_stream().synchronize()   # the writer threads work on another stream
+            if common:
+                held.extend(zip(chunk, Js))
+                return
             for image, J in zip(chunk, Js):
-                written.append(writers.submit(_write_applied, image, J, water, light_model, output_dir, device))
+                written.append(writers.submit(_write_applied, image, J, water, light_model, output_dir, device, stretch))
             while len(written) > 64:   # bound the memory held by queued outputs
                 written.pop(0).result()
 
@@ -961,8 +1108,31 @@ def apply_water(images: list, colmap_model: sfm.COLMAPModel, output_dir: Path, w
             pending.append((slot, chunk, Js))
         for item in pending:
             finish(*item)
+        if common:   # every rank takes part, also one without an image
+            with torch.cuda.device(device):
+                lo, hi, n_valid = common_stretch([J for _, J in held])
+            _write_common_stretch(output_dir, lo, hi, n_valid, request if request is not None else [im.name for im in images], rank)
+            for image, J in held:
+                written.append(writers.submit(_write_applied, image, J, water, light_model, output_dir, device, (lo, hi)))
+                while len(written) > 64:
+                    written.pop(0).result()
+            held.clear()
         for f in written:
             f.result()   # re-raises anything a writer thread hit
+
+
+def _refuse_stretch_flags(args) -> None:
+    """What --common-stretch and --stretch-from do not combine with, refused before any file is opened."""
+    if not getattr(args, 'common_stretch', False):
+        return
+    if getattr(args, 'stretch_from', None) is not None:
+        raise SystemExit('--common-stretch: --stretch-from gives the stretch already; drop one of the two flags')
+    if not getattr(args, 'shared_water', False) and getattr(args, 'apply_water', None) is None:
+        raise SystemExit('--common-stretch: only with --shared-water or --apply-water -- images restored with their own water each '
+                         'have no common scale; take the stretch.pt of such a run and give it to this one with --stretch-from')
+    if args.save_interval is not None:
+        raise SystemExit('--common-stretch: --save-interval snapshots are written before the pool is complete; drop one of the two '
+                         'flags (--stretch-from combines with snapshots)')
 
 
 def _refuse_apply_flags(args) -> None:
@@ -986,6 +1156,11 @@ def parse_args(args: argparse.Namespace):
     rank, local_rank, world = sdist.env_rank_world()
     shared = bool(getattr(args, 'shared_water', False))
     apply = getattr(args, 'apply_water', None)
+    _refuse_stretch_flags(args)
+    common = bool(getattr(args, 'common_stretch', False))
+    stretch = None
+    if getattr(args, 'stretch_from', None) is not None:   # read and checked before any image is opened
+        stretch = read_stretch_file(args.stretch_from)
     if apply is not None:
         _refuse_apply_flags(args)
         water = read_water_file(apply, args.light_model)
@@ -1048,18 +1223,22 @@ def parse_args(args: argparse.Namespace):
         torch.set_num_threads(host_threads)
     try:
         if apply is not None:
-            apply_water(images, colmap_model, args.output_dir, water, light_model=args.light_model, device=device, in_flight=in_flight)
+            if common and world > 1:   # the pool spans the ranks: its histograms are all-reduced
+                sdist.init_process_group()
+            apply_water(images, colmap_model, args.output_dir, water, light_model=args.light_model, device=device, in_flight=in_flight,
+                        stretch='common' if common else stretch, request=request, rank=rank)
         elif shared:
-            restore_shared_water(images, colmap_model, args, image_list, device, request, rank, world)
+            restore_shared_water(images, colmap_model, args, image_list, device, request, rank, world,
+                                 stretch='common' if common else stretch)
         else:
-            _run_request(args, images, image_list, colmap_model, device, survey, in_flight)
+            _run_request(args, images, image_list, colmap_model, device, survey, in_flight, stretch=stretch)
     finally:
         _pixelio.stop_pool()
         if host_threads > 0:
             torch.set_num_threads(threads_before)
 
 
-def _run_request(args, images, image_list, colmap_model, device, survey: bool, in_flight: int) -> None:
+def _run_request(args, images, image_list, colmap_model, device, survey: bool, in_flight: int, stretch=None) -> None:
     if str(device).startswith('cuda') and images:   # start decoding + uploading the scene now, in the background
         loader.prefetch_for_targets(images, image_list, device, num_workers=args.num_workers, min_cover=args.min_cover)
     quality = {'save_quality': True} if getattr(args, 'save_quality', False) else {}
@@ -1068,6 +1247,8 @@ def _run_request(args, images, image_list, colmap_model, device, survey: bool, i
         quality.update(trim_outliers=float(trim), trim_rounds=int(getattr(args, 'trim_rounds', 1)))
     if getattr(args, 'view_gains', False):
         quality.update(view_gains=True, gain_rounds=int(getattr(args, 'gain_rounds', 1)), gain_limit=float(getattr(args, 'gain_limit', 2.0)))
+    if stretch is not None:
+        quality.update(stretch=stretch)
     if survey:
         restore_images(images, colmap_model, args.output_dir, in_flight=in_flight, keep_matches=args.keep_matches,
                        device=device, light_model=args.light_model, use_closed_form=args.use_closed_form,
@@ -1157,11 +1338,14 @@ def _check_shared_memory(images: list, image_list: list, light_model: bool, devi
 
 
 def restore_shared_water(images: list, colmap_model: sfm.COLMAPModel, args, image_list: list, device, request: list,
-                         rank: int = 0, world: int = 1) -> None:
+                         rank: int = 0, world: int = 1, stretch=None) -> None:
     """--shared-water: every image of this rank is matched into its own workspace, then all are fitted jointly with one
     B, beta, gamma (and, with --light-model, one cam2light, sigma) for the whole request -- every image keeps its own J --
     through engine.HipWaterGroup under dist.fit_shared_water (one all-reduce of the sums per iteration across the ranks).
-    Per image the outputs of a plain run; rank 0 also writes ``shared_water.pt`` (the shared parameters, ``trace``, ``images``)."""
+    Per image the outputs of a plain run; rank 0 also writes ``shared_water.pt`` (the shared parameters, ``trace``, ``images``).
+    ``stretch``: ``(lo, hi)`` -- every ``_rgb.png`` by this fixed stretch (--stretch-from); ``'common'`` -- by the 1st and 99th
+    percentile of the pool of the valid pixels of the J of all images of all ranks, pooled where they are once the group has
+    finished (``common_stretch``); rank 0 then also writes ``stretch.pt`` (--common-stretch)."""
     from . import engine
     if world > 1:
         sdist.init_process_group()
@@ -1173,7 +1357,8 @@ def restore_shared_water(images: list, colmap_model: sfm.COLMAPModel, args, imag
             jobs.append(_restore_submit(image, colmap_model, args.output_dir, args.light_model, args.use_closed_form,
                                         args.min_cover, image_list, args.learning_rate, args.num_iter, args.params_path,
                                         args.force_compute_matches, args.num_workers, device,
-                                        save_quality=bool(getattr(args, 'save_quality', False))))
+                                        save_quality=bool(getattr(args, 'save_quality', False)),
+                                        stretch=None if isinstance(stretch, str) else stretch))
     restos = [_adam_begin(j.sucre, j.matches_data, params0=jobs[0].params0) for j in jobs]
     T = int(args.num_iter)
     trace = torch.zeros((T, 20 if args.light_model else 10), dtype=torch.float64, device=restos[0].device)
@@ -1188,6 +1373,11 @@ def restore_shared_water(images: list, colmap_model: sfm.COLMAPModel, args, imag
     for job, resto in zip(jobs, restos):
         _pull_results(job.sucre, resto)
     shared = {k: v.detach().cpu().clone() for k, v in jobs[0].sucre.state_dict().items() if k != 'J'}
+    if isinstance(stretch, str):   # 'common': the J of this rank are resident; every rank obtains the same six numbers
+        lo, hi, n_valid = common_stretch([job.sucre.J.detach().contiguous() for job in jobs])
+        _write_common_stretch(args.output_dir, lo, hi, n_valid, request, rank)
+        for job in jobs:
+            job.sucre.stretch = (lo, hi)
     for job in jobs:
         _restore_finish(job, args.keep_matches)
     if rank == 0:
@@ -1263,6 +1453,13 @@ def build_parser() -> argparse.ArgumentParser:
                           help='do not fit: restore every image of the request from its own depth map with the B, beta, gamma (and, '
                                'with --light-model, cam2light, sigma) of this .pt file -- a shared_water.pt or a <name>.pt of an '
                                'earlier run; writes <stem>_rgb.png and <name>.pt (and <stem>_vignetting.png) per image')
+    p.extras.add_argument('--common-stretch', action='store_true', default=argparse.SUPPRESS,
+                          help='with --shared-water or --apply-water: stretch every <stem>_rgb.png between the SAME per-channel 1st '
+                               'and 99th percentile, those of the valid pixels of all images of the request pooled (all ranks), '
+                               'instead of each image\'s own; also writes stretch.pt (lo, hi, q, n_valid, images)')
+    p.extras.add_argument('--stretch-from', type=Path, metavar='PATH', default=argparse.SUPPRESS,
+                          help='stretch every <stem>_rgb*.png between the per-channel lo and hi (3 floats each) of this .pt file -- '
+                               'the stretch.pt of a --common-stretch run -- instead of each image\'s own percentiles; in every mode')
     p.extras.add_argument('--trim-rounds', type=int, metavar='N', default=argparse.SUPPRESS,
                           help='rounds of --trim-outliers (1 unless given)')
     p.extras.add_argument('--view-gains', action='store_true', default=argparse.SUPPRESS,
