@@ -168,15 +168,17 @@ class _Samples:
 
 
 def fit(H: int, W: int, samples, J0: np.ndarray | None, params0=None, num_iter: int = 200, lr: float = 0.05,
-        use_closed_form: bool = False):
-    """sucre.adam (sucre.py:124-157).  Returns (J (H,W,3), params (9,), trace (num_iter,10))."""
+        use_closed_form: bool = False, betas=(0.9, 0.999), eps: float = 1e-8):
+    """sucre.adam (sucre.py:124-157).  ``betas``, ``eps``: Adam's (torch.optim.Adam's defaults).
+    Returns (J (H,W,3), params (9,), trace (num_iter,10))."""
     s = _Samples(samples)
     J = np.ascontiguousarray(J0, np.float32).copy() if J0 is not None else np.zeros((H, W, 3), np.float32)
     params = np.full(9, 0.1, np.float32) if params0 is None else np.ascontiguousarray(params0, np.float32).copy()
     trace = np.zeros((num_iter, 10), np.float64)
     rc = lib().oracle_fit(C.c_int(H), C.c_int(W), C.c_int(s.n), _p(s.counts, C.c_int64), s.us, s.vs, s.cPs, s.Is,
                           _p(J, C.c_float), _p(params, C.c_float), C.c_int(num_iter), C.c_double(lr),
-                          C.c_int(int(use_closed_form)), _p(trace, C.c_double))
+                          C.c_int(int(use_closed_form)), _p(trace, C.c_double), C.c_double(betas[0]), C.c_double(betas[1]),
+                          C.c_double(eps))
     if rc != 0:
         raise MemoryError('oracle_fit')
     return J, params, trace
@@ -265,9 +267,9 @@ def se3_exp(xi) -> tuple[np.ndarray, np.ndarray]:
 
 
 def fit_light(H: int, W: int, samples, J0, params0=None, num_iter: int = 200, lr: float = 0.05,
-              use_closed_form: bool = False):
+              use_closed_form: bool = False, betas=(0.9, 0.999), eps: float = 1e-8):
     """sucre.adam with light_model=True (sucre.py:54-61, 124-157).  params: B, beta, gamma, cam2light[6], sigma[4].
-    Returns (J, params (19,), trace (num_iter, 20))."""
+    ``betas``, ``eps``: Adam's (torch.optim.Adam's defaults).  Returns (J, params (19,), trace (num_iter, 20))."""
     s = _Samples(samples)
     J = np.ascontiguousarray(J0, np.float32).copy() if J0 is not None else np.zeros((H, W, 3), np.float32)
     if params0 is None:
@@ -278,7 +280,8 @@ def fit_light(H: int, W: int, samples, J0, params0=None, num_iter: int = 200, lr
     lib().oracle_fit_light.restype = C.c_int
     rc = lib().oracle_fit_light(C.c_int(H), C.c_int(W), C.c_int(s.n), _p(s.counts, C.c_int64), s.us, s.vs, s.cPs, s.Is,
                                 _p(J, C.c_float), _p(params, C.c_float), C.c_int(num_iter), C.c_double(lr),
-                                C.c_int(int(use_closed_form)), _p(trace, C.c_double))
+                                C.c_int(int(use_closed_form)), _p(trace, C.c_double), C.c_double(betas[0]),
+                                C.c_double(betas[1]), C.c_double(eps))
     if rc != 0:
         raise MemoryError('oracle_fit_light')
     return J, params, trace

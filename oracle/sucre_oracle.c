@@ -242,7 +242,8 @@ static inline void adam_step(float *p, float *m, float *v, float g, const adam_c
  */
 int oracle_fit(int H, int W, int n_samples, const int64_t *counts, const int16_t *const *us,
                const int16_t *const *vs, const float *const *cPs, const float *const *Is,
-               float *J, float *params, int num_iter, double lr, int use_closed_form, double *trace) {
+               float *J, float *params, int num_iter, double lr, int use_closed_form, double *trace,
+               double beta1, double beta2, double eps) {
     const size_t npx = (size_t)H * W * 3;
     int64_t n_obs = 0;
     for (int s = 0; s < n_samples; ++s) n_obs += counts[s];
@@ -290,7 +291,7 @@ int oracle_fit(int H, int W, int n_samples, const int64_t *counts, const int16_t
             for (int c = 0; c < 3; ++c) { gB[c] += tB[c]; gbeta[c] += tb[c]; ggamma[c] += tg[c]; }
             cost += tc;
         }
-        const adam_coef_t co = adam_coef(it + 1, lr, 0.9, 0.999, 1e-8);
+        const adam_coef_t co = adam_coef(it + 1, lr, beta1, beta2, eps);
         for (int c = 0; c < 3; ++c) {
             adam_step(&B[c], &mP[c], &vP[c], (float)gB[c], &co);
             adam_step(&beta[c], &mP[3 + c], &vP[3 + c], (float)gbeta[c], &co);
@@ -521,11 +522,13 @@ int oracle_update_J_light(int H, int W, int n_samples, const int64_t *counts, co
 
 /*
  * sucre.adam with light_model=True (sucre.py:124-157); use_closed_form as in oracle_fit.  params: 19 floats in/out.
- * trace: num_iter x 20 doubles (cost, 19 parameters after the step).
+ * trace: num_iter x 20 doubles (cost, 19 parameters after the step).  beta1, beta2, eps: Adam's (torch's defaults are
+ * 0.9, 0.999, 1e-8; with eps well above |g| one step is an almost linear image of the gradient, tests/light64.py).
  */
 int oracle_fit_light(int H, int W, int n_samples, const int64_t *counts, const int16_t *const *us,
                      const int16_t *const *vs, const float *const *cPs, const float *const *Is, float *J,
-                     float *params, int num_iter, double lr, int use_closed_form, double *trace) {
+                     float *params, int num_iter, double lr, int use_closed_form, double *trace,
+                     double beta1, double beta2, double eps) {
     const size_t npx = (size_t)H * W * 3;
     int64_t n_obs = 0;
     for (int s = 0; s < n_samples; ++s) n_obs += counts[s];
@@ -600,7 +603,7 @@ int oracle_fit_light(int H, int W, int n_samples, const int64_t *counts, const i
             const double sym[4] = {2 * dS[0], dS[1] + dS[2], dS[1] + dS[2], 2 * dS[3]};
             mat_mul(sg, sym, g + 15, 2);   /* dsigma = sigma (dSigma + dSigma^T) */
         }
-        const adam_coef_t co = adam_coef(it + 1, lr, 0.9, 0.999, 1e-8);
+        const adam_coef_t co = adam_coef(it + 1, lr, beta1, beta2, eps);
         for (int k = 0; k < 19; ++k) adam_step(&params[k], &mP[k], &vP[k], (float)g[k], &co);
         if (!use_closed_form)
             for (size_t i = 0; i < npx; ++i) adam_step(&J[i], &mJ[i], &vJ[i], gJ[i], &co);
