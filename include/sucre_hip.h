@@ -56,6 +56,9 @@ extern "C" {
 #define SUCRE_FIT_KEEP_J 8u      /* with SUCRE_FIT_CLOSED_FORM: do not append the final update_J (sucre.py:156), i.e. leave
                                     J = J(theta_k) of the last iteration k next to theta_{k+1} -- the pair the reference
                                     plots at a --save-interval stop (sucre.py:141,153-154) */
+#define SUCRE_FIT_UNPAIRED 32u   /* sucre_fit_run without SUCRE_FIT_CLOSED_FORM: one launch per iteration, as before the
+                                    iterations were taken in pairs of launches that touch a pixel's Adam moments once per pair.
+                                    Either way every result bit is the same (tests, A/B measurements) */
 
 /*
  * Observation formats of the store the fit streams.  SUCRE_OBS_F32: float32 range + 3 uint8
@@ -117,10 +120,15 @@ enum {
     SUCRE_WS_PARAMS = 3,     /* float32[9]       B[3], beta[3], gamma[3], sucre.py:41-43                  */
     SUCRE_WS_SUMS = 4,       /* float64[12]      reduced gradient sums of the last sucre_fit_grad (multi-GPU) */
     SUCRE_WS_N_OBS_TOTAL = 5,/* uint64[1]        n_obs used for the 1/(3 n_obs) scale (shared-water: summed over ranks) */
-    SUCRE_WS_STORE_FORMAT = 6/* uint32[4]        how sucre_finalize_matches* laid the observations out: 0 = float32 ranges,
+    SUCRE_WS_STORE_FORMAT = 6,/* uint32[4]       how sucre_finalize_matches* laid the observations out: 0 = float32 ranges,
                                                  1 = uint16 millimetres, 2 = 24-bit, 3 = 26-bit offsets of the float32 bit
                                                  patterns; the offset; the smallest and the largest float32 bit pattern among
                                                  the ranges */
+    SUCRE_WS_STATE = 7,      /* float32[4 tiles][9][64]  J, exp_avg, exp_avg_sq (three channel planes each) of every strip of 64
+                                                 count-sorted pixels, tiles = ceil(H/16) ceil(W/16): the fit's per-pixel state */
+    SUCRE_WS_PAIR_GRADIENT = 8 /* float32[4 tiles][3][64]  scratch of a sucre_fit_run call that pairs its iterations: the only
+                                                 bytes of a workspace that depend on SUCRE_FIT_UNPAIRED; runs to the workspace's end
+                                                 together with the paired launches' item lists */
 };
 
 int sucre_version(void);
@@ -214,6 +222,8 @@ int sucre_fit_init(void *ws, int H, int W, int n_views, const uint8_t *rgb1_dev,
  * With SUCRE_FIT_CLOSED_FORM the final update_J of sucre.py:156 is included (unless SUCRE_FIT_KEEP_J), and a run that
  * starts at t0 = 0 first solves J once from the initial parameters, so that the one-pass kernel measures its
  * residuals from a J that is already close (accuracy only: iteration 0 re-solves J from the observations anyway).
+ * Without SUCRE_FIT_CLOSED_FORM the T iterations run as T / 2 pairs of launches (and one single launch if T is odd) unless
+ * SUCRE_FIT_UNPAIRED: nothing is pending when the call returns, and the workspace holds what T single launches leave.
  */
 int sucre_fit_run(void *ws, int H, int W, int n_views, int t0, int T, double lr, double beta1, double beta2,
                   double eps, unsigned flags, double *trace_dev, void *stream);

@@ -18,10 +18,11 @@ FIT_OBS_U16MM = 2
 FIT_EXT_COLOUR = 4
 FIT_EXT_BOTH = 16
 FIT_KEEP_J = 8
+FIT_UNPAIRED = 32   # sucre_fit_run, J-parameter mode: one launch per iteration instead of pairs of launches (same bits)
 OBS_F32, OBS_U16MM, OBS_F32_PLAIN, OBS_F32_Z26 = 0, 1, 2, 3
 EXT_POINTS, EXT_COLOUR, EXT_POINTS_COLOUR = 1, 2, 3
 OBS_FORMATS = {'f32': OBS_F32, 'u16mm': OBS_U16MM, 'f32plain': OBS_F32_PLAIN, 'f32z26': OBS_F32_Z26}
-WS_VIEW_COUNT, WS_VIEW_KEEP, WS_N_OBS, WS_PARAMS, WS_SUMS, WS_N_OBS_TOTAL, WS_STORE_FORMAT = range(7)
+WS_VIEW_COUNT, WS_VIEW_KEEP, WS_N_OBS, WS_PARAMS, WS_SUMS, WS_N_OBS_TOTAL, WS_STORE_FORMAT, WS_STATE, WS_PAIR_GRADIENT = range(9)
 INVERT_LIGHT, INVERT_FLOAT_COLOUR = 1, 2
 INVERT_MAX_IMAGES = 4096   # kInvertMaxImages of csrc/invert.h: images per sucre_invert_images call
 POOL_MAX_IMAGES = 4096     # kPoolMaxImages of csrc/pool.h: images per sucre_pool_select_pass call

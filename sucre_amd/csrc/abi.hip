@@ -90,6 +90,8 @@ int64_t sucre_ws_offset(int H, int W, int n_views, int region) {
         case SUCRE_WS_SUMS: return (int64_t)L.off_sums;
         case SUCRE_WS_N_OBS_TOTAL: return (int64_t)L.off_n_obs_total;
         case SUCRE_WS_STORE_FORMAT: return (int64_t)off_store_format(L);
+        case SUCRE_WS_STATE: return (int64_t)L.off_state;
+        case SUCRE_WS_PAIR_GRADIENT: return (int64_t)L.off_gplane;
         default: return fail(SUCRE_ERR_RANGE, "unknown workspace region %d", region);
     }
 }
@@ -218,17 +220,26 @@ int sucre_fit_run(void *ws, int H, int W, int n_views, int t0, int T, double lr,
     if (int rc = check_ws(ws, H, W, n_views, &L)) return rc;
     if (t0 < 0 || T < 0) return fail(SUCRE_ERR_RANGE, "t0=%d T=%d must be >= 0", t0, T);
     if (int rc = check_adam(t0 + 1, lr, beta1, beta2, eps)) return rc;
-    if (flags & ~(SUCRE_FIT_CLOSED_FORM | SUCRE_FIT_OBS_U16MM | SUCRE_FIT_KEEP_J)) return fail(SUCRE_ERR_ARG, "unknown fit flags 0x%x", flags);
+    if (flags & ~(SUCRE_FIT_CLOSED_FORM | SUCRE_FIT_OBS_U16MM | SUCRE_FIT_KEEP_J | SUCRE_FIT_UNPAIRED)) return fail(SUCRE_ERR_ARG, "unknown fit flags 0x%x", flags);
     if (trace_dev && !aligned(trace_dev, 8)) return fail(SUCRE_ERR_ARG, "trace must be 8-byte aligned");
     auto *w = static_cast<uint8_t *>(ws);
     auto s = static_cast<hipStream_t>(stream);
     const int fmt = (flags & SUCRE_FIT_OBS_U16MM) ? SUCRE_OBS_U16MM : SUCRE_OBS_F32;
+    // J-parameter iterations go in pairs of launches (fit.hip, 'Paired iterations'); an odd one out runs alone, behind them
+    const bool paired = fit_pair_built() && !(flags & (SUCRE_FIT_CLOSED_FORM | SUCRE_FIT_UNPAIRED));
+    flags &= ~SUCRE_FIT_UNPAIRED;
     // The one-pass closed-form kernel forms its sums relative to the previous J (fit.hip, AccOne): at t0 = 0 that is
     // the initial image, far from the solved J, and the differences S - dJ S' cancel digits in iteration 0 (seen as
     // 2.6e-5 relative on the logged cost at 4K x 25 views).  One plain update_J first makes dJ small from the start.
     if ((flags & SUCRE_FIT_CLOSED_FORM) && t0 == 0 && T > 0)
         if (int rc = check_hip(launch_update_J(L, w, fmt, s), "sucre_fit_run/initial update_J")) return rc;
-    for (int it = 0; it < T; ++it) {
+    int it = 0;
+    for (; paired && it + 1 < T; it += 2) {
+        const AdamCoef co0 = adam_coef(t0 + it + 1, lr, beta1, beta2, eps), co1 = adam_coef(t0 + it + 2, lr, beta1, beta2, eps);
+        if (int rc = check_hip(launch_fit_pair_fused(L, w, co0, co1, flags, trace_dev ? trace_dev + (size_t)it * 10 : nullptr,
+                                                     trace_dev ? trace_dev + (size_t)(it + 1) * 10 : nullptr, s), "sucre_fit_run")) return rc;
+    }
+    for (; it < T; ++it) {
         const AdamCoef co = adam_coef(t0 + it + 1, lr, beta1, beta2, eps);
         if (int rc = check_hip(launch_fit_iter_fused(L, w, co, flags, trace_dev ? trace_dev + (size_t)it * 10 : nullptr, s),
                                "sucre_fit_run")) return rc;

@@ -81,6 +81,17 @@ constexpr bool kExactJAdam = SUCRE_EXACT_J_ADAM != 0;
 #endif
 constexpr bool kScaledBBuilt = SUCRE_SCALED_B != 0;
 
+// fit.hip / abi.hip: sucre_fit_run takes its J-parameter iterations in PAIRS of launches that read and write a pixel's Adam moments
+// once per pair instead of once per launch (1; fit.hip, 'Paired iterations': same operations in the same order, same bits) or one
+// by one as until round 11 (0: no paired kernel is built, the plan kernel writes no paired streams, and fit_grad_kernel's text is
+// the parent's).  At run time SUCRE_FIT_UNPAIRED (sucre_hip.h) picks the launches one by one in a build that has both; whether
+// the engine pairs by default follows the measurement in profiles/r12_paired_j_ab.txt (engine.py, PAIRED_FIT).
+// (tests/test_paired_host.py builds the 0 form, so that it cannot rot.)
+#if !defined(SUCRE_PAIRED_J)
+#define SUCRE_PAIRED_J 1
+#endif
+constexpr bool kPairedBuilt = SUCRE_PAIRED_J != 0;
+
 // fit.hip, timing only: every wave of a J-parameter launch records when it entered and left its strips (100 MHz wall clock) --
 // how much of a launch is its ragged end (tools/exp/wave_times.py).
 #ifdef SUCRE_EXP_WAVE_TIMES

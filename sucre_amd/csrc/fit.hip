@@ -270,17 +270,7 @@ __device__ __forceinline__ uint32_t lds_addr(const void *p) {
     return static_cast<uint32_t>(reinterpret_cast<uintptr_t>(p));  // low 32 bits of a flat LDS address = LDS offset
 }
 
-// PlanItem.shape: [6:0] nA - 1, [14:8] max(nB, 1) - 1, [22:16] B's first 16-byte piece (nA, or nA - 1 when nB = 0: B then
-// re-reads the item's last piece), [31] a full chunk (nA = 64 and nB = kFullB: both offsets are per-lane constants).
-constexpr uint32_t kShapeFull = 1u << 31;
-constexpr uint32_t kShapeTrail = 1u << 30;   // one of the trailing items behind a wave's last strip (nobody consumes it; a batch
-                                             // launch copies the NEXT image's first items in its place: StreamChain)
-__host__ __device__ constexpr uint32_t full_chunk_b(int fmt) { return (uint32_t)(chunk_bytes(fmt) - 1024) / 16u; }   // 48 / 16 / 32 lanes
-__host__ __device__ __forceinline__ uint32_t item_shape(uint32_t bytes, bool full_chunk) {
-    const uint32_t pieces = bytes / 16u;   // every item is a multiple of 16 bytes (static_asserts below)
-    const uint32_t nA = pieces < 64u ? pieces : 64u, nB = pieces - nA;
-    return (nA - 1u) | ((nB ? nB - 1u : 0u) << 8) | ((nB ? nA : nA - 1u) << 16) | (full_chunk ? kShapeFull : 0u);
-}
+// (PlanItem.shape, item_shape, kShapeFull / kShapeTrail: layout.h, next to the writers of the item streams.)
 static_assert(level_bytes(0) % 16 == 0 && level_bytes(1) % 16 == 0 && level_bytes(2) % 16 == 0 && level_bytes(3) % 16 == 0 && kChunk % 16 == 0 && kChunk16 % 16 == 0 && kChunk24 % 16 == 0 && kChunk26 % 16 == 0, "items are copied in 16-byte pieces");
 static_assert(kChunk <= 2048 && kChunk >= 1024 && kChunk16 >= 1024 && kChunk24 >= 1024 && kChunk26 >= 1024 && kChunk26 <= kChunk, "a full chunk is one whole DMA + a partial one");
 static_assert(level_bytes(0) % 64 == 0 && level_bytes(1) % 64 == 0 && level_bytes(2) % 64 == 0 && (kGroupLv * level_bytes(3)) % 64 == 0, "items start on 64-byte units (PlanItem.src64; a kStoreZ26 strip starts on a whole chunk)");
@@ -341,14 +331,16 @@ static_assert(2 * kAhead + 9 <= 63, "s_waitcnt vmcnt takes six bits");
 // strip's items start in the wave's list from the level counts of the wave's earlier strips (at most a handful) and
 // writes them.  (The first version replayed the issue order serially, one thread per wave over all its strips: 90 + 60 us
 // per image for the two modes.)
-__device__ __forceinline__ uint32_t strip_items(uint32_t levels, int mode) { return 1u + ((levels + 3u) >> 2) + (mode == 0 ? 1u : 0u); }
-
+// The J-parameter plan's thread also writes the strip in the two streams of a paired iteration (kStreamL, kStreamF: layout.h): the
+// same wave, the same strips in the same order -- they share plan 0's strip lists and counts --, one item per strip fewer (L) or
+// more (F), so the strip's items start k places earlier or later in the wave's list.
 __global__ __launch_bounds__(256) void plan_kernel(const StripMeta *__restrict__ meta, int n_strips, const uint32_t *__restrict__ store_fmt, uint32_t W0, uint32_t W1,
                                                    uint32_t Kmax, uint32_t stride0, uint32_t stride1, uint32_t kmax0, uint32_t kmax1,
                                                    PlanItem *__restrict__ plan0, PlanItem *__restrict__ plan1,
                                                    StripEntry *__restrict__ strips0, StripEntry *__restrict__ strips1,
                                                    uint32_t *__restrict__ count0, uint32_t *__restrict__ count1, uint64_t comp_off,
-                                                   uint64_t state_off) {
+                                                   uint64_t state_off, uint32_t stride_pair, PlanItem *__restrict__ planL, PlanItem *__restrict__ planF,
+                                                   uint64_t gplane_off) {
     const int mode = blockIdx.y;   // both plans in one launch
     const int fmt = (int)store_fmt[0];   // kStoreF32 / kStoreU16 / kStoreZ24 / kStoreZ26: what the compaction has just written (decide_store_format)
     const uint32_t W = mode ? W1 : W0, stride = mode ? stride1 : stride0, kmax = mode ? kmax1 : kmax0;
@@ -358,33 +350,7 @@ __global__ __launch_bounds__(256) void plan_kernel(const StripMeta *__restrict__
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
     const uint32_t wid = idx / Kmax, k = idx - wid * Kmax;
     if (wid >= W) return;
-    // the wave's strips up to its k-th (layout.h, deal_walk): where that one's items start in the wave's list, and how many strips
-    // the wave has in all
-    const DealShares sh = deal_shares(mode, W / 4u);
-    uint32_t start = 0u, strip = 0u, strip0 = 0u;
-    const uint32_t K = deal_walk(wid, W, (uint32_t)n_strips, sh, [&](uint32_t s) { return meta[s].levels; }, [&](uint32_t kk, uint32_t s) {
-        if (kk == 0u) strip0 = s;
-        if (kk < k) start += strip_items(meta[s].levels, mode);
-        if (kk == k) strip = s;
-    });
-    if (k == 0u) count[wid] = K;
-    if (k >= K) return;
-    const StripMeta m = meta[strip];
-    const uint32_t nfull = m.levels >> 2, r = m.levels & 3u;   // full chunks, levels of the short last one
-    const uint32_t nu = min(nfull, m.full >> 2);               // chunks wholly below the strip's smallest pixel count
-    const uint32_t lb = (uint32_t)level_bytes(fmt);
-    const uint64_t st = state_off + (uint64_t)strip * (kStateFloats * 4);
-    PlanItem *out = plan + (size_t)wid * stride + start;
-    strips[(size_t)wid * kmax + k] = StripEntry{strip, strip_counts(nu, nfull - nu, r)};
-    *out++ = PlanItem{(uint32_t)(st >> 6), item_shape(3u * kStripPx * 4u, false)};
-    for (uint32_t g = 0; g < nfull; ++g)
-        *out++ = PlanItem{(uint32_t)((comp_off + (m.lvoff + (uint64_t)g * kGroupLv) * lb) >> 6), item_shape((uint32_t)chunk_bytes(fmt), true)};
-    if (r) *out++ = PlanItem{(uint32_t)((comp_off + (m.lvoff + (uint64_t)nfull * kGroupLv) * lb) >> 6), item_shape(r * lb, false)};
-    if (mode == 0) *out++ = PlanItem{(uint32_t)((st + 3 * kStripPx * 4) >> 6), item_shape(6u * kStripPx * 4u, false)};
-    if (k + 1u == K) {   // the kAhead trailing items nobody consumes (+ one spare the descriptor prefetch may touch)
-        const uint64_t st0 = state_off + (uint64_t)strip0 * (kStateFloats * 4);
-        for (int j = 0; j < kAhead + 1; ++j) *out++ = PlanItem{(uint32_t)(st0 >> 6), item_shape(3u * kStripPx * 4u, false) | kShapeTrail};
-    }
+    plan_thread(mode, fmt, wid, k, W, (uint32_t)n_strips, meta, plan, strips, count, stride, kmax, comp_off, state_off, planL, planF, stride_pair, gplane_off);
 }
 
 // Plan items are read through the constant address space: for it the compiler emits scalar loads (s_load) whenever the
@@ -542,7 +508,10 @@ struct StreamChain {
     uint32_t cs, behind;
 };
 
-template <int kFmt, int kStores, bool kMoments, bool kPrimed = false, class Chain = NoChain, class OnJ, class OnChunk, class OnTail, class OnEnd>
+// kStart = 3 (kStreamF, layout.h): a strip begins with THREE items -- J plane, G plane, moments -- and on_J(slot pointer, which)
+// is called for each in turn.  The waits need no other change: what a step may leave outstanding depends on how many items were
+// issued behind the one it consumes and on whether the last strip's stores were issued behind it, not on what the items are.
+template <int kFmt, int kStores, bool kMoments, bool kPrimed = false, class Chain = NoChain, int kStart = 1, class OnJ, class OnChunk, class OnTail, class OnEnd>
 __device__ __forceinline__ void stream_strips(FitLds &lds, const PlanItem *__restrict__ plan, const StripEntry *__restrict__ strip_list,
                                               uint32_t K, const uint8_t *__restrict__ ws, int wave, int lane, uint32_t fullB, OnJ on_J,
                                               OnChunk on_chunk, OnTail on_tail, OnEnd on_end, Chain *chain = nullptr) {
@@ -604,7 +573,14 @@ __device__ __forceinline__ void stream_strips(FitLds &lds, const PlanItem *__res
         const uint32_t strip = se.x, counts = se.y;
         if (k + 1u < K) se = strips[k + 1u];
         const uint32_t nu = counts_unmasked(counts), nm = counts_masked(counts), r = counts_tail(counts);
-        on_J(step());
+        if constexpr (kStart == 3) {
+            static_assert(!kMoments, "the moments are among the start items");
+            on_J(step(), std::integral_constant<int, 0>{});
+            on_J(step(), std::integral_constant<int, 1>{});
+            on_J(step(), std::integral_constant<int, 2>{});
+        } else {
+            on_J(step());
+        }
         for (uint32_t g = 0; g < nu; ++g) on_chunk(step(), false);
         for (uint32_t g = 0; g < nm; ++g) on_chunk(step(), true);
         if (r) on_tail(step(), r);
@@ -860,6 +836,104 @@ __device__ __forceinline__ void run_grad_pass(bool scaled, FitLds &lds, const Pl
     else grad_pass<kFmt, false, kPrimed, Chain>(lds, plan, strips, n_strips_wave, ws, state, wave, lane, w, gscale, co, acc, sBeta, rc, chain);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Paired iterations (sucre_fit_run, J-parameter mode; experiment.h SUCRE_PAIRED_J).  The gradient pass of iteration t needs J_t
+// only; a pixel's moments are needed to take the step.  Two iterations t, t + 1 are therefore two launches that touch the
+// moments once:
+//   L (kPair 1)  streams [J plane][chunks] (kStreamL), forms sBeta from J_t as grad_pass does, and at the strip's end stores the
+//                gradient grad_pass would have handed to adam_update_J -- the float gscale * acc.pa[c] itself -- to the G plane:
+//                3 stores, 768 B read and 768 B written per strip instead of 2304 and 2304.
+//   F (kPair 2)  streams [J plane][G plane][moments][chunks] (kStreamF): at the strip's START it takes the step L deferred,
+//                adam_update_J(J_t, m_(t-1), v_(t-1), G_t, co_t), keeps J_(t+1), m_t, v_t in registers, runs iteration t + 1's
+//                pass on J_(t+1) and takes its step, with co_(t+1), at the strip's end: 3072 B read, 2304 B written.
+// Every value goes through the operations grad_pass puts it through, in the same order (the file is built with
+// -ffp-contract=off: the product gscale * pa is one rounding wherever it is formed), and the strips, their order in a wave and
+// the reduction trees are plan 0's: J, the moments, the water parameters and the log keep every bit (tests/test_gpu_paired.py).
+// The water step and the log row of both iterations are the launches' own finishers, unchanged.  Nothing is pending when F ends.
+// ---------------------------------------------------------------------------------------------------------------
+template <int kFmt, bool kScaledB, int kPair>
+__device__ __forceinline__ void pair_pass(FitLds &lds, const PlanItem *__restrict__ plan, const StripEntry *__restrict__ strips, uint32_t n_strips_wave,
+                                          const uint8_t *__restrict__ ws, float *__restrict__ state, float *__restrict__ gplane, int wave, int lane,
+                                          const Water &w, float gscale, const AdamCoef &co_prev, const AdamCoef &co, Acc &acc, float (&sBeta)[3],
+                                          const RangeCodes &rc) {
+    static_assert(kPair == 1 || kPair == 2, "L or F");
+    float J[3] = {0.f, 0.f, 0.f}, G[3] = {0.f, 0.f, 0.f}, M[3] = {0.f, 0.f, 0.f}, V[3] = {0.f, 0.f, 0.f};
+    auto begin = [&](const uint8_t *sp) {  // J plane
+        const float *f = reinterpret_cast<const float *>(sp);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { J[c] = f[c * kStripPx + lane]; acc.pa[c] = 0.f; acc.pb[c] = 0.f; }
+    };
+    auto on_chunk = [&](const uint8_t *sp, bool masked) {  // chunk of four levels
+        float zz[kGroupLv];
+        uint32_t cc[3];
+        read_chunk<kFmt>(sp, lane, zz, cc, rc, masked);
+        if (masked) accumulate_chunk<true, kScaledB>(zz, cc, w, J, acc);
+        else accumulate_chunk<false, kScaledB>(zz, cc, w, J, acc);
+    };
+    auto on_tail = [&](const uint8_t *sp, uint32_t r) {  // the strip's short last chunk
+        for (uint32_t j = 0; j < r; ++j) {
+            float z;
+            uint32_t k[3];
+            read_level<kFmt>(sp, lane, r, j, z, k, rc);
+            accumulate_level<kScaledB>(z, k, w, J, acc);
+        }
+    };
+    if constexpr (kPair == 1) {
+        stream_strips<kFmt, 3, false>(
+            lds, plan, strips, n_strips_wave, ws, wave, lane, rc.fullB, begin, on_chunk, on_tail,
+            [&](uint32_t strip, const uint8_t *) {  // the gradient of this pixel's J, for F to step with
+                float *gp = gplane + (size_t)strip * (3 * kStripPx);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    // unobserved pixels: zero sum, and J (possibly NaN) must not leak into the beta gradient
+                    sBeta[c] += (acc.pb[c] == 0.0f) ? 0.0f : J[c] * acc.pb[c];
+                    const float g = gscale * acc.pa[c];
+                    if (kExpNoStore) {   // ablation build only
+                        asm volatile("" ::"v"(g));
+                        continue;
+                    }
+                    store_stepped<NoChain>(&gp[c * kStripPx + lane], g);
+                }
+            });
+    } else {
+        stream_strips<kFmt, 9, false, false, NoChain, 3>(
+            lds, plan, strips, n_strips_wave, ws, wave, lane, rc.fullB,
+            [&](const uint8_t *sp, auto which) {
+                const float *f = reinterpret_cast<const float *>(sp);
+                if constexpr (which.value == 0) {
+                    begin(sp);
+                } else if constexpr (which.value == 1) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) G[c] = f[c * kStripPx + lane];
+                } else {   // moments landed: the step L deferred, on the gradient it left
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        M[c] = f[c * kStripPx + lane];
+                        V[c] = f[(3 + c) * kStripPx + lane];
+                        adam_update_J(J[c], M[c], V[c], G[c], co_prev);
+                    }
+                }
+            },
+            on_chunk, on_tail,
+            [&](uint32_t strip, const uint8_t *) {  // this iteration's own step, on the moments kept since the strip began
+                float *st = state + (size_t)strip * kStateFloats;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    float Jc = J[c], m = M[c], v = V[c];
+                    sBeta[c] += (acc.pb[c] == 0.0f) ? 0.0f : Jc * acc.pb[c];
+                    adam_update_J(Jc, m, v, gscale * acc.pa[c], co);
+                    if (kExpNoStore) {   // ablation build only
+                        asm volatile("" ::"v"(Jc), "v"(m), "v"(v));
+                        continue;
+                    }
+                    store_stepped<NoChain>(&st[c * kStripPx + lane], Jc);
+                    store_stepped<NoChain>(&st[(3 + c) * kStripPx + lane], m);
+                    store_stepped<NoChain>(&st[(6 + c) * kStripPx + lane], v);
+                }
+            });
+    }
+}
+
 __device__ __forceinline__ void zero_acc(Acc &acc) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) { acc.pa[c] = 0.f; acc.pb[c] = 0.f; acc.sB[c] = 0.f; acc.sGZ[c] = 0.f; }
@@ -876,15 +950,18 @@ SUCRE_EXP_EXPORT int sucre_exp_wave_times(unsigned long long *out) {   // export
 }
 namespace sucre {
 
-// J-parameter iteration of one image: one launch.
-template <bool kFused, int kFmt>
+// J-parameter iteration of one image: one launch.  kPair 0: the whole iteration (plan 0); 1 / 2: launch L / F of a pair of
+// iterations (pair_pass; plan: the launch's own stream; gplane, co_prev: what only they use -- co_prev the coefficients of the
+// step L deferred, co this launch's own).
+template <bool kFused, int kFmt, int kPair = 0>
 __global__ __launch_bounds__(256, kFitWaves) void fit_grad_kernel(const uint8_t *__restrict__ ws,
                                                        const PlanItem *__restrict__ plan, const StripEntry *__restrict__ plan_strips, const uint32_t *__restrict__ plan_count,
                                                        uint32_t plan_stride, uint32_t plan_kmax,
                                                        float *pstate, const uint64_t *__restrict__ n_obs_total,
                                                        float *__restrict__ state, float *partials, const AdamCoef co,
                                                        unsigned *ticket, double *gpart, int n_groups, double *sums,
-                                                       double *trace_row, const uint32_t *__restrict__ obs_format) {
+                                                       double *trace_row, const uint32_t *__restrict__ obs_format,
+                                                       float *__restrict__ gplane, const AdamCoef co_prev) {
     __shared__ FitLds lds;  // 21.9 KB
     const unsigned long long exp_t_in = kExpWaveTimes ? wall_clock64() : 0ull, exp_c_in = kExpWaveTimes ? clock64() : 0ull;
     const int t = threadIdx.x;
@@ -905,7 +982,12 @@ __global__ __launch_bounds__(256, kFitWaves) void fit_grad_kernel(const uint8_t 
     if (!fmt_ok) acc.cost = __builtin_nanf("");
     float sBeta[3] = {0.f, 0.f, 0.f};
     if (kExpWaveTimes && lane == 0 && wid < kExpWaveSlots) g_exp_wave_times[0][wid] = wall_clock64();
-    run_grad_pass<kFmt>(pass_scaled_b(w), lds, plan + (size_t)wid * plan_stride, plan_strips + (size_t)wid * plan_kmax, n_mine, ws, state, wave, lane, w, gscale, co, acc, sBeta, rc);
+    if constexpr (kPair == 0) {
+        run_grad_pass<kFmt>(pass_scaled_b(w), lds, plan + (size_t)wid * plan_stride, plan_strips + (size_t)wid * plan_kmax, n_mine, ws, state, wave, lane, w, gscale, co, acc, sBeta, rc);
+    } else {   // (one wave-uniform branch per pass, as run_grad_pass takes it)
+        if (pass_scaled_b(w)) pair_pass<kFmt, true, kPair>(lds, plan + (size_t)wid * plan_stride, plan_strips + (size_t)wid * plan_kmax, n_mine, ws, state, gplane, wave, lane, w, gscale, co_prev, co, acc, sBeta, rc);
+        else pair_pass<kFmt, false, kPair>(lds, plan + (size_t)wid * plan_stride, plan_strips + (size_t)wid * plan_kmax, n_mine, ws, state, gplane, wave, lane, w, gscale, co_prev, co, acc, sBeta, rc);
+    }
     if (kExpWaveTimes && lane == 0 && wid < kExpWaveSlots) g_exp_wave_times[1][wid] = wall_clock64();
 
     float s[kNumSums];
@@ -1520,20 +1602,27 @@ hipError_t launch_fit_init(const Layout &L, uint8_t *ws, const uint8_t *rgb1, co
     return hipGetLastError();
 }
 
-template <class Kernel>
-static void launch_fit_kernel(Kernel kernel, int mode, const Layout &L, uint8_t *ws, const AdamCoef &co, double *trace_row,
-                              hipStream_t s) {
+// plan_off, plan_stride: the item stream the launch walks (a mode's plan, or a paired launch's own); extra: the kernel's arguments
+// behind the common ones.
+template <class Kernel, class... Extra>
+static void launch_fit_kernel_on(Kernel kernel, int mode, size_t plan_off, size_t plan_stride, const Layout &L, uint8_t *ws, const AdamCoef &co, double *trace_row,
+                                 hipStream_t s, Extra... extra) {
     hipLaunchKernelGGL(kernel, dim3(L.fit_blocks[mode]), dim3(256), 0, s, ws,
-                       reinterpret_cast<const PlanItem *>(ws + L.off_plan[mode]),
+                       reinterpret_cast<const PlanItem *>(ws + plan_off),
                        reinterpret_cast<const StripEntry *>(ws + L.off_plan_strips[mode]),
-                       reinterpret_cast<const uint32_t *>(ws + L.off_plan_count[mode]), (uint32_t)L.plan_stride[mode], (uint32_t)L.plan_kmax[mode],
+                       reinterpret_cast<const uint32_t *>(ws + L.off_plan_count[mode]), (uint32_t)plan_stride, (uint32_t)L.plan_kmax[mode],
                        reinterpret_cast<float *>(ws + L.off_params),
                        reinterpret_cast<const uint64_t *>(ws + L.off_n_obs_total),
                        reinterpret_cast<float *>(ws + L.off_state), reinterpret_cast<float *>(ws + L.off_partials), co,
                        reinterpret_cast<unsigned *>(ws + L.off_ticket),
                        reinterpret_cast<double *>(ws + L.off_gpartials), L.fit_groups[mode],
                        reinterpret_cast<double *>(ws + L.off_sums), trace_row,
-                       reinterpret_cast<const uint32_t *>(ws + off_store_format(L)));
+                       reinterpret_cast<const uint32_t *>(ws + off_store_format(L)), extra...);
+}
+template <class Kernel>
+static void launch_fit_kernel(Kernel kernel, int mode, const Layout &L, uint8_t *ws, const AdamCoef &co, double *trace_row,
+                              hipStream_t s) {
+    launch_fit_kernel_on(kernel, mode, L.off_plan[mode], L.plan_stride[mode], L, ws, co, trace_row, s);
 }
 
 // The (J mode, store format) of a call -> the compile-time (kMode, kFmt) of the kernel instantiation that serves it: f is called
@@ -1555,7 +1644,7 @@ static void launch_grad_variant(const Layout &L, uint8_t *ws, const AdamCoef &co
                                 hipStream_t s) {
     dispatch_fit(fit_mode(flags), fit_u16(flags), [&](auto mode, auto fmt) {
         if constexpr (mode.value) launch_fit_kernel(fit_closed_kernel<kFused, fmt.value, false>, 1, L, ws, co, trace_row, s);
-        else launch_fit_kernel(fit_grad_kernel<kFused, fmt.value>, 0, L, ws, co, trace_row, s);
+        else launch_fit_kernel_on(fit_grad_kernel<kFused, fmt.value>, 0, L.off_plan[0], L.plan_stride[0], L, ws, co, trace_row, s, (float *)nullptr, co);
     });
 }
 
@@ -1564,6 +1653,23 @@ hipError_t launch_fit_iter_fused(const Layout &L, uint8_t *ws, const AdamCoef &c
                                  double *trace_row, hipStream_t s) {
     launch_grad_variant<true>(L, ws, co, flags, trace_row, s);
     return hipGetLastError();
+}
+
+// Two whole J-parameter iterations in two launches that touch a pixel's moments once (pair_pass): L with the first iteration's
+// coefficients, F with both.  The workspace is afterwards what two launch_fit_iter_fused calls leave, bit for bit.
+bool fit_pair_built() { return kPairedBuilt; }
+hipError_t launch_fit_pair_fused(const Layout &L, uint8_t *ws, const AdamCoef &co0, const AdamCoef &co1, unsigned flags,
+                                 double *trace_row0, double *trace_row1, hipStream_t s) {
+    if constexpr (kPairedBuilt) {
+        float *gplane = reinterpret_cast<float *>(ws + L.off_gplane);
+        dispatch_fit(0, fit_u16(flags), [&](auto, auto fmt) {
+            launch_fit_kernel_on(fit_grad_kernel<true, fmt.value, 1>, 0, L.off_plan_pair[0], L.plan_stride_pair, L, ws, co0, trace_row0, s, gplane, co0);
+            launch_fit_kernel_on(fit_grad_kernel<true, fmt.value, 2>, 0, L.off_plan_pair[1], L.plan_stride_pair, L, ws, co1, trace_row1, s, gplane, co0);
+        });
+        return hipGetLastError();
+    } else {
+        return hipErrorNotSupported;
+    }
 }
 
 // Split form for multi-GPU shared-water runs: gradient pass + reduction, sums left at off_sums for the host's
@@ -1592,7 +1698,8 @@ hipError_t launch_update_J(const Layout &L, uint8_t *ws, int fmt, hipStream_t s)
     return hipGetLastError();
 }
 
-// Writes both plans (J-parameter and closed-form item streams) for the store the compaction has just built.
+// Writes both plans (J-parameter and closed-form item streams; with the former the two streams of a paired iteration) for the
+// store the compaction has just built.
 hipError_t launch_plan(const Layout &L, uint8_t *ws, hipStream_t s) {
     auto *meta = reinterpret_cast<const StripMeta *>(ws + L.off_strip_meta);
     const uint32_t W0 = (uint32_t)L.fit_blocks[0] * 4u, W1 = (uint32_t)L.fit_blocks[1] * 4u;
@@ -1609,7 +1716,9 @@ hipError_t launch_plan(const Layout &L, uint8_t *ws, hipStream_t s) {
                        reinterpret_cast<PlanItem *>(ws + L.off_plan[0]), reinterpret_cast<PlanItem *>(ws + L.off_plan[1]),
                        reinterpret_cast<StripEntry *>(ws + L.off_plan_strips[0]), reinterpret_cast<StripEntry *>(ws + L.off_plan_strips[1]),
                        reinterpret_cast<uint32_t *>(ws + L.off_plan_count[0]),
-                       reinterpret_cast<uint32_t *>(ws + L.off_plan_count[1]), (uint64_t)L.off_comp, (uint64_t)L.off_state);
+                       reinterpret_cast<uint32_t *>(ws + L.off_plan_count[1]), (uint64_t)L.off_comp, (uint64_t)L.off_state,
+                       (uint32_t)L.plan_stride_pair, reinterpret_cast<PlanItem *>(ws + L.off_plan_pair[0]), reinterpret_cast<PlanItem *>(ws + L.off_plan_pair[1]),
+                       (uint64_t)L.off_gplane);
     return hipGetLastError();
 }
 

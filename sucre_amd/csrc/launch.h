@@ -51,6 +51,9 @@ hipError_t launch_fit_init(const Layout &L, uint8_t *ws, const uint8_t *rgb1, co
                            const float *params0, const float *J0, hipStream_t s);
 hipError_t launch_fit_iter_fused(const Layout &L, uint8_t *ws, const AdamCoef &co, unsigned flags, double *trace_row,
                                  hipStream_t s);
+bool fit_pair_built();   // experiment.h SUCRE_PAIRED_J: does the library hold the paired launches?
+hipError_t launch_fit_pair_fused(const Layout &L, uint8_t *ws, const AdamCoef &co0, const AdamCoef &co1, unsigned flags,
+                                 double *trace_row0, double *trace_row1, hipStream_t s);
 hipError_t launch_fit_grad(const Layout &L, uint8_t *ws, const AdamCoef &co, unsigned flags, hipStream_t s);
 hipError_t launch_fit_step(const Layout &L, uint8_t *ws, const AdamCoef &co, double *trace_row, hipStream_t s);
 hipError_t launch_update_J(const Layout &L, uint8_t *ws, int fmt, hipStream_t s);

@@ -178,6 +178,93 @@ __host__ __device__ constexpr uint32_t counts_tail(uint32_t c) { return (c >> (2
 static_assert(counts_unmasked(strip_counts(kMaxViews / kGroupLv, 0, 3)) == kMaxViews / kGroupLv && counts_masked(strip_counts(0, kMaxViews / kGroupLv, 3)) == kMaxViews / kGroupLv
               && counts_masked(strip_counts(kMaxViews / kGroupLv, 0, 3)) == 0 && counts_tail(strip_counts(1023, 1, 3)) == 3, "StripEntry.counts round trip at the largest strip");
 
+// PlanItem.shape: [6:0] nA - 1, [14:8] max(nB, 1) - 1, [22:16] B's first 16-byte piece (nA, or nA - 1 when nB = 0: B then
+// re-reads the item's last piece), [31] a full chunk (nA = 64 and nB = kFullB: both offsets are per-lane constants).
+// (nA, nB: lanes of the two LDS-DMA instructions that copy the item; fit.hip, 'Item stream'.)
+constexpr uint32_t kShapeFull = 1u << 31;
+constexpr uint32_t kShapeTrail = 1u << 30;   // one of the trailing items behind a wave's last strip (nobody consumes it; a batch
+                                             // launch copies the NEXT image's first items in its place: StreamChain)
+__host__ __device__ constexpr uint32_t full_chunk_b(int fmt) { return (uint32_t)(chunk_bytes(fmt) - 1024) / 16u; }   // 48 / 16 / 32 lanes
+__host__ __device__ inline uint32_t item_shape(uint32_t bytes, bool full_chunk) {
+    const uint32_t pieces = bytes / 16u;   // every item is a multiple of 16 bytes (static_asserts in fit.hip)
+    const uint32_t nA = pieces < 64u ? pieces : 64u, nB = pieces - nA;
+    return (nA - 1u) | ((nB ? nB - 1u : 0u) << 8) | ((nB ? nA : nA - 1u) << 16) | (full_chunk ? kShapeFull : 0u);
+}
+// Bytes the two copies of an item read, from its first byte on (fmt: the store's format, for a full chunk).
+__host__ __device__ constexpr uint32_t shape_bytes(uint32_t shape, int fmt) {
+    const uint32_t a = (shape & 127u) + 1u, b = ((shape >> 16) & 127u) + ((shape >> 8) & 127u) + 1u;
+    return (shape & kShapeFull) ? (uint32_t)chunk_bytes(fmt) : (a > b ? a : b) * 16u;
+}
+
+// The four item streams a strip can be walked in (plan_kernel writes them; stream_strips consumes them).  kStreamJ and
+// kStreamClosed are the plans of the two J modes (Layout.off_plan[0 / 1]).  kStreamL and kStreamF are the two launches of a PAIR
+// of J-parameter iterations (fit.hip, 'Paired iterations'): L reads J only and leaves the pixel's gradient in the G plane, F takes
+// the step L deferred at the strip's START -- its three first items are the J plane, the G plane and the moments -- and its own
+// at the end.  Both walk plan 0's strips in plan 0's order (they share its StripEntry lists and counts).
+constexpr int kStreamJ = 0, kStreamClosed = 1, kStreamL = 2, kStreamF = 3;
+__host__ __device__ constexpr uint32_t stream_strip_items(uint32_t levels, int stream) {
+    return ((levels + 3u) >> 2) + (stream == kStreamJ ? 2u : stream == kStreamF ? 3u : 1u);
+}
+// Writes the items of one strip in the given stream; returns how many.  fmt: the store's format (kStore*); comp_off, state_off,
+// gplane_off: byte offsets of the compact store, the state block and the G plane in the workspace.
+__host__ __device__ inline uint32_t write_strip_items(int stream, const StripMeta &m, uint32_t strip, int fmt, uint64_t comp_off, uint64_t state_off,
+                                                      uint64_t gplane_off, PlanItem *out) {
+    const uint32_t nfull = m.levels >> 2, r = m.levels & 3u;   // full chunks, levels of the short last one
+    const uint32_t lb = (uint32_t)level_bytes(fmt);
+    const uint64_t st = state_off + (uint64_t)strip * (kStateFloats * 4);
+    const PlanItem moments = PlanItem{(uint32_t)((st + 3 * kStripPx * 4) >> 6), item_shape(6u * kStripPx * 4u, false)};
+    PlanItem *o = out;
+    *o++ = PlanItem{(uint32_t)(st >> 6), item_shape(3u * kStripPx * 4u, false)};
+    if (stream == kStreamF) {
+        *o++ = PlanItem{(uint32_t)((gplane_off + (uint64_t)strip * (3 * kStripPx * 4)) >> 6), item_shape(3u * kStripPx * 4u, false)};
+        *o++ = moments;
+    }
+    for (uint32_t g = 0; g < nfull; ++g)
+        *o++ = PlanItem{(uint32_t)((comp_off + (m.lvoff + (uint64_t)g * kGroupLv) * lb) >> 6), item_shape((uint32_t)chunk_bytes(fmt), true)};
+    if (r) *o++ = PlanItem{(uint32_t)((comp_off + (m.lvoff + (uint64_t)nfull * kGroupLv) * lb) >> 6), item_shape(r * lb, false)};
+    if (stream == kStreamJ) *o++ = moments;
+    return (uint32_t)(o - out);
+}
+// The trailing items behind a wave's last strip: SUCRE_RING of them (kAhead that are issued and never consumed + one spare the
+// descriptor prefetch may touch), all re-reading the J plane of the wave's first strip.
+__host__ __device__ inline void write_trailing_items(uint32_t strip0, uint64_t state_off, PlanItem *out) {
+    const uint64_t st0 = state_off + (uint64_t)strip0 * (kStateFloats * 4);
+    for (int j = 0; j < SUCRE_RING; ++j) out[j] = PlanItem{(uint32_t)(st0 >> 6), item_shape(3u * kStripPx * 4u, false) | kShapeTrail};
+}
+
+// What thread (wid, k) of the plan kernel does: the k-th strip of fit wave wid (of W) in the mode's deal -> its StripEntry and its
+// items in the mode's plan; the J-parameter plan's thread (mode 0) also writes the strip in the two streams of a paired iteration,
+// whose items start k places earlier (L: one item per strip fewer) or later (F: one more) in the wave's list.  Thread k = 0
+// records how many strips the wave has.
+__host__ __device__ inline void plan_thread(int mode, int fmt, uint32_t wid, uint32_t k, uint32_t W, uint32_t n_strips, const StripMeta *meta,
+                                            PlanItem *plan, StripEntry *strips, uint32_t *count, uint32_t stride, uint32_t kmax, uint64_t comp_off,
+                                            uint64_t state_off, PlanItem *planL, PlanItem *planF, uint32_t stride_pair, uint64_t gplane_off) {
+    // the wave's strips up to its k-th (deal_walk): where that one's items start in the wave's list, and how many strips the wave
+    // has in all
+    const DealShares sh = deal_shares(mode, W / 4u);
+    uint32_t start = 0u, strip = 0u, strip0 = 0u;
+    const uint32_t K = deal_walk(wid, W, n_strips, sh, [&](uint32_t s) { return meta[s].levels; }, [&](uint32_t kk, uint32_t s) {
+        if (kk == 0u) strip0 = s;
+        if (kk < k) start += stream_strip_items(meta[s].levels, mode);
+        if (kk == k) strip = s;
+    });
+    if (k == 0u) count[wid] = K;
+    if (k >= K) return;
+    const StripMeta m = meta[strip];
+    const uint32_t nfull = m.levels >> 2, r = m.levels & 3u;   // full chunks, levels of the short last one
+    const uint32_t nu = nfull < (m.full >> 2) ? nfull : (m.full >> 2);   // chunks wholly below the strip's smallest pixel count
+    strips[(size_t)wid * kmax + k] = StripEntry{strip, strip_counts(nu, nfull - nu, r)};
+    auto write = [&](int stream, PlanItem *out) {
+        out += write_strip_items(stream, m, strip, fmt, comp_off, state_off, gplane_off, out);
+        if (k + 1u == K) write_trailing_items(strip0, state_off, out);
+    };
+    write(mode, plan + (size_t)wid * stride + start);
+    if (kPairedBuilt && mode == 0) {
+        write(kStreamL, planL + (size_t)wid * stride_pair + (start - k));
+        write(kStreamF, planF + (size_t)wid * stride_pair + (start + k));
+    }
+}
+
 struct Layout {
     int H, W, n_views, tiles_x, tiles_y, n_tiles;
     size_t off_obs;         // uint8  chunks of kChunk bytes, chunk(tile, k) at tile*obs_tile_stride + k*obs_view_stride
@@ -218,6 +305,10 @@ struct Layout {
     size_t off_plan_count[2];  // uint32 [4 n_blocks] strips of every wave
     size_t plan_stride[2];  // items reserved per wave (its strips' items + the never-consumed trailing items + one spare)
     size_t plan_kmax[2];    // strips reserved per wave
+    // Paired J-parameter iterations (kStreamL / kStreamF).  Behind everything else, so that no other offset moves.
+    size_t off_gplane;      // float [n_strips][3][64]: the gradient launch L hands to launch F (written and read inside one sucre_fit_run call)
+    size_t off_plan_pair[2];// PlanItem [4 fit_blocks[0]][plan_stride_pair]: L's [0] and F's [1] item streams (strips and counts: plan 0's)
+    size_t plan_stride_pair;// plan_stride[0] + one item per strip (F's G plane)
     size_t total;
 };
 
@@ -289,6 +380,9 @@ inline bool make_layout(int H, int W, int n_views, Layout *L) {
             L->off_plan_count[m] = take(waves * sizeof(uint32_t));
         }
     }
+    L->off_gplane = take((size_t)L->n_strips * 3 * kStripPx * sizeof(float));
+    L->plan_stride_pair = L->plan_stride[0] + L->plan_kmax[0];
+    for (int q = 0; q < 2; ++q) L->off_plan_pair[q] = take((size_t)L->fit_blocks[0] * 4 * L->plan_stride_pair * sizeof(PlanItem));
     L->total = o;
     return true;
 }

@@ -195,6 +195,10 @@ def _pack_stream(dev) -> 'torch.cuda.Stream':
 # engine knob: neighbour views as 8-byte {depth, colour} records (one gather per landing pixel; +8 bytes per pixel and view)
 PACKED_VIEWS = os.environ.get('SUCRE_PACKED_VIEWS', '1') != '0'
 
+# engine knob: sucre_fit_run takes its J-parameter iterations in pairs of launches that touch a pixel's Adam moments once per pair
+# (csrc/fit.hip, 'Paired iterations'; every result bit is the same either way); 0 = one launch per iteration
+PAIRED_FIT = os.environ.get('SUCRE_PAIRED_FIT', '1') != '0'
+
 MAX_VIEWS = 4096   # kMaxViews of csrc/layout.h: views of one restoration (after the overlap cull of sfm.Image.match_images)
 
 
@@ -477,7 +481,7 @@ class Restoration:
         self.steps_done = 0
 
     def fit(self, num_iter: int = 200, lr: float = 0.05, use_closed_form: bool = False, betas=(0.9, 0.999),
-            eps: float = 1e-8, record_trace: bool = True, keep_J: bool = False) -> torch.Tensor | None:
+            eps: float = 1e-8, record_trace: bool = True, keep_J: bool = False, paired: bool | None = None) -> torch.Tensor | None:
         """Enqueues ``num_iter`` Adam iterations without any host sync; returns the (num_iter,10) float64
         device trace (cost, B, beta, gamma per iteration) or None.  In closed-form mode the C ABI appends the
         final ``update_J`` of sucre.py:156 to a ``sucre_fit_run`` call unless ``keep_J``: then J stays the J(theta_k)
@@ -486,13 +490,18 @@ class Restoration:
         behind the last, the launches are those of the unsplit fit and so are the bits.  Without it the appended
         ``update_J`` leaves J(theta_{k+1}) where the unsplit fit has J(theta_k); the light-model kernel re-solves J from
         zero and does not notice, the plain one-pass kernel (fit.hip, AccOne) measures its sums from the J it finds, so
-        the split fit ends in the same state up to rounding only (tests/test_gpu_snapshots.py)."""
+        the split fit ends in the same state up to rounding only (tests/test_gpu_snapshots.py).
+        ``paired`` (J-parameter mode of the plain model; None: the engine knob ``SUCRE_PAIRED_FIT``): the iterations of this call
+        run as pairs of launches (and a single one if ``num_iter`` is odd) or, False, one by one -- nothing is pending between
+        calls, and state, J, parameters and trace are bit for bit the same either way (tests/test_gpu_paired.py)."""
         ext = self.light or self.float_colour
         width = 20 if ext else 10
         trace = torch.zeros((num_iter, width), dtype=torch.float64, device=self.device) if record_trace else None
         flags = (_lib.FIT_CLOSED_FORM if use_closed_form else 0) | self._fmt_flag | self._ext_flag
         if keep_J and use_closed_form:
             flags |= _lib.FIT_KEEP_J
+        if not ext and not use_closed_form and not (PAIRED_FIT if paired is None else paired):
+            flags |= _lib.FIT_UNPAIRED
         ws, H, W, n = self._geom
         tp = C.c_void_p(trace.data_ptr()) if trace is not None else None
         with torch.cuda.device(self.device):

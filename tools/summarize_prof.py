@@ -17,10 +17,13 @@ root, mode, tag = Path(sys.argv[1]), sys.argv[2], sys.argv[3]
 out = root / mode
 dest = root / 'summaries'
 dest.mkdir(exist_ok=True)
-DOMINANT = {'jparam': 'fit_grad_kernel<true, 0>', 'jparam_inflight2': 'fit_grad_kernel<true, 0>', 'closed': 'fit_closed_kernel<true, 0, false>',
-            'light': 'light_grad_kernel<false, false', 'light_closed': 'light_grad_kernel<true, false', 'u16mm_4k': 'fit_grad_kernel<true, 1>',
+# (a prefix: 'fit_grad_kernel<true, 0' takes the one-launch kernel <true, 0, 0> and the two launches of a paired iteration, <true, 0, 1>
+# and <true, 0, 2>, together -- the record is then the mean over the dispatches, the pair's mean, with every kernel's own figures
+# under 'kernels' -- and the <true, 0> of the rounds before the pairs)
+DOMINANT = {'jparam': 'fit_grad_kernel<true, 0', 'jparam_inflight2': 'fit_grad_kernel<true, 0', 'closed': 'fit_closed_kernel<true, 0, false>',
+            'light': 'light_grad_kernel<false, false', 'light_closed': 'light_grad_kernel<true, false', 'u16mm_4k': 'fit_grad_kernel<true, 1',
             'shared4': 'group_iter_kernel<0, 0>', 'jparam_batch32': 'batch_iter_kernel<0, 0>', 'closed_batch32': 'batch_iter_kernel<1, 0>',
-            'jparam_f32plain': 'fit_grad_kernel<true, 0>', 'jparam_f32z26': 'fit_grad_kernel<true, 0>', 'jparam_deep': 'fit_grad_kernel<true, 0>', 'jparam_deep_f32z26': 'fit_grad_kernel<true, 0>'}
+            'jparam_f32plain': 'fit_grad_kernel<true, 0', 'jparam_f32z26': 'fit_grad_kernel<true, 0', 'jparam_deep': 'fit_grad_kernel<true, 0', 'jparam_deep_f32z26': 'fit_grad_kernel<true, 0'}
 MATCH_STAGE = ('match_kernel', 'view_partial_kernel', 'view_total_kernel', 'pixel_count_kernel', 'bin_scan_kernel',
                'permute_kernel', 'strip_table_kernel', 'strip_levels_kernel', 'tile_offset_kernel', 'strip_offset_kernel',
                'scatter_kernel', 'tail_bits_clear_kernel', 'plan_kernel')
@@ -63,10 +66,12 @@ if pmc:
 
 
 def avg(kernel_sub, counter):
+    """Mean over the dispatches of every kernel whose name starts with ``kernel_sub``."""
+    tot = n = 0
     for k, cs in pmc.items():
         if k.startswith(kernel_sub) and counter in cs:
-            return cs[counter][0] / cs[counter][1]
-    return None
+            tot += cs[counter][0]; n += cs[counter][1]
+    return tot / n if n else None
 
 
 def hbm_bytes(kernel_sub):
@@ -81,10 +86,16 @@ rec = {'mode': mode, 'kernel': kernel}
 b = hbm_bytes(kernel)
 if b[0] is not None:
     rec.update(fetch_size_kb=b[1], write_size_kb=b[2], hbm_bytes_per_launch=b[0])
-for k, r in stats.items():
-    if k.startswith(kernel):
-        rec['rocprofv3_avg_ns'] = float(r['AverageNs'])
-        rec['rocprofv3_calls'] = int(r['Calls'])
+mine = {k: r for k, r in stats.items() if k.startswith(kernel)}
+if mine:
+    rec['rocprofv3_calls'] = sum(int(r['Calls']) for r in mine.values())
+    rec['rocprofv3_avg_ns'] = sum(float(r['AverageNs']) * int(r['Calls']) for r in mine.values()) / rec['rocprofv3_calls']
+if len(mine) > 1 or len([k for k in pmc if k.startswith(kernel)]) > 1:   # several kernels share the record: each one's own figures
+    rec['kernels'] = {}
+    for k in sorted(set(mine) | {k for k in pmc if k.startswith(kernel)}):
+        bb = hbm_bytes(k)
+        rec['kernels'][k] = {'fetch_size_kb': bb[1], 'write_size_kb': bb[2], 'hbm_bytes_per_launch': bb[0],
+                             'rocprofv3_avg_ns': float(mine[k]['AverageNs']) if k in mine else None, 'rocprofv3_calls': int(mine[k]['Calls']) if k in mine else None}
 stage = {}
 for k in pmc:
     if any(k.startswith(m) for m in MATCH_STAGE):
