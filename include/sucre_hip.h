@@ -569,6 +569,34 @@ int sucre_invert_images(void *table_dev, int n_images, const sucre_invert_image_
                         void *stream);
 
 /*
+ * ---- cross-view colour consistency of restored images -----------------------------------------------------------------------
+ * SUCRe's premise is that one point of the seabed has one restored colour whichever camera saw it.  This call measures it, with
+ * no fit and no workspace, from depth maps, poses and the J images a run wrote: for every view k of `views_dev` and every target
+ * pixel the match is the one sucre_match_map returns for (target, view k) -- the same device function -- and no map is written.
+ * A matched pair is VALID when neither a = J_target[v1,u1,:] nor b = J_k[v2,u2,:] holds a NaN in any channel (plot_J's rule,
+ * sucre.py:86-87).  Over the valid pairs:
+ *   count_dev  int32   (H,W)          views with a valid pair at the pixel
+ *   ssd_dev    float32 (H,W,3)        sum over k, ascending, of (a_c - b_c)^2, accumulated as fmaf(d, d, acc); 0 where count is 0
+ *   stats_dev  float64 (n_views,26)   per view: [0] matches (the map's entries >= 0: len(matches) of sfm.py:136, whatever J holds),
+ *                                     [1] valid pairs, [2:14] sum d^2, sum a^2, sum b^2, sum a b of J (R, G, B each), [14:26] the same
+ *                                     four sums of the raw colours (float)k / 255.0f of the same pixels of the same valid pairs
+ * all written in full.  `target`: HOST struct, `views_dev`: device table of n_views entries, as for sucre_match_map; the views may
+ * differ in size from the target and from each other and are in PLAIN form (depth map, uint8 rgb -- no sucre_pack_view records).  A
+ * view's rgb may be NULL: it is then not read and the view's raw sums are zero (all raw sums, when the target's is); its J sums are
+ * formed all the same.  J_target_dev: (H,W,3) float32.  J_views_dev: DEVICE array of n_views device pointers to (H_k,W_k,3) float32;
+ * a NULL entry means the view takes no part -- its stats row is zero, it adds nothing to any pixel.  Every sum is formed in float32
+ * per (16x16 tile, view), then in float64 over the tiles in a fixed order; no atomics: two calls give the same bits.
+ * scratch_dev: sucre_consistency_scratch_bytes() bytes (0 on invalid arguments) of caller-owned device memory that must stay
+ * untouched until the launches have run; it may hold anything before.  Checked before any launch: NULL target, views_dev, J_*,
+ * outputs or scratch, outputs or scratch not 16-byte aligned, H or W outside 1..32767, a target of another size (SUCRE_ERR_ARG);
+ * n_views outside 1..4096 (SUCRE_ERR_RANGE).  The call only enqueues: two launches, no allocation, nothing copied from the host.
+ */
+size_t sucre_consistency_scratch_bytes(int H, int W, int n_views);
+int sucre_view_consistency(int H, int W, int n_views, const sucre_view_t *target, const sucre_view_t *views_dev,
+                           const float *J_target_dev, const float *const *J_views_dev, int32_t *count_dev, float *ssd_dev,
+                           double *stats_dev, void *scratch_dev, void *stream);
+
+/*
  * Shared water AND light over several light-model images (the group above for the 19-parameter model; sucre.py:54-61 with
  * the objective of sucre.py:124-157 summed over the images: one B, beta, gamma, cam2light, sigma, every image its own J, one
  * n_obs).  `group_dev`: sucre_light_group_bytes(n_images) bytes of device memory, 256-byte aligned; `images` (host array)

@@ -25,7 +25,8 @@ OBS_FORMATS = {'f32': OBS_F32, 'u16mm': OBS_U16MM, 'f32plain': OBS_F32_PLAIN, 'f
 WS_VIEW_COUNT, WS_VIEW_KEEP, WS_N_OBS, WS_PARAMS, WS_SUMS, WS_N_OBS_TOTAL, WS_STORE_FORMAT, WS_STATE, WS_PAIR_GRADIENT = range(9)
 INVERT_LIGHT, INVERT_FLOAT_COLOUR = 1, 2
 INVERT_MAX_IMAGES = 4096   # kInvertMaxImages of csrc/invert.h: images per sucre_invert_images call
-POOL_MAX_IMAGES = 4096     # kPoolMaxImages of csrc/pool.h: images per sucre_pool_select_pass call
+CONSISTENCY_STATS = 26     # kConsistStats of csrc/consist.h: columns of a view's row of sucre_view_consistency's stats
+POOL_MAX_IMAGES = 4096    # kPoolMaxImages of csrc/pool.h: images per sucre_pool_select_pass call
 POOL_MAX_RANKS = 8
 POOL_HIST_WORDS = 3 * 8 * 256   # uint64 hist[3][8][256] at the head of the pooled select's state
 STORE_F32, STORE_U16MM, STORE_Z24, STORE_Z26 = 0, 1, 2, 3   # what the compaction chose (SUCRE_WS_STORE_FORMAT)
@@ -137,6 +138,8 @@ SIGNATURES = {
     'sucre_apply_view_gains_ext': (_i, [_vp, _vp, _i, _i, _i, C.c_uint, _vp, _vp, _vp, _vp]),
     'sucre_invert_bytes': (C.c_size_t, [_i]),
     'sucre_invert_images': (_i, [_vp, _i, C.POINTER(InvertImage), C.POINTER(C.c_float), C.c_uint, _vp]),
+    'sucre_consistency_scratch_bytes': (C.c_size_t, [_i, _i, _i]),
+    'sucre_view_consistency': (_i, [_i, _i, _i, C.POINTER(SucreView), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'sucre_light_group_bytes': (C.c_size_t, [_i]),
     'sucre_light_group_sums_offset': (C.c_int64, []),
     'sucre_light_group_init': (_i, [_vp, _i, C.POINTER(LightGroupImage), C.POINTER(C.c_float), _vp]),

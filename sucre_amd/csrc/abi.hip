@@ -6,6 +6,7 @@
 #include <mutex>
 #include <vector>
 
+#include "consist.h"
 #include "invert.h"
 #include "launch.h"
 #include "pool.h"
@@ -847,6 +848,41 @@ int sucre_invert_images(void *table_dev, int n_images, const sucre_invert_image_
     }
     if (blocks > 0x7fffffffull) return fail(SUCRE_ERR_RANGE, "%llu workgroups: the images of one call may hold 2^41 pixels together", (unsigned long long)blocks);
     return check_hip(launch_invert(table_dev, n_images, images, params, flags, static_cast<hipStream_t>(stream)), "sucre_invert_images");
+}
+
+/* ---- cross-view colour consistency of restored images (plot_J's valid rule, sucre.py:86-87, over sfm.py:121-125's matches) -- */
+
+}  // extern "C"
+
+namespace sucre {
+static int check_consistency_geometry(int H, int W, int n_views) {
+    if (H < 1 || W < 1 || H > 32767 || W > 32767) return fail(SUCRE_ERR_ARG, "invalid image size %dx%d (need 1..32767)", W, H);
+    if (n_views < 1 || n_views > kMaxViews) return fail(SUCRE_ERR_RANGE, "n_views=%d outside [1,%d]", n_views, kMaxViews);
+    return SUCRE_OK;
+}
+}  // namespace sucre
+
+extern "C" {
+
+size_t sucre_consistency_scratch_bytes(int H, int W, int n_views) {
+    if (check_consistency_geometry(H, W, n_views)) return 0;
+    return consist_scratch_bytes(((H + kTile - 1) / kTile) * ((W + kTile - 1) / kTile), n_views);
+}
+
+int sucre_view_consistency(int H, int W, int n_views, const sucre_view_t *target, const sucre_view_t *views_dev,
+                           const float *J_target_dev, const float *const *J_views_dev, int32_t *count_dev, float *ssd_dev,
+                           double *stats_dev, void *scratch_dev, void *stream) {
+    if (int rc = check_consistency_geometry(H, W, n_views)) return rc;
+    if (!target || !views_dev || !J_target_dev || !J_views_dev) return fail(SUCRE_ERR_ARG, "target / views_dev / J_target_dev / J_views_dev is NULL");
+    if (!count_dev || !ssd_dev || !stats_dev || !scratch_dev) return fail(SUCRE_ERR_ARG, "count_dev / ssd_dev / stats_dev / scratch_dev is NULL");
+    if (!aligned(count_dev, 16) || !aligned(ssd_dev, 16) || !aligned(stats_dev, 16) || !aligned(scratch_dev, 16))
+        return fail(SUCRE_ERR_ARG, "count_dev / ssd_dev / stats_dev / scratch_dev must be 16-byte aligned");
+    if (!target->depth) return fail(SUCRE_ERR_ARG, "target depth map is NULL");
+    if (target->H != H || target->W != W) return fail(SUCRE_ERR_ARG, "target is %dx%d, expected %dx%d", target->W, target->H, W, H);
+    if (!aligned(views_dev, 8) || !aligned(J_views_dev, 8) || !aligned(J_target_dev, 4))
+        return fail(SUCRE_ERR_ARG, "views_dev / J_views_dev must be 8-byte aligned, J_target_dev 4-byte aligned");
+    return check_hip(launch_consistency(H, W, n_views, *target, views_dev, J_target_dev, J_views_dev, count_dev, ssd_dev, stats_dev,
+                                        scratch_dev, static_cast<hipStream_t>(stream)), "sucre_view_consistency");
 }
 
 /* ---- shared water and light over the light-model images of a rank (sucre.py:54-61, 124-157) ------------------------ */

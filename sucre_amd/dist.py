@@ -55,6 +55,15 @@ def all_reduce_sum(t: torch.Tensor, group=None) -> None:
         dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
 
 
+def all_gather_objects(obj, group=None) -> list:
+    """Every rank's ``obj`` (anything picklable, small), in rank order, on every rank; ``[obj]`` without a process group."""
+    if not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return [obj]
+    out = [None] * dist.get_world_size(group)
+    dist.all_gather_object(out, obj, group=group)
+    return out
+
+
 def shard_images(image_ids: list, rank: int, world: int) -> list:
     """Contiguous, balanced partition of the target images over ranks (first ``len % world`` ranks get one
     extra).  Every image belongs to exactly one rank; order inside a rank is preserved."""

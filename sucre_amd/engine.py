@@ -921,6 +921,64 @@ def invert_images(views: list, params, light: bool = False) -> list:
     return outs
 
 
+def view_consistency(target: DeviceView, J_target: torch.Tensor, views: list, Js: list):
+    """Cross-view colour consistency of restored images (``sucre_view_consistency``): every pixel of ``target`` is matched
+    against every view of ``views`` -- ``Restoration.match_map``'s matches, by the same device function, no map in memory -- and
+    the restored colours ``a = J_target[v1,u1]`` and ``b = Js[k][v2,u2]`` of every pair without a NaN are compared.  Returns
+    ``(count, ssd, stats)`` on the device: int32 (H,W) views with a valid pair at the pixel, float32 (H,W,3) sum of (a - b)^2 over
+    them, float64 (n_views, 26) per view {matches, valid pairs, sum d^2, a^2, b^2, a b of J per channel, the same four sums of
+    the raw uint8 colours / 255 of the same pairs}.  ``Js[k]``: (H_k,W_k,3) float32 on the views' device, or None -- the view then
+    takes no part and its row is zero.  The views may differ in size; their colours must be uint8 (a view with float32 colours --
+    a resized input -- is given without them: its raw sums are zero).  Two launches on the current stream, no host wait; no
+    ``Restoration`` and no workspace.  Two calls on the same inputs give the same bits."""
+    views, Js = list(views), list(Js)
+    n = len(views)
+    if not 1 <= n <= MAX_VIEWS:
+        raise ValueError(f'view_consistency: {n} views, need 1..{MAX_VIEWS}')
+    if len(Js) != n:
+        raise ValueError(f'view_consistency: {n} views but {len(Js)} restored images')
+    H, W = target.depth.shape
+    dev = target.depth.device
+    if dev.type != 'cuda':
+        raise _lib.SucreError('view_consistency: the views must sit on a GPU device (there is no CPU fallback)')
+
+    def plain(v: DeviceView) -> _lib.SucreView:   # uint8 colours or none; never the packed form
+        if v.rgb.dtype == torch.uint8:
+            return v.to_struct()
+        H_, W_ = v.depth.shape
+        return camera_struct(v.K, v.R, v.t, H_, W_, v.depth.data_ptr(), 0, Kinv=v.Kinv, tinv=v.tinv)
+
+    def restored(J, v: DeviceView, what: str) -> torch.Tensor:
+        if J.device != dev or J.dtype != torch.float32 or tuple(J.shape) != tuple(v.depth.shape) + (3,):
+            raise ValueError(f'view_consistency: {what} must be float32 {tuple(v.depth.shape) + (3,)} on {dev}, '
+                             f'not {J.dtype} {tuple(J.shape)} on {J.device}')
+        return J.contiguous()
+
+    J_target = restored(J_target, target, 'J_target')
+    Js = [None if J is None else restored(J, v, f'Js[{k}]') for k, (J, v) in enumerate(zip(Js, views))]
+    lib = _lib.load()
+    tgt = plain(target)
+    table = (_lib.SucreView * n)(*[plain(v) for v in views])
+    ptrs = (C.c_void_p * n)(*[None if J is None else J.data_ptr() for J in Js])
+    count = torch.empty((H, W), dtype=torch.int32, device=dev)
+    ssd = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+    stats = torch.empty((n, _lib.CONSISTENCY_STATS), dtype=torch.float64, device=dev)
+    nbytes = lib.sucre_consistency_scratch_bytes(H, W, n)
+    if nbytes == 0:
+        raise _lib.SucreError(lib.sucre_last_error().decode())
+    with torch.cuda.device(dev):
+        # the view table and the pointer array in one pinned staging buffer (torch's host allocator keeps it until the copy has
+        # run), and, like the scratch, in device blocks the caching allocator keeps for this stream until the launches have run
+        host = torch.frombuffer(bytearray(bytes(table) + bytes(ptrs)), dtype=torch.uint8).pin_memory()
+        staged = host.to(dev, non_blocking=True)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _lib.check(lib.sucre_view_consistency(H, W, n, C.byref(tgt), C.c_void_p(staged.data_ptr()), C.c_void_p(J_target.data_ptr()),
+                                              C.c_void_p(staged.data_ptr() + C.sizeof(table)), C.c_void_p(count.data_ptr()),
+                                              C.c_void_p(ssd.data_ptr()), C.c_void_p(stats.data_ptr()), C.c_void_p(scratch.data_ptr()),
+                                              _stream_ptr()))
+    return count, ssd, stats
+
+
 def device_views_from_scene(scene, device='cuda') -> list[DeviceView]:
     """Uploads a synthetic scene (sucre_amd.synth) the way the loaders would: float32 depth, uint8 colour."""
     out = []

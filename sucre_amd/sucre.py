@@ -14,6 +14,7 @@ Under ``torchrun`` (WORLD_SIZE > 1) the images to restore are sharded over the r
 from __future__ import annotations
 
 import argparse
+import collections
 import os
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
@@ -1121,6 +1122,242 @@ def apply_water(images: list, colmap_model: sfm.COLMAPModel, output_dir: Path, w
             f.result()   # re-raises anything a writer thread hit
 
 
+# ---- --check-consistency: do the restored images agree where they see the same seabed? ------------------------------------
+
+def consistency_summary(stats, H: int, W: int, min_cover: float) -> dict:
+    """What the per-view rows of ``engine.view_consistency`` say, in float64 numpy.  Per view: ``kept`` -- the cover rule of
+    sfm.py:136 on the matches, ``stats[:, 0] / (W H) > min_cover``; ``n`` -- valid pairs; ``rms_restored`` and ``rms_raw`` (n_views, 3)
+    -- ``sqrt(sum d^2 / n)`` of the restored and of the raw colours; ``gain`` -- ``sum a b / sum b^2``, the brightness ratio target :
+    view per channel (1 where ``sum b^2`` is not positive); ``rms_restored_gain`` -- ``sqrt(max(0, sum a^2 - (sum a b)^2 / sum b^2) / n)``,
+    what a gain per pair could not remove: the part no common stretch can fix.  A view without a valid pair has zeros (gain 1).
+    ``pooled_restored``, ``pooled_raw``, ``pooled_restored_gain`` (3,): ``sqrt(sum sum d^2 / sum n)`` over the kept views, and
+    ``pooled_n``, their pairs."""
+    stats = np.asarray(stats, np.float64).reshape(-1, 26)
+    n = stats[:, 1]
+    kept = stats[:, 0] / (int(W) * int(H)) > min_cover
+    nn = np.where(n > 0, n, 1.0)[:, None]
+    sd, saa, sbb, sab = (stats[:, 2 + 3 * i:5 + 3 * i] for i in range(4))
+    positive = sbb > 0
+    safe = np.where(positive, sbb, 1.0)
+    left = np.where(positive, np.maximum(0.0, saa - sab * sab / safe), saa)   # sum (a - g b)^2 at the best g
+    pooled_n = float(n[kept].sum())
+
+    def pooled(s):
+        return np.sqrt(s[kept].sum(axis=0) / pooled_n) if pooled_n > 0 else np.zeros(3)
+
+    return {'kept': kept, 'n_matches': stats[:, 0].copy(), 'n': n.copy(),
+            'rms_restored': np.sqrt(sd / nn), 'rms_raw': np.sqrt(stats[:, 14:17] / nn),
+            'gain': np.where(positive, sab / safe, 1.0), 'rms_restored_gain': np.sqrt(left / nn),
+            'pooled_restored': pooled(sd), 'pooled_raw': pooled(stats[:, 14:17]), 'pooled_restored_gain': pooled(left),
+            'pooled_n': pooled_n}
+
+
+def merge_consistency(records: list, request: list, min_cover: float) -> dict:
+    """The survey's ``consistency.pt`` from the targets' records -- ``{'target', 'views', 'stats', 'H', 'W'}``, in any order and
+    however they were split over ranks: the targets are taken in ``request`` order, so the result does not depend on the world
+    size.  One row per directed kept pair (a, b) with a valid pixel pair: ``n``, ``rms_restored``, ``rms_raw``, ``gain``,
+    ``rms_restored_gain``; the pooled figures are ``sqrt(sum sum d^2 / sum n)`` over all rows."""
+    order = {name: i for i, name in enumerate(request)}
+    records = sorted(records, key=lambda r: order[r['target']])
+    a, b, n = [], [], []
+    cols = {k: [] for k in ('rms_restored', 'rms_raw', 'gain', 'rms_restored_gain')}
+    sums = np.zeros((3, 3))   # sum d^2 of the restored, the raw and the gain-compensated colours
+    for r in records:
+        stats = np.asarray(r['stats'], np.float64).reshape(-1, 26)
+        s = consistency_summary(stats, r['H'], r['W'], min_cover)
+        for k in np.nonzero(s['kept'] & (s['n'] > 0))[0]:
+            a.append(r['target']); b.append(r['views'][k]); n.append(int(round(s['n'][k])))
+            for key in cols:
+                cols[key].append(s[key][k])
+            sums[0] += stats[k, 2:5]
+            sums[1] += stats[k, 14:17]
+            sums[2] += s['rms_restored_gain'][k] ** 2 * s['n'][k]
+    total = float(sum(n))
+    pooled = np.sqrt(sums / total) if total > 0 else np.zeros((3, 3))
+    out = {'a': a, 'b': b, 'n': torch.tensor(n, dtype=torch.int64), 'images': list(request), 'targets': [r['target'] for r in records],
+           'min_cover': float(min_cover), 'pooled_n': int(total), 'pooled_restored': torch.from_numpy(pooled[0].copy()),
+           'pooled_raw': torch.from_numpy(pooled[1].copy()), 'pooled_restored_gain': torch.from_numpy(pooled[2].copy())}
+    for key, rows in cols.items():
+        out[key] = torch.from_numpy(np.asarray(rows, np.float64).reshape(-1, 3))
+    return out
+
+
+def _consistency_file(results_dir: Path, image) -> Path:
+    return (Path(results_dir) / image.name).with_suffix('.pt')   # sucre.py:213-215
+
+
+def _read_restored(path: Path, image, lazy: bool = False) -> Tensor:
+    """``J`` of a result file, checked against the image's camera.  ``lazy``: only the shape is wanted -- the file is mapped, not
+    read, where torch can (a zip archive, what torch.save writes)."""
+    try:
+        try:
+            data = torch.load(path, map_location='cpu', mmap=True) if lazy else torch.load(path, map_location='cpu')
+        except (RuntimeError, ValueError, TypeError):
+            if not lazy:
+                raise
+            data = torch.load(path, map_location='cpu')
+        J = data['J']
+    except Exception as e:
+        raise SystemExit(f'--check-consistency: cannot read J from {path}: {e}')
+    want = (int(image.camera.height), int(image.camera.width), 3)
+    if not torch.is_tensor(J) or tuple(J.shape) != want:
+        raise SystemExit(f'--check-consistency: J of {path} has shape {tuple(J.shape) if torch.is_tensor(J) else type(J).__name__}, '
+                         f'but the camera of {image.name} is {want[1]}x{want[0]}: (H, W, 3) = {want} expected')
+    return J
+
+
+def consistency_cache_budget(device) -> int:
+    """Bytes of restored images (12 per pixel) --check-consistency keeps on the device across targets:
+    SUCRE_CONSISTENCY_CACHE_GB, by default a quarter of the device's memory (the pixel cache of sfm.py takes up to half)."""
+    gb = os.environ.get('SUCRE_CONSISTENCY_CACHE_GB')
+    if gb is not None:
+        return int(float(gb) * 2 ** 30)
+    return int(torch.cuda.mem_get_info(device)[1]) // 4
+
+
+class _RestoredCache:
+    """The restored images on the device, least recently used dropped first once ``budget`` bytes are exceeded; the images
+    named in ``pinned`` (the current target and its neighbours) are never dropped."""
+
+    def __init__(self, results_dir: Path, device, budget: int):
+        self.results_dir, self.device, self.budget = Path(results_dir), device, int(budget)
+        self.entries: 'collections.OrderedDict[str, Tensor]' = collections.OrderedDict()
+        self.total = 0
+
+    @staticmethod
+    def nbytes(image) -> int:
+        return int(image.camera.height) * int(image.camera.width) * 12
+
+    def get(self, image, pinned: set) -> Tensor:
+        J = self.entries.get(image.name)
+        if J is not None:
+            self.entries.move_to_end(image.name)
+            return J
+        need = self.nbytes(image)
+        for name in [k for k in self.entries if k not in pinned]:
+            if self.total + need <= self.budget:
+                break
+            self.total -= self.entries.pop(name).numel() * 4
+        J = _read_restored(_consistency_file(self.results_dir, image), image).to(torch.float32).contiguous().to(self.device)
+        self.entries[image.name] = J
+        self.total += need
+        return J
+
+
+def _write_consistency(image, views: list, count, ssd, stats, min_cover: float, output_dir: Path) -> dict:
+    """``<stem>_consistency.pt``, ``<stem>_consistency.png`` and the printed line of one target; returns its record."""
+    H, W = int(image.camera.height), int(image.camera.width)
+    s = consistency_summary(stats.numpy(), H, W, min_cover)
+    stem = Path(image.name).stem
+    torch.save({'views': list(views), 'stats': stats, 'kept': torch.from_numpy(s['kept'].copy()), 'count': count, 'ssd': ssd,
+                'min_cover': float(min_cover), 'pooled_n': int(s['pooled_n']),
+                **{k: torch.from_numpy(np.ascontiguousarray(s[k])) for k in ('n_matches', 'n', 'rms_restored', 'rms_raw', 'gain',
+                                                                             'rms_restored_gain', 'pooled_restored', 'pooled_raw',
+                                                                             'pooled_restored_gain')}},
+               output_dir / f'{stem}_consistency.pt')
+    _save_png(PILImage.fromarray(residual_image(count.numpy(), ssd.numpy())), output_dir / f'{stem}_consistency.png')
+    r, raw = s['pooled_restored'], s['pooled_raw']
+    line = (f'{image.name}: consistency with {int(s["kept"].sum())} views over {int(s["pooled_n"])} pixel pairs: restored RMS '
+            f'R {r[0]:.4f} G {r[1]:.4f} B {r[2]:.4f} (raw R {raw[0]:.4f} G {raw[1]:.4f} B {raw[2]:.4f})')
+    per_view = np.sqrt((s['rms_restored'] ** 2).mean(axis=1))   # sqrt(sum_c sum d^2 / (3 n))
+    per_view[~(s['kept'] & (s['n'] > 0))] = -1.0
+    if (per_view >= 0).any():
+        worst = int(per_view.argmax())
+        line += f'; least consistent with {views[worst]} (RMS {per_view[worst]:.4f})'
+    print(line)
+    return {'target': image.name, 'views': list(views), 'stats': stats.numpy().copy(), 'H': H, 'W': W}
+
+
+def check_consistency(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, output_dir: Path, image_list: list | None = None,
+                      min_cover: float = 0.000001, device: str = 'cuda', request: list | None = None, rank: int = 0,
+                      num_workers: int = 0) -> dict | None:
+    """Cross-view colour consistency of a finished restoration: for every image of ``images`` (``sfm.Image`` objects or names of
+    ``colmap_model``) its restored ``J`` -- ``results_dir / <name>.pt``, key ``J``, what this project and the reference write --
+    is compared with the ``J`` of every other image of ``image_list`` (the model's images unless given) that has such a file,
+    on the pixels the two-way match of their depth maps pairs (``engine.view_consistency``).  Nothing is fitted.  The
+    neighbours keep ``image_list`` order, go through ``overlapping_views`` unless SUCRE_CULL_VIEWS=0 and are capped at
+    ``engine.MAX_VIEWS``; images of ``image_list`` without a file are skipped and counted.  Every target's file is checked
+    before any image is decoded: a missing one, or a ``J`` (of a target or of a neighbour) that is not (H, W, 3) of its camera,
+    stops the run naming it.  The restored images stay on the device across targets, least recently used dropped first, within
+    ``consistency_cache_budget``; a target whose own neighbours exceed it is refused.  Per target: ``<stem>_consistency.pt``
+    (``views, stats, kept, count, ssd, min_cover`` and the arrays of ``consistency_summary``), ``<stem>_consistency.png``
+    (``residual_image`` of the squared differences) and one line.  Every rank takes part in the gather of the records (when a
+    process group is up); rank 0 writes ``consistency.pt`` (``merge_consistency``), prints the survey's line and returns the
+    merged dictionary, the others return None."""
+    from . import engine
+    sfm.require_gpu(device, 'check_consistency')
+    images = [colmap_model[im] if isinstance(im, str) else im for im in images]
+    image_list = list(colmap_model.images.values()) if image_list is None else list(image_list)
+    results_dir, output_dir = Path(results_dir), Path(output_dir)
+    for image in images:   # before anything is decoded
+        path = _consistency_file(results_dir, image)
+        if not path.is_file():
+            raise SystemExit(f'--check-consistency: {path} is missing: {image.name} has no restored image in {results_dir}')
+    have = [im for im in image_list if _consistency_file(results_dir, im).is_file()]
+    n_without = len(image_list) - len(have)
+    for image in {im.name: im for im in images + have}.values():
+        _read_restored(_consistency_file(results_dir, image), image, lazy=True)
+    if n_without:
+        print(f'--check-consistency: {n_without} of {len(image_list)} images have no restored image in {results_dir} and are skipped.')
+    output_dir.mkdir(parents=True, exist_ok=True)
+    cull = os.environ.get('SUCRE_CULL_VIEWS', '1') != '0'
+    if images:
+        loader.prefetch_for_targets(images, have, device, num_workers=num_workers, min_cover=0.0 if cull else -1.0)
+    cache = _RestoredCache(results_dir, device, consistency_cache_budget(device))
+    records = []
+    for image in images:
+        others = [im for im in have if im.name != image.name]
+        if cull and len(others) > 1:
+            others = [others[i] for i in image.overlapping_views(others, device)]
+        others = others[:engine.MAX_VIEWS]
+        if not others:
+            raise SystemExit(f'--check-consistency: {image.name} has no neighbour with a restored image in {results_dir}')
+        need = sum(cache.nbytes(im) for im in others + [image])
+        if need > cache.budget:
+            raise SystemExit(f'--check-consistency: the restored images of {image.name} and its {len(others)} neighbours take {need} '
+                             f'bytes, more than the {cache.budget} bytes kept on {device} (SUCRE_CONSISTENCY_CACHE_GB); list images '
+                             f'to leave out in --filter-images-path')
+        pinned = {im.name for im in others} | {image.name}
+        with torch.cuda.device(device):
+            J = cache.get(image, pinned)
+            Js = [cache.get(im, pinned) for im in others]
+            target = image.device_view(device)
+            views = [im.device_view(device) for im in others]
+            count, ssd, stats = engine.view_consistency(target, J, views, Js)
+            count, ssd, stats = count.cpu(), ssd.cpu(), stats.cpu()
+        records.append(_write_consistency(image, [im.name for im in others], count, ssd, stats, min_cover, output_dir))
+    gathered = [r for part in sdist.all_gather_objects(records) for r in part]
+    if rank != 0:
+        return None
+    request = list(request) if request is not None else [im.name for im in images]
+    merged = merge_consistency(gathered, request, min_cover)
+    torch.save(merged, output_dir / 'consistency.pt')
+    r, raw = merged['pooled_restored'].numpy(), merged['pooled_raw'].numpy()
+    print(f'consistency over {len(merged["a"])} pairs of {len(merged["targets"])} images: restored RMS R {r[0]:.4f} G {r[1]:.4f} '
+          f'B {r[2]:.4f}, raw R {raw[0]:.4f} G {raw[1]:.4f} B {raw[2]:.4f}')
+    return merged
+
+
+def _refuse_consistency_flags(args) -> None:
+    """What --check-consistency does not combine with, refused before any file is opened."""
+    refused = [('--shared-water', bool(getattr(args, 'shared_water', False)), 'nothing is fitted, so nothing is shared'),
+               ('--apply-water', getattr(args, 'apply_water', None) is not None, 'restore first, into the directory to check, then check it'),
+               ('--trim-outliers', getattr(args, 'trim_outliers', None) is not None or getattr(args, 'trim_rounds', None) is not None,
+                'there is no fit to trim'),
+               ('--view-gains', bool(getattr(args, 'view_gains', False)) or getattr(args, 'gain_rounds', None) is not None
+                or getattr(args, 'gain_limit', None) is not None, 'there is no fit to estimate gains from'),
+               ('--save-quality', bool(getattr(args, 'save_quality', False)), 'there is no fit, hence no residuals'),
+               ('--save-interval', args.save_interval is not None, 'there are no iterations to snapshot'),
+               ('--params-path', args.params_path is not None, 'no parameters are read: the restored images are'),
+               ('--keep-matches', bool(args.keep_matches), 'no match list is kept: the pairs are compared where they are found'),
+               ('--common-stretch', bool(getattr(args, 'common_stretch', False)), 'no picture of J is written'),
+               ('--stretch-from', getattr(args, 'stretch_from', None) is not None, 'no picture of J is written'),
+               ('--image-scale', args.image_scale != 1, 'resized images have float32 colours, and the raw comparison reads uint8')]
+    for flag, given, why in refused:
+        if given:
+            raise SystemExit(f'--check-consistency: {flag} does not combine with it ({why}); drop one of the two flags')
+
+
 def _refuse_stretch_flags(args) -> None:
     """What --common-stretch and --stretch-from do not combine with, refused before any file is opened."""
     if not getattr(args, 'common_stretch', False):
@@ -1156,6 +1393,9 @@ def parse_args(args: argparse.Namespace):
     rank, local_rank, world = sdist.env_rank_world()
     shared = bool(getattr(args, 'shared_water', False))
     apply = getattr(args, 'apply_water', None)
+    check = getattr(args, 'check_consistency', None)
+    if check is not None:
+        _refuse_consistency_flags(args)
     _refuse_stretch_flags(args)
     common = bool(getattr(args, 'common_stretch', False))
     stretch = None
@@ -1206,6 +1446,10 @@ def parse_args(args: argparse.Namespace):
         survey = len(images) > 1 and str(device).startswith('cuda')   # (the worker processes: decoding and PNG encoding)
         print(f'--apply-water: single-view inversion at the parameters of {apply}; nothing is fitted or matched, so --num-iter, '
               f'--learning-rate, --batch-size, --use-closed-form, --min-cover, --filter-images-path and --force-compute-matches are ignored.')
+    if check is not None:
+        survey = False
+        print(f'--check-consistency: the restored images of {check} are compared where they see the same seabed; nothing is fitted, '
+              f'so --num-iter, --learning-rate, --batch-size, --use-closed-form, --light-model and --force-compute-matches are ignored.')
     if survey:
         # image files are decoded and the result pictures encoded by child processes (_pixelio.WorkerPool: CPU work in
         # the process that drives the GPU slows its launches down, and PIL's decoder does not scale over threads);
@@ -1222,7 +1466,12 @@ def parse_args(args: argparse.Namespace):
     if host_threads > 0:
         torch.set_num_threads(host_threads)
     try:
-        if apply is not None:
+        if check is not None:
+            if world > 1:   # the targets' records are gathered on rank 0
+                sdist.init_process_group()
+            check_consistency(images, colmap_model, check, args.output_dir, image_list=image_list, min_cover=args.min_cover,
+                              device=device, request=request, rank=rank, num_workers=args.num_workers)
+        elif apply is not None:
             if common and world > 1:   # the pool spans the ranks: its histograms are all-reduced
                 sdist.init_process_group()
             apply_water(images, colmap_model, args.output_dir, water, light_model=args.light_model, device=device, in_flight=in_flight,
@@ -1453,6 +1702,11 @@ def build_parser() -> argparse.ArgumentParser:
                           help='do not fit: restore every image of the request from its own depth map with the B, beta, gamma (and, '
                                'with --light-model, cam2light, sigma) of this .pt file -- a shared_water.pt or a <name>.pt of an '
                                'earlier run; writes <stem>_rgb.png and <name>.pt (and <stem>_vignetting.png) per image')
+    p.extras.add_argument('--check-consistency', type=Path, metavar='DIR', default=argparse.SUPPRESS,
+                          help='do not fit: compare the restored J of every image of the request (DIR/<name>.pt, as this tool and the '
+                               'reference write them) with the restored J of the other images on the pixels their depth maps match, '
+                               'and the raw pictures likewise; writes <stem>_consistency.pt and <stem>_consistency.png per image and '
+                               'consistency.pt, and prints the RMS colour difference of both')
     p.extras.add_argument('--common-stretch', action='store_true', default=argparse.SUPPRESS,
                           help='with --shared-water or --apply-water: stretch every <stem>_rgb.png between the SAME per-channel 1st '
                                'and 99th percentile, those of the valid pixels of all images of the request pooled (all ranks), '
