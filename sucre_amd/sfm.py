@@ -18,6 +18,7 @@ import numpy as np
 import collections
 import os
 import threading
+import weakref
 
 import torch
 from torch import Tensor
@@ -144,10 +145,12 @@ _STACKED: dict = {}
 
 def _stacked_cameras(image_list):
     """float64 stacks (R, t, K, W, H) of the images' poses and cameras, kept for the list that was asked about last (a
-    survey asks about the same list for every target)."""
-    key = (len(image_list), id(image_list[0]), id(image_list[-1]), id(image_list[len(image_list) // 2]))
+    survey asks about the same list for every target).  The same list means the same image objects, every one of them, in the
+    same order: lists that share their length and their first, middle and last image are still different lists (the neighbours
+    of two targets of --check-consistency are), and an image that no longer exists is none of the new ones."""
     hit = _STACKED.get('entry')
-    if hit is None or hit[0] != key:
+    if hit is None or len(hit[0]) != len(image_list) or any(ref() is not im for ref, im in zip(hit[0], image_list)):
+        key = [weakref.ref(im) for im in image_list]
         R = np.stack([im.pose.R.numpy() for im in image_list]).astype(np.float64)              # (N, 3, 3) world-from-camera
         t = np.stack([im.pose.t.numpy() for im in image_list]).astype(np.float64)              # (N, 3, 1)
         K = np.stack([im.camera.K.numpy() for im in image_list]).astype(np.float64)

@@ -24,9 +24,10 @@ def lists_of_map(match_map, W2):
 
 
 def _four_sums(a, b):
-    d = a - b
-    terms = [d * d, a * a, b * b, a * b]
-    return np.concatenate([t.sum(axis=0) for t in terms]), np.concatenate([np.abs(t).sum(axis=0) for t in terms])
+    with np.errstate(invalid='ignore'):   # infinities in J are data: inf - inf and inf + -inf are NaN, silently
+        d = a - b
+        terms = [d * d, a * a, b * b, a * b]
+        return np.concatenate([t.sum(axis=0) for t in terms]), np.concatenate([np.abs(t).sum(axis=0) for t in terms])
 
 
 def reference(J_A, rgb_A, views):
@@ -54,5 +55,6 @@ def reference(J_A, rgb_A, views):
             rb = unit_from_u8(np.asarray(rgb_B)[v2, u2][valid]).astype(np.float64)
             stats[k, 14:26], stats_abs[k, 14:26] = _four_sums(ra, rb)
         np.add.at(count, (v1[valid], u1[valid]), 1)
-        np.add.at(ssd, (v1[valid], u1[valid]), (a - b) ** 2)
+        with np.errstate(invalid='ignore'):
+            np.add.at(ssd, (v1[valid], u1[valid]), (a - b) ** 2)
     return count, ssd, stats, stats_abs, valids

@@ -249,3 +249,121 @@ def test_engine_entry_point_refuses_on_the_host():
         engine.view_consistency(v, J, [v, v], [J])
     with pytest.raises(_lib.SucreError, match='no CPU fallback'):
         engine.view_consistency(v, J, [v], [J])
+
+
+# ---- _RestoredCache on the host: what --check-consistency keeps on the device across targets ------------------------------------
+def cache_with_files(tmp_path, monkeypatch, sizes, budget):
+    """One restored image per (H, W) of ``sizes`` -- J filled with the image's index, so a tensor names its file --, a cache of
+    ``budget`` bytes on the CPU, and the list the non-lazy ``_read_restored`` calls append their file name to."""
+    images = [fake_image(f'im{k}.png', H, W) for k, (H, W) in enumerate(sizes)]
+    for k, im in enumerate(images):
+        torch.save({'J': torch.full((im.camera.height, im.camera.width, 3), float(k))}, (tmp_path / im.name).with_suffix('.pt'))
+    reads = []
+    real = sucre._read_restored
+
+    def spy(path, image, lazy=False):
+        if not lazy:
+            reads.append(path.name)
+        return real(path, image, lazy)
+
+    monkeypatch.setattr(sucre, '_read_restored', spy)
+    return images, sucre._RestoredCache(tmp_path, 'cpu', budget), reads
+
+
+def held(cache):
+    """The names the cache holds, least recently used first, after checking its byte count against what it holds."""
+    assert cache.total == sum(J.numel() * J.element_size() for J in cache.entries.values())
+    return list(cache.entries)
+
+
+def test_cache_hit_moves_the_entry_to_the_end_and_reads_nothing(tmp_path, monkeypatch):
+    images, cache, reads = cache_with_files(tmp_path, monkeypatch, [(6, 8)] * 3, 3 * 6 * 8 * 12)
+    assert cache.nbytes(images[0]) == 6 * 8 * 12
+    first = [cache.get(im, set()) for im in images]
+    assert reads == ['im0.pt', 'im1.pt', 'im2.pt'] and held(cache) == ['im0.png', 'im1.png', 'im2.png']
+    assert all(J.dtype == torch.float32 and tuple(J.shape) == (6, 8, 3) and bool((J == k).all()) for k, J in enumerate(first))
+    again = cache.get(images[0], set())
+    assert again is first[0] and len(reads) == 3 and held(cache) == ['im1.png', 'im2.png', 'im0.png']
+    assert cache.get(images[2], {'im1.png'}) is first[2] and len(reads) == 3 and held(cache) == ['im1.png', 'im0.png', 'im2.png']
+    assert cache.total == 3 * 6 * 8 * 12 == cache.budget
+
+
+def test_cache_evicts_least_recently_used_first_skips_pinned_and_stops_when_the_image_fits(tmp_path, monkeypatch):
+    unit = 4 * 4 * 12
+    #          im0     im1     im2     im3     im4 (2 units)  im5 (3 units)  im6
+    sizes = [(4, 4), (4, 4), (4, 4), (4, 4), (8, 4),        (4, 12),       (4, 4)]
+    images, cache, reads = cache_with_files(tmp_path, monkeypatch, sizes, 4 * unit)
+    for im in images[:4]:
+        cache.get(im, set())
+    assert held(cache) == ['im0.png', 'im1.png', 'im2.png', 'im3.png'] and cache.total == 4 * unit
+    cache.get(images[0], set())                                  # im0 becomes the most recently used
+    assert held(cache) == ['im1.png', 'im2.png', 'im3.png', 'im0.png']
+    # two units wanted: the two least recently used go, no more
+    J4 = cache.get(images[4], set())
+    assert held(cache) == ['im3.png', 'im0.png', 'im4.png'] and cache.total == 4 * unit and bool((J4 == 4).all())
+    # one unit wanted, the least recently used pinned: the next one goes, and only that one
+    cache.get(images[1], {'im3.png', 'im1.png'})
+    assert held(cache) == ['im3.png', 'im4.png', 'im1.png'] and cache.total == 4 * unit
+    # three units wanted, im4 (two units) pinned: both others go -- images of different sizes leave, the count follows
+    J5 = cache.get(images[5], {'im4.png', 'im5.png'})
+    assert held(cache) == ['im4.png', 'im5.png'] and cache.total == 5 * unit and bool((J5 == 5).all())   # (the pinned pair exceeds the budget)
+    # one unit wanted, nothing pinned: im4 alone does not make room (3 + 1 = 4 fits after it), so im5 stays
+    cache.get(images[6], {'im6.png'})
+    assert held(cache) == ['im5.png', 'im6.png'] and cache.total == 4 * unit
+    # an evicted image is read again, and is the right one
+    n = len(reads)
+    J0 = cache.get(images[0], {'im0.png', 'im6.png'})
+    assert reads[n:] == ['im0.pt'] and bool((J0 == 0).all()) and held(cache) == ['im6.png', 'im0.png'] and cache.total == 2 * unit
+    assert reads == ['im0.pt', 'im1.pt', 'im2.pt', 'im3.pt', 'im4.pt', 'im1.pt', 'im5.pt', 'im6.pt', 'im0.pt']
+
+
+def test_cache_with_a_pinned_set_that_fills_the_budget_evicts_nothing(tmp_path, monkeypatch):
+    unit = 6 * 8 * 12
+    images, cache, reads = cache_with_files(tmp_path, monkeypatch, [(6, 8)] * 4, 3 * unit)
+    pinned = {im.name for im in images[:3]}
+    got = [cache.get(im, pinned) for im in images[:3]]
+    assert cache.total == cache.budget and held(cache) == ['im0.png', 'im1.png', 'im2.png']
+    # a fourth image while all three are pinned: nothing can go; the cache grows past its budget rather than hand out a wrong J
+    J3 = cache.get(images[3], pinned | {'im3.png'})
+    assert held(cache) == ['im0.png', 'im1.png', 'im2.png', 'im3.png'] and cache.total == 4 * unit and bool((J3 == 3).all())
+    for k, im in enumerate(images[:3]):
+        J = cache.get(im, pinned)
+        assert J is got[k] and bool((J == k).all()), im.name
+    assert reads == ['im0.pt', 'im1.pt', 'im2.pt', 'im3.pt']
+    # the next target pins other names: the budget holds again as soon as something may go
+    cache.get(images[3], {'im3.png'})
+    J0 = cache.get(images[0], {'im3.png', 'im0.png'})
+    assert J0 is got[0] and len(reads) == 4   # (a hit evicts nothing)
+    assert held(cache) == ['im1.png', 'im2.png', 'im3.png', 'im0.png']
+
+
+# ---- the overlap cull on the neighbour lists --check-consistency asks about ----------------------------------------------------
+def test_overlap_cull_answers_for_the_list_it_is_given_not_for_a_look_alike():
+    """check_consistency asks ``overlapping_views`` about another list for every target: the images with a restored image but
+    the target.  Two such lists can share their length and their first, middle and last image -- of the strip of eight without
+    image 3, the lists of targets 1 and 2 do -- and are still different lists: each must get its own answer (the camera stacks
+    kept from the previous question were once taken for the look-alike's, and target 4 got image 1 for a neighbour)."""
+    from pathlib import Path
+    from sucre_amd import sfm, synth
+    survey = synth.make_survey(96, 64, 8, 1, seed=5, spacing=0.5)
+    images = [sfm.Image(i + 1, Path(v.name), Path('depth_' + v.name), sfm.Pose(v.R, v.t), sfm.Camera(i + 1, 96, 64, survey.K))
+              for i, v in enumerate(survey.views)]
+    for im, v in zip(images, survey.views):
+        d = v.depth_f32()
+        im.__dict__['_depth_range'] = (float(d[d > 0].min()), float(d[d > 0].max()))
+    have = [im for im in images if im.name != 'img_0003.png']
+    lists = {im.name: [o for o in have if o is not im] for im in have}
+    a, b = lists['img_0001.png'], lists['img_0002.png']
+    assert len(a) == len(b) and a[0] is b[0] and a[-1] is b[-1] and a[len(a) // 2] is b[len(b) // 2] and a[1] is not b[1]
+    whole = {}
+    for im in have:   # one question about the whole list, the target taken out afterwards: what each list's answer must be
+        whole[im.name] = [have[i].name for i in im.overlapping_views(have, 'cpu') if have[i] is not im]
+    assert whole['img_0004.png'] == ['img_0002.png', 'img_0005.png', 'img_0006.png']
+    assert [len(whole[im.name]) for im in have] == [2, 2, 3, 3, 3, 3, 2]   # (2, 3, 4, 4, 4, 4, 3, 2 with image 3: each of its four neighbours loses one)
+    for im in have:   # in the order of a run, every answer with the previous list's stacks still kept
+        others = lists[im.name]
+        assert [others[i].name for i in im.overlapping_views(others, 'cpu')] == whole[im.name], im.name
+    # the same list asked about again is still served from what was kept
+    kept = sfm._STACKED['entry']
+    have[-1].overlapping_views(lists[have[-1].name], 'cpu')
+    assert sfm._STACKED['entry'] is kept
