@@ -597,6 +597,63 @@ int sucre_view_consistency(int H, int W, int n_views, const sucre_view_t *target
                            double *stats_dev, void *scratch_dev, void *stream);
 
 /*
+ * ---- seabed mosaic of restored images: best-view ortho splat -------------------------------------------------------------------
+ * Every pixel of every image is dropped onto a plane grid and the pixel seen through the least water wins its cell; nothing is
+ * blended and no hole is filled.  Image i of the request (its ORDINAL: first_ordinal + its index in the call) has a depth map, a
+ * camera, a world-from-camera pose, its restored J (H,W,3) float32 and its raw uint8 colours.  Pixel p = v W + u TAKES PART when
+ * depth > 0 and J[p] holds no NaN in any channel (plot_J's rule, sucre.py:86-87).  In float32, every FMA explicit:
+ *   cP = Kinv (d [u+.5, v+.5, 1])                     sfm.py:90-93 (Image.unproject_depth), the match kernels' chain
+ *   z  = sqrt(cP.x cP.x + cP.y cP.y + cP.z cP.z)       the range, as sucre_invert_images forms it
+ *   wP = R cP + t                                      sfm.py:49-55 (Pose.transform)
+ *   a_s = e1 . wP, a_t = e2 . wP                       e1, e2: rows 0 and 1 of `axes` (row-major 3x3), x*e[0], fma(e[1], y, .), fma(e[2], z, .)
+ *   q_s = (a_s - lo_s) / gsd, q_t = (a_t - lo_t) / gsd (IEEE); dropped unless 0 <= q_s < Wm and 0 <= q_t < Hm;
+ *   cell = (int)q_t * Wm + (int)q_s
+ * The winner of a cell is the pixel with the lexicographically smallest (bits of z, ordinal, p); the result does not depend on
+ * the order of arrival, so two runs give the same bits.  Four phases, each one call per batch of images, each call one launch per
+ * 32 images (plus the table's) on `stream`; nothing is copied from the host, nothing allocated, nothing waited for:
+ *   sucre_mosaic_bounds   bounds_dev[0..3] (uint32) = min a_s, min a_t, max a_s, max a_t over the pixels that take part, as
+ *                         order-preserving keys: key(x) = bits(x) ^ (bits(x) >> 31 ? 0xffffffff : 0x80000000).  The call
+ *                         ACCUMULATES: the caller starts the two min words at 0xffffffff and the two max words at 0
+ *   sucre_mosaic_splat    key_dev[cell] (uint64) = min over the pixels of the cell of bits(z) << 32 | ordinal; the caller starts
+ *                         every word at all ones (an empty cell keeps that).  z > 0, so a key stays below 2^63.
+ *                         flags: SUCRE_MOSAIC_PLAIN_ATOMIC -- issue the 64-bit atomic min for every pixel instead of loading the
+ *                         word first and skipping the atomic when it is already smaller (same result; for measurements)
+ *   sucre_mosaic_resolve  pix_dev[cell] (uint32) = min p over the pixels whose key equals key_dev[cell]; starts at all ones
+ *   sucre_mosaic_gather   the one pixel per filled cell with the cell's key and pix_dev[cell] == p writes J_out (Hm,Wm,3)
+ *                         float32 bit for bit, raw_out (Hm,Wm,3) uint8, source_out (Hm,Wm) int32 its ordinal, pixel_out (Hm,Wm)
+ *                         int32 p, range_out (Hm,Wm) float32 z.  Empty cells are not touched: the caller fills the outputs first
+ * All calls of one mosaic get the same images with the same ordinals, and splat / resolve / gather the same grid.
+ * `images`: HOST array; `table_dev`: sucre_mosaic_table_bytes(n_images) bytes of device memory, 256-byte aligned, that must stay
+ * untouched until the call's launches have run.  Checked before any launch (SUCRE_ERR_ARG): a NULL or misaligned pointer,
+ * n_images or first_ordinal + n_images outside 1..4096, an image size outside 1..32767, gsd or a bound that is not finite, gsd <= 0,
+ * Hm or Wm outside 1..2^24, unknown flags.
+ */
+#define SUCRE_MOSAIC_PLAIN_ATOMIC 1u
+typedef struct sucre_mosaic_image {
+    const float *depth;   /* (H,W) float32 */
+    const uint8_t *rgb;   /* (H,W,3) uint8 */
+    const float *J;       /* (H,W,3) float32 */
+    int32_t H, W;
+    float Kinv[9], R[9], t[3];
+    int32_t reserved[3];
+} sucre_mosaic_image_t;
+typedef struct sucre_mosaic_grid {
+    float axes[9];        /* rows e1, e2, e3 */
+    float gsd, lo_s, lo_t;
+    int32_t Hm, Wm;
+} sucre_mosaic_grid_t;
+size_t sucre_mosaic_table_bytes(int n_images);
+int sucre_mosaic_bounds(void *table_dev, int n_images, const sucre_mosaic_image_t *images, const float *axes, uint32_t *bounds_dev,
+                        void *stream);
+int sucre_mosaic_splat(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                       const sucre_mosaic_grid_t *grid, uint64_t *key_dev, unsigned flags, void *stream);
+int sucre_mosaic_resolve(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                         const sucre_mosaic_grid_t *grid, const uint64_t *key_dev, uint32_t *pix_dev, void *stream);
+int sucre_mosaic_gather(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                        const sucre_mosaic_grid_t *grid, const uint64_t *key_dev, const uint32_t *pix_dev, float *J_out,
+                        uint8_t *raw_out, int32_t *source_out, int32_t *pixel_out, float *range_out, void *stream);
+
+/*
  * Shared water AND light over several light-model images (the group above for the 19-parameter model; sucre.py:54-61 with
  * the objective of sucre.py:124-157 summed over the images: one B, beta, gamma, cam2light, sigma, every image its own J, one
  * n_obs).  `group_dev`: sucre_light_group_bytes(n_images) bytes of device memory, 256-byte aligned; `images` (host array)

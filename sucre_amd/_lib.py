@@ -26,6 +26,7 @@ WS_VIEW_COUNT, WS_VIEW_KEEP, WS_N_OBS, WS_PARAMS, WS_SUMS, WS_N_OBS_TOTAL, WS_ST
 INVERT_LIGHT, INVERT_FLOAT_COLOUR = 1, 2
 INVERT_MAX_IMAGES = 4096   # kInvertMaxImages of csrc/invert.h: images per sucre_invert_images call
 CONSISTENCY_STATS = 26     # kConsistStats of csrc/consist.h: columns of a view's row of sucre_view_consistency's stats
+MOSAIC_PLAIN_ATOMIC = 1     # SUCRE_MOSAIC_PLAIN_ATOMIC: sucre_mosaic_splat without the load that filters its atomics
 POOL_MAX_IMAGES = 4096    # kPoolMaxImages of csrc/pool.h: images per sucre_pool_select_pass call
 POOL_MAX_RANKS = 8
 POOL_HIST_WORDS = 3 * 8 * 256   # uint64 hist[3][8][256] at the head of the pooled select's state
@@ -67,6 +68,21 @@ class PoolImage(C.Structure):
 
 
 assert C.sizeof(PoolImage) == 16
+
+
+class MosaicImage(C.Structure):
+    """sucre_mosaic_image_t"""
+    _fields_ = [('depth', C.c_void_p), ('rgb', C.c_void_p), ('J', C.c_void_p), ('H', C.c_int32), ('W', C.c_int32),
+                ('Kinv', C.c_float * 9), ('R', C.c_float * 9), ('t', C.c_float * 3), ('reserved', C.c_int32 * 3)]
+
+
+class MosaicGrid(C.Structure):
+    """sucre_mosaic_grid_t"""
+    _fields_ = [('axes', C.c_float * 9), ('gsd', C.c_float), ('lo_s', C.c_float), ('lo_t', C.c_float), ('Hm', C.c_int32),
+                ('Wm', C.c_int32)]
+
+
+assert C.sizeof(MosaicImage) == 128 and C.sizeof(MosaicGrid) == 56
 
 
 # name -> (restype, argtypes); mirrors include/sucre_hip.h one to one (tests/test_abi.py checks both ways)
@@ -140,6 +156,11 @@ SIGNATURES = {
     'sucre_invert_images': (_i, [_vp, _i, C.POINTER(InvertImage), C.POINTER(C.c_float), C.c_uint, _vp]),
     'sucre_consistency_scratch_bytes': (C.c_size_t, [_i, _i, _i]),
     'sucre_view_consistency': (_i, [_i, _i, _i, C.POINTER(SucreView), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sucre_mosaic_table_bytes': (C.c_size_t, [_i]),
+    'sucre_mosaic_bounds': (_i, [_vp, _i, C.POINTER(MosaicImage), C.POINTER(C.c_float), _vp, _vp]),
+    'sucre_mosaic_splat': (_i, [_vp, _i, C.POINTER(MosaicImage), _i, C.POINTER(MosaicGrid), _vp, C.c_uint, _vp]),
+    'sucre_mosaic_resolve': (_i, [_vp, _i, C.POINTER(MosaicImage), _i, C.POINTER(MosaicGrid), _vp, _vp, _vp]),
+    'sucre_mosaic_gather': (_i, [_vp, _i, C.POINTER(MosaicImage), _i, C.POINTER(MosaicGrid), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'sucre_light_group_bytes': (C.c_size_t, [_i]),
     'sucre_light_group_sums_offset': (C.c_int64, []),
     'sucre_light_group_init': (_i, [_vp, _i, C.POINTER(LightGroupImage), C.POINTER(C.c_float), _vp]),

@@ -9,6 +9,7 @@
 #include "consist.h"
 #include "invert.h"
 #include "launch.h"
+#include "mosaic.h"
 #include "pool.h"
 
 namespace sucre {
@@ -883,6 +884,111 @@ int sucre_view_consistency(int H, int W, int n_views, const sucre_view_t *target
         return fail(SUCRE_ERR_ARG, "views_dev / J_views_dev must be 8-byte aligned, J_target_dev 4-byte aligned");
     return check_hip(launch_consistency(H, W, n_views, *target, views_dev, J_target_dev, J_views_dev, count_dev, ssd_dev, stats_dev,
                                         scratch_dev, static_cast<hipStream_t>(stream)), "sucre_view_consistency");
+}
+
+/* ---- seabed mosaic of restored images: best-view ortho splat (sfm.py:90-93, 49-55; plot_J's valid rule, sucre.py:86-87) ---- */
+
+}  // extern "C"
+
+namespace sucre {
+
+static int check_mosaic_images(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal) {
+    if (!table_dev || !aligned(table_dev, 256)) return fail(SUCRE_ERR_ARG, "mosaic table is NULL or not 256-byte aligned");
+    if (n_images < 1 || n_images > kMaxViews) return fail(SUCRE_ERR_ARG, "n_images=%d outside [1,%d]", n_images, kMaxViews);
+    if (first_ordinal < 0 || first_ordinal > kMaxViews - n_images)
+        return fail(SUCRE_ERR_ARG, "ordinals %d..%d outside [0,%d)", first_ordinal, first_ordinal + n_images - 1, kMaxViews);
+    if (!images) return fail(SUCRE_ERR_ARG, "images is NULL");
+    uint64_t blocks = 0;
+    for (int i = 0; i < n_images; ++i) {
+        const sucre_mosaic_image_t &im = images[i];
+        if (im.H < 1 || im.W < 1 || im.H > 32767 || im.W > 32767) return fail(SUCRE_ERR_ARG, "image %d: invalid size %dx%d (need 1..32767)", i, im.W, im.H);
+        if (!im.depth || !im.rgb || !im.J) return fail(SUCRE_ERR_ARG, "image %d: depth / rgb / J is NULL", i);
+        if (!aligned(im.depth, 4) || !aligned(im.J, 4)) return fail(SUCRE_ERR_ARG, "image %d: depth / J must be 4-byte aligned", i);
+        if (i % kMosaicLaunch == 0) blocks = 0;
+        blocks += mosaic_blocks(im.H, im.W);
+        if (blocks > 0x7fffffffull) return fail(SUCRE_ERR_ARG, "image %d: the 32 images of one launch may hold 2^39 pixels together", i);
+    }
+    return SUCRE_OK;
+}
+
+static int check_mosaic_grid(const sucre_mosaic_grid_t *g, MosaicGrid *out) {
+    if (!g) return fail(SUCRE_ERR_ARG, "grid is NULL");
+    for (int i = 0; i < 9; ++i) if (!std::isfinite(g->axes[i])) return fail(SUCRE_ERR_ARG, "axes[%d] is not finite", i);
+    if (!std::isfinite(g->gsd) || !(g->gsd > 0.0f)) return fail(SUCRE_ERR_ARG, "gsd=%g must be finite and > 0", (double)g->gsd);
+    if (!std::isfinite(g->lo_s) || !std::isfinite(g->lo_t)) return fail(SUCRE_ERR_ARG, "lo=(%g, %g) is not finite", (double)g->lo_s, (double)g->lo_t);
+    if (g->Hm < 1 || g->Wm < 1 || g->Hm > (1 << 24) || g->Wm > (1 << 24))
+        return fail(SUCRE_ERR_ARG, "mosaic of %dx%d cells (need 1..2^24 each way)", g->Wm, g->Hm);
+    for (int i = 0; i < 9; ++i) out->axes[i] = g->axes[i];
+    out->gsd = g->gsd; out->lo_s = g->lo_s; out->lo_t = g->lo_t; out->Hm = g->Hm; out->Wm = g->Wm;
+    return SUCRE_OK;
+}
+
+}  // namespace sucre
+
+extern "C" {
+
+size_t sucre_mosaic_table_bytes(int n_images) {
+    if (n_images < 1 || n_images > kMaxViews) {
+        fail(SUCRE_ERR_ARG, "n_images=%d outside [1,%d]", n_images, kMaxViews);
+        return 0;
+    }
+    return mosaic_table_bytes(n_images);
+}
+
+int sucre_mosaic_bounds(void *table_dev, int n_images, const sucre_mosaic_image_t *images, const float *axes, uint32_t *bounds_dev,
+                        void *stream) {
+    if (int rc = check_mosaic_images(table_dev, n_images, images, 0)) return rc;
+    if (!axes) return fail(SUCRE_ERR_ARG, "axes is NULL");
+    if (!bounds_dev || !aligned(bounds_dev, 4)) return fail(SUCRE_ERR_ARG, "bounds_dev is NULL or misaligned");
+    MosaicGrid g = {};
+    for (int i = 0; i < 9; ++i) {
+        if (!std::isfinite(axes[i])) return fail(SUCRE_ERR_ARG, "axes[%d] is not finite", i);
+        g.axes[i] = axes[i];
+    }
+    return check_hip(launch_mosaic(kMosaicBounds, table_dev, n_images, images, 0, g, bounds_dev, nullptr, nullptr, MosaicOut{},
+                                   static_cast<hipStream_t>(stream)), "sucre_mosaic_bounds");
+}
+
+int sucre_mosaic_splat(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                       const sucre_mosaic_grid_t *grid, uint64_t *key_dev, unsigned flags, void *stream) {
+    if (int rc = check_mosaic_images(table_dev, n_images, images, first_ordinal)) return rc;
+    MosaicGrid g;
+    if (int rc = check_mosaic_grid(grid, &g)) return rc;
+    if (!key_dev || !aligned(key_dev, 8)) return fail(SUCRE_ERR_ARG, "key_dev is NULL or not 8-byte aligned");
+    if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
+    return check_hip(launch_mosaic((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) ? kMosaicSplatPlain : kMosaicSplat, table_dev, n_images, images,
+                                   first_ordinal, g, nullptr, reinterpret_cast<unsigned long long *>(key_dev), nullptr, MosaicOut{},
+                                   static_cast<hipStream_t>(stream)), "sucre_mosaic_splat");
+}
+
+int sucre_mosaic_resolve(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                         const sucre_mosaic_grid_t *grid, const uint64_t *key_dev, uint32_t *pix_dev, void *stream) {
+    if (int rc = check_mosaic_images(table_dev, n_images, images, first_ordinal)) return rc;
+    MosaicGrid g;
+    if (int rc = check_mosaic_grid(grid, &g)) return rc;
+    if (!key_dev || !aligned(key_dev, 8)) return fail(SUCRE_ERR_ARG, "key_dev is NULL or not 8-byte aligned");
+    if (!pix_dev || !aligned(pix_dev, 4)) return fail(SUCRE_ERR_ARG, "pix_dev is NULL or misaligned");
+    return check_hip(launch_mosaic(kMosaicResolve, table_dev, n_images, images, first_ordinal, g, nullptr,
+                                   reinterpret_cast<unsigned long long *>(const_cast<uint64_t *>(key_dev)), pix_dev, MosaicOut{},
+                                   static_cast<hipStream_t>(stream)), "sucre_mosaic_resolve");
+}
+
+int sucre_mosaic_gather(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                        const sucre_mosaic_grid_t *grid, const uint64_t *key_dev, const uint32_t *pix_dev, float *J_out,
+                        uint8_t *raw_out, int32_t *source_out, int32_t *pixel_out, float *range_out, void *stream) {
+    if (int rc = check_mosaic_images(table_dev, n_images, images, first_ordinal)) return rc;
+    MosaicGrid g;
+    if (int rc = check_mosaic_grid(grid, &g)) return rc;
+    if (!key_dev || !aligned(key_dev, 8)) return fail(SUCRE_ERR_ARG, "key_dev is NULL or not 8-byte aligned");
+    if (!pix_dev || !aligned(pix_dev, 4)) return fail(SUCRE_ERR_ARG, "pix_dev is NULL or misaligned");
+    if (!J_out || !raw_out || !source_out || !pixel_out || !range_out)
+        return fail(SUCRE_ERR_ARG, "J_out / raw_out / source_out / pixel_out / range_out is NULL");
+    if (!aligned(J_out, 4) || !aligned(source_out, 4) || !aligned(pixel_out, 4) || !aligned(range_out, 4))
+        return fail(SUCRE_ERR_ARG, "J_out / source_out / pixel_out / range_out must be 4-byte aligned");
+    MosaicOut out = {J_out, raw_out, source_out, pixel_out, range_out};
+    return check_hip(launch_mosaic(kMosaicGather, table_dev, n_images, images, first_ordinal, g, nullptr,
+                                   reinterpret_cast<unsigned long long *>(const_cast<uint64_t *>(key_dev)),
+                                   const_cast<uint32_t *>(pix_dev), out, static_cast<hipStream_t>(stream)), "sucre_mosaic_gather");
 }
 
 /* ---- shared water and light over the light-model images of a rank (sucre.py:54-61, 124-157) ------------------------ */

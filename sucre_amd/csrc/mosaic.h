@@ -1,0 +1,80 @@
+// Seabed mosaic of restored images (sucre_mosaic_*): a best-view ortho splat.  Every pixel of every image is dropped onto a
+// plane grid; the pixel seen through the LEAST water wins its cell.  No blending, no hole filling, no float atomics.
+//
+// A pixel p = v W + u of image i (its ordinal: the position in the request) TAKES PART when d > 0 and J[p] holds no NaN in any
+// channel (plot_J's rule, sucre.py:86-87).  Then, all in float32 with explicit FMAs (the library is built with
+// -ffp-contract=off and IEEE divide / sqrt):
+//   cP = unproject(Kinv, u, v, d)                 match_pixel.h, sfm.py:90-93
+//   z  = sqrtf(cP.x cP.x + cP.y cP.y + cP.z cP.z) the range, invert.h's chain for the same quantity
+//   wP = rigid(R, t, cP)                          match_pixel.h, sfm.py:49-55
+//   a_s = dot3(e1, wP), a_t = dot3(e2, wP)        e1, e2: rows 0 and 1 of the mosaic's axes
+//   q_s = (a_s - lo_s) / gsd, q_t = (a_t - lo_t) / gsd;  the pixel is dropped unless 0 <= q_s < Wm and 0 <= q_t < Hm;
+//   cell = (int)q_t * Wm + (int)q_s
+// The WINNER of a cell is the pixel with the lexicographically smallest (bits of z, ordinal, p): z > 0, so its bit pattern
+// orders like its value; ties on z to the bit go to the earlier image, ties within an image to the lower pixel index.  The rule
+// does not depend on the order in which pixels arrive: two runs give the same bits.
+//
+// Four phases, one entry each (a caller with several ranks can all-reduce bounds, keys and pixel words between them):
+//   bounds   min / max of a_s, a_t over the pixels that take part: reduced per wave (shuffles) and per workgroup (LDS), then at
+//            most ONE atomicMin / atomicMax per workgroup on each of four order_key words (order_key.h), skipped when a load of
+//            the word shows that it has passed the workgroup's extreme already (as the splat's filter: a stale value is safe)
+//   splat    atomicMin of (uint64)bits(z) << 32 | ordinal into key[cell] (empty: all ones; below 2^63, a valid int64 as well).
+//            Unless SUCRE_MOSAIC_PLAIN_ATOMIC is given, key[cell] is loaded first and the atomic skipped when the stored key is
+//            already smaller: a stale value can only be larger than the current one, so nothing that could win is skipped
+//   resolve  a pixel whose key equals key[cell] does atomicMin(pix[cell], p) (uint32; empty: all ones)
+//   gather   the pixel with the cell's key AND pix[cell] == p writes the cell's five outputs: exactly one per filled cell
+// Every phase forms a pixel's numbers with the same function (mosaic_pixel), so the phases agree on who takes part and where.
+// Walk (invert_kernel's): one lane per pixel, rows contiguous across the lanes, workgroup b of the grid finds its image by
+// bisecting the first-workgroup column of a device table of up to 32 images; the image's camera is wave-uniform and read with
+// scalar loads (SGPR-resident, as CamDev is for a single target).
+// Measured on one MI355X, 65 resident images of 1080p, 74 pixels per cell (tools/mosaic_time.py, profiles/mosaic_time.txt): bounds
+// 0.97 ms, splat 0.86 ms, resolve 0.59 ms, gather 0.61 ms, against 0.58-0.62 ms for invert_kernel on the same images.  The plain
+// 64-bit atomic min for every pixel: 2.77 ms (48 G atomics/s; 25 G/s at 1176 pixels per cell) -- the load ahead of it is kept.  The
+// bounds phase without ITS load: 12.0 ms (every workgroup's four atomics land on one cache line).
+#pragma once
+#include "launch.h"
+
+namespace sucre {
+
+constexpr int kMosaicSet = 16;          // table entries per set launch (by value: 16 x 128 bytes of kernel arguments)
+constexpr int kMosaicLaunch = 32;       // images per phase launch (the bisection: 5 steps)
+constexpr uint32_t kMosaicBlockPx = 256;   // one lane per pixel
+
+struct MosaicImage {   // sucre_mosaic_image_t with its reserved words put to use
+    const float *depth;
+    const uint8_t *rgb;
+    const float *J;
+    int32_t H, W;
+    float Kinv[9], R[9], t[3];
+    uint32_t block0;    // the image's first workgroup in ITS launch's grid
+    int32_t ordinal;
+    int32_t pad;
+};
+static_assert(sizeof(MosaicImage) == sizeof(sucre_mosaic_image_t) && sizeof(MosaicImage) == 128, "the device table entry is the public struct");
+
+struct MosaicGrid {   // sucre_mosaic_grid_t
+    float axes[9];
+    float gsd, lo_s, lo_t;
+    int32_t Hm, Wm;
+};
+static_assert(sizeof(MosaicGrid) == sizeof(sucre_mosaic_grid_t), "the grid is the public struct");
+
+struct MosaicOut {   // the five outputs of sucre_mosaic_gather
+    float *J;
+    uint8_t *raw;
+    int32_t *source, *pixel;
+    float *range;
+};
+
+enum MosaicPhase { kMosaicBounds, kMosaicSplat, kMosaicSplatPlain, kMosaicResolve, kMosaicGather };
+
+inline size_t mosaic_table_bytes(int n_images) { return align_up((size_t)n_images * sizeof(MosaicImage), 256); }
+inline uint64_t mosaic_blocks(int H, int W) { return ((uint64_t)H * (uint64_t)W + kMosaicBlockPx - 1) / kMosaicBlockPx; }
+
+// One phase over images[0 .. n): ceil(n / 32) launches (plus the table's set launches) on s.  Only the arguments of the phase
+// are read: bounds (kMosaicBounds), key (splat: written; resolve, gather: read), pix (resolve: written; gather: read), out (gather).
+hipError_t launch_mosaic(MosaicPhase phase, void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                         const MosaicGrid &grid, uint32_t *bounds, unsigned long long *key, uint32_t *pix, const MosaicOut &out,
+                         hipStream_t s);
+
+}  // namespace sucre

@@ -979,6 +979,175 @@ def view_consistency(target: DeviceView, J_target: torch.Tensor, views: list, Js
     return count, ssd, stats
 
 
+def mosaic_max_cells() -> int:
+    """Cells a mosaic may have: SUCRE_MOSAIC_MAX_CELLS, 2^27 unless set (37 bytes per cell: key, pixel word and the five outputs)."""
+    return int(os.environ.get('SUCRE_MOSAIC_MAX_CELLS', 1 << 27))
+
+
+def mosaic_cells(lo: float, hi: float, gsd: float) -> int:
+    """``(int)((hi - lo) / gsd) + 1``, the float32 subtraction and IEEE division the kernels apply to a pixel."""
+    with np.errstate(all='ignore'):
+        return int((np.float32(hi) - np.float32(lo)) / np.float32(gsd)) + 1
+
+
+class Mosaic:
+    """The seabed mosaic (``sucre_mosaic_*``, csrc/mosaic.h) phase by phase, in the style of ``PoolSelect``: every pixel with a
+    valid depth and a restored colour without NaN is dropped onto the grid ``axes`` (3,3 float32, rows e1, e2, e3) x ``gsd`` metres
+    per cell, and the pixel with the smallest (range bits, ordinal, pixel index) wins its cell.  ``add_bounds(views, Js)`` any number
+    of times; ``begin(bounds=None)`` -- waits for the bounds (or takes the caller's ``(lo_s, lo_t, hi_s, hi_t)``; pixels outside
+    are dropped), allocates and returns ``(Hm, Wm)``; then ``splat``, ``resolve`` and ``gather``, each over ALL the images (in any
+    batches, every batch with the ordinal of its first image) before the next phase starts; ``result()``.  ``views``:
+    ``DeviceView`` with uint8 colours; ``Js``: their (H,W,3) float32 device images.  The words a later all-reduce over ranks would
+    combine are tensors: ``bounds_words`` (int32 x 4), ``key`` (int64, min), ``pix`` (int32 bit patterns of uint32, unsigned min)."""
+
+    def __init__(self, axes, gsd, device):
+        _lib.load()
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise _lib.SucreError('Mosaic runs on a GPU device (there is no CPU fallback)')
+        if self.device.index is None:   # 'cuda' names the current GPU: the views' tensors carry its index
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        a = torch.as_tensor(axes).detach().cpu().to(torch.float32).reshape(-1)
+        if a.numel() != 9 or not bool(torch.isfinite(a).all()):
+            raise ValueError('Mosaic: axes must be nine finite numbers (3x3, rows e1, e2, e3)')
+        self.axes = a.reshape(3, 3).clone()
+        self.gsd = np.float32(gsd)
+        if not (np.isfinite(self.gsd) and self.gsd > 0):
+            raise ValueError(f'Mosaic: gsd must be finite and > 0, not {gsd}')
+        self._axes_c = (C.c_float * 9)(*a.tolist())
+        self.bounds_words = torch.tensor([-1, -1, 0, 0], dtype=torch.int32, device=self.device)   # two min keys, two max keys
+        self.grid = None
+        self.Hm = self.Wm = None
+        self.lo = self.hi = None
+        self.key = self.pix = None
+        self._out = None
+
+    def _images(self, views: list, Js: list):
+        views, Js = list(views), list(Js)
+        if len(views) != len(Js):
+            raise ValueError(f'Mosaic: {len(views)} views but {len(Js)} restored images')
+        if not 1 <= len(views) <= MAX_VIEWS:
+            raise ValueError(f'Mosaic: {len(views)} images in one call, need 1..{MAX_VIEWS}')
+        arr = (_lib.MosaicImage * len(views))()
+        keep = []
+        for e, v, J in zip(arr, views, Js):
+            H, W = v.depth.shape
+            if v.rgb.dtype != torch.uint8:
+                raise ValueError(f'Mosaic: {v.name or "a view"} has {v.rgb.dtype} colours; the raw mosaic takes uint8')
+            if v.depth.device != self.device or J.device != self.device or J.dtype != torch.float32 or tuple(J.shape) != (H, W, 3):
+                raise ValueError(f'Mosaic: the restored image of {v.name or "a view"} must be float32 {(H, W, 3)} on {self.device}, '
+                                 f'not {J.dtype} {tuple(J.shape)} on {J.device}')
+            s = v.to_struct()   # (checks shapes and dtypes; Kinv derived the way the reference derives it, cached)
+            J = J.contiguous()
+            keep.append(J)
+            e.depth, e.rgb, e.J, e.H, e.W = v.depth.data_ptr(), v.rgb.data_ptr(), J.data_ptr(), H, W
+            e.Kinv, e.R, e.t = s.Kinv, s.R, s.t
+        # (the table, like `keep`: torch's caching allocator keeps a freed block for this stream until the launches queued here
+        # have run)
+        table = torch.empty(_lib.load().sucre_mosaic_table_bytes(len(views)), dtype=torch.uint8, device=self.device)
+        return arr, len(views), table, keep
+
+    def add_bounds(self, views: list, Js: list) -> None:
+        arr, n, table, _ = self._images(views, Js)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().sucre_mosaic_bounds(C.c_void_p(table.data_ptr()), n, arr, self._axes_c,
+                                                       C.c_void_p(self.bounds_words.data_ptr()), _stream_ptr()))
+
+    def bounds(self):
+        """``(lo_s, lo_t, hi_s, hi_t)`` float32 of what ``add_bounds`` has seen (waits for it), or None when no pixel took part."""
+        k = self.bounds_words.cpu().numpy().view(np.uint32)
+        if k[0] == 0xffffffff:
+            return None
+        bits = np.where(k & 0x80000000, k & 0x7fffffff, ~k).astype(np.uint32)   # key_value of csrc/order_key.h
+        return tuple(bits.view(np.float32).tolist())
+
+    def begin(self, bounds=None):
+        if bounds is None:
+            bounds = self.bounds()
+            if bounds is None:
+                raise ValueError('Mosaic.begin: no pixel takes part (no valid depth with a restored colour), so there are no bounds')
+        lo_s, lo_t, hi_s, hi_t = (np.float32(x) for x in bounds)
+        if not all(np.isfinite(x) for x in (lo_s, lo_t, hi_s, hi_t)) or hi_s < lo_s or hi_t < lo_t:
+            raise ValueError(f'Mosaic.begin: bounds {tuple(float(x) for x in (lo_s, lo_t, hi_s, hi_t))} are not finite and ordered')
+        Wm, Hm = mosaic_cells(lo_s, hi_s, self.gsd), mosaic_cells(lo_t, hi_t, self.gsd)
+        limit = mosaic_max_cells()
+        if Wm * Hm > limit or max(Wm, Hm) > 1 << 24:   # before anything is allocated
+            raise ValueError(f'mosaic of {Wm} x {Hm} cells of {float(self.gsd):.6g} m: more than the {limit} cells allowed '
+                             f'(SUCRE_MOSAIC_MAX_CELLS); give a coarser grid with --mosaic-gsd')
+        self.Hm, self.Wm, self.lo, self.hi = Hm, Wm, (lo_s, lo_t), (hi_s, hi_t)
+        g = _lib.MosaicGrid()
+        g.axes, g.gsd, g.lo_s, g.lo_t, g.Hm, g.Wm = self._axes_c, float(self.gsd), float(lo_s), float(lo_t), Hm, Wm
+        self.grid = g
+        dev = self.device
+        self.key = torch.full((Hm * Wm,), -1, dtype=torch.int64, device=dev)    # all ones: empty
+        self.pix = torch.full((Hm * Wm,), -1, dtype=torch.int32, device=dev)
+        nan = float('nan')
+        self._out = {'J': torch.full((Hm, Wm, 3), nan, dtype=torch.float32, device=dev),
+                     'raw': torch.zeros((Hm, Wm, 3), dtype=torch.uint8, device=dev),
+                     'source': torch.full((Hm, Wm), -1, dtype=torch.int32, device=dev),
+                     'pixel': torch.full((Hm, Wm), -1, dtype=torch.int32, device=dev),
+                     'range': torch.full((Hm, Wm), nan, dtype=torch.float32, device=dev)}
+        return Hm, Wm
+
+    def _begun(self, what: str) -> None:
+        if self.grid is None:
+            raise ValueError(f'Mosaic.{what}: begin() comes first (it fixes the grid)')
+
+    def splat(self, views: list, Js: list, first_ordinal: int, plain_atomic: bool = False) -> None:
+        self._begun('splat')
+        arr, n, table, _ = self._images(views, Js)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().sucre_mosaic_splat(C.c_void_p(table.data_ptr()), n, arr, int(first_ordinal), C.byref(self.grid),
+                                                      C.c_void_p(self.key.data_ptr()), _lib.MOSAIC_PLAIN_ATOMIC if plain_atomic else 0,
+                                                      _stream_ptr()))
+
+    def resolve(self, views: list, Js: list, first_ordinal: int) -> None:
+        self._begun('resolve')
+        arr, n, table, _ = self._images(views, Js)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().sucre_mosaic_resolve(C.c_void_p(table.data_ptr()), n, arr, int(first_ordinal), C.byref(self.grid),
+                                                        C.c_void_p(self.key.data_ptr()), C.c_void_p(self.pix.data_ptr()), _stream_ptr()))
+
+    def gather(self, views: list, Js: list, first_ordinal: int) -> None:
+        self._begun('gather')
+        arr, n, table, _ = self._images(views, Js)
+        o = self._out
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().sucre_mosaic_gather(C.c_void_p(table.data_ptr()), n, arr, int(first_ordinal), C.byref(self.grid),
+                                                       C.c_void_p(self.key.data_ptr()), C.c_void_p(self.pix.data_ptr()),
+                                                       C.c_void_p(o['J'].data_ptr()), C.c_void_p(o['raw'].data_ptr()),
+                                                       C.c_void_p(o['source'].data_ptr()), C.c_void_p(o['pixel'].data_ptr()),
+                                                       C.c_void_p(o['range'].data_ptr()), _stream_ptr()))
+
+    def result(self) -> dict:
+        """``J`` (Hm,Wm,3) float32 (NaN: empty), ``raw`` (Hm,Wm,3) uint8 (0), ``source`` and ``pixel`` (Hm,Wm) int32 (-1), ``range``
+        (Hm,Wm) float32 (NaN), on the device, complete once ``gather`` has seen every image."""
+        self._begun('result')
+        return dict(self._out)
+
+
+def mosaic_of(views: list, Js: list, axes, gsd, bounds=None, batch: int = 32, plain_atomic: bool = False) -> 'Mosaic':
+    """All four phases over device-resident ``views`` / ``Js`` (ordinal = position in the list), ``batch`` images per call."""
+    views, Js = list(views), list(Js)
+    if not views:
+        raise ValueError('mosaic_of: no view')
+    if len(views) > MAX_VIEWS:
+        raise ValueError(f'mosaic_of: {len(views)} images, at most {MAX_VIEWS}')
+    m = Mosaic(axes, gsd, views[0].depth.device)
+    chunks = [(i, views[i:i + batch], Js[i:i + batch]) for i in range(0, len(views), batch)]
+    if bounds is None:
+        for _, v, J in chunks:
+            m.add_bounds(v, J)
+    m.begin(bounds)
+    for i, v, J in chunks:
+        m.splat(v, J, i, plain_atomic=plain_atomic)
+    for i, v, J in chunks:
+        m.resolve(v, J, i)
+    for i, v, J in chunks:
+        m.gather(v, J, i)
+    return m
+
+
 def device_views_from_scene(scene, device='cuda') -> list[DeviceView]:
     """Uploads a synthetic scene (sucre_amd.synth) the way the loaders would: float32 depth, uint8 colour."""
     out = []

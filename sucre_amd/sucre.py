@@ -163,16 +163,7 @@ class SUCRe(torch.nn.Module):
         very numbers ``np.percentile`` returns for the whole array.  After the clip the minimum is the lower
         percentile itself and the maximum of the shifted values the float32 difference of the two, so what remains is
         one elementwise pass of IEEE-exact operations (``sucre_plot_stretch``): the same bits as the host path."""
-        from . import engine
-        J = self.J.detach().contiguous()
-        n = engine.count_valid(J)
-        if n == 0:
-            return torch.zeros(J.shape, dtype=torch.uint8, device=J.device)   # (numpy raises on an empty percentile)
-        plan = [percentile_plan(n, q) for q in (1, 99)]
-        stats = engine.select_ranks(J, [plan[0][0], plan[0][1], plan[1][0], plan[1][1]]).cpu().numpy()   # (3, 4)
-        lo = np.array([percentile_lerp(stats[c, 0], stats[c, 1], plan[0][2]) for c in range(3)], np.float32)
-        hi = np.array([percentile_lerp(stats[c, 2], stats[c, 3], plan[1][2]) for c in range(3)], np.float32)
-        return engine.plot_stretch(J, lo, hi)
+        return _plot_J_on_device(self.J.detach().contiguous())
 
     @torch.no_grad()
     def plot_reconstruction(self) -> PILImage.Image:
@@ -210,6 +201,19 @@ class SUCRe(torch.nn.Module):
         _save_png(self.plot_reconstruction(), Path(save_dir) / f'{stem}_reconstruction{tag}.png')
         if self.light_model:
             _save_png(self.plot_l(), Path(save_dir) / f'{stem}_vignetting{tag}.png')
+
+
+def _plot_J_on_device(J: Tensor) -> Tensor:
+    """``SUCRe._plot_J_device`` of any (H,W,3) float32 contiguous device image (a restored image, a mosaic of them)."""
+    from . import engine
+    n = engine.count_valid(J)
+    if n == 0:
+        return torch.zeros(J.shape, dtype=torch.uint8, device=J.device)   # (numpy raises on an empty percentile)
+    plan = [percentile_plan(n, q) for q in (1, 99)]
+    stats = engine.select_ranks(J, [plan[0][0], plan[0][1], plan[1][0], plan[1][1]]).cpu().numpy()   # (3, 4)
+    lo = np.array([percentile_lerp(stats[c, 0], stats[c, 1], plan[0][2]) for c in range(3)], np.float32)
+    hi = np.array([percentile_lerp(stats[c, 2], stats[c, 3], plan[1][2]) for c in range(3)], np.float32)
+    return engine.plot_stretch(J, lo, hi)
 
 
 def _save_png(img: PILImage.Image, path: Path) -> None:
@@ -1186,9 +1190,9 @@ def _consistency_file(results_dir: Path, image) -> Path:
     return (Path(results_dir) / image.name).with_suffix('.pt')   # sucre.py:213-215
 
 
-def _read_restored(path: Path, image, lazy: bool = False) -> Tensor:
+def _read_restored(path: Path, image, lazy: bool = False, flag: str = '--check-consistency') -> Tensor:
     """``J`` of a result file, checked against the image's camera.  ``lazy``: only the shape is wanted -- the file is mapped, not
-    read, where torch can (a zip archive, what torch.save writes)."""
+    read, where torch can (a zip archive, what torch.save writes).  ``flag``: the mode that asks, named in the refusals."""
     try:
         try:
             data = torch.load(path, map_location='cpu', mmap=True) if lazy else torch.load(path, map_location='cpu')
@@ -1198,10 +1202,10 @@ def _read_restored(path: Path, image, lazy: bool = False) -> Tensor:
             data = torch.load(path, map_location='cpu')
         J = data['J']
     except Exception as e:
-        raise SystemExit(f'--check-consistency: cannot read J from {path}: {e}')
+        raise SystemExit(f'{flag}: cannot read J from {path}: {e}')
     want = (int(image.camera.height), int(image.camera.width), 3)
     if not torch.is_tensor(J) or tuple(J.shape) != want:
-        raise SystemExit(f'--check-consistency: J of {path} has shape {tuple(J.shape) if torch.is_tensor(J) else type(J).__name__}, '
+        raise SystemExit(f'{flag}: J of {path} has shape {tuple(J.shape) if torch.is_tensor(J) else type(J).__name__}, '
                          f'but the camera of {image.name} is {want[1]}x{want[0]}: (H, W, 3) = {want} expected')
     return J
 
@@ -1219,8 +1223,8 @@ class _RestoredCache:
     """The restored images on the device, least recently used dropped first once ``budget`` bytes are exceeded; the images
     named in ``pinned`` (the current target and its neighbours) are never dropped."""
 
-    def __init__(self, results_dir: Path, device, budget: int):
-        self.results_dir, self.device, self.budget = Path(results_dir), device, int(budget)
+    def __init__(self, results_dir: Path, device, budget: int, flag: str = '--check-consistency'):
+        self.results_dir, self.device, self.budget, self.flag = Path(results_dir), device, int(budget), flag
         self.entries: 'collections.OrderedDict[str, Tensor]' = collections.OrderedDict()
         self.total = 0
 
@@ -1238,7 +1242,8 @@ class _RestoredCache:
             if self.total + need <= self.budget:
                 break
             self.total -= self.entries.pop(name).numel() * 4
-        J = _read_restored(_consistency_file(self.results_dir, image), image).to(torch.float32).contiguous().to(self.device)
+        named = {} if self.flag == '--check-consistency' else {'flag': self.flag}
+        J = _read_restored(_consistency_file(self.results_dir, image), image, **named).to(torch.float32).contiguous().to(self.device)
         self.entries[image.name] = J
         self.total += need
         return J
@@ -1338,6 +1343,184 @@ def check_consistency(images: list, colmap_model: sfm.COLMAPModel, results_dir: 
     return merged
 
 
+# ---- --mosaic: one georeferenced picture of the seabed from the restored images ---------------------------------------------
+
+MOSAIC_IMAGES_PER_CALL = 32   # images per phase call: one launch each (csrc/mosaic.h)
+
+
+def _rotation_of(image) -> np.ndarray:
+    R = image.pose.R if hasattr(image, 'pose') else image.R
+    return np.asarray(R.detach().cpu().numpy() if torch.is_tensor(R) else R, np.float64).reshape(3, 3)
+
+
+def mosaic_axes(images: list) -> Tensor:
+    """The default frame of a mosaic, (3,3) float32 with rows e1, e2, e3, from the world-from-camera rotations of ``images``
+    (``sfm.Image`` objects, or anything with ``R``): e3 is the normalised mean of the cameras' optical axes ``R[:, 2]`` -- the
+    mosaic looks the way the cameras look --, e1 the first image's ``R[:, 0]`` with its e3 component removed, normalised
+    (``R[:, 1]`` instead, when less than 1e-6 of it remains), e2 = e3 x e1.  Computed in float64, rounded once."""
+    Rs = [_rotation_of(im) for im in images]
+    if not Rs:
+        raise ValueError('mosaic_axes: no image')
+    mean = np.sum([R[:, 2] for R in Rs], axis=0) / len(Rs)
+    length = np.linalg.norm(mean)
+    if not length > 1e-6:
+        raise ValueError('mosaic_axes: the cameras\' optical axes cancel out; give the axes')
+    e3 = mean / length
+    for column in (0, 1):
+        e1 = Rs[0][:, column] - np.dot(Rs[0][:, column], e3) * e3
+        if np.linalg.norm(e1) >= 1e-6:
+            break
+    e1 = e1 / np.linalg.norm(e1)
+    e2 = np.cross(e3, e1)
+    return torch.from_numpy(np.stack([e1, e2, e3]).astype(np.float32))
+
+
+def mosaic_default_gsd(depths: list, fxs: list) -> np.float32:
+    """``float32(2 median_i(median(valid depths of image i) / fx_i))`` in float64: twice the footprint of a typical pixel, so
+    that a typical cell is hit by a few pixels of every image that sees it.  ``depths``: the decoded depth maps (tensors or
+    arrays, <= 0: invalid); images without a valid depth are left out."""
+    per_image = []
+    for d, fx in zip(depths, fxs):
+        d = np.asarray(d.detach().cpu().numpy() if torch.is_tensor(d) else d, np.float64)
+        d = d[d > 0]
+        if d.size:
+            per_image.append(np.median(d) / float(fx))
+    if not per_image:
+        raise ValueError('mosaic_default_gsd: no image has a valid depth')
+    return np.float32(2.0 * np.median(np.asarray(per_image, np.float64)))
+
+
+def mosaic_source_picture(source: np.ndarray) -> np.ndarray:
+    """(Hm,Wm,3) uint8: every ordinal hashed to a colour of its own (channels in 64..255), empty cells black."""
+    source = np.asarray(source)
+    h = ((source.astype(np.int64) + 1) * 2654435761) & 0xffffffff
+    h ^= h >> 15
+    out = np.stack([64 + ((h >> s) & 0xff) * 191 // 255 for s in (0, 8, 16)], axis=-1).astype(np.uint8)
+    out[source < 0] = 0
+    return out
+
+
+def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, output_dir: Path, gsd: float | None = None, axes=None,
+           stretch=None, device: str = 'cuda') -> dict:
+    """One picture of the seabed from a finished restoration: every pixel of ``images`` (``sfm.Image`` objects or names of
+    ``colmap_model``; at most ``engine.MAX_VIEWS``, ordinal = position) with a valid depth and a restored colour --
+    ``results_dir / <name>.pt``, key ``J`` -- is dropped onto the plane grid ``axes`` (``mosaic_axes`` unless given) of ``gsd``
+    metres per cell (``mosaic_default_gsd`` unless given; printed), and the pixel seen through the least water wins its cell
+    (``engine.Mosaic``; csrc/mosaic.h).  No blending, no hole filling.  Every file is checked before any image is decoded.  The
+    restored images stay on the device across the four phases within ``consistency_cache_budget`` and are read again per phase
+    otherwise: the same bits either way.  Writes ``mosaic.png`` (``plot_J``'s stretch over the filled cells, or the fixed
+    ``stretch``), ``mosaic_raw.png``, ``mosaic_source.png`` (``mosaic_source_picture``) and ``mosaic.pt`` (``J, raw, source, pixel,
+    range, axes, gsd, lo, images, n_filled, per_image``), prints one line and returns the dictionary of ``mosaic.pt``."""
+    from . import engine
+    sfm.require_gpu(device, 'mosaic')
+    images = [colmap_model[im] if isinstance(im, str) else im for im in images]
+    if not images:
+        raise SystemExit('--mosaic: no image in the request')
+    if len(images) > engine.MAX_VIEWS:
+        raise SystemExit(f'--mosaic: {len(images)} images in the request, at most {engine.MAX_VIEWS} go into one mosaic')
+    if stretch is not None:
+        stretch = check_stretch(stretch)
+    results_dir, output_dir = Path(results_dir), Path(output_dir)
+    for image in images:   # before anything is decoded
+        path = _consistency_file(results_dir, image)
+        if not path.is_file():
+            raise SystemExit(f'--mosaic: {path} is missing: {image.name} has no restored image in {results_dir}')
+    for image in images:
+        _read_restored(_consistency_file(results_dir, image), image, lazy=True, flag='--mosaic')
+    output_dir.mkdir(parents=True, exist_ok=True)
+    axes = mosaic_axes(images) if axes is None else torch.as_tensor(axes, dtype=torch.float32).reshape(3, 3)
+    cache = _RestoredCache(results_dir, device, consistency_cache_budget(device), flag='--mosaic')
+    batches = []   # (ordinal of the first image, images): consecutive images, at most 32, whose restored images fit the cache together
+    for i, image in enumerate(images):
+        if batches and len(batches[-1][1]) < MOSAIC_IMAGES_PER_CALL \
+                and sum(cache.nbytes(im) for im in batches[-1][1]) + cache.nbytes(image) <= cache.budget:
+            batches[-1][1].append(image)
+        else:
+            batches.append((i, [image]))
+    loader.prefetch_device_views(batches[0][1], device, background=True)
+
+    def resident(batch):
+        pinned = {im.name for im in batch}
+        return [im.device_view(device) for im in batch], [cache.get(im, pinned) for im in batch]
+
+    with torch.cuda.device(device):
+        if gsd is None:
+            depths = [im.device_view(device).depth for im in images]
+            gsd = mosaic_default_gsd(depths, [float(im.camera.K[0, 0]) for im in images])
+            del depths
+            print(f'--mosaic: ground sample distance {float(gsd):.6g} m (twice the median pixel footprint; --mosaic-gsd sets it).')
+        m = engine.Mosaic(axes, gsd, device)
+        for _, batch in batches:
+            m.add_bounds(*resident(batch))
+        try:
+            Hm, Wm = m.begin()
+        except ValueError as e:
+            raise SystemExit(f'--mosaic: {e}')
+        for phase in (m.splat, m.resolve, m.gather):
+            for first, batch in batches:
+                phase(*resident(batch), first)
+        out = m.result()
+        picture = engine.plot_stretch(out['J'], *stretch) if stretch is not None else None
+        if picture is None:
+            picture = _plot_J_on_device(out['J']) if _NUMPY_2 else None
+        out = {k: v.cpu() for k, v in out.items()}
+        picture = None if picture is None else picture.cpu().numpy()
+    if picture is None:   # numpy 1.x: np.percentile itself, as plot_J does there
+        J = out['J'].numpy().copy()
+        ok = ~np.isnan(J).any(axis=2)
+        vals = J[ok]
+        lo, hi = np.percentile(vals, 1, axis=0), np.percentile(vals, 99, axis=0)
+        vals = np.clip(vals, lo, hi)
+        vals = vals - vals.min(axis=0)
+        vals = vals / vals.max(axis=0)
+        J[~ok] = 0.0
+        J[ok] = vals
+        picture = np.uint8(J * 255)
+    source = out['source']
+    filled = source >= 0
+    n_filled, n_cells = int(filled.sum()), Hm * Wm
+    per_image = torch.bincount(source[filled].to(torch.int64), minlength=len(images))
+    _save_png(PILImage.fromarray(picture), output_dir / 'mosaic.png')
+    _save_png(PILImage.fromarray(out['raw'].numpy()), output_dir / 'mosaic_raw.png')
+    _save_png(PILImage.fromarray(mosaic_source_picture(source.numpy())), output_dir / 'mosaic_source.png')
+    data = {**out, 'axes': m.axes.clone(), 'gsd': float(m.gsd), 'lo': torch.tensor([float(m.lo[0]), float(m.lo[1])], dtype=torch.float32),
+            'images': [im.name for im in images], 'n_filled': n_filled, 'per_image': per_image}
+    torch.save(data, output_dir / 'mosaic.pt')
+    top = int(per_image.argmax())
+    print(f'mosaic of {len(images)} images: {Wm} x {Hm} cells of {float(m.gsd):.6g} m, {n_filled} filled '
+          f'({100.0 * n_filled / n_cells:.1f} %), {n_cells - n_filled} empty; largest share {images[top].name} '
+          f'({100.0 * int(per_image[top]) / max(1, n_filled):.1f} %)')
+    return data
+
+
+def _refuse_mosaic_flags(args, world: int = 1) -> None:
+    """What --mosaic does not combine with, refused before any file is opened."""
+    refused = [('--shared-water', bool(getattr(args, 'shared_water', False)), 'nothing is fitted, so nothing is shared'),
+               ('--apply-water', getattr(args, 'apply_water', None) is not None, 'restore first, into the directory to mosaic, then mosaic it'),
+               ('--check-consistency', getattr(args, 'check_consistency', None) is not None, 'check the directory in a run of its own'),
+               ('--trim-outliers', getattr(args, 'trim_outliers', None) is not None or getattr(args, 'trim_rounds', None) is not None,
+                'there is no fit to trim'),
+               ('--view-gains', bool(getattr(args, 'view_gains', False)) or getattr(args, 'gain_rounds', None) is not None
+                or getattr(args, 'gain_limit', None) is not None, 'there is no fit to estimate gains from'),
+               ('--save-quality', bool(getattr(args, 'save_quality', False)), 'there is no fit, hence no residuals'),
+               ('--save-interval', args.save_interval is not None, 'there are no iterations to snapshot'),
+               ('--params-path', args.params_path is not None, 'no parameters are read: the restored images are'),
+               ('--keep-matches', bool(args.keep_matches), 'nothing is matched'),
+               ('--common-stretch', bool(getattr(args, 'common_stretch', False)),
+                'the mosaic is one picture: it is stretched by its own percentiles, or by --stretch-from'),
+               ('--image-scale', args.image_scale != 1, 'resized images have float32 colours, and the raw mosaic takes uint8')]
+    for flag, given, why in refused:
+        if given:
+            raise SystemExit(f'--mosaic: {flag} does not combine with it ({why}); drop one of the two flags')
+    gsd = getattr(args, 'mosaic_gsd', None)
+    if gsd is not None and not (np.isfinite(gsd) and gsd > 0):
+        raise SystemExit(f'--mosaic-gsd: G must be a finite size > 0 in metres, not {gsd}')
+    if world > 1:
+        raise SystemExit(f'--mosaic: a world size of {world} is not supported yet: the four phases are separate entries of the library '
+                         f'so that ranks can all-reduce bounds, keys and pixel words between them, but that all-reduce is not built; '
+                         f'run one process')
+
+
 def _refuse_consistency_flags(args) -> None:
     """What --check-consistency does not combine with, refused before any file is opened."""
     refused = [('--shared-water', bool(getattr(args, 'shared_water', False)), 'nothing is fitted, so nothing is shared'),
@@ -1352,7 +1535,8 @@ def _refuse_consistency_flags(args) -> None:
                ('--keep-matches', bool(args.keep_matches), 'no match list is kept: the pairs are compared where they are found'),
                ('--common-stretch', bool(getattr(args, 'common_stretch', False)), 'no picture of J is written'),
                ('--stretch-from', getattr(args, 'stretch_from', None) is not None, 'no picture of J is written'),
-               ('--image-scale', args.image_scale != 1, 'resized images have float32 colours, and the raw comparison reads uint8')]
+               ('--image-scale', args.image_scale != 1, 'resized images have float32 colours, and the raw comparison reads uint8'),
+               ('--mosaic', getattr(args, 'mosaic', None) is not None, 'make the mosaic in a run of its own')]
     for flag, given, why in refused:
         if given:
             raise SystemExit(f'--check-consistency: {flag} does not combine with it ({why}); drop one of the two flags')
@@ -1382,7 +1566,8 @@ def _refuse_apply_flags(args) -> None:
                ('--save-quality', bool(getattr(args, 'save_quality', False)), 'a single-view inversion has no residuals'),
                ('--save-interval', args.save_interval is not None, 'there are no iterations to snapshot'),
                ('--params-path', args.params_path is not None, 'the parameters come from the --apply-water file'),
-               ('--keep-matches', bool(args.keep_matches), 'nothing is matched')]
+               ('--keep-matches', bool(args.keep_matches), 'nothing is matched'),
+               ('--mosaic', getattr(args, 'mosaic', None) is not None, 'restore first, then make the mosaic of that directory')]
     for flag, given, why in refused:
         if given:
             raise SystemExit(f'--apply-water: {flag} does not combine with it ({why}); drop one of the two flags')
@@ -1394,6 +1579,11 @@ def parse_args(args: argparse.Namespace):
     shared = bool(getattr(args, 'shared_water', False))
     apply = getattr(args, 'apply_water', None)
     check = getattr(args, 'check_consistency', None)
+    mosaic_dir = getattr(args, 'mosaic', None)
+    if mosaic_dir is None and getattr(args, 'mosaic_gsd', None) is not None:
+        raise SystemExit('--mosaic-gsd: only with --mosaic DIR')
+    if mosaic_dir is not None:
+        _refuse_mosaic_flags(args, world)
     if check is not None:
         _refuse_consistency_flags(args)
     _refuse_stretch_flags(args)
@@ -1450,6 +1640,11 @@ def parse_args(args: argparse.Namespace):
         survey = False
         print(f'--check-consistency: the restored images of {check} are compared where they see the same seabed; nothing is fitted, '
               f'so --num-iter, --learning-rate, --batch-size, --use-closed-form, --light-model and --force-compute-matches are ignored.')
+    if mosaic_dir is not None:
+        survey = False
+        print(f'--mosaic: the restored images of {mosaic_dir} are dropped onto one grid; nothing is fitted or matched, so --num-iter, '
+              f'--learning-rate, --batch-size, --use-closed-form, --light-model, --min-cover, --filter-images-path and '
+              f'--force-compute-matches are ignored.')
     if survey:
         # image files are decoded and the result pictures encoded by child processes (_pixelio.WorkerPool: CPU work in
         # the process that drives the GPU slows its launches down, and PIL's decoder does not scale over threads);
@@ -1466,7 +1661,9 @@ def parse_args(args: argparse.Namespace):
     if host_threads > 0:
         torch.set_num_threads(host_threads)
     try:
-        if check is not None:
+        if mosaic_dir is not None:
+            mosaic(images, colmap_model, mosaic_dir, args.output_dir, gsd=getattr(args, 'mosaic_gsd', None), stretch=stretch, device=device)
+        elif check is not None:
             if world > 1:   # the targets' records are gathered on rank 0
                 sdist.init_process_group()
             check_consistency(images, colmap_model, check, args.output_dir, image_list=image_list, min_cover=args.min_cover,
@@ -1707,6 +1904,13 @@ def build_parser() -> argparse.ArgumentParser:
                                'reference write them) with the restored J of the other images on the pixels their depth maps match, '
                                'and the raw pictures likewise; writes <stem>_consistency.pt and <stem>_consistency.png per image and '
                                'consistency.pt, and prints the RMS colour difference of both')
+    p.extras.add_argument('--mosaic', type=Path, metavar='DIR', default=argparse.SUPPRESS,
+                          help='do not fit: drop every pixel of the images of the request that has a valid depth and a restored colour '
+                               '(DIR/<name>.pt, as this tool and the reference write them) onto one plane grid that looks the way the '
+                               'cameras look; the pixel seen through the least water wins its cell, nothing is blended and no hole is '
+                               'filled; writes mosaic.png, mosaic_raw.png, mosaic_source.png and mosaic.pt and prints the size and the cover')
+    p.extras.add_argument('--mosaic-gsd', type=float, metavar='G', default=argparse.SUPPRESS,
+                          help='with --mosaic: metres per cell (twice the median pixel footprint of the images unless given)')
     p.extras.add_argument('--common-stretch', action='store_true', default=argparse.SUPPRESS,
                           help='with --shared-water or --apply-water: stretch every <stem>_rgb.png between the SAME per-channel 1st '
                                'and 99th percentile, those of the valid pixels of all images of the request pooled (all ranks), '
