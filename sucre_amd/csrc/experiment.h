@@ -92,6 +92,19 @@ constexpr bool kScaledBBuilt = SUCRE_SCALED_B != 0;
 #endif
 constexpr bool kPairedBuilt = SUCRE_PAIRED_J != 0;
 
+// fit.hip: the terms behind a full chunk's exponentials in the J-parameter kernels carry three s_nop per observation-channel --
+// behind Ihat, behind r, behind the last accumulation (1, the product: grad_terms' kYield; same operations in the same order on
+// every value, so the same bits) -- or none, the form until round 12 (0: make VARIANT=unstaged EXTRA=-DSUCRE_STAGED_TERMS=0 gives
+// the parent's instruction sequences, tools/isa_digest.py).  The knob is named after the design it was opened for, the chains of a
+// chunk issued stage by stage: built and measured in the probe and in the kernels, that form gains exactly what the s_nops gain
+// which the compiler places behind its stages (profiles/r13_staged_terms_probe.txt, r13_staged_terms_ab.txt), at 50 more lines
+// and 6 more registers; the s_nops alone were kept.
+// (tests/test_staged_host.py builds the 0 form, so that it cannot rot.)
+#if !defined(SUCRE_STAGED_TERMS)
+#define SUCRE_STAGED_TERMS 1
+#endif
+constexpr bool kStagedTerms = SUCRE_STAGED_TERMS != 0;
+
 // fit.hip, timing only: every wave of a J-parameter launch records when it entered and left its strips (100 MHz wall clock) --
 // how much of a launch is its ragged end (tools/exp/wave_times.py).
 #ifdef SUCRE_EXP_WAVE_TIMES

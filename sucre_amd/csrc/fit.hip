@@ -114,24 +114,36 @@ __device__ __forceinline__ void chunk_exps(const float (&zz)[kGroupLv], const Wa
 // kScaledB: the backscatter term B (1 - g) in ONE instruction, bo = fma(-B, g, B) (one rounding instead of two), and acc.sB takes
 // r bo: B sum r (1 - g), which the launch's finisher divides by B (unscale_sum).  Otherwise the form until round 10, 1 - g on its
 // own: one instruction more, and legal for every B (fit_math.h scaled_b_ok picks per launch).
-template <bool kScaledB>
+// kYield (full chunks only; experiment.h SUCRE_STAGED_TERMS): an s_nop behind Ihat, behind r and behind the last accumulation.
+// Short of registers the compiler emits this function depth first, every instruction directly behind the one it waits for, and
+// the SIMD issues its oldest wave first; an s_nop -- no vector instruction, no register -- seems to hand the issue slot to a wave
+// that is ready (a supposition: what is measured is the time).  tools/probes/chunk_probe.hip: 9.5 % fewer cycles per chunk at five waves
+// per SIMD; issuing the chains stage by stage, three to twelve at a time, gains what the s_nops gain that the compiler puts
+// behind its stages, and nothing without them (profiles/r13_staged_terms_probe.txt).  The empty-looking "+v" ties each s_nop to
+// the value it stands behind, so that no scheduler moves it; every value keeps its operations and their order.
+template <bool kScaledB, bool kYield = false>
 __device__ __forceinline__ void grad_terms(float z, float a, float g, uint32_t k, bool valid, float Bc, float Jc, int c, Acc &acc) {
     const float omg = kScaledB ? __builtin_fmaf(-Bc, g, Bc) : 1.0f - g;   // scaled: bo = B (1 - g)
-    const float Ihat = __builtin_fmaf(Jc, a, kScaledB ? omg : Bc * omg);
+    float Ihat = __builtin_fmaf(Jc, a, kScaledB ? omg : Bc * omg);
+    if (kYield) asm volatile("s_nop 0" : "+v"(Ihat));
     // I = k/255 folded into the residual: one rounding instead of two, two VALU ops fewer
     float r = __builtin_fmaf((float)k, kInv255, -Ihat);
     r = valid ? r : 0.0f;  // select, not multiply: J may be NaN where unobserved
+    if (kYield) asm volatile("s_nop 0" : "+v"(r));
     const float rz = r * z;
     acc.cost = __builtin_fmaf(r, r, acc.cost);
     acc.pa[c] = __builtin_fmaf(r, a, acc.pa[c]);
     acc.pb[c] = __builtin_fmaf(rz, a, acc.pb[c]);
     acc.sB[c] = __builtin_fmaf(r, omg, acc.sB[c]);
     acc.sGZ[c] = __builtin_fmaf(rz, g, acc.sGZ[c]);
+    if (kYield) asm volatile("s_nop 0" : "+v"(acc.sGZ[c]));
 }
 
 // kMasked = false: every level of the chunk is a real observation of every pixel of the strip (chunks wholly below
 // the strip's smallest pixel count), so the z > 0 test and the selects are compiled out.
-template <bool kMasked, bool kScaledB>
+// kYield: grad_terms with its yields (experiment.h SUCRE_STAGED_TERMS) -- every J-parameter kernel but batch_iter_kernel, whose
+// launches gain nothing from them (config 1, profiles/r13_staged_terms_ab.txt) and keep the text they had.
+template <bool kMasked, bool kScaledB, bool kYield = kStagedTerms>
 __device__ __forceinline__ void accumulate_chunk(const float (&zz)[kGroupLv], const uint32_t (&cc)[3], const Water &w,
                                                  const float (&J)[3], Acc &acc) {
     if (kExpNoCompute) {  // ablation build only (experiment.h): touch the data, skip the model
@@ -145,7 +157,7 @@ __device__ __forceinline__ void accumulate_chunk(const float (&zz)[kGroupLv], co
         const float z = zz[j];
         const bool valid = !kMasked || z > 0.0f;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) grad_terms<kScaledB>(z, e.a[j][c], e.g[j][c], (cc[c] >> (8 * j)) & 255u, valid, w.B[c], J[c], c, acc);
+        for (int c = 0; c < 3; ++c) grad_terms<kScaledB, kYield>(z, e.a[j][c], e.g[j][c], (cc[c] >> (8 * j)) & 255u, valid, w.B[c], J[c], c, acc);
     }
 }
 
@@ -789,8 +801,9 @@ __device__ __forceinline__ void grad_pass(FitLds &lds, const PlanItem *__restric
             float zz[kGroupLv];
             uint32_t cc[3];
             read_chunk<kFmt>(sp, lane, zz, cc, rc, masked);
-            if (masked) accumulate_chunk<true, kScaledB>(zz, cc, w, J, acc);
-            else accumulate_chunk<false, kScaledB>(zz, cc, w, J, acc);
+            constexpr bool kYield = kStagedTerms && !Chain::kOn;   // (not in a batch launch: accumulate_chunk)
+            if (masked) accumulate_chunk<true, kScaledB, kYield>(zz, cc, w, J, acc);
+            else accumulate_chunk<false, kScaledB, kYield>(zz, cc, w, J, acc);
         },
         [&](const uint8_t *sp, uint32_t r) {  // the strip's short last chunk
             for (uint32_t j = 0; j < r; ++j) {
