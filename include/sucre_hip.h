@@ -627,8 +627,30 @@ int sucre_view_consistency(int H, int W, int n_views, const sucre_view_t *target
  * untouched until the call's launches have run.  Checked before any launch (SUCRE_ERR_ARG): a NULL or misaligned pointer,
  * n_images or first_ordinal + n_images outside 1..4096, an image size outside 1..32767, gsd or a bound that is not finite, gsd <= 0,
  * Hm or Wm outside 1..2^24, unknown flags.
+ *
+ * The blend: a range-weighted mean of all the pixels of a cell, next to the best-view outputs, summed in FIXED POINT so that
+ * the result has the same bits in any order of arrival and any split into calls.  Once sucre_mosaic_splat has seen every image,
+ * key_dev[cell] >> 32 holds the bits of zmin, the cell's smallest range.  For every pixel that takes part and has a cell, with
+ * range z, in float32, one IEEE operation per step, inv_h = 1 / H for a blend depth of H metres:
+ *   d = z - zmin;  t = max(1 - d inv_h, 0) (product rounded, then the difference);  wq = (int)rintf((t t) 4096), 0..4096, 4096
+ *   for the winner and its ties;  Jq_c = (int64)rintf(min(max(J_c, -1024), 1024) 1048576), |Jq_c| <= 2^30 (infinities clamped)
+ *   sucre_mosaic_accumulate  a pixel with wq > 0 adds to the SUCRE_MOSAIC_ACC_WORDS = 8 int64 words of its cell, cell-major
+ *                         (acc_dev[8 cell + k]; Hm Wm 64 bytes, 8-byte aligned, the caller starts every word at 0):
+ *                         k = 0..2: wq Jq_c;  k = 3..5: wq rgb_c (raw uint8);  k = 6: wq;  k = 7: 1, the sample count.
+ *                         64-bit integer atomic adds.  THE BOUND: with fewer than 2^20 samples in a cell every sum stays below
+ *                         2^62.  Word 7 counts on its own, so a cell that reached 2^20 samples is detected there (any count
+ *                         below 2^32): the caller checks samples_out after sucre_mosaic_normalize and discards the blend then.
+ *                         flags: SUCRE_MOSAIC_PLAIN_ATOMIC -- eight atomics per pixel instead of eight per run of adjacent
+ *                         pixels of a wave that share a cell (same words; for measurements)
+ *   sucre_mosaic_normalize   one pass over the cells, no image read; for a cell with word 7 > 0:
+ *                         J_out (Hm,Wm,3) float32 = (float)(((double)acc_c / (double)wsum) 2^-20), raw_out (Hm,Wm,3) uint8 =
+ *                         (2 racc_c + wsum) / (2 wsum) in integers, weight_out (Hm,Wm) float32 = (float)((double)wsum 2^-12),
+ *                         samples_out (Hm,Wm) int32 = the count (2^31 - 1 when above).  Empty cells are not touched: the caller
+ *                         fills the outputs first.  A filled cell has wsum >= 4096.
+ * Checked before any launch as above, and: inv_h not finite or <= 0, a NULL or misaligned acc_dev or output, Hm Wm above 2^39.
  */
 #define SUCRE_MOSAIC_PLAIN_ATOMIC 1u
+#define SUCRE_MOSAIC_ACC_WORDS 8
 typedef struct sucre_mosaic_image {
     const float *depth;   /* (H,W) float32 */
     const uint8_t *rgb;   /* (H,W,3) uint8 */
@@ -652,6 +674,11 @@ int sucre_mosaic_resolve(void *table_dev, int n_images, const sucre_mosaic_image
 int sucre_mosaic_gather(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
                         const sucre_mosaic_grid_t *grid, const uint64_t *key_dev, const uint32_t *pix_dev, float *J_out,
                         uint8_t *raw_out, int32_t *source_out, int32_t *pixel_out, float *range_out, void *stream);
+int sucre_mosaic_accumulate(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                            const sucre_mosaic_grid_t *grid, const uint64_t *key_dev, float inv_h, int64_t *acc_dev, unsigned flags,
+                            void *stream);
+int sucre_mosaic_normalize(const sucre_mosaic_grid_t *grid, const int64_t *acc_dev, float *J_out, uint8_t *raw_out, float *weight_out,
+                           int32_t *samples_out, void *stream);
 
 /*
  * Shared water AND light over several light-model images (the group above for the 19-parameter model; sucre.py:54-61 with

@@ -26,7 +26,9 @@ WS_VIEW_COUNT, WS_VIEW_KEEP, WS_N_OBS, WS_PARAMS, WS_SUMS, WS_N_OBS_TOTAL, WS_ST
 INVERT_LIGHT, INVERT_FLOAT_COLOUR = 1, 2
 INVERT_MAX_IMAGES = 4096   # kInvertMaxImages of csrc/invert.h: images per sucre_invert_images call
 CONSISTENCY_STATS = 26     # kConsistStats of csrc/consist.h: columns of a view's row of sucre_view_consistency's stats
-MOSAIC_PLAIN_ATOMIC = 1     # SUCRE_MOSAIC_PLAIN_ATOMIC: sucre_mosaic_splat without the load that filters its atomics
+MOSAIC_PLAIN_ATOMIC = 1     # SUCRE_MOSAIC_PLAIN_ATOMIC: sucre_mosaic_splat without the load that filters its atomics;
+#                             sucre_mosaic_accumulate with eight atomics per pixel instead of eight per run of a wave's lanes
+MOSAIC_ACC_WORDS = 8        # SUCRE_MOSAIC_ACC_WORDS: int64 words per cell of the blend's accumulator
 POOL_MAX_IMAGES = 4096    # kPoolMaxImages of csrc/pool.h: images per sucre_pool_select_pass call
 POOL_MAX_RANKS = 8
 POOL_HIST_WORDS = 3 * 8 * 256   # uint64 hist[3][8][256] at the head of the pooled select's state
@@ -161,6 +163,8 @@ SIGNATURES = {
     'sucre_mosaic_splat': (_i, [_vp, _i, C.POINTER(MosaicImage), _i, C.POINTER(MosaicGrid), _vp, C.c_uint, _vp]),
     'sucre_mosaic_resolve': (_i, [_vp, _i, C.POINTER(MosaicImage), _i, C.POINTER(MosaicGrid), _vp, _vp, _vp]),
     'sucre_mosaic_gather': (_i, [_vp, _i, C.POINTER(MosaicImage), _i, C.POINTER(MosaicGrid), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sucre_mosaic_accumulate': (_i, [_vp, _i, C.POINTER(MosaicImage), _i, C.POINTER(MosaicGrid), _vp, C.c_float, _vp, C.c_uint, _vp]),
+    'sucre_mosaic_normalize': (_i, [C.POINTER(MosaicGrid), _vp, _vp, _vp, _vp, _vp, _vp]),
     'sucre_light_group_bytes': (C.c_size_t, [_i]),
     'sucre_light_group_sums_offset': (C.c_int64, []),
     'sucre_light_group_init': (_i, [_vp, _i, C.POINTER(LightGroupImage), C.POINTER(C.c_float), _vp]),

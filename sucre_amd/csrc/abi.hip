@@ -991,6 +991,36 @@ int sucre_mosaic_gather(void *table_dev, int n_images, const sucre_mosaic_image_
                                    const_cast<uint32_t *>(pix_dev), out, static_cast<hipStream_t>(stream)), "sucre_mosaic_gather");
 }
 
+int sucre_mosaic_accumulate(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                            const sucre_mosaic_grid_t *grid, const uint64_t *key_dev, float inv_h, int64_t *acc_dev, unsigned flags,
+                            void *stream) {
+    if (int rc = check_mosaic_images(table_dev, n_images, images, first_ordinal)) return rc;
+    MosaicGrid g;
+    if (int rc = check_mosaic_grid(grid, &g)) return rc;
+    if (!key_dev || !aligned(key_dev, 8)) return fail(SUCRE_ERR_ARG, "key_dev is NULL or not 8-byte aligned");
+    if (!std::isfinite(inv_h) || !(inv_h > 0.0f)) return fail(SUCRE_ERR_ARG, "inv_h=%g must be finite and > 0", (double)inv_h);
+    if (!acc_dev || !aligned(acc_dev, 8)) return fail(SUCRE_ERR_ARG, "acc_dev is NULL or not 8-byte aligned");
+    if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
+    return check_hip(launch_mosaic_accumulate((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) != 0, table_dev, n_images, images, first_ordinal, g,
+                                              reinterpret_cast<const unsigned long long *>(key_dev), inv_h,
+                                              reinterpret_cast<unsigned long long *>(acc_dev), static_cast<hipStream_t>(stream)),
+                     "sucre_mosaic_accumulate");
+}
+
+int sucre_mosaic_normalize(const sucre_mosaic_grid_t *grid, const int64_t *acc_dev, float *J_out, uint8_t *raw_out, float *weight_out,
+                           int32_t *samples_out, void *stream) {
+    MosaicGrid g;
+    if (int rc = check_mosaic_grid(grid, &g)) return rc;
+    if ((uint64_t)g.Hm * (uint64_t)g.Wm > (1ull << 39)) return fail(SUCRE_ERR_ARG, "mosaic of %dx%d cells: one pass takes 2^39 cells", g.Wm, g.Hm);
+    if (!acc_dev || !aligned(acc_dev, 8)) return fail(SUCRE_ERR_ARG, "acc_dev is NULL or not 8-byte aligned");
+    if (!J_out || !raw_out || !weight_out || !samples_out) return fail(SUCRE_ERR_ARG, "J_out / raw_out / weight_out / samples_out is NULL");
+    if (!aligned(J_out, 4) || !aligned(weight_out, 4) || !aligned(samples_out, 4))
+        return fail(SUCRE_ERR_ARG, "J_out / weight_out / samples_out must be 4-byte aligned");
+    MosaicBlend out = {J_out, raw_out, weight_out, samples_out};
+    return check_hip(launch_mosaic_normalize(g, reinterpret_cast<const long long *>(acc_dev), out, static_cast<hipStream_t>(stream)),
+                     "sucre_mosaic_normalize");
+}
+
 /* ---- shared water and light over the light-model images of a rank (sucre.py:54-61, 124-157) ------------------------ */
 
 }  // extern "C"

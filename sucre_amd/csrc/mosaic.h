@@ -1,5 +1,6 @@
 // Seabed mosaic of restored images (sucre_mosaic_*): a best-view ortho splat.  Every pixel of every image is dropped onto a
-// plane grid; the pixel seen through the LEAST water wins its cell.  No blending, no hole filling, no float atomics.
+// plane grid; the pixel seen through the LEAST water wins its cell.  No hole filling, no float atomics: the optional blend
+// ("The blend" below) sums in fixed point.
 //
 // A pixel p = v W + u of image i (its ordinal: the position in the request) TAKES PART when d > 0 and J[p] holds no NaN in any
 // channel (plot_J's rule, sucre.py:86-87).  Then, all in float32 with explicit FMAs (the library is built with
@@ -31,6 +32,33 @@
 // 0.97 ms, splat 0.86 ms, resolve 0.59 ms, gather 0.61 ms, against 0.58-0.62 ms for invert_kernel on the same images.  The plain
 // 64-bit atomic min for every pixel: 2.77 ms (48 G atomics/s; 25 G/s at 1176 pixels per cell) -- the load ahead of it is kept.  The
 // bounds phase without ITS load: 12.0 ms (every workgroup's four atomics land on one cache line).
+//
+// The blend (sucre_mosaic_accumulate, sucre_mosaic_normalize): a range-weighted mean of ALL the pixels of a cell, next to the
+// best-view outputs.  A float sum would depend on the order of arrival; a sum of integers does not, so the weights and the
+// colours are quantised first and summed with 64-bit integer atomics: the same bits in any order and any batch split.
+// After the splat key[cell] >> 32 holds the bits of zmin, the cell's smallest range.  A pixel that takes part (mosaic_pixel)
+// and has a cell (mosaic_cell), with range z, float32, one IEEE operation per step (inv_h = 1 / H from the host, H the blend depth):
+//   d    = z - zmin                                >= 0; 0 for the winner and its ties
+//   t    = fmaxf(1 - d inv_h, 0)                   the product rounded, then the difference
+//   wq   = (int)rintf((t t) 4096)                  0 .. 4096; 4096 for the winner
+//   Jq_c = (int64)rintf(fminf(fmaxf(J_c, -1024), 1024) 1048576)     |Jq_c| <= 2^30; an infinity is clamped too
+// A pixel with wq == 0 adds nothing.  Every other one adds into its cell's eight int64 words (kMosaicAccWords; cell-major, 64
+// bytes per cell, so one sample's adds land in one 64-byte request):
+//   words 0..2  wq Jq_c     words 3..5  wq rgb_c (the raw uint8 colours)     word 6  wq     word 7  1, the sample count
+// with no-return, agent-scope, relaxed 64-bit atomic adds.  THE BOUND: with fewer than 2^20 samples in a cell every sum stays below
+// 2^20 x 2^12 x 2^30 = 2^62.  The count has a word of its own, so a cell that reaches 2^20 samples shows in word 7 whatever has
+// become of the other words; the caller checks the largest count after the normalise pass (engine.Mosaic.normalize).
+// Unless SUCRE_MOSAIC_PLAIN_ATOMIC is given, the lanes of a wave -- consecutive pixels of a row -- first sum over every run of
+// adjacent lanes with one cell (a segmented suffix sum by shuffles: 11 words, 6 steps) and the run's first lane issues the eight
+// atomics for the run; integer sums, so the words end up the same to the bit.
+// The normalise pass, one lane per cell, no atomics, reads no image; for a cell with word 7 > 0:
+//   J_blend_c = (float)(((double)acc_c / (double)wsum) 2^-20)     raw_blend_c = (uint8)((2 racc_c + wsum) / (2 wsum))
+//   weight = (float)((double)wsum 2^-12)                            samples = count (2^31 - 1 when above)
+// (int64 -> double: the compiler's conversion, correctly rounded, as numpy's astype is; IEEE double division.)  Empty cells are
+// not touched.  As H -> 0 the blend tends to the best-view mosaic quantised to 2^-20, as H -> infinity to the plain mean.
+// Measured on the shape above (profiles/mosaic_blend_time.txt; H = 0.5 m, 119 M samples): accumulate 23.8 ms with the run sums,
+// 47.7 ms with the plain atomics (7.5 against 58.2 ms at 1176 pixels per cell), against the splat's 0.87 ms in the same run -- a
+// sum can skip none of its atomics --; normalise 0.04 ms.
 #pragma once
 #include "launch.h"
 
@@ -66,6 +94,16 @@ struct MosaicOut {   // the five outputs of sucre_mosaic_gather
     float *range;
 };
 
+struct MosaicBlend {   // the four outputs of sucre_mosaic_normalize
+    float *J;
+    uint8_t *raw;
+    float *weight;
+    int32_t *samples;
+};
+
+constexpr int kMosaicAccWords = 8;      // int64 words per cell of the blend's accumulator (SUCRE_MOSAIC_ACC_WORDS)
+static_assert(kMosaicAccWords == SUCRE_MOSAIC_ACC_WORDS, "the accumulator's layout is public");
+
 enum MosaicPhase { kMosaicBounds, kMosaicSplat, kMosaicSplatPlain, kMosaicResolve, kMosaicGather };
 
 inline size_t mosaic_table_bytes(int n_images) { return align_up((size_t)n_images * sizeof(MosaicImage), 256); }
@@ -76,5 +114,12 @@ inline uint64_t mosaic_blocks(int H, int W) { return ((uint64_t)H * (uint64_t)W 
 hipError_t launch_mosaic(MosaicPhase phase, void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
                          const MosaicGrid &grid, uint32_t *bounds, unsigned long long *key, uint32_t *pix, const MosaicOut &out,
                          hipStream_t s);
+
+// The blend's accumulate phase over images[0 .. n) (the same launches as a phase above; key: read, acc: added to) and its
+// per-cell pass (one launch).
+hipError_t launch_mosaic_accumulate(bool plain, void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                                    const MosaicGrid &grid, const unsigned long long *key, float inv_h, unsigned long long *acc,
+                                    hipStream_t s);
+hipError_t launch_mosaic_normalize(const MosaicGrid &grid, const long long *acc, const MosaicBlend &out, hipStream_t s);
 
 }  // namespace sucre

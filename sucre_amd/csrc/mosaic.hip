@@ -56,10 +56,10 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t x) {
     return x;
 }
 
-template <int kPhase>
-__global__ __launch_bounds__(256) void mosaic_kernel(const MosaicImage *__restrict__ table, int n_images, const MosaicGrid g,
-                                                     uint32_t *__restrict__ bounds, unsigned long long *__restrict__ key,
-                                                     uint32_t *__restrict__ pix, const MosaicOut out) {
+// The walk of every phase: the workgroup's image, the lane's pixel and what mosaic_pixel says of it.  False for a lane past the
+// image's last pixel and for a pixel that does not take part.
+__device__ __forceinline__ bool mosaic_walk(const MosaicImage *__restrict__ table, int n_images, const MosaicGrid &g,
+                                            const MosaicImage *__restrict__ *image, uint32_t *pixel, MosaicPixel *m) {
     // the image of this workgroup: the last one whose first workgroup is not behind blockIdx.x (wave-uniform: scalar loads)
     int lo = 0, hi = n_images - 1;
     while (lo < hi) {
@@ -77,9 +77,21 @@ __global__ __launch_bounds__(256) void mosaic_kernel(const MosaicImage *__restri
 #pragma unroll
     for (int i = 0; i < 3; ++i) t[i] = im->t[i];
     const bool pin = pinhole_form(Kinv);
-    MosaicPixel m = {};
-    if (inside) m = mosaic_pixel(im, Kinv, pin, R, t, g.axes, p, W);
-    const bool in = inside && m.in;
+    *m = MosaicPixel{};
+    if (inside) *m = mosaic_pixel(im, Kinv, pin, R, t, g.axes, p, W);
+    *image = im;
+    *pixel = p;
+    return inside && m->in;
+}
+
+template <int kPhase>
+__global__ __launch_bounds__(256) void mosaic_kernel(const MosaicImage *__restrict__ table, int n_images, const MosaicGrid g,
+                                                     uint32_t *__restrict__ bounds, unsigned long long *__restrict__ key,
+                                                     uint32_t *__restrict__ pix, const MosaicOut out) {
+    const MosaicImage *__restrict__ im;
+    uint32_t p;
+    MosaicPixel m;
+    const bool in = mosaic_walk(table, n_images, g, &im, &p, &m);
 
     if constexpr (kPhase == kMosaicBounds) {
         // words 0, 1: min of a_s, a_t; words 2, 3: max -- as the min of the complemented key, so that one reduction serves all four
@@ -133,15 +145,101 @@ __global__ __launch_bounds__(256) void mosaic_kernel(const MosaicImage *__restri
     }
 }
 
+// ---- the blend (mosaic.h, "The blend"): fixed-point sums per cell, then one pass over the cells ----
+
+// Suffix sum over the lane's run: after the step with offset o, x holds the sum over lanes lane .. min(lane + 2 o, end of run) - 1.
+// `left`: lanes from this one to the end of its run, this one included.
+template <typename T>
+__device__ __forceinline__ T run_sum(T x, int left) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T y = __shfl_down(x, o);
+        if (o < left) x += y;
+    }
+    return x;
+}
+
+template <bool kPlain>
+__global__ __launch_bounds__(256) void mosaic_accumulate_kernel(const MosaicImage *__restrict__ table, int n_images, const MosaicGrid g,
+                                                                const unsigned long long *__restrict__ key, float inv_h,
+                                                                unsigned long long *__restrict__ acc) {
+    const MosaicImage *__restrict__ im;
+    uint32_t p;
+    MosaicPixel m;
+    const bool in = mosaic_walk(table, n_images, g, &im, &p, &m);
+    size_t cell = 0;
+    int32_t wq = 0;
+    if (in && mosaic_cell(g, m, &cell)) {
+        const float zmin = __uint_as_float((uint32_t)(key[cell] >> 32));   // an unsplatted cell: NaN, and fmaxf gives weight 0
+        const float d = m.z - zmin;
+        const float t = fmaxf(1.0f - d * inv_h, 0.0f);
+        wq = (int32_t)rintf((t * t) * 4096.0f);
+    }
+    // (no lane leaves before the shuffles of the aggregated form)
+    long long jq[3] = {0, 0, 0};
+    uint32_t rq[3] = {0, 0, 0};
+    if (wq > 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            jq[c] = (long long)wq * (long long)rintf(fminf(fmaxf(m.J[c], -1024.0f), 1024.0f) * 1048576.0f);
+            rq[c] = (uint32_t)wq * (uint32_t)global_ptr(im->rgb)[(size_t)p * 3 + c];
+        }
+    }
+    uint32_t wsum = (uint32_t)wq, count = wq > 0 ? 1u : 0u;
+    bool issue = wq > 0;
+    if constexpr (!kPlain) {
+        // Lanes hold consecutive pixels of a row, so runs of adjacent lanes share a cell: one lane per run adds the run's sums.
+        // Integer adds: the same bits as one add per lane.  Within a wave the colour sums stay below 64 x 4096 x 255 < 2^26.
+        const int lane = threadIdx.x & 63;
+        const uint32_t id_lo = wq > 0 ? (uint32_t)cell : ~0u, id_hi = wq > 0 ? (uint32_t)((uint64_t)cell >> 32) : ~0u;   // cells stay below 2^48
+        const uint32_t before_lo = (uint32_t)__shfl_up((int)id_lo, 1), before_hi = (uint32_t)__shfl_up((int)id_hi, 1);
+        const bool head = lane == 0 || wq <= 0 || before_lo != id_lo || before_hi != id_hi;
+        const unsigned long long heads = __ballot(head);
+        const unsigned long long above = (heads >> lane) >> 1;   // heads of the lanes after this one
+        const int left = above ? __ffsll((long long)above) : 64 - lane;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { jq[c] = run_sum(jq[c], left); rq[c] = run_sum(rq[c], left); }
+        wsum = run_sum(wsum, left);
+        count = run_sum(count, left);
+        issue = head && wq > 0;
+    }
+    if (!issue) return;
+    unsigned long long *a = acc + cell * kMosaicAccWords;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        __hip_atomic_fetch_add(a + c, (unsigned long long)jq[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(a + 3 + c, (unsigned long long)rq[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __hip_atomic_fetch_add(a + 6, (unsigned long long)wsum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add(a + 7, (unsigned long long)count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// One lane per cell: the sums of a filled cell become its four outputs; an empty cell's outputs are not touched.
+__global__ __launch_bounds__(256) void mosaic_normalize_kernel(size_t n_cells, const long long *__restrict__ acc, const MosaicBlend out) {
+    const size_t cell = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (cell >= n_cells) return;
+    const long long *a = acc + cell * kMosaicAccWords;
+    const long long wsum = a[6], count = a[7];
+    if (count <= 0) return;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        out.J[cell * 3 + c] = (float)(((double)a[c] / (double)wsum) * 0x1p-20);
+        out.raw[cell * 3 + c] = (uint8_t)((2 * a[3 + c] + wsum) / (2 * wsum));
+    }
+    out.weight[cell] = (float)((double)wsum * 0x1p-12);
+    out.samples[cell] = count > 0x7fffffffll ? 0x7fffffff : (int32_t)count;
+}
+
 template <int kPhase>
 static void mosaic_launch(uint32_t n_blocks, hipStream_t s, const MosaicImage *table, int n, const MosaicGrid &g, uint32_t *bounds,
                           unsigned long long *key, uint32_t *pix, const MosaicOut &out) {
     hipLaunchKernelGGL((mosaic_kernel<kPhase>), dim3(n_blocks), dim3(256), 0, s, table, n, g, bounds, key, pix, out);
 }
 
-hipError_t launch_mosaic(MosaicPhase phase, void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
-                         const MosaicGrid &grid, uint32_t *bounds, unsigned long long *key, uint32_t *pix, const MosaicOut &out,
-                         hipStream_t s) {
+// The launches of one phase over images[0 .. n): per 32 images, the table's set launches, then launch(workgroups, table, images).
+template <typename Launch>
+static void mosaic_for_each_launch(void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal, hipStream_t s,
+                                   Launch launch) {
     auto *entries = static_cast<MosaicImage *>(table);
     for (int l0 = 0; l0 < n_images; l0 += kMosaicLaunch) {
         const int nl = n_images - l0 < kMosaicLaunch ? n_images - l0 : kMosaicLaunch;
@@ -161,15 +259,38 @@ hipError_t launch_mosaic(MosaicPhase phase, void *table, int n_images, const suc
             }
             hipLaunchKernelGGL(mosaic_set_kernel, dim3(1), dim3(64), 0, s, entries + i0, src, n);
         }
-        const uint32_t nb = (uint32_t)block0;
-        switch (phase) {
-            case kMosaicBounds: mosaic_launch<kMosaicBounds>(nb, s, entries + l0, nl, grid, bounds, key, pix, out); break;
-            case kMosaicSplat: mosaic_launch<kMosaicSplat>(nb, s, entries + l0, nl, grid, bounds, key, pix, out); break;
-            case kMosaicSplatPlain: mosaic_launch<kMosaicSplatPlain>(nb, s, entries + l0, nl, grid, bounds, key, pix, out); break;
-            case kMosaicResolve: mosaic_launch<kMosaicResolve>(nb, s, entries + l0, nl, grid, bounds, key, pix, out); break;
-            case kMosaicGather: mosaic_launch<kMosaicGather>(nb, s, entries + l0, nl, grid, bounds, key, pix, out); break;
-        }
+        launch((uint32_t)block0, entries + l0, nl);
     }
+}
+
+hipError_t launch_mosaic(MosaicPhase phase, void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                         const MosaicGrid &grid, uint32_t *bounds, unsigned long long *key, uint32_t *pix, const MosaicOut &out,
+                         hipStream_t s) {
+    mosaic_for_each_launch(table, n_images, images, first_ordinal, s, [&](uint32_t nb, const MosaicImage *entries, int nl) {
+        switch (phase) {
+            case kMosaicBounds: mosaic_launch<kMosaicBounds>(nb, s, entries, nl, grid, bounds, key, pix, out); break;
+            case kMosaicSplat: mosaic_launch<kMosaicSplat>(nb, s, entries, nl, grid, bounds, key, pix, out); break;
+            case kMosaicSplatPlain: mosaic_launch<kMosaicSplatPlain>(nb, s, entries, nl, grid, bounds, key, pix, out); break;
+            case kMosaicResolve: mosaic_launch<kMosaicResolve>(nb, s, entries, nl, grid, bounds, key, pix, out); break;
+            case kMosaicGather: mosaic_launch<kMosaicGather>(nb, s, entries, nl, grid, bounds, key, pix, out); break;
+        }
+    });
+    return hipGetLastError();
+}
+
+hipError_t launch_mosaic_accumulate(bool plain, void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                                    const MosaicGrid &grid, const unsigned long long *key, float inv_h, unsigned long long *acc,
+                                    hipStream_t s) {
+    mosaic_for_each_launch(table, n_images, images, first_ordinal, s, [&](uint32_t nb, const MosaicImage *entries, int nl) {
+        if (plain) hipLaunchKernelGGL((mosaic_accumulate_kernel<true>), dim3(nb), dim3(256), 0, s, entries, nl, grid, key, inv_h, acc);
+        else hipLaunchKernelGGL((mosaic_accumulate_kernel<false>), dim3(nb), dim3(256), 0, s, entries, nl, grid, key, inv_h, acc);
+    });
+    return hipGetLastError();
+}
+
+hipError_t launch_mosaic_normalize(const MosaicGrid &grid, const long long *acc, const MosaicBlend &out, hipStream_t s) {
+    const size_t n_cells = (size_t)grid.Hm * (size_t)grid.Wm;   // the caller has checked that the workgroups fit a launch
+    hipLaunchKernelGGL(mosaic_normalize_kernel, dim3((uint32_t)((n_cells + 255) / 256)), dim3(256), 0, s, n_cells, acc, out);
     return hipGetLastError();
 }
 

@@ -980,8 +980,24 @@ def view_consistency(target: DeviceView, J_target: torch.Tensor, views: list, Js
 
 
 def mosaic_max_cells() -> int:
-    """Cells a mosaic may have: SUCRE_MOSAIC_MAX_CELLS, 2^27 unless set (37 bytes per cell: key, pixel word and the five outputs)."""
+    """Cells a mosaic may have: SUCRE_MOSAIC_MAX_CELLS, 2^27 unless set (37 bytes per cell: key, pixel word and the five outputs;
+    124 with a blend: 64 more for the accumulator's eight int64 words and 23 for the four blended outputs)."""
     return int(os.environ.get('SUCRE_MOSAIC_MAX_CELLS', 1 << 27))
+
+
+MOSAIC_BLEND_RANGE = (1e-6, 1e6)   # blend depths H a mosaic takes, metres
+MOSAIC_MAX_SAMPLES = 1 << 20       # samples of one cell from which the blend's int64 sums may pass 2^62 (csrc/mosaic.h)
+
+
+def mosaic_blend_depth(blend) -> np.float32:
+    """``blend`` as the float32 blend depth H, or ValueError unless it is finite and within ``MOSAIC_BLEND_RANGE``."""
+    try:
+        H = float(blend)
+    except (TypeError, ValueError):
+        H = float('nan')
+    if not (np.isfinite(H) and MOSAIC_BLEND_RANGE[0] <= H <= MOSAIC_BLEND_RANGE[1]):
+        raise ValueError(f'mosaic blend depth H must be finite and within [{MOSAIC_BLEND_RANGE[0]:g}, {MOSAIC_BLEND_RANGE[1]:g}] metres, not {blend}')
+    return np.float32(H)
 
 
 def mosaic_cells(lo: float, hi: float, gsd: float) -> int:
@@ -998,7 +1014,12 @@ class Mosaic:
     are dropped), allocates and returns ``(Hm, Wm)``; then ``splat``, ``resolve`` and ``gather``, each over ALL the images (in any
     batches, every batch with the ordinal of its first image) before the next phase starts; ``result()``.  ``views``:
     ``DeviceView`` with uint8 colours; ``Js``: their (H,W,3) float32 device images.  The words a later all-reduce over ranks would
-    combine are tensors: ``bounds_words`` (int32 x 4), ``key`` (int64, min), ``pix`` (int32 bit patterns of uint32, unsigned min)."""
+    combine are tensors: ``bounds_words`` (int32 x 4), ``key`` (int64, min), ``pix`` (int32 bit patterns of uint32, unsigned min).
+
+    The blend: ``begin(blend=H)`` also allocates ``acc`` ((Hm Wm, 8) int64, zeros: per cell the fixed-point sums ``wq Jq`` x 3,
+    ``wq rgb`` x 3, ``wq`` and the sample count -- csrc/mosaic.h, "The blend"; the tensor a later all-reduce (sum) over ranks would
+    combine, next to ``key`` (min) and ``pix``) and four more outputs; ``accumulate`` over ALL the images once ``splat`` has seen
+    every one of them, then ``normalize()``; ``result()`` then holds ``J_blend``, ``raw_blend``, ``weight`` and ``samples`` as well."""
 
     def __init__(self, axes, gsd, device):
         _lib.load()
@@ -1021,6 +1042,8 @@ class Mosaic:
         self.lo = self.hi = None
         self.key = self.pix = None
         self._out = None
+        self.blend = self.inv_h = self.acc = None
+        self._blend_out = None
 
     def _images(self, views: list, Js: list):
         views, Js = list(views), list(Js)
@@ -1061,7 +1084,11 @@ class Mosaic:
         bits = np.where(k & 0x80000000, k & 0x7fffffff, ~k).astype(np.uint32)   # key_value of csrc/order_key.h
         return tuple(bits.view(np.float32).tolist())
 
-    def begin(self, bounds=None):
+    def begin(self, bounds=None, blend=None):
+        """Fixes the grid and allocates; ``blend``: the blend depth H in metres (``MOSAIC_BLEND_RANGE``) -- a pixel whose range
+        exceeds its cell's smallest one by d gets the weight ``max(1 - d / H, 0)^2`` -- or None for the best view alone."""
+        if blend is not None:
+            blend = mosaic_blend_depth(blend)   # before anything is allocated
         if bounds is None:
             bounds = self.bounds()
             if bounds is None:
@@ -1087,6 +1114,14 @@ class Mosaic:
                      'source': torch.full((Hm, Wm), -1, dtype=torch.int32, device=dev),
                      'pixel': torch.full((Hm, Wm), -1, dtype=torch.int32, device=dev),
                      'range': torch.full((Hm, Wm), nan, dtype=torch.float32, device=dev)}
+        self.blend, self.inv_h, self.acc, self._blend_out = blend, None, None, None
+        if blend is not None:
+            self.inv_h = np.float32(1) / blend
+            self.acc = torch.zeros((Hm * Wm, _lib.MOSAIC_ACC_WORDS), dtype=torch.int64, device=dev)
+            self._blend_out = {'J_blend': torch.full((Hm, Wm, 3), nan, dtype=torch.float32, device=dev),
+                               'raw_blend': torch.zeros((Hm, Wm, 3), dtype=torch.uint8, device=dev),
+                               'weight': torch.zeros((Hm, Wm), dtype=torch.float32, device=dev),
+                               'samples': torch.zeros((Hm, Wm), dtype=torch.int32, device=dev)}
         return Hm, Wm
 
     def _begun(self, what: str) -> None:
@@ -1119,32 +1154,76 @@ class Mosaic:
                                                        C.c_void_p(o['source'].data_ptr()), C.c_void_p(o['pixel'].data_ptr()),
                                                        C.c_void_p(o['range'].data_ptr()), _stream_ptr()))
 
+    def _blending(self, what: str) -> None:
+        self._begun(what)
+        if self.blend is None:
+            raise ValueError(f'Mosaic.{what}: begin() was not given a blend depth, so there is nothing to blend into')
+
+    def accumulate(self, views: list, Js: list, first_ordinal: int, plain: bool = False) -> None:
+        """Adds the images' weighted samples to ``acc``.  Valid once ``splat`` has seen every image (``key`` holds every cell's
+        smallest range then).  ``plain``: eight atomics per pixel instead of eight per run of a wave's lanes (the same ``acc``)."""
+        self._blending('accumulate')
+        arr, n, table, _ = self._images(views, Js)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().sucre_mosaic_accumulate(C.c_void_p(table.data_ptr()), n, arr, int(first_ordinal), C.byref(self.grid),
+                                                           C.c_void_p(self.key.data_ptr()), C.c_float(float(self.inv_h)),
+                                                           C.c_void_p(self.acc.data_ptr()), _lib.MOSAIC_PLAIN_ATOMIC if plain else 0,
+                                                           _stream_ptr()))
+
+    def normalize(self, check: bool = True) -> None:
+        """The per-cell pass from ``acc`` to the four blended outputs; waits for it, and raises ValueError when a cell holds
+        ``MOSAIC_MAX_SAMPLES`` = 2^20 samples or more (its 64-bit sums may have wrapped).  ``check=False`` only enqueues the
+        pass (for measurements: the caller looks at ``samples`` itself)."""
+        self._blending('normalize')
+        o = self._blend_out
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().sucre_mosaic_normalize(C.byref(self.grid), C.c_void_p(self.acc.data_ptr()),
+                                                          C.c_void_p(o['J_blend'].data_ptr()), C.c_void_p(o['raw_blend'].data_ptr()),
+                                                          C.c_void_p(o['weight'].data_ptr()), C.c_void_p(o['samples'].data_ptr()),
+                                                          _stream_ptr()))
+        if not check:
+            return
+        most = int(o['samples'].max())
+        if most >= MOSAIC_MAX_SAMPLES:
+            raise ValueError(f'mosaic blend: a cell holds {most} samples, and from {MOSAIC_MAX_SAMPLES} on its 64-bit sums may overflow; '
+                             f'give a finer grid with --mosaic-gsd')
+
     def result(self) -> dict:
         """``J`` (Hm,Wm,3) float32 (NaN: empty), ``raw`` (Hm,Wm,3) uint8 (0), ``source`` and ``pixel`` (Hm,Wm) int32 (-1), ``range``
-        (Hm,Wm) float32 (NaN), on the device, complete once ``gather`` has seen every image."""
+        (Hm,Wm) float32 (NaN), on the device, complete once ``gather`` has seen every image.  With a blend also ``J_blend``
+        (Hm,Wm,3) float32 (NaN), ``raw_blend`` (Hm,Wm,3) uint8 (0), ``weight`` (Hm,Wm) float32 -- the sum of the samples' weights,
+        each at most 1 -- (0) and ``samples`` (Hm,Wm) int32 (0), complete once ``normalize`` has run."""
         self._begun('result')
-        return dict(self._out)
+        return {**self._out, **self._blend_out} if self.blend is not None else dict(self._out)
 
 
-def mosaic_of(views: list, Js: list, axes, gsd, bounds=None, batch: int = 32, plain_atomic: bool = False) -> 'Mosaic':
-    """All four phases over device-resident ``views`` / ``Js`` (ordinal = position in the list), ``batch`` images per call."""
+def mosaic_of(views: list, Js: list, axes, gsd, bounds=None, batch: int = 32, plain_atomic: bool = False, blend=None) -> 'Mosaic':
+    """All four phases over device-resident ``views`` / ``Js`` (ordinal = position in the list), ``batch`` images per call; with
+    ``blend`` (the blend depth H, metres) the accumulate phase and the normalise pass after them (``plain_atomic``: both the
+    splat and the accumulate phase in their plain forms)."""
     views, Js = list(views), list(Js)
     if not views:
         raise ValueError('mosaic_of: no view')
     if len(views) > MAX_VIEWS:
         raise ValueError(f'mosaic_of: {len(views)} images, at most {MAX_VIEWS}')
+    if blend is not None:
+        mosaic_blend_depth(blend)   # before anything is allocated
     m = Mosaic(axes, gsd, views[0].depth.device)
     chunks = [(i, views[i:i + batch], Js[i:i + batch]) for i in range(0, len(views), batch)]
     if bounds is None:
         for _, v, J in chunks:
             m.add_bounds(v, J)
-    m.begin(bounds)
+    m.begin(bounds, blend=blend)
     for i, v, J in chunks:
         m.splat(v, J, i, plain_atomic=plain_atomic)
     for i, v, J in chunks:
         m.resolve(v, J, i)
     for i, v, J in chunks:
         m.gather(v, J, i)
+    if blend is not None:
+        for i, v, J in chunks:
+            m.accumulate(v, J, i, plain=plain_atomic)
+        m.normalize()
     return m
 
 

@@ -1400,17 +1400,44 @@ def mosaic_source_picture(source: np.ndarray) -> np.ndarray:
     return out
 
 
+def _mosaic_picture(J: Tensor, stretch) -> np.ndarray:
+    """(Hm,Wm,3) uint8 of a mosaic's ``J`` on the device: the fixed ``stretch`` when given, ``plot_J``'s own percentiles over the
+    filled cells otherwise."""
+    from . import engine
+    if stretch is not None:
+        return engine.plot_stretch(J, *stretch).cpu().numpy()
+    if _NUMPY_2:
+        return _plot_J_on_device(J).cpu().numpy()
+    J = J.cpu().numpy().copy()   # numpy 1.x: np.percentile itself, as plot_J does there
+    ok = ~np.isnan(J).any(axis=2)
+    vals = J[ok]
+    lo, hi = np.percentile(vals, 1, axis=0), np.percentile(vals, 99, axis=0)
+    vals = np.clip(vals, lo, hi)
+    vals = vals - vals.min(axis=0)
+    vals = vals / vals.max(axis=0)
+    J[~ok] = 0.0
+    J[ok] = vals
+    return np.uint8(J * 255)
+
+
 def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, output_dir: Path, gsd: float | None = None, axes=None,
-           stretch=None, device: str = 'cuda') -> dict:
+           stretch=None, device: str = 'cuda', blend: float | None = None) -> dict:
     """One picture of the seabed from a finished restoration: every pixel of ``images`` (``sfm.Image`` objects or names of
     ``colmap_model``; at most ``engine.MAX_VIEWS``, ordinal = position) with a valid depth and a restored colour --
     ``results_dir / <name>.pt``, key ``J`` -- is dropped onto the plane grid ``axes`` (``mosaic_axes`` unless given) of ``gsd``
     metres per cell (``mosaic_default_gsd`` unless given; printed), and the pixel seen through the least water wins its cell
-    (``engine.Mosaic``; csrc/mosaic.h).  No blending, no hole filling.  Every file is checked before any image is decoded.  The
+    (``engine.Mosaic``; csrc/mosaic.h).  No hole filling.  Every file is checked before any image is decoded.  The
     restored images stay on the device across the four phases within ``consistency_cache_budget`` and are read again per phase
     otherwise: the same bits either way.  Writes ``mosaic.png`` (``plot_J``'s stretch over the filled cells, or the fixed
     ``stretch``), ``mosaic_raw.png``, ``mosaic_source.png`` (``mosaic_source_picture``) and ``mosaic.pt`` (``J, raw, source, pixel,
-    range, axes, gsd, lo, images, n_filled, per_image``), prints one line and returns the dictionary of ``mosaic.pt``."""
+    range, axes, gsd, lo, images, n_filled, per_image``), prints one line and returns the dictionary of ``mosaic.pt``.
+
+    ``blend``: a blend depth H in metres (``engine.MOSAIC_BLEND_RANGE``).  One more pass over the batches then sums, per cell, ALL
+    its pixels in fixed point, each with the weight ``max(1 - (z - zmin) / H, 0)^2`` of its range z over the cell's smallest one,
+    and a pass over the cells divides (csrc/mosaic.h, "The blend": the same bits in any order).  The four files above stay the
+    best-view ones, byte for byte -- their seams are the diagnostic --; ``mosaic_blend.png`` (``J_blend`` through the function that
+    makes ``mosaic.png``) and ``mosaic_blend_raw.png`` come next to them, ``mosaic.pt`` gains ``J_blend, raw_blend, weight, samples,
+    blend`` and one more line is printed.  Not built: feathering by the distance to the image border, multi-band blending."""
     from . import engine
     sfm.require_gpu(device, 'mosaic')
     images = [colmap_model[im] if isinstance(im, str) else im for im in images]
@@ -1420,6 +1447,11 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
         raise SystemExit(f'--mosaic: {len(images)} images in the request, at most {engine.MAX_VIEWS} go into one mosaic')
     if stretch is not None:
         stretch = check_stretch(stretch)
+    if blend is not None:
+        try:
+            blend = engine.mosaic_blend_depth(blend)
+        except ValueError as e:
+            raise SystemExit(f'--mosaic-blend: {e}')
     results_dir, output_dir = Path(results_dir), Path(output_dir)
     for image in images:   # before anything is decoded
         path = _consistency_file(results_dir, image)
@@ -1453,29 +1485,21 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
         for _, batch in batches:
             m.add_bounds(*resident(batch))
         try:
-            Hm, Wm = m.begin()
+            Hm, Wm = m.begin(blend=blend)
         except ValueError as e:
             raise SystemExit(f'--mosaic: {e}')
-        for phase in (m.splat, m.resolve, m.gather):
+        for phase in (m.splat, m.resolve, m.gather) + ((m.accumulate,) if blend is not None else ()):
             for first, batch in batches:
                 phase(*resident(batch), first)
+        if blend is not None:
+            try:
+                m.normalize()
+            except ValueError as e:
+                raise SystemExit(f'--mosaic-blend: {e}')
         out = m.result()
-        picture = engine.plot_stretch(out['J'], *stretch) if stretch is not None else None
-        if picture is None:
-            picture = _plot_J_on_device(out['J']) if _NUMPY_2 else None
+        picture = _mosaic_picture(out['J'], stretch)
+        blend_picture = _mosaic_picture(out['J_blend'], stretch) if blend is not None else None
         out = {k: v.cpu() for k, v in out.items()}
-        picture = None if picture is None else picture.cpu().numpy()
-    if picture is None:   # numpy 1.x: np.percentile itself, as plot_J does there
-        J = out['J'].numpy().copy()
-        ok = ~np.isnan(J).any(axis=2)
-        vals = J[ok]
-        lo, hi = np.percentile(vals, 1, axis=0), np.percentile(vals, 99, axis=0)
-        vals = np.clip(vals, lo, hi)
-        vals = vals - vals.min(axis=0)
-        vals = vals / vals.max(axis=0)
-        J[~ok] = 0.0
-        J[ok] = vals
-        picture = np.uint8(J * 255)
     source = out['source']
     filled = source >= 0
     n_filled, n_cells = int(filled.sum()), Hm * Wm
@@ -1483,13 +1507,23 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
     _save_png(PILImage.fromarray(picture), output_dir / 'mosaic.png')
     _save_png(PILImage.fromarray(out['raw'].numpy()), output_dir / 'mosaic_raw.png')
     _save_png(PILImage.fromarray(mosaic_source_picture(source.numpy())), output_dir / 'mosaic_source.png')
+    if blend is not None:
+        _save_png(PILImage.fromarray(blend_picture), output_dir / 'mosaic_blend.png')
+        _save_png(PILImage.fromarray(out['raw_blend'].numpy()), output_dir / 'mosaic_blend_raw.png')
     data = {**out, 'axes': m.axes.clone(), 'gsd': float(m.gsd), 'lo': torch.tensor([float(m.lo[0]), float(m.lo[1])], dtype=torch.float32),
             'images': [im.name for im in images], 'n_filled': n_filled, 'per_image': per_image}
+    if blend is not None:
+        data['blend'] = float(blend)
     torch.save(data, output_dir / 'mosaic.pt')
     top = int(per_image.argmax())
     print(f'mosaic of {len(images)} images: {Wm} x {Hm} cells of {float(m.gsd):.6g} m, {n_filled} filled '
           f'({100.0 * n_filled / n_cells:.1f} %), {n_cells - n_filled} empty; largest share {images[top].name} '
           f'({100.0 * int(per_image[top]) / max(1, n_filled):.1f} %)')
+    if blend is not None:
+        samples = out['samples'].to(torch.int64)
+        total, most, several = int(samples.sum()), int(samples.max()), int((samples > 1).sum())
+        print(f'mosaic blend of depth {float(blend):.6g} m: {total} samples, {total / max(1, n_filled):.2f} per filled cell on average, '
+              f'{most} at most; {100.0 * several / max(1, n_filled):.1f} % of the filled cells blend more than one sample')
     return data
 
 
@@ -1515,6 +1549,9 @@ def _refuse_mosaic_flags(args, world: int = 1) -> None:
     gsd = getattr(args, 'mosaic_gsd', None)
     if gsd is not None and not (np.isfinite(gsd) and gsd > 0):
         raise SystemExit(f'--mosaic-gsd: G must be a finite size > 0 in metres, not {gsd}')
+    blend = getattr(args, 'mosaic_blend', None)
+    if blend is not None and not (np.isfinite(blend) and 1e-6 <= blend <= 1e6):
+        raise SystemExit(f'--mosaic-blend: H must be a finite depth within [1e-06, 1e+06] metres, not {blend}')
     if world > 1:
         raise SystemExit(f'--mosaic: a world size of {world} is not supported yet: the four phases are separate entries of the library '
                          f'so that ranks can all-reduce bounds, keys and pixel words between them, but that all-reduce is not built; '
@@ -1582,6 +1619,8 @@ def parse_args(args: argparse.Namespace):
     mosaic_dir = getattr(args, 'mosaic', None)
     if mosaic_dir is None and getattr(args, 'mosaic_gsd', None) is not None:
         raise SystemExit('--mosaic-gsd: only with --mosaic DIR')
+    if mosaic_dir is None and getattr(args, 'mosaic_blend', None) is not None:
+        raise SystemExit('--mosaic-blend: only with --mosaic DIR')
     if mosaic_dir is not None:
         _refuse_mosaic_flags(args, world)
     if check is not None:
@@ -1662,7 +1701,8 @@ def parse_args(args: argparse.Namespace):
         torch.set_num_threads(host_threads)
     try:
         if mosaic_dir is not None:
-            mosaic(images, colmap_model, mosaic_dir, args.output_dir, gsd=getattr(args, 'mosaic_gsd', None), stretch=stretch, device=device)
+            mosaic(images, colmap_model, mosaic_dir, args.output_dir, gsd=getattr(args, 'mosaic_gsd', None), stretch=stretch, device=device,
+                   blend=getattr(args, 'mosaic_blend', None))
         elif check is not None:
             if world > 1:   # the targets' records are gathered on rank 0
                 sdist.init_process_group()
@@ -1911,6 +1951,12 @@ def build_parser() -> argparse.ArgumentParser:
                                'filled; writes mosaic.png, mosaic_raw.png, mosaic_source.png and mosaic.pt and prints the size and the cover')
     p.extras.add_argument('--mosaic-gsd', type=float, metavar='G', default=argparse.SUPPRESS,
                           help='with --mosaic: metres per cell (twice the median pixel footprint of the images unless given)')
+    p.extras.add_argument('--mosaic-blend', type=float, metavar='H', default=argparse.SUPPRESS,
+                          help='with --mosaic: also a blended mosaic -- every cell the mean of ALL its pixels, each weighted by '
+                               'max(1 - d / H, 0)^2 of the metres d of water it looked through beyond the cell\'s nearest view, summed in '
+                               'fixed point (the same bits in any order); writes mosaic_blend.png and mosaic_blend_raw.png next to the '
+                               'best-view files, which stay as they are, adds J_blend, raw_blend, weight, samples and blend to mosaic.pt '
+                               'and prints one more line')
     p.extras.add_argument('--common-stretch', action='store_true', default=argparse.SUPPRESS,
                           help='with --shared-water or --apply-water: stretch every <stem>_rgb.png between the SAME per-channel 1st '
                                'and 99th percentile, those of the valid pixels of all images of the request pooled (all ranks), '
