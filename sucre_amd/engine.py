@@ -1412,6 +1412,10 @@ def slot_lane(index: int):
         _TLS.lane = prev
 
 
+def view_capacity(n: int) -> int:   # in steps, so targets whose surviving view counts differ a little share one workspace
+    return (n + 7) // 8 * 8 if n <= 256 else (n + 31) // 32 * 32   # (65 views -> 72, not 96: +11 % HBM per slot, not +48 %)
+
+
 def acquire_restoration(height: int, width: int, n_views: int, device='cuda', light: bool = False,
                         obs_format: str | None = None, float_colour: bool = False, tag: str = '') -> Restoration:
     """Workspace pool: one Restoration per (geometry, device, in-flight slot, tag), reused image after image (the
@@ -1423,16 +1427,13 @@ def acquire_restoration(height: int, width: int, n_views: int, device='cuda', li
         dev = torch.device('cuda', torch.cuda.current_device())
     if obs_format is None:   # engine knob for the reference-compatible CLI, which has no flag for it
         obs_format = 'f32' if (light or float_colour) else os.environ.get('SUCRE_OBS_FORMAT', 'f32')
-    # capacities come in steps, so targets whose surviving view counts differ a little share one workspace
     n = int(n_views)
-    cap = (n + 7) // 8 * 8 if n <= 256 else (n + 31) // 32 * 32   # (65 views -> 72, not 96: +11 % HBM per slot, not +48 %)
     key = (int(height), int(width), str(dev), bool(light), (current_slot(), current_lane()), obs_format, bool(float_colour), tag)
     have = _POOL.get(key)
     if have is None or have.capacity < n:
         _POOL.pop(key, None)   # release the smaller workspace before allocating the larger one
         del have
-        _POOL[key] = Restoration(height, width, cap, device=dev, light=light, obs_format=obs_format,
-                                 float_colour=float_colour)
+        _POOL[key] = Restoration(height, width, view_capacity(n), device=dev, light=light, obs_format=obs_format, float_colour=float_colour)
     return _POOL[key]
 
 
@@ -1461,8 +1462,7 @@ def lease_restoration(height: int, width: int, n_views: int, device='cuda', ligh
                     for ev in r.__dict__.pop('_idle_after', []):
                         torch.cuda.current_stream(dev).wait_event(ev)
                 return r
-    cap = (n + 7) // 8 * 8 if n <= 256 else (n + 31) // 32 * 32
-    return Restoration(height, width, cap, device=dev, light=light, obs_format=obs_format, float_colour=float_colour)
+    return Restoration(height, width, view_capacity(n), device=dev, light=light, obs_format=obs_format, float_colour=float_colour)
 
 
 def return_restoration(r: Restoration) -> None:

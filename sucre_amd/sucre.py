@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import argparse
 import collections
+import dataclasses
 import os
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
@@ -414,10 +415,59 @@ def snapshot_stops(num_iter: int, save_interval: int | None) -> list[tuple[int, 
     return [(stop, stop >= 1 and (stop - 1) % save_interval == 0) for stop in stops]
 
 
+@dataclasses.dataclass(frozen=True)
+class _Extras:
+    """What a restoration can be asked for beyond the reference's arguments: --save-quality; --trim-outliers, --trim-rounds;
+    --view-gains, --gain-rounds, --gain-limit; the ``(lo, hi)`` of --stretch-from.  Built from the command line (``_run_request``),
+    from the keywords of ``restore_images`` and from those of ``adam``; everything between them hands the record on."""
+    save_quality: bool = False
+    trim_outliers: float = None
+    trim_rounds: int = 1
+    view_gains: bool = False
+    gain_rounds: int = 1
+    gain_limit: float = 2.0
+    stretch: tuple = None
+
+    def checked(self, save_interval: int = None) -> '_Extras':
+        """The record with its stretch as ``check_stretch`` returns it.  ``ValueError`` for a value out of range, for gains next
+        to a trim and for either next to ``save_interval`` snapshots."""
+        stretch = None if self.stretch is None else check_stretch(self.stretch)
+        if self.trim_outliers is not None:
+            if not (np.isfinite(float(self.trim_outliers)) and float(self.trim_outliers) > 0):
+                raise ValueError(f'trim_outliers must be a finite multiple > 0, not {self.trim_outliers!r}')
+            if int(self.trim_rounds) < 1:
+                raise ValueError(f'trim_rounds must be >= 1, not {self.trim_rounds!r}')
+        if self.view_gains:
+            if int(self.gain_rounds) < 1:
+                raise ValueError(f'gain_rounds must be >= 1, not {self.gain_rounds!r}')
+            if not (np.isfinite(float(self.gain_limit)) and float(self.gain_limit) >= 1):
+                raise ValueError(f'gain_limit must be finite and >= 1, not {self.gain_limit!r}')
+            if self.trim_outliers is not None:
+                raise ValueError('view_gains does not combine with trim_outliers')
+        for name, on in (('trim_outliers', self.trim_outliers is not None), ('view_gains', self.view_gains)):
+            if on and save_interval is not None:
+                raise ValueError(f'{name} does not combine with save_interval snapshots')
+        return dataclasses.replace(self, stretch=stretch)
+
+
+_NO_EXTRAS = _Extras()
+
+
+class _Job:
+    """One image between ``_restore_submit`` (everything enqueued, nothing waited for) and ``_restore_finish``.  ``extras``: what
+    was asked for; ``trace``: the last fit's; ``quality``, ``trim``, ``gains``: the records of --save-quality and of every round."""
+    extras = _NO_EXTRAS
+    params0 = None   # the start of every fit, on the host; None: read from the module (``adam``)
+    trace = quality = trim = gains = None
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
 def adam(sucre: SUCRe, matches_data: loader.MatchesData, lr: float = 0.05, num_iter: int = 200, batch_size: int = 1,
          save_dir: Path = None, save_interval: int = None, device: str = 'cpu', verbose: bool = True,
          trim_outliers: float = None, trim_rounds: int = 1, view_gains: bool = False, gain_rounds: int = 1,
-         gain_limit: float = 2.0) -> SUCRe:
+         gain_limit: float = 2.0, _job: _Job = None) -> SUCRe:
     """``num_iter`` steps of ``torch.optim.Adam(lr)`` on the least-squares cost (sucre.py:124-157).
 
     ``batch_size`` is accepted for compatibility: the engine always uses the full batch in one pass, which is
@@ -429,15 +479,16 @@ def adam(sucre: SUCRe, matches_data: loader.MatchesData, lr: float = 0.05, num_i
 
     ``view_gains`` (not a reference argument): after the fit, ``gain_rounds`` rounds of estimate the per-view gains -> divide
     them out of the store -> fit anew from the same initial values with the same ``num_iter`` (``_enqueue_gains``);
-    ``sucre._gains`` holds every round's record.  Not together with ``trim_outliers``."""
-    _check_trim(trim_outliers, trim_rounds)
-    _check_gains(view_gains, gain_rounds, gain_limit, trim_outliers)
-    if trim_outliers is not None and save_dir is not None and save_interval is not None:
-        raise ValueError('trim_outliers does not combine with save_interval snapshots')
-    if view_gains and save_dir is not None and save_interval is not None:
-        raise ValueError('view_gains does not combine with save_interval snapshots')
+    ``sucre._gains`` holds every round's record.  Not together with ``trim_outliers``.
+
+    ``_job`` (internal, ``_restore_one``): its ``extras`` stand in for the five keywords above and may ask for the quality pass
+    behind the last fit; it receives the records."""
+    extras = _job.extras if _job is not None else _Extras(trim_outliers=trim_outliers, trim_rounds=trim_rounds, view_gains=view_gains,
+                                                          gain_rounds=gain_rounds, gain_limit=gain_limit)
+    extras = extras.checked(save_interval if save_dir is not None else None)
+    job = _Job(sucre=sucre, matches_data=matches_data, extras=extras)   # (no params0: every fit starts from what the module holds)
     print(f'Solve least squares with Adam optimizer ({num_iter} iterations).')
-    resto = _adam_begin(sucre, matches_data)
+    job.resto = resto = _begin(job)
     done = 0
     for stop, snapshot in snapshot_stops(num_iter, save_interval if save_dir is not None else None):
         if stop > done:
@@ -452,28 +503,30 @@ def adam(sucre: SUCRe, matches_data: loader.MatchesData, lr: float = 0.05, num_i
             sucre.save_plots(save_dir=save_dir, iteration=done - 1)
             if sucre.use_closed_form and done == num_iter:
                 resto.update_J()   # the final update_J of sucre.py:156, held back for the snapshot
-    if trim_outliers is not None:
-        sucre._trim = []
-        for i in range(int(trim_rounds)):   # (no snapshot stops here: nothing has been pulled into the model yet, so
-            sucre._trim.append(_enqueue_trim(resto, trim_outliers))   # _adam_begin starts from the same values again)
-            print(f'Solve least squares with Adam optimizer ({num_iter} iterations) after trim round {i + 1}.')
-            _adam_begin(sucre, matches_data)
-            trace = resto.fit(num_iter, lr=lr, use_closed_form=sucre.use_closed_form)
-            if verbose:
-                _log_trace(trace.cpu().numpy(), 0)
-    if view_gains:
-        sucre._gains = []
-        for i in range(int(gain_rounds)):
-            sucre._gains.append(_enqueue_gains(resto, gain_limit))
-            print(f'Solve least squares with Adam optimizer ({num_iter} iterations) after gain round {i + 1}.')
-            _adam_begin(sucre, matches_data)
-            trace = resto.fit(num_iter, lr=lr, use_closed_form=sucre.use_closed_form)
-            if verbose:
-                _log_trace(trace.cpu().numpy(), 0)
-    if getattr(sucre, '_quality_wanted', False):   # --save-quality: the pass right behind the fit, read with the results
-        sucre._quality = _enqueue_residuals(resto)
+
+    def fit_again(jobs, after):
+        print(f'Solve least squares with Adam optimizer ({num_iter} iterations) after {after}.')
+        trace = resto.fit(num_iter, lr=lr, use_closed_form=sucre.use_closed_form)
+        if verbose:
+            _log_trace(trace.cpu().numpy(), 0)
+    # (no snapshot stops in the rounds: nothing has been pulled into the model yet, so each starts from the same values again)
+    _enqueue_refits([job], fit_again)
+    _enqueue_quality(job)   # --save-quality: the pass right behind the fit, read with the results
+    if job.trim is not None:
+        sucre._trim = job.trim
+    if job.gains is not None:
+        sucre._gains = job.gains
+    if _job is not None:
+        _job.quality, _job.trim, _job.gains = job.quality, job.trim, job.gains
     _pull_results(sucre, resto)
     return sucre
+
+
+def _begin(job: _Job):
+    """``_adam_begin`` of a job: from its start values on the host when it has them, from the module otherwise."""
+    if job.params0 is None:
+        return _adam_begin(job.sucre, job.matches_data)
+    return _adam_begin(job.sucre, job.matches_data, params0=job.params0)
 
 
 def _adam_begin(sucre: SUCRe, matches_data: loader.MatchesData, params0: np.ndarray | None = None):
@@ -517,17 +570,22 @@ def _enqueue_residuals(resto) -> tuple:
     return resto.residuals() + (resto.view_keep().clone(),)
 
 
-def _enqueue_quality(job, resto=None) -> None:
-    if getattr(job, 'save_quality', False):
-        job.quality = _enqueue_residuals(resto if resto is not None else _restoration_of(job.matches_data))
+def _enqueue_quality(job) -> None:
+    if job.extras.save_quality:
+        job.quality = _enqueue_residuals(job.resto)
+
+
+def _view_names(job, n_views: int) -> list:
+    """The names of the views a job's records have their rows for; their indices where the matches carry no image list."""
+    image_list = getattr(job.matches_data, 'image_list', None)
+    return [im.name for im in image_list] if image_list else [str(k) for k in range(n_views)]
 
 
 def _write_quality(job) -> None:
     """``<stem>_quality.pt``, ``<stem>_coverage.png``, ``<stem>_residual.png`` and one printed line."""
     count, ssr, stats, keep = job.quality   # host tensors (_restore_finish)
     stem = Path(job.image.name).stem
-    image_list = getattr(job.matches_data, 'image_list', None)
-    views = [im.name for im in image_list] if image_list else [str(k) for k in range(stats.shape[0])]
+    views = _view_names(job, stats.shape[0])
     view_kept = keep != 0
     view_n = stats[:, 0].round().to(torch.int64)
     view_ssr = stats[:, 1:].clone()
@@ -547,15 +605,6 @@ def _write_quality(job) -> None:
 
 
 # ---- --trim-outliers: sigma-clip single observations on the device, fit again ------------------------------------------
-def _check_trim(trim_outliers, trim_rounds) -> None:
-    if trim_outliers is None:
-        return
-    if not (np.isfinite(float(trim_outliers)) and float(trim_outliers) > 0):
-        raise ValueError(f'trim_outliers must be a finite multiple > 0, not {trim_outliers!r}')
-    if int(trim_rounds) < 1:
-        raise ValueError(f'trim_rounds must be >= 1, not {trim_rounds!r}')
-
-
 def _enqueue_trim(resto, k_sigma: float) -> dict:
     """One round on the current stream, no host wait (``Restoration.trim_outliers`` behind the residual pass it takes its scale
     from); the fit must be started over.  The round's record, on the device."""
@@ -563,19 +612,6 @@ def _enqueue_trim(resto, k_sigma: float) -> dict:
     dropped, view_dropped, thresholds = resto.trim_outliers(k_sigma, resto.residuals())
     return {'dropped': dropped, 'view_dropped': view_dropped, 'thresholds': thresholds, 'n_obs': n_obs, 'view_kept': kept,
             'k': float(k_sigma)}
-
-
-def _enqueue_trim_refits(jobs: list, fit) -> None:
-    """The rounds of ``--trim-outliers`` for images whose first fit is enqueued: trim, ``fit_init`` with the initial values of
-    the first fit, and ``fit(jobs)`` -- the caller's way of fitting them, alone or in a batch launch -- again."""
-    for job in jobs:
-        job.trim = [] if job.trim_outliers is not None else None
-    for i in range(max((int(j.trim_rounds) for j in jobs if j.trim_outliers is not None), default=0)):
-        again = [j for j in jobs if j.trim_outliers is not None and i < int(j.trim_rounds)]
-        for job in again:
-            job.trim.append(_enqueue_trim(job.resto, job.trim_outliers))
-            _adam_begin(job.sucre, job.matches_data, params0=job.params0)
-        fit(again)
 
 
 def trimmed_image(dropped_rounds, n_kept: int) -> np.ndarray:
@@ -589,9 +625,7 @@ def _write_trim(job) -> None:
     """``<stem>_trim.pt``, ``<stem>_trimmed.png`` and one printed line per round."""
     rounds = job.trim   # host tensors (_restore_finish)
     stem = Path(job.image.name).stem
-    image_list = getattr(job.matches_data, 'image_list', None)
-    n_views = int(rounds[0]['view_dropped'].shape[0])
-    views = [im.name for im in image_list] if image_list else [str(k) for k in range(n_views)]
+    views = _view_names(job, int(rounds[0]['view_dropped'].shape[0]))
     dropped = torch.stack([r['dropped'] for r in rounds])
     torch.save({'dropped': dropped, 'views': views, 'view_dropped': torch.stack([r['view_dropped'] for r in rounds]),
                 'thresholds': torch.stack([r['thresholds'] for r in rounds]), 'k': rounds[0]['k'],
@@ -606,17 +640,6 @@ def _write_trim(job) -> None:
 
 
 # ---- --view-gains: one multiplicative gain per view and channel, estimated on the device and divided out; fit again ------
-def _check_gains(view_gains, gain_rounds, gain_limit, trim_outliers=None) -> None:
-    if not view_gains:
-        return
-    if int(gain_rounds) < 1:
-        raise ValueError(f'gain_rounds must be >= 1, not {gain_rounds!r}')
-    if not (np.isfinite(float(gain_limit)) and float(gain_limit) >= 1):
-        raise ValueError(f'gain_limit must be finite and >= 1, not {gain_limit!r}')
-    if trim_outliers is not None:
-        raise ValueError('view_gains does not combine with trim_outliers')
-
-
 def _enqueue_gains(resto, limit: float) -> dict:
     """One round on the current stream, no host wait (``Restoration.view_gains``, then ``apply_view_gains`` with what it
     estimated); the fit must be started over.  The round's record, on the device."""
@@ -626,26 +649,12 @@ def _enqueue_gains(resto, limit: float) -> dict:
     return {'gains': gains, 'inv': inv, 'sums': sums, 'view_clipped': view_clipped, 'view_kept': kept, 'limit': float(limit)}
 
 
-def _enqueue_gain_refits(jobs: list, fit) -> None:
-    """The rounds of ``--view-gains`` for images whose first fit is enqueued: estimate and apply, ``fit_init`` with the initial
-    values of the first fit, and ``fit(jobs)`` -- the caller's way of fitting them, alone or in a batch launch -- again."""
-    for job in jobs:
-        job.gains = [] if job.view_gains else None
-    for i in range(max((int(j.gain_rounds) for j in jobs if j.view_gains), default=0)):
-        again = [j for j in jobs if j.view_gains and i < int(j.gain_rounds)]
-        for job in again:
-            job.gains.append(_enqueue_gains(job.resto, job.gain_limit))
-            _adam_begin(job.sucre, job.matches_data, params0=job.params0)
-        fit(again)
-
-
 def _write_gains(job) -> None:
     """``<stem>_gains.pt`` and one printed line per round."""
     rounds = job.gains   # host tensors (_restore_finish)
     stem = Path(job.image.name).stem
-    image_list = getattr(job.matches_data, 'image_list', None)
     n_views = int(rounds[0]['gains'].shape[0])
-    views = [im.name for im in image_list] if image_list else [str(k) for k in range(n_views)]
+    views = _view_names(job, n_views)
     gain = torch.ones((n_views, 3), dtype=torch.float64)
     for r in rounds:
         gain = gain * r['gains']
@@ -660,19 +669,33 @@ def _write_gains(job) -> None:
               f'(gain R {g[worst, 0]:.4f} G {g[worst, 1]:.4f} B {g[worst, 2]:.4f}; {int(r["view_clipped"].sum())} values clipped)')
 
 
-class _Job:
-    """One image between ``_restore_submit`` (everything enqueued, nothing waited for) and ``_restore_finish``."""
+# ---- the rounds behind a fit: change the store, start over, fit again ----------------------------------------------------------
+# per kind, in the order they run: the field of _Extras that switches it on, the field with its rounds, what a round enqueues
+# (with the workspace and the field that holds its argument), the attribute of _Job that collects the records, its word in a line
+_REFITS = (('trim_outliers', 'trim_rounds', _enqueue_trim, 'trim_outliers', 'trim', 'trim'),
+           ('view_gains', 'gain_rounds', _enqueue_gains, 'gain_limit', 'gains', 'gain'))
 
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
+
+def _enqueue_refits(jobs: list, fit) -> None:
+    """The rounds of --trim-outliers, then those of --view-gains, for images whose first fit is enqueued.  A round: for every image
+    that still has one to run, what the kind enqueues and ``fit_init`` with the initial values of the first fit; then
+    ``fit(images, 'trim round 1')`` -- the caller's way of fitting them again, alone or in a batch launch, and of saying so."""
+    for switch, rounds, enqueue, argument, records, word in _REFITS:
+        on = [j for j in jobs if getattr(j.extras, switch) not in (None, False)]
+        for job in on:
+            setattr(job, records, [])
+        for i in range(max((int(getattr(j.extras, rounds)) for j in on), default=0)):
+            again = [j for j in on if i < int(getattr(j.extras, rounds))]
+            for job in again:
+                getattr(job, records).append(enqueue(job.resto, getattr(job.extras, argument)))
+                _begin(job)
+            fit(again, f'{word} round {i + 1}')
 
 
 def _restore_submit(image: sfm.Image, colmap_model: sfm.COLMAPModel, output_dir: Path, light_model: bool,
                     use_closed_form: bool, min_cover: float, image_list: list[sfm.Image], lr: float, num_iter: int,
                     params_path: Path, force_compute_matches: bool, num_workers: int, device: str,
-                    defer_checks: bool = False, save_quality: bool = False, trim_outliers: float = None,
-                    trim_rounds: int = 1, view_gains: bool = False, gain_rounds: int = 1, gain_limit: float = 2.0,
-                    stretch=None) -> _Job:
+                    defer_checks: bool = False, extras: _Extras = _NO_EXTRAS) -> _Job:
     """Stages of sucre.py:160-210 up to and including the enqueued fit; the trace and J stay on the device.
     ``defer_checks``: the integrity verdicts and the observation count stay on the device until ``_restore_finish``
     reads them with the results -- waiting for them here would make the host wait for the matching, which shares the
@@ -694,7 +717,7 @@ def _restore_submit(image: sfm.Image, colmap_model: sfm.COLMAPModel, output_dir:
     if params_path is not None:
         sucre.load_state_dict(torch.load(params_path), strict=False)
     params0 = sucre.water_vector().detach().cpu().numpy()   # still on the host: no wait
-    sucre.stretch = stretch   # (lo, hi): every _rgb*.png of this model, snapshots included (plot_J)
+    sucre.stretch = extras.stretch   # (lo, hi): every _rgb*.png of this model, snapshots included (plot_J)
     sucre = sucre.to(device)
 
     reuse = not force_compute_matches and matches_file.on_disk()
@@ -718,10 +741,8 @@ def _restore_submit(image: sfm.Image, colmap_model: sfm.COLMAPModel, output_dir:
         _report_observations(image, len(matches_data))
 
     return _Job(image=image, sucre=sucre, matches_file=matches_file, matches_data=matches_data,
-                matches_path=matches_path, output_dir=output_dir, lr=lr, num_iter=num_iter, trace=None,
-                deferred_checks=defer_checks, params0=params0, save_quality=bool(save_quality), quality=None,
-                trim_outliers=trim_outliers, trim_rounds=int(trim_rounds), trim=None,
-                view_gains=bool(view_gains), gain_rounds=int(gain_rounds), gain_limit=float(gain_limit), gains=None)
+                matches_path=matches_path, output_dir=output_dir, lr=lr, num_iter=num_iter, deferred_checks=defer_checks,
+                params0=params0, extras=extras)
 
 
 def _report_observations(image: sfm.Image, n_obs: int) -> None:
@@ -730,63 +751,44 @@ def _report_observations(image: sfm.Image, n_obs: int) -> None:
         raise RuntimeError(f'{image.name}: no observation survived matching; nothing to fit')
 
 
-def _restore_enqueue_fit(job: _Job) -> None:
-    """The whole fit of sucre.py:138-156 enqueued in one go (no intermediate plots): no host synchronisation."""
-    print(f'Solve least squares with Adam optimizer ({job.num_iter} iterations).')
-    job.resto = resto = _adam_begin(job.sucre, job.matches_data, params0=job.params0)
-
-    def fit(jobs):
-        for j in jobs:
-            j.trace = j.resto.fit(j.num_iter, lr=j.lr, use_closed_form=j.sucre.use_closed_form)
-    fit([job])
-    _enqueue_trim_refits([job], fit)
-    _enqueue_gain_refits([job], fit)
-    _enqueue_quality(job, resto)
-
-
 def _restore_enqueue_fits(jobs: list) -> None:
-    """The fits of several images submitted together.  Images of one size without the extension planes (light model,
-    float32 colours) advance in ONE launch per iteration (``engine.fit_batch``: what a small image pays for most is its own
-    launches -- 640x480 x 5 views: 16.7 us per image and iteration alone, 7.3 in a launch of 32); every image's results are
-    the bits of ``_restore_enqueue_fit``.  Whatever does not fit a batch is fitted by itself."""
+    """The whole fit of sucre.py:138-156 of every image of a chunk enqueued in one go (no intermediate plots): no host
+    synchronisation.  Images of one size without the extension planes (light model, float32 colours) advance in ONE launch per
+    iteration (``engine.fit_batch``: what a small image pays for most is its own launches -- 640x480 x 5 views: 16.7 us per image
+    and iteration alone, 7.3 in a launch of 32), with the bits of a fit by itself.  Whatever does not fit a batch is fitted by
+    itself; a chunk of one says so once, a larger one before every refit too."""
     from . import engine
     groups: dict = {}
     singles = []
     for job in jobs:
-        resto = _adam_begin(job.sucre, job.matches_data, params0=job.params0)
-        job.resto = resto
+        job.resto = resto = _begin(job)
         if resto.light or resto.float_colour:
             singles.append(job)
         else:
             groups.setdefault((resto.H, resto.W, resto.obs_format, job.num_iter, job.lr, job.sucre.use_closed_form), []).append(job)
 
-    def fit_alone(members):
+    def fit_alone(members, after=None):
         for job in members:
-            print(f'Solve least squares with Adam optimizer ({job.num_iter} iterations).')
+            if after is None or len(jobs) > 1:
+                print(f'Solve least squares with Adam optimizer ({job.num_iter} iterations).')
             job.trace = job.resto.fit(job.num_iter, lr=job.lr, use_closed_form=job.sucre.use_closed_form)
 
-    for key, members in groups.items():
+    def fit_together(members, after=None):   # (the refits too: a batch launch gives every image its own bits)
         if len(members) == 1:
-            singles.extend(members)
-            continue
+            return fit_alone(members, after)
+        first = members[0]   # (one group: one num_iter, lr and use_closed_form)
+        print(f'Solve least squares with Adam optimizer ({first.num_iter} iterations), {len(members)} images per launch.')
+        traces = engine.fit_batch([j.resto for j in members], first.num_iter, lr=first.lr, use_closed_form=first.sucre.use_closed_form)
+        for j, t in zip(members, traces):
+            j.trace = t
 
-        def fit_together(members, key=key):   # (the refits after a trim too: a batch launch gives every image its own bits)
-            if len(members) == 1:
-                return fit_alone(members)
-            print(f'Solve least squares with Adam optimizer ({key[3]} iterations), {len(members)} images per launch.')
-            traces = engine.fit_batch([j.resto for j in members], key[3], lr=key[4], use_closed_form=key[5])
-            for j, t in zip(members, traces):
-                j.trace = t
-        fit_together(members)
-        _enqueue_trim_refits(members, fit_together)
-        _enqueue_gain_refits(members, fit_together)
-        for j in members:
-            _enqueue_quality(j, j.resto)
-    fit_alone(singles)
-    _enqueue_trim_refits(singles, fit_alone)
-    _enqueue_gain_refits(singles, fit_alone)
-    for job in singles:
-        _enqueue_quality(job, job.resto)
+    batches = [members for members in groups.values() if len(members) > 1]
+    singles += [members[0] for members in groups.values() if len(members) == 1]
+    for members, fit in [(members, fit_together) for members in batches] + [(singles, fit_alone)]:
+        fit(members)
+        _enqueue_refits(members, fit)
+        for job in members:
+            _enqueue_quality(job)
 
 
 def fit_batch_size(images: list, light_model: bool = False, in_flight: int = 2, n_views: int | None = None, device='cuda') -> int:
@@ -806,9 +808,8 @@ def fit_batch_size(images: list, light_model: bool = False, in_flight: int = 2, 
     batch = 8 if W * H < 1_000_000 else 1
     if batch > 1 and n_views:
         from . import _lib, engine
-        n = min(int(n_views), engine.MAX_VIEWS)
-        cap = (n + 7) // 8 * 8 if n <= 256 else (n + 31) // 32 * 32    # engine.acquire_restoration's capacity steps
-        need = int(_lib.load().sucre_workspace_bytes(H, W, min(cap, engine.MAX_VIEWS)))
+        cap = min(engine.view_capacity(min(int(n_views), engine.MAX_VIEWS)), engine.MAX_VIEWS)
+        need = int(_lib.load().sucre_workspace_bytes(H, W, cap))
         try:
             free = int(torch.cuda.mem_get_info(device)[0]) + int(torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device))
         except Exception:   # no device to ask: keep the plain rule
@@ -816,6 +817,11 @@ def fit_batch_size(images: list, light_model: bool = False, in_flight: int = 2, 
         while batch > 1 and need * batch * max(1, int(in_flight)) > 0.8 * free:
             batch //= 2
     return batch
+
+
+def _rounds_on_host(rounds: list | None) -> list | None:
+    """The records of a job's trim or gain rounds with their tensors copied to the host; None when it ran none."""
+    return None if rounds is None else [{k: (v.cpu() if torch.is_tensor(v) else v) for k, v in r.items()} for r in rounds]
 
 
 def _restore_finish(job: _Job, keep_matches: bool, writers: ThreadPoolExecutor | None = None):
@@ -832,10 +838,7 @@ def _restore_finish(job: _Job, keep_matches: bool, writers: ThreadPoolExecutor |
         _pull_results(sucre, _restoration_of(job.matches_data))
     if job.quality is not None:
         job.quality = tuple(t.cpu() for t in job.quality)
-    if job.trim is not None:
-        job.trim = [{k: (v.cpu() if torch.is_tensor(v) else v) for k, v in r.items()} for r in job.trim]
-    if job.gains is not None:
-        job.gains = [{k: (v.cpu() if torch.is_tensor(v) else v) for k, v in r.items()} for r in job.gains]
+    job.trim, job.gains = _rounds_on_host(job.trim), _rounds_on_host(job.gains)
     if keep_matches and job.matches_file.restoration._views_dev is not None:   # freshly matched (not loaded from this
         if job.trim is not None:                                               # very file); needs the live workspace
             print(f'Keep {job.matches_file.save(survivors=True)} (the observations that survived the trim).')
@@ -881,33 +884,14 @@ def restore_image(image: sfm.Image, colmap_model: sfm.COLMAPModel, output_dir: P
 
 
 def _restore_one(image, colmap_model, output_dir, light_model, use_closed_form, min_cover, image_list, lr, num_iter, batch_size,
-                 save_interval, params_path, force_compute_matches, keep_matches, num_workers, device, save_quality: bool = False,
-                 trim_outliers: float = None, trim_rounds: int = 1, view_gains: bool = False, gain_rounds: int = 1,
-                 gain_limit: float = 2.0, stretch=None):
-    """``restore_image`` plus what its pinned signature has no room for (``save_quality``: --save-quality; ``trim_outliers``,
-    ``trim_rounds``: --trim-outliers, --trim-rounds; ``view_gains``, ``gain_rounds``, ``gain_limit``: --view-gains, --gain-rounds,
-    --gain-limit; ``stretch``: the ``(lo, hi)`` of --stretch-from)."""
+                 save_interval, params_path, force_compute_matches, keep_matches, num_workers, device, extras: _Extras = _NO_EXTRAS):
+    """``restore_image`` plus what its pinned signature has no room for (``_Extras``)."""
     sfm.require_gpu(device, 'restore_image')
-    if stretch is not None:
-        stretch = check_stretch(stretch)
-    _check_trim(trim_outliers, trim_rounds)
-    _check_gains(view_gains, gain_rounds, gain_limit, trim_outliers)
-    if trim_outliers is not None and save_interval is not None:
-        raise ValueError('trim_outliers does not combine with save_interval snapshots')
-    if view_gains and save_interval is not None:
-        raise ValueError('view_gains does not combine with save_interval snapshots')
+    extras = extras.checked(save_interval)
     job = _restore_submit(image, colmap_model, output_dir, light_model, use_closed_form, min_cover, image_list, lr,
-                          num_iter, params_path, force_compute_matches, num_workers, device, save_quality=save_quality,
-                          trim_outliers=trim_outliers, trim_rounds=trim_rounds, view_gains=view_gains, gain_rounds=gain_rounds,
-                          gain_limit=gain_limit, stretch=stretch)
-    if save_quality:
-        job.sucre._quality_wanted = True   # adam enqueues the pass behind its last fit
+                          num_iter, params_path, force_compute_matches, num_workers, device, extras=extras)
     adam(sucre=job.sucre, matches_data=job.matches_data, lr=lr, num_iter=num_iter, batch_size=batch_size,
-         save_dir=job.output_dir, save_interval=save_interval, device=device, trim_outliers=trim_outliers, trim_rounds=trim_rounds,
-         view_gains=view_gains, gain_rounds=gain_rounds, gain_limit=gain_limit)
-    job.quality = job.sucre.__dict__.pop('_quality', None)
-    job.trim = job.sucre.__dict__.pop('_trim', None)
-    job.gains = job.sucre.__dict__.pop('_gains', None)
+         save_dir=job.output_dir, save_interval=save_interval, device=device, _job=job)
     return _restore_finish(job, keep_matches)
 
 
@@ -922,20 +906,18 @@ def restore_images(images: list[sfm.Image], colmap_model: sfm.COLMAPModel, outpu
     ``kw``): the rounds of --trim-outliers, enqueued with the image behind its first fit, no host wait added; ``view_gains=False,
     gain_rounds=1, gain_limit=2.0``: those of --view-gains, likewise; ``stretch=(lo, hi)``: every ``_rgb.png`` by this fixed
     stretch (``check_stretch``) instead of the image's own percentiles (--stretch-from)."""
-    if kw.get('stretch') is not None:
-        kw['stretch'] = check_stretch(kw['stretch'])
-    _check_trim(kw.get('trim_outliers'), kw.get('trim_rounds', 1))
-    _check_gains(kw.get('view_gains', False), kw.get('gain_rounds', 1), kw.get('gain_limit', 2.0), kw.get('trim_outliers'))
+    extras = _Extras(**{f.name: kw.pop(f.name) for f in dataclasses.fields(_Extras) if f.name in kw}).checked()
     pending: list[tuple[int, list]] = []
     written = []
     if fit_batch is None:
         candidates = kw.get('image_list')
         n_views = len(candidates) if candidates is not None else len(colmap_model.images)
         fit_batch = fit_batch_size(images, bool(kw.get('light_model', False)), in_flight=in_flight, n_views=n_views, device=device)
-    _restore_pipeline(images, colmap_model, output_dir, in_flight, keep_matches, device, pending, written, kw, max(1, int(fit_batch)))
+    _restore_pipeline(images, colmap_model, output_dir, in_flight, keep_matches, device, pending, written, kw, extras, max(1, int(fit_batch)))
 
 
-def _restore_pipeline(images, colmap_model, output_dir, in_flight, keep_matches, device, pending, written, kw, fit_batch: int = 1) -> None:
+def _restore_pipeline(images, colmap_model, output_dir, in_flight, keep_matches, device, pending, written, kw, extras: _Extras,
+                      fit_batch: int = 1) -> None:
     from . import engine
     # writer threads: the CPUs this process may use minus two (this thread and the HIP runtime's), at most 32
     with ThreadPoolExecutor(max_workers=max(1, int(os.environ.get('SUCRE_WRITER_THREADS', min(32, loader.effective_cpus() - 2)))),
@@ -956,11 +938,8 @@ def _restore_pipeline(images, colmap_model, output_dir, in_flight, keep_matches,
                 jobs = []
                 for k, image in enumerate(chunk):
                     with engine.slot_lane(k):   # every image of the chunk in its own workspace
-                        jobs.append(_restore_submit(image, colmap_model, output_dir, device=device, defer_checks=True, **kw))
-                if len(jobs) == 1:
-                    _restore_enqueue_fit(jobs[0])
-                else:
-                    _restore_enqueue_fits(jobs)
+                        jobs.append(_restore_submit(image, colmap_model, output_dir, device=device, defer_checks=True, extras=extras, **kw))
+                _restore_enqueue_fits(jobs)
             pending.append((slot, jobs))
         for slot, jobs in pending:
             finish(slot, jobs)
@@ -1527,25 +1506,54 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
     return data
 
 
-def _refuse_mosaic_flags(args, world: int = 1) -> None:
-    """What --mosaic does not combine with, refused before any file is opened."""
-    refused = [('--shared-water', bool(getattr(args, 'shared_water', False)), 'nothing is fitted, so nothing is shared'),
-               ('--apply-water', getattr(args, 'apply_water', None) is not None, 'restore first, into the directory to mosaic, then mosaic it'),
-               ('--check-consistency', getattr(args, 'check_consistency', None) is not None, 'check the directory in a run of its own'),
-               ('--trim-outliers', getattr(args, 'trim_outliers', None) is not None or getattr(args, 'trim_rounds', None) is not None,
-                'there is no fit to trim'),
-               ('--view-gains', bool(getattr(args, 'view_gains', False)) or getattr(args, 'gain_rounds', None) is not None
-                or getattr(args, 'gain_limit', None) is not None, 'there is no fit to estimate gains from'),
-               ('--save-quality', bool(getattr(args, 'save_quality', False)), 'there is no fit, hence no residuals'),
-               ('--save-interval', args.save_interval is not None, 'there are no iterations to snapshot'),
-               ('--params-path', args.params_path is not None, 'no parameters are read: the restored images are'),
-               ('--keep-matches', bool(args.keep_matches), 'nothing is matched'),
-               ('--common-stretch', bool(getattr(args, 'common_stretch', False)),
-                'the mosaic is one picture: it is stretched by its own percentiles, or by --stretch-from'),
-               ('--image-scale', args.image_scale != 1, 'resized images have float32 colours, and the raw mosaic takes uint8')]
-    for flag, given, why in refused:
-        if given:
-            raise SystemExit(f'--mosaic: {flag} does not combine with it ({why}); drop one of the two flags')
+# ---- what the modes that do not fit refuse ------------------------------------------------------------------------------------
+_GIVEN_WITH = {'--trim-outliers': ('--trim-rounds',), '--view-gains': ('--gain-rounds', '--gain-limit')}   # flags that count as it
+
+
+def _given(args, flag: str) -> bool:
+    """Whether ``flag`` stands on the command line, told from the namespace: a flag of the reference is there with its default,
+    one of this engine's own only when it was given (``_Parser``); a flag that only goes with another counts as that one."""
+    if flag == '--image-scale':
+        return args.image_scale != 1
+    value = getattr(args, flag[2:].replace('-', '_'), None)
+    return (value is not None and value is not False) or any(_given(args, other) for other in _GIVEN_WITH.get(flag, ()))
+
+
+_NOTHING_SHARED, _NO_TRIM, _NO_GAINS = 'nothing is fitted, so nothing is shared', 'there is no fit to trim', 'there is no fit to estimate gains from'
+_NO_RESIDUALS, _NO_SNAPSHOT = 'there is no fit, hence no residuals', 'there are no iterations to snapshot'
+_NO_PARAMETERS, _NO_PICTURE = 'no parameters are read: the restored images are', 'no picture of J is written'
+_MODE_REFUSES = {   # mode -> (flag, why), in the order they are looked at
+    '--mosaic': [('--shared-water', _NOTHING_SHARED),
+                 ('--apply-water', 'restore first, into the directory to mosaic, then mosaic it'),
+                 ('--check-consistency', 'check the directory in a run of its own'),
+                 ('--trim-outliers', _NO_TRIM), ('--view-gains', _NO_GAINS), ('--save-quality', _NO_RESIDUALS),
+                 ('--save-interval', _NO_SNAPSHOT), ('--params-path', _NO_PARAMETERS), ('--keep-matches', 'nothing is matched'),
+                 ('--common-stretch', 'the mosaic is one picture: it is stretched by its own percentiles, or by --stretch-from'),
+                 ('--image-scale', 'resized images have float32 colours, and the raw mosaic takes uint8')],
+    '--check-consistency': [('--shared-water', _NOTHING_SHARED),
+                            ('--apply-water', 'restore first, into the directory to check, then check it'),
+                            ('--trim-outliers', _NO_TRIM), ('--view-gains', _NO_GAINS), ('--save-quality', _NO_RESIDUALS),
+                            ('--save-interval', _NO_SNAPSHOT), ('--params-path', _NO_PARAMETERS),
+                            ('--keep-matches', 'no match list is kept: the pairs are compared where they are found'),
+                            ('--common-stretch', _NO_PICTURE), ('--stretch-from', _NO_PICTURE),
+                            ('--image-scale', 'resized images have float32 colours, and the raw comparison reads uint8'),
+                            ('--mosaic', 'make the mosaic in a run of its own')],
+    '--apply-water': [('--shared-water', _NOTHING_SHARED), ('--trim-outliers', _NO_TRIM), ('--view-gains', _NO_GAINS),
+                      ('--save-quality', 'a single-view inversion has no residuals'), ('--save-interval', _NO_SNAPSHOT),
+                      ('--params-path', 'the parameters come from the --apply-water file'), ('--keep-matches', 'nothing is matched'),
+                      ('--mosaic', 'restore first, then make the mosaic of that directory')],
+}
+
+
+def _refuse_mode_flags(args, mode: str) -> None:
+    """What ``mode`` (--mosaic, --check-consistency, --apply-water) does not combine with, refused before any file is opened."""
+    for flag, why in _MODE_REFUSES[mode]:
+        if _given(args, flag):
+            raise SystemExit(f'{mode}: {flag} does not combine with it ({why}); drop one of the two flags')
+
+
+def _refuse_mosaic_values(args, world: int = 1) -> None:
+    """The values of --mosaic-gsd and --mosaic-blend and the world size a mosaic takes, refused before any file is opened."""
     gsd = getattr(args, 'mosaic_gsd', None)
     if gsd is not None and not (np.isfinite(gsd) and gsd > 0):
         raise SystemExit(f'--mosaic-gsd: G must be a finite size > 0 in metres, not {gsd}')
@@ -1556,27 +1564,6 @@ def _refuse_mosaic_flags(args, world: int = 1) -> None:
         raise SystemExit(f'--mosaic: a world size of {world} is not supported yet: the four phases are separate entries of the library '
                          f'so that ranks can all-reduce bounds, keys and pixel words between them, but that all-reduce is not built; '
                          f'run one process')
-
-
-def _refuse_consistency_flags(args) -> None:
-    """What --check-consistency does not combine with, refused before any file is opened."""
-    refused = [('--shared-water', bool(getattr(args, 'shared_water', False)), 'nothing is fitted, so nothing is shared'),
-               ('--apply-water', getattr(args, 'apply_water', None) is not None, 'restore first, into the directory to check, then check it'),
-               ('--trim-outliers', getattr(args, 'trim_outliers', None) is not None or getattr(args, 'trim_rounds', None) is not None,
-                'there is no fit to trim'),
-               ('--view-gains', bool(getattr(args, 'view_gains', False)) or getattr(args, 'gain_rounds', None) is not None
-                or getattr(args, 'gain_limit', None) is not None, 'there is no fit to estimate gains from'),
-               ('--save-quality', bool(getattr(args, 'save_quality', False)), 'there is no fit, hence no residuals'),
-               ('--save-interval', args.save_interval is not None, 'there are no iterations to snapshot'),
-               ('--params-path', args.params_path is not None, 'no parameters are read: the restored images are'),
-               ('--keep-matches', bool(args.keep_matches), 'no match list is kept: the pairs are compared where they are found'),
-               ('--common-stretch', bool(getattr(args, 'common_stretch', False)), 'no picture of J is written'),
-               ('--stretch-from', getattr(args, 'stretch_from', None) is not None, 'no picture of J is written'),
-               ('--image-scale', args.image_scale != 1, 'resized images have float32 colours, and the raw comparison reads uint8'),
-               ('--mosaic', getattr(args, 'mosaic', None) is not None, 'make the mosaic in a run of its own')]
-    for flag, given, why in refused:
-        if given:
-            raise SystemExit(f'--check-consistency: {flag} does not combine with it ({why}); drop one of the two flags')
 
 
 def _refuse_stretch_flags(args) -> None:
@@ -1593,23 +1580,6 @@ def _refuse_stretch_flags(args) -> None:
                          'flags (--stretch-from combines with snapshots)')
 
 
-def _refuse_apply_flags(args) -> None:
-    """What --apply-water does not combine with, refused before any file is opened."""
-    refused = [('--shared-water', bool(getattr(args, 'shared_water', False)), 'nothing is fitted, so nothing is shared'),
-               ('--trim-outliers', getattr(args, 'trim_outliers', None) is not None or getattr(args, 'trim_rounds', None) is not None,
-                'there is no fit to trim'),
-               ('--view-gains', bool(getattr(args, 'view_gains', False)) or getattr(args, 'gain_rounds', None) is not None
-                or getattr(args, 'gain_limit', None) is not None, 'there is no fit to estimate gains from'),
-               ('--save-quality', bool(getattr(args, 'save_quality', False)), 'a single-view inversion has no residuals'),
-               ('--save-interval', args.save_interval is not None, 'there are no iterations to snapshot'),
-               ('--params-path', args.params_path is not None, 'the parameters come from the --apply-water file'),
-               ('--keep-matches', bool(args.keep_matches), 'nothing is matched'),
-               ('--mosaic', getattr(args, 'mosaic', None) is not None, 'restore first, then make the mosaic of that directory')]
-    for flag, given, why in refused:
-        if given:
-            raise SystemExit(f'--apply-water: {flag} does not combine with it ({why}); drop one of the two flags')
-
-
 def parse_args(args: argparse.Namespace):
     """Runs the CLI request (sucre.py:222-261); with WORLD_SIZE > 1 each rank restores its shard of the images."""
     rank, local_rank, world = sdist.env_rank_world()
@@ -1622,16 +1592,17 @@ def parse_args(args: argparse.Namespace):
     if mosaic_dir is None and getattr(args, 'mosaic_blend', None) is not None:
         raise SystemExit('--mosaic-blend: only with --mosaic DIR')
     if mosaic_dir is not None:
-        _refuse_mosaic_flags(args, world)
+        _refuse_mode_flags(args, '--mosaic')
+        _refuse_mosaic_values(args, world)
     if check is not None:
-        _refuse_consistency_flags(args)
+        _refuse_mode_flags(args, '--check-consistency')
     _refuse_stretch_flags(args)
     common = bool(getattr(args, 'common_stretch', False))
     stretch = None
     if getattr(args, 'stretch_from', None) is not None:   # read and checked before any image is opened
         stretch = read_stretch_file(args.stretch_from)
     if apply is not None:
-        _refuse_apply_flags(args)
+        _refuse_mode_flags(args, '--apply-water')
         water = read_water_file(apply, args.light_model)
     _refuse_trim_flags(args)
     _refuse_gain_flags(args)
@@ -1724,36 +1695,27 @@ def parse_args(args: argparse.Namespace):
             torch.set_num_threads(threads_before)
 
 
+def _extras_of(args, stretch=None) -> _Extras:
+    """The record of a command line; a flag of this engine's own is in the namespace only when it was given (``_Parser``)."""
+    given = {f.name: getattr(args, f.name) for f in dataclasses.fields(_Extras) if hasattr(args, f.name)}
+    return _Extras(**{**given, 'stretch': stretch})
+
+
 def _run_request(args, images, image_list, colmap_model, device, survey: bool, in_flight: int, stretch=None) -> None:
     if str(device).startswith('cuda') and images:   # start decoding + uploading the scene now, in the background
         loader.prefetch_for_targets(images, image_list, device, num_workers=args.num_workers, min_cover=args.min_cover)
-    quality = {'save_quality': True} if getattr(args, 'save_quality', False) else {}
-    trim = getattr(args, 'trim_outliers', None)
-    if trim is not None:
-        quality.update(trim_outliers=float(trim), trim_rounds=int(getattr(args, 'trim_rounds', 1)))
-    if getattr(args, 'view_gains', False):
-        quality.update(view_gains=True, gain_rounds=int(getattr(args, 'gain_rounds', 1)), gain_limit=float(getattr(args, 'gain_limit', 2.0)))
-    if stretch is not None:
-        quality.update(stretch=stretch)
+    extras = _extras_of(args, stretch)
     if survey:
         restore_images(images, colmap_model, args.output_dir, in_flight=in_flight, keep_matches=args.keep_matches,
                        device=device, light_model=args.light_model, use_closed_form=args.use_closed_form,
                        min_cover=args.min_cover, image_list=image_list, lr=args.learning_rate, num_iter=args.num_iter,
                        params_path=args.params_path, force_compute_matches=args.force_compute_matches,
-                       num_workers=args.num_workers, **quality)
+                       num_workers=args.num_workers, **vars(extras))
         return
     for image in images:
-        if quality:
-            _restore_one(image, colmap_model, args.output_dir, args.light_model, args.use_closed_form, args.min_cover, image_list,
-                         args.learning_rate, args.num_iter, args.batch_size, args.save_interval, args.params_path,
-                         args.force_compute_matches, args.keep_matches, args.num_workers, device, **quality)
-            continue
-        restore_image(image=image, colmap_model=colmap_model, output_dir=args.output_dir,
-                      light_model=args.light_model, use_closed_form=args.use_closed_form, min_cover=args.min_cover,
-                      image_list=image_list, lr=args.learning_rate, num_iter=args.num_iter,
-                      batch_size=args.batch_size, save_interval=args.save_interval, params_path=args.params_path,
-                      force_compute_matches=args.force_compute_matches, keep_matches=args.keep_matches,
-                      num_workers=args.num_workers, device=device)
+        _restore_one(image, colmap_model, args.output_dir, args.light_model, args.use_closed_form, args.min_cover, image_list,
+                     args.learning_rate, args.num_iter, args.batch_size, args.save_interval, args.params_path,
+                     args.force_compute_matches, args.keep_matches, args.num_workers, device, extras)
 
 
 def _refuse_trim_flags(args) -> None:
@@ -1808,9 +1770,7 @@ def _check_shared_memory(images: list, image_list: list, light_model: bool, devi
     sucre_light_workspace_bytes with the light model, at the engine's capacity steps) must fit into what is free now."""
     from . import _lib, engine
     lib = _lib.load()
-    n = min(len(image_list), engine.MAX_VIEWS)
-    cap = (n + 7) // 8 * 8 if n <= 256 else (n + 31) // 32 * 32    # engine.acquire_restoration's capacity steps
-    cap = min(cap, engine.MAX_VIEWS)
+    cap = min(engine.view_capacity(min(len(image_list), engine.MAX_VIEWS)), engine.MAX_VIEWS)
     need = 0
     for im in images:
         H, W = int(im.camera.height), int(im.camera.width)
@@ -1837,23 +1797,24 @@ def restore_shared_water(images: list, colmap_model: sfm.COLMAPModel, args, imag
         sdist.init_process_group()
     if str(device).startswith('cuda') and images:
         loader.prefetch_for_targets(images, image_list, device, num_workers=args.num_workers, min_cover=args.min_cover)
+    extras = _extras_of(args, None if isinstance(stretch, str) else stretch)
     jobs = []
     for k, image in enumerate(images):
         with engine.slot_lane(k):   # every image in its own workspace
             jobs.append(_restore_submit(image, colmap_model, args.output_dir, args.light_model, args.use_closed_form,
                                         args.min_cover, image_list, args.learning_rate, args.num_iter, args.params_path,
-                                        args.force_compute_matches, args.num_workers, device,
-                                        save_quality=bool(getattr(args, 'save_quality', False)),
-                                        stretch=None if isinstance(stretch, str) else stretch))
-    restos = [_adam_begin(j.sucre, j.matches_data, params0=jobs[0].params0) for j in jobs]
+                                        args.force_compute_matches, args.num_workers, device, extras=extras))
+    for job in jobs:
+        job.resto = _adam_begin(job.sucre, job.matches_data, params0=jobs[0].params0)
+    restos = [job.resto for job in jobs]
     T = int(args.num_iter)
     trace = torch.zeros((T, 20 if args.light_model else 10), dtype=torch.float64, device=restos[0].device)
     print(f'Solve least squares with Adam optimizer ({T} iterations), shared water over {len(request)} images.')
     group = engine.HipWaterGroup(restos, lr=args.learning_rate, use_closed_form=args.use_closed_form, trace=trace,
                                  params0=jobs[0].params0)
     sdist.fit_shared_water(group, T)
-    for job, resto in zip(jobs, restos):   # --save-quality: behind the group's finish, per image, before anything is read
-        _enqueue_quality(job, resto)
+    for job in jobs:   # --save-quality: behind the group's finish, per image, before anything is read
+        _enqueue_quality(job)
     trace = trace.cpu().numpy()
     _log_trace(trace, 0)
     for job, resto in zip(jobs, restos):

@@ -117,10 +117,13 @@ def test_refused_values(extra, word, monkeypatch):
 
 
 def test_keywords_of_the_host_entry_points():
+    import dataclasses
     import inspect
-    for fn in (sucre.adam, sucre._restore_one, sucre._restore_submit):
-        par = inspect.signature(fn).parameters
-        assert par['view_gains'].default is False and par['gain_rounds'].default == 1 and par['gain_limit'].default == 2.0, fn
+    par = inspect.signature(sucre.adam).parameters
+    assert par['view_gains'].default is False and par['gain_rounds'].default == 1 and par['gain_limit'].default == 2.0
+    field = {f.name: f.default for f in dataclasses.fields(sucre._Extras)}     # what _restore_one and _restore_submit take
+    assert field['view_gains'] is False and field['gain_rounds'] == 1 and field['gain_limit'] == 2.0
+    sucre.restore_images([], None, None, fit_batch=1, view_gains=False, gain_rounds=1, gain_limit=2.0)     # accepted: no image
     assert 'view_gains' not in inspect.signature(sucre.restore_image).parameters      # the reference's signature stays
     with pytest.raises(ValueError, match='gain_rounds'):
         sucre.restore_images([], None, None, view_gains=True, gain_rounds=0)
@@ -133,7 +136,7 @@ def test_keywords_of_the_host_entry_points():
         sucre.adam(None, None, save_dir='x', save_interval=5, view_gains=True)
     with pytest.raises(ValueError, match='trim_outliers'):
         sucre.adam(None, None, view_gains=True, trim_outliers=3.0)
-    sucre._check_gains(False, 0, 0.5)      # without view_gains the other two are not looked at
+    sucre._Extras(view_gains=False, gain_rounds=0, gain_limit=0.5).checked()      # without view_gains the other two are not looked at
 
 
 # ---- the C ABI --------------------------------------------------------------------------------------------------------------

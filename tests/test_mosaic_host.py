@@ -165,9 +165,9 @@ def test_stretch_from_combines_with_mosaic(tmp_path, monkeypatch):
 
 def test_the_other_modes_refuse_mosaic_in_their_own_wording():
     args = sucre.build_parser().parse_args(BASE + ['--mosaic', 'r'])
-    for refuse, flag in ((sucre._refuse_consistency_flags, '--check-consistency'), (sucre._refuse_apply_flags, '--apply-water')):
+    for flag in ('--check-consistency', '--apply-water'):
         with pytest.raises(SystemExit) as e:
-            refuse(args)
+            sucre._refuse_mode_flags(args, flag)
         assert str(e.value.code).startswith(f'{flag}: --mosaic does not combine with it (') and str(e.value.code).endswith('; drop one of the two flags')
 
 

@@ -46,10 +46,13 @@ def test_refused_values(extra, word, monkeypatch):
 
 
 def test_keywords_of_the_host_entry_points():
+    import dataclasses
     import inspect
-    for fn in (sucre.adam, sucre._restore_one, sucre._restore_submit):
-        par = inspect.signature(fn).parameters
-        assert par['trim_outliers'].default is None and par['trim_rounds'].default == 1, fn
+    par = inspect.signature(sucre.adam).parameters
+    assert par['trim_outliers'].default is None and par['trim_rounds'].default == 1
+    field = {f.name: f.default for f in dataclasses.fields(sucre._Extras)}     # what _restore_one and _restore_submit take
+    assert field['trim_outliers'] is None and field['trim_rounds'] == 1
+    sucre.restore_images([], None, None, fit_batch=1, trim_outliers=None, trim_rounds=1)     # accepted: no image, nothing to do
     with pytest.raises(ValueError, match='trim_outliers'):
         sucre.restore_images([], None, None, trim_outliers=-1.0)
     with pytest.raises(ValueError, match='trim_rounds'):

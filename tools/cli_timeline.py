@@ -36,7 +36,7 @@ def main():
     spacing = float(sys.argv[6]) if len(sys.argv) > 6 else 0.1
     survey = synth.make_survey(W, H, gx, gy, seed=3, spacing=spacing, device='cuda')
     for owner, name in ((loader, '_imread_rgb_u8'), (loader, '_imread_depth_u16'), (sucre, '_restore_submit'),
-                        (sucre, '_restore_enqueue_fit'), (sucre, '_restore_finish'), (sucre, '_write_outputs'),
+                        (sucre, '_restore_enqueue_fits'), (sucre, '_restore_finish'), (sucre, '_write_outputs'),
                         (sucre.SUCRe, 'save_plots'), (sucre.SUCRe, '_plot_J_device'), (sucre.SUCRe, 'plot_J'),
                         (sucre.SUCRe, 'plot_reconstruction'), (torch, 'save'),
                         (sfm.Image, 'match_images'), (sfm.Image, 'overlapping_views'), (loader, 'prefetch_device_views'),
@@ -128,7 +128,7 @@ def main():
         print(f'  {kind:18s} {label:40s} {c:5d} {s:8.3f} {s / c * 1e3:8.1f}')
     print('main-thread timeline (s): submit[start-end] enqueue[end] finish[start-end]')
     rows = [(a, b, label) for th, label, a, b in SPANS if th == 'MainThread' and label in
-            ('sucre._restore_submit', 'sucre._restore_enqueue_fit', 'sucre._restore_finish')]
+            ('sucre._restore_submit', 'sucre._restore_enqueue_fits', 'sucre._restore_finish')]
     for a, b, label in sorted(rows)[:40]:
         print(f'  {a:7.3f} {b:7.3f} {(b - a) * 1e3:7.1f} ms  {label}')
     third = sorted((a, b) for th, label, a, b in SPANS if th == 'MainThread' and label == 'sucre._restore_submit')
