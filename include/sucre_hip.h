@@ -599,9 +599,10 @@ int sucre_view_consistency(int H, int W, int n_views, const sucre_view_t *target
 /*
  * ---- seabed mosaic of restored images: best-view ortho splat -------------------------------------------------------------------
  * Every pixel of every image is dropped onto a plane grid and the pixel seen through the least water wins its cell; nothing is
- * blended and no hole is filled.  Image i of the request (its ORDINAL: first_ordinal + its index in the call) has a depth map, a
- * camera, a world-from-camera pose, its restored J (H,W,3) float32 and its raw uint8 colours.  Pixel p = v W + u TAKES PART when
- * depth > 0 and J[p] holds no NaN in any channel (plot_J's rule, sucre.py:86-87).  In float32, every FMA explicit:
+ * blended here (the blend: below) and no hole is filled (sucre_mosaic_fill_*, further below).  Image i of the request (its
+ * ORDINAL: first_ordinal + its index in the call) has a depth map, a camera, a world-from-camera pose, its restored J (H,W,3)
+ * float32 and its raw uint8 colours.  Pixel p = v W + u TAKES PART when depth > 0 and J[p] holds no NaN in any channel (plot_J's
+ * rule, sucre.py:86-87).  In float32, every FMA explicit:
  *   cP = Kinv (d [u+.5, v+.5, 1])                     sfm.py:90-93 (Image.unproject_depth), the match kernels' chain
  *   z  = sqrt(cP.x cP.x + cP.y cP.y + cP.z cP.z)       the range, as sucre_invert_images forms it
  *   wP = R cP + t                                      sfm.py:49-55 (Pose.transform)
@@ -679,6 +680,38 @@ int sucre_mosaic_accumulate(void *table_dev, int n_images, const sucre_mosaic_im
                             void *stream);
 int sucre_mosaic_normalize(const sucre_mosaic_grid_t *grid, const int64_t *acc_dev, float *J_out, uint8_t *raw_out, float *weight_out,
                            int32_t *samples_out, void *stream);
+
+/*
+ * ---- hole filling of the finished mosaic: a bounded push-pull over a pyramid of the grid ------------------------------------------
+ * A pure grid operation on the outputs of sucre_mosaic_gather (or of sucre_mosaic_normalize with the same source): no image is
+ * read, no atomic issued, every number is a fixed chain of float32 operations, one IEEE operation per step -- the same bits on
+ * every run.  Level 0 is the mosaic (Hm x Wm), level l+1 has ((H_l + 1) >> 1) x ((W_l + 1) >> 1) cells; `levels` = L in 1..24.  A
+ * record is 8 float32 (32 bytes): c[0..2] for J, c[3..5] for the raw colour as float, w, g.  Level 0 is read in place: a cell is
+ * valid (w = 1, c its J and raw values) when source >= 0 and its three J channels are finite, otherwise w = 0 and every c counts
+ * as +0.0f.
+ *   sucre_mosaic_fill_bytes  the bytes of levels 1..L, each level row-major and 256-byte aligned (0 and an error for bad sizes)
+ *   sucre_mosaic_fill_pull   levels 1..L, one launch each: with the children (2y+dy, 2x+dx) in the order (0,0), (0,1), (1,0), (1,1),
+ *                         one outside the level a record of zeros, Wt = ((w0 + w1) + w2) + w3 and S_k = ((w0 c0_k + w1 c1_k) +
+ *                         w2 c2_k) + w3 c3_k, every product rounded before its add.  Wt > 0: c_k = S_k / Wt, w = Wt 0.25f,
+ *                         g = l+1; otherwise the record is all +0.0f.  Every record of the pyramid is written.
+ *   sucre_mosaic_fill_push   l = L-1 .. 0, one launch each, in place: a cell with w > 0 is untouched; for a cell (y, x) with
+ *                         w == 0, py = y >> 1, ny = clamp(py + (y & 1 ? 1 : -1), 0, H_(l+1) - 1), px and nx likewise, the taps
+ *                         (py,px), (py,nx), (ny,px), (ny,nx) of level l+1 have a_i = 9/16, 3/16, 3/16, 1/16 where the tap's w > 0 and
+ *                         0 elsewhere; A and S_k are summed as Wt and S_k above.  A > 0: c_k = S_k / A, w = 1, g = the largest g of
+ *                         the taps with a_i > 0; otherwise the cell stays empty.  Level 0 writes, for EVERY cell: J_filled
+ *                         (Hm,Wm,3) float32 -- a measured cell (source >= 0) its J bit for bit, finite or not, a filled cell
+ *                         c[0..2], an unfilled one the NaN 0x7fc00000 --, raw_filled (Hm,Wm,3) uint8 -- raw, (uint8)rintf(min(max(
+ *                         c[3+k], 0), 255)), 0 -- and level_out (Hm,Wm) int32 -- 0, g in 1..L, -1.
+ * Every empty cell within 2^(L-1) cells (Chebyshev) of a valid cell is filled; none at 3 x 2^L cells or more from every valid one.
+ * Push comes after pull with the same sizes, inputs and pyramid.  Checked before any launch (SUCRE_ERR_ARG): Hm or Wm outside
+ * 1..2^24, Hm Wm above 2^39, levels outside 1..24, a NULL pointer, J / source / J_filled / level_out not 4-byte aligned, pyramid_dev
+ * not 256-byte aligned.
+ */
+size_t sucre_mosaic_fill_bytes(int Hm, int Wm, int levels);
+int sucre_mosaic_fill_pull(int Hm, int Wm, int levels, const float *J, const uint8_t *raw, const int32_t *source, void *pyramid_dev,
+                           void *stream);
+int sucre_mosaic_fill_push(int Hm, int Wm, int levels, const float *J, const uint8_t *raw, const int32_t *source, void *pyramid_dev,
+                           float *J_filled, uint8_t *raw_filled, int32_t *level_out, void *stream);
 
 /*
  * Shared water AND light over several light-model images (the group above for the 19-parameter model; sucre.py:54-61 with

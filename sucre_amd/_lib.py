@@ -165,6 +165,9 @@ SIGNATURES = {
     'sucre_mosaic_gather': (_i, [_vp, _i, C.POINTER(MosaicImage), _i, C.POINTER(MosaicGrid), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'sucre_mosaic_accumulate': (_i, [_vp, _i, C.POINTER(MosaicImage), _i, C.POINTER(MosaicGrid), _vp, C.c_float, _vp, C.c_uint, _vp]),
     'sucre_mosaic_normalize': (_i, [C.POINTER(MosaicGrid), _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sucre_mosaic_fill_bytes': (C.c_size_t, [_i, _i, _i]),
+    'sucre_mosaic_fill_pull': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'sucre_mosaic_fill_push': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'sucre_light_group_bytes': (C.c_size_t, [_i]),
     'sucre_light_group_sums_offset': (C.c_int64, []),
     'sucre_light_group_init': (_i, [_vp, _i, C.POINTER(LightGroupImage), C.POINTER(C.c_float), _vp]),

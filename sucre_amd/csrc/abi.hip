@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "consist.h"
+#include "fill.h"
 #include "invert.h"
 #include "launch.h"
 #include "mosaic.h"
@@ -1019,6 +1020,57 @@ int sucre_mosaic_normalize(const sucre_mosaic_grid_t *grid, const int64_t *acc_d
     MosaicBlend out = {J_out, raw_out, weight_out, samples_out};
     return check_hip(launch_mosaic_normalize(g, reinterpret_cast<const long long *>(acc_dev), out, static_cast<hipStream_t>(stream)),
                      "sucre_mosaic_normalize");
+}
+
+/* ---- hole filling of the finished mosaic: a bounded push-pull over a pyramid of the grid (fill.h) ---- */
+
+}  // extern "C"
+
+namespace sucre {
+
+static int check_fill_geometry(int Hm, int Wm, int levels) {
+    if (Hm < 1 || Wm < 1 || Hm > (1 << 24) || Wm > (1 << 24)) return fail(SUCRE_ERR_ARG, "mosaic of %dx%d cells (need 1..2^24 each way)", Wm, Hm);
+    if ((uint64_t)Hm * (uint64_t)Wm > (1ull << 39) || fill_blocks(Hm, Wm) > 0x7fffffffull)
+        return fail(SUCRE_ERR_ARG, "mosaic of %dx%d cells: one pass takes 2^39 cells", Wm, Hm);
+    if (levels < 1 || levels > kFillMaxLevels) return fail(SUCRE_ERR_ARG, "levels=%d outside [1,%d]", levels, kFillMaxLevels);
+    return SUCRE_OK;
+}
+
+static int check_fill_base(const float *J, const uint8_t *raw, const int32_t *source, const void *pyramid_dev) {
+    if (!J || !aligned(J, 4)) return fail(SUCRE_ERR_ARG, "J is NULL or not 4-byte aligned");
+    if (!raw) return fail(SUCRE_ERR_ARG, "raw is NULL");
+    if (!source || !aligned(source, 4)) return fail(SUCRE_ERR_ARG, "source is NULL or not 4-byte aligned");
+    if (!pyramid_dev || !aligned(pyramid_dev, 256)) return fail(SUCRE_ERR_ARG, "pyramid_dev is NULL or not 256-byte aligned");
+    return SUCRE_OK;
+}
+
+}  // namespace sucre
+
+extern "C" {
+
+size_t sucre_mosaic_fill_bytes(int Hm, int Wm, int levels) {
+    if (check_fill_geometry(Hm, Wm, levels)) return 0;
+    return fill_pyramid_bytes(Hm, Wm, levels);
+}
+
+int sucre_mosaic_fill_pull(int Hm, int Wm, int levels, const float *J, const uint8_t *raw, const int32_t *source, void *pyramid_dev,
+                           void *stream) {
+    if (int rc = check_fill_geometry(Hm, Wm, levels)) return rc;
+    if (int rc = check_fill_base(J, raw, source, pyramid_dev)) return rc;
+    const FillBase base = {reinterpret_cast<const uint32_t *>(J), raw, source};
+    return check_hip(launch_fill_pull(Hm, Wm, levels, base, pyramid_dev, static_cast<hipStream_t>(stream)), "sucre_mosaic_fill_pull");
+}
+
+int sucre_mosaic_fill_push(int Hm, int Wm, int levels, const float *J, const uint8_t *raw, const int32_t *source, void *pyramid_dev,
+                           float *J_filled, uint8_t *raw_filled, int32_t *level_out, void *stream) {
+    if (int rc = check_fill_geometry(Hm, Wm, levels)) return rc;
+    if (int rc = check_fill_base(J, raw, source, pyramid_dev)) return rc;
+    if (!J_filled || !aligned(J_filled, 4)) return fail(SUCRE_ERR_ARG, "J_filled is NULL or not 4-byte aligned");
+    if (!raw_filled) return fail(SUCRE_ERR_ARG, "raw_filled is NULL");
+    if (!level_out || !aligned(level_out, 4)) return fail(SUCRE_ERR_ARG, "level_out is NULL or not 4-byte aligned");
+    const FillBase base = {reinterpret_cast<const uint32_t *>(J), raw, source};
+    const FillOut out = {reinterpret_cast<uint32_t *>(J_filled), raw_filled, level_out};
+    return check_hip(launch_fill_push(Hm, Wm, levels, base, pyramid_dev, out, static_cast<hipStream_t>(stream)), "sucre_mosaic_fill_push");
 }
 
 /* ---- shared water and light over the light-model images of a rank (sucre.py:54-61, 124-157) ------------------------ */

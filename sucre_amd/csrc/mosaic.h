@@ -1,6 +1,6 @@
 // Seabed mosaic of restored images (sucre_mosaic_*): a best-view ortho splat.  Every pixel of every image is dropped onto a
-// plane grid; the pixel seen through the LEAST water wins its cell.  No hole filling, no float atomics: the optional blend
-// ("The blend" below) sums in fixed point.
+// plane grid; the pixel seen through the LEAST water wins its cell.  No float atomics: the optional blend
+// ("The blend" below) sums in fixed point.  Cells no pixel lands in stay empty here; closing them is fill.h.
 //
 // A pixel p = v W + u of image i (its ordinal: the position in the request) TAKES PART when d > 0 and J[p] holds no NaN in any
 // channel (plot_J's rule, sucre.py:86-87).  Then, all in float32 with explicit FMAs (the library is built with

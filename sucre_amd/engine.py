@@ -981,7 +981,9 @@ def view_consistency(target: DeviceView, J_target: torch.Tensor, views: list, Js
 
 def mosaic_max_cells() -> int:
     """Cells a mosaic may have: SUCRE_MOSAIC_MAX_CELLS, 2^27 unless set (37 bytes per cell: key, pixel word and the five outputs;
-    124 with a blend: 64 more for the accumulator's eight int64 words and 23 for the four blended outputs)."""
+    124 with a blend: 64 more for the accumulator's eight int64 words and 23 for the four blended outputs; a fill adds at most 30:
+    19 for its three outputs and up to 11 for the pyramid, 32-byte records on a third as many cells -- 49 with a blend, whose two
+    filled outputs take 15 and whose own levels 4)."""
     return int(os.environ.get('SUCRE_MOSAIC_MAX_CELLS', 1 << 27))
 
 
@@ -998,6 +1000,33 @@ def mosaic_blend_depth(blend) -> np.float32:
     if not (np.isfinite(H) and MOSAIC_BLEND_RANGE[0] <= H <= MOSAIC_BLEND_RANGE[1]):
         raise ValueError(f'mosaic blend depth H must be finite and within [{MOSAIC_BLEND_RANGE[0]:g}, {MOSAIC_BLEND_RANGE[1]:g}] metres, not {blend}')
     return np.float32(H)
+
+
+MOSAIC_FILL_RANGE = (1e-6, 1e6)    # fill reaches R a mosaic takes, metres
+
+
+def mosaic_fill_reach(fill) -> float:
+    """``fill`` as the reach R in metres, or ValueError unless it is finite and within ``MOSAIC_FILL_RANGE``."""
+    try:
+        R = float(fill)
+    except (TypeError, ValueError):
+        R = float('nan')
+    if not (np.isfinite(R) and MOSAIC_FILL_RANGE[0] <= R <= MOSAIC_FILL_RANGE[1]):
+        raise ValueError(f'mosaic fill reach R must be finite and within [{MOSAIC_FILL_RANGE[0]:g}, {MOSAIC_FILL_RANGE[1]:g}] metres, not {fill}')
+    return R
+
+
+def mosaic_fill_levels(R, gsd, Hm: int, Wm: int) -> int:
+    """L, the levels of the fill's pyramid above the ``Hm`` x ``Wm`` mosaic (csrc/fill.h): the smallest integer >= 1 with
+    ``gsd 2^L >= R`` in float64 -- every hole up to R metres across is closed then --, capped at the first level that is 1x1."""
+    R, gsd, Hm, Wm = mosaic_fill_reach(R), float(gsd), int(Hm), int(Wm)
+    if not (np.isfinite(gsd) and gsd > 0) or Hm < 1 or Wm < 1:
+        raise ValueError(f'mosaic_fill_levels: gsd {gsd} must be finite and > 0 and the mosaic {Wm} x {Hm} at least 1 x 1')
+    cap = max(1, (max(Hm, Wm) - 1).bit_length())   # halvings (rounded up) until the longer side is 1
+    L = 1
+    while L < cap and gsd * 2.0 ** L < R:
+        L += 1
+    return L
 
 
 def mosaic_cells(lo: float, hi: float, gsd: float) -> int:
@@ -1019,7 +1048,12 @@ class Mosaic:
     The blend: ``begin(blend=H)`` also allocates ``acc`` ((Hm Wm, 8) int64, zeros: per cell the fixed-point sums ``wq Jq`` x 3,
     ``wq rgb`` x 3, ``wq`` and the sample count -- csrc/mosaic.h, "The blend"; the tensor a later all-reduce (sum) over ranks would
     combine, next to ``key`` (min) and ``pix``) and four more outputs; ``accumulate`` over ALL the images once ``splat`` has seen
-    every one of them, then ``normalize()``; ``result()`` then holds ``J_blend``, ``raw_blend``, ``weight`` and ``samples`` as well."""
+    every one of them, then ``normalize()``; ``result()`` then holds ``J_blend``, ``raw_blend``, ``weight`` and ``samples`` as well.
+
+    Hole filling: ``fill(R)`` once ``gather`` (with a blend: ``normalize`` too) is through -- a bounded push-pull over a pyramid of
+    the grid (csrc/fill.h) that closes every hole up to ``R`` metres across and reaches at most ``3 x 2^L`` cells beyond the
+    footprint; ``result()`` then also holds ``J_filled``, ``raw_filled`` and ``fill_level`` (with a blend ``J_blend_filled`` and
+    ``raw_blend_filled``).  The other outputs are not touched."""
 
     def __init__(self, axes, gsd, device):
         _lib.load()
@@ -1044,6 +1078,8 @@ class Mosaic:
         self._out = None
         self.blend = self.inv_h = self.acc = None
         self._blend_out = None
+        self.fill_reach = self.fill_levels = self.pyramid = None
+        self._fill_out = None
 
     def _images(self, views: list, Js: list):
         views, Js = list(views), list(Js)
@@ -1115,6 +1151,7 @@ class Mosaic:
                      'pixel': torch.full((Hm, Wm), -1, dtype=torch.int32, device=dev),
                      'range': torch.full((Hm, Wm), nan, dtype=torch.float32, device=dev)}
         self.blend, self.inv_h, self.acc, self._blend_out = blend, None, None, None
+        self.fill_reach = self.fill_levels = self.pyramid = self._fill_out = None
         if blend is not None:
             self.inv_h = np.float32(1) / blend
             self.acc = torch.zeros((Hm * Wm, _lib.MOSAIC_ACC_WORDS), dtype=torch.int64, device=dev)
@@ -1188,19 +1225,60 @@ class Mosaic:
             raise ValueError(f'mosaic blend: a cell holds {most} samples, and from {MOSAIC_MAX_SAMPLES} on its 64-bit sums may overflow; '
                              f'give a finer grid with --mosaic-gsd')
 
+    def fill(self, R) -> int:
+        """Closes the holes up to ``R`` metres across (``MOSAIC_FILL_RANGE``; ValueError before anything is allocated) and returns
+        L, the levels used (``mosaic_fill_levels``).  Valid once ``gather`` has seen every image and, with a blend, ``normalize``
+        has run.  ``J_filled`` / ``raw_filled`` are ``J`` / ``raw`` with every cell without a source (``source < 0``) replaced by
+        the pyramid's value where one reaches it (``fill_level``: 0 measured, 1..L the coarsest level a filled cell drew on, -1
+        still empty; NaN and 0 there); with a blend ``J_blend_filled`` / ``raw_blend_filled`` come from ``J_blend`` / ``raw_blend``
+        and the same ``source`` through the same pyramid buffer.  Only enqueues.  Like the other phases it cannot tell whether
+        the phases before it have seen every image: called earlier on a begun mosaic it fills from the grid as it stands then
+        (from an empty grid: nothing, every cell -1)."""
+        self._begun('fill')
+        R = mosaic_fill_reach(R)
+        L = mosaic_fill_levels(R, self.gsd, self.Hm, self.Wm)
+        lib, dev, Hm, Wm = _lib.load(), self.device, self.Hm, self.Wm
+        n_bytes = lib.sucre_mosaic_fill_bytes(Hm, Wm, L)
+        if n_bytes == 0:
+            raise _lib.SucreError(f'sucre_mosaic_fill_bytes: {lib.sucre_last_error().decode()}')
+        self.fill_reach, self.fill_levels = R, L
+        self.pyramid = torch.empty(n_bytes, dtype=torch.uint8, device=dev)    # (256-byte aligned: the allocator's blocks are)
+        pairs = [('J', 'raw', 'J_filled', 'raw_filled')]
+        if self.blend is not None:
+            pairs.append(('J_blend', 'raw_blend', 'J_blend_filled', 'raw_blend_filled'))
+        src = {**self._out, **(self._blend_out or {})}
+        self._fill_out = {'fill_level': torch.empty((Hm, Wm), dtype=torch.int32, device=dev)}
+        with torch.cuda.device(dev):
+            for J, raw, J_to, raw_to in pairs:
+                # (the blend's own levels are not a result: a blended colour is always finite, a best-view one need not be)
+                level = self._fill_out['fill_level'] if J == 'J' else torch.empty_like(self._fill_out['fill_level'])
+                self._fill_out[J_to] = torch.empty((Hm, Wm, 3), dtype=torch.float32, device=dev)
+                self._fill_out[raw_to] = torch.empty((Hm, Wm, 3), dtype=torch.uint8, device=dev)
+                base = (Hm, Wm, L, C.c_void_p(src[J].data_ptr()), C.c_void_p(src[raw].data_ptr()), C.c_void_p(src['source'].data_ptr()),
+                        C.c_void_p(self.pyramid.data_ptr()))
+                _lib.check(lib.sucre_mosaic_fill_pull(*base, _stream_ptr()))
+                _lib.check(lib.sucre_mosaic_fill_push(*base, C.c_void_p(self._fill_out[J_to].data_ptr()),
+                                                      C.c_void_p(self._fill_out[raw_to].data_ptr()), C.c_void_p(level.data_ptr()),
+                                                      _stream_ptr()))
+        return L
+
     def result(self) -> dict:
         """``J`` (Hm,Wm,3) float32 (NaN: empty), ``raw`` (Hm,Wm,3) uint8 (0), ``source`` and ``pixel`` (Hm,Wm) int32 (-1), ``range``
         (Hm,Wm) float32 (NaN), on the device, complete once ``gather`` has seen every image.  With a blend also ``J_blend``
         (Hm,Wm,3) float32 (NaN), ``raw_blend`` (Hm,Wm,3) uint8 (0), ``weight`` (Hm,Wm) float32 -- the sum of the samples' weights,
-        each at most 1 -- (0) and ``samples`` (Hm,Wm) int32 (0), complete once ``normalize`` has run."""
+        each at most 1 -- (0) and ``samples`` (Hm,Wm) int32 (0), complete once ``normalize`` has run.  After ``fill`` also
+        ``J_filled`` (Hm,Wm,3) float32 (NaN: still empty), ``raw_filled`` (Hm,Wm,3) uint8 (0), ``fill_level`` (Hm,Wm) int32 (-1)
+        and, with a blend, ``J_blend_filled`` and ``raw_blend_filled``."""
         self._begun('result')
-        return {**self._out, **self._blend_out} if self.blend is not None else dict(self._out)
+        out = {**self._out, **self._blend_out} if self.blend is not None else dict(self._out)
+        return {**out, **self._fill_out} if self._fill_out is not None else out
 
 
-def mosaic_of(views: list, Js: list, axes, gsd, bounds=None, batch: int = 32, plain_atomic: bool = False, blend=None) -> 'Mosaic':
+def mosaic_of(views: list, Js: list, axes, gsd, bounds=None, batch: int = 32, plain_atomic: bool = False, blend=None,
+              fill=None) -> 'Mosaic':
     """All four phases over device-resident ``views`` / ``Js`` (ordinal = position in the list), ``batch`` images per call; with
     ``blend`` (the blend depth H, metres) the accumulate phase and the normalise pass after them (``plain_atomic``: both the
-    splat and the accumulate phase in their plain forms)."""
+    splat and the accumulate phase in their plain forms); with ``fill`` (the reach R, metres) the hole filling after all of them."""
     views, Js = list(views), list(Js)
     if not views:
         raise ValueError('mosaic_of: no view')
@@ -1208,6 +1286,8 @@ def mosaic_of(views: list, Js: list, axes, gsd, bounds=None, batch: int = 32, pl
         raise ValueError(f'mosaic_of: {len(views)} images, at most {MAX_VIEWS}')
     if blend is not None:
         mosaic_blend_depth(blend)   # before anything is allocated
+    if fill is not None:
+        mosaic_fill_reach(fill)
     m = Mosaic(axes, gsd, views[0].depth.device)
     chunks = [(i, views[i:i + batch], Js[i:i + batch]) for i in range(0, len(views), batch)]
     if bounds is None:
@@ -1224,6 +1304,8 @@ def mosaic_of(views: list, Js: list, axes, gsd, bounds=None, batch: int = 32, pl
         for i, v, J in chunks:
             m.accumulate(v, J, i, plain=plain_atomic)
         m.normalize()
+    if fill is not None:
+        m.fill(fill)
     return m
 
 

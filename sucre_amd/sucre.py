@@ -1400,12 +1400,12 @@ def _mosaic_picture(J: Tensor, stretch) -> np.ndarray:
 
 
 def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, output_dir: Path, gsd: float | None = None, axes=None,
-           stretch=None, device: str = 'cuda', blend: float | None = None) -> dict:
+           stretch=None, device: str = 'cuda', blend: float | None = None, fill: float | None = None) -> dict:
     """One picture of the seabed from a finished restoration: every pixel of ``images`` (``sfm.Image`` objects or names of
     ``colmap_model``; at most ``engine.MAX_VIEWS``, ordinal = position) with a valid depth and a restored colour --
     ``results_dir / <name>.pt``, key ``J`` -- is dropped onto the plane grid ``axes`` (``mosaic_axes`` unless given) of ``gsd``
     metres per cell (``mosaic_default_gsd`` unless given; printed), and the pixel seen through the least water wins its cell
-    (``engine.Mosaic``; csrc/mosaic.h).  No hole filling.  Every file is checked before any image is decoded.  The
+    (``engine.Mosaic``; csrc/mosaic.h).  Holes stay empty unless ``fill`` is given.  Every file is checked before any image is decoded.  The
     restored images stay on the device across the four phases within ``consistency_cache_budget`` and are read again per phase
     otherwise: the same bits either way.  Writes ``mosaic.png`` (``plot_J``'s stretch over the filled cells, or the fixed
     ``stretch``), ``mosaic_raw.png``, ``mosaic_source.png`` (``mosaic_source_picture``) and ``mosaic.pt`` (``J, raw, source, pixel,
@@ -1416,7 +1416,16 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
     and a pass over the cells divides (csrc/mosaic.h, "The blend": the same bits in any order).  The four files above stay the
     best-view ones, byte for byte -- their seams are the diagnostic --; ``mosaic_blend.png`` (``J_blend`` through the function that
     makes ``mosaic.png``) and ``mosaic_blend_raw.png`` come next to them, ``mosaic.pt`` gains ``J_blend, raw_blend, weight, samples,
-    blend`` and one more line is printed.  Not built: feathering by the distance to the image border, multi-band blending."""
+    blend`` and one more line is printed.
+
+    ``fill``: a reach R in metres (``engine.MOSAIC_FILL_RANGE``).  After the other phases a bounded push-pull over a pyramid of
+    the grid (``engine.Mosaic.fill``; csrc/fill.h) closes every hole up to R across and does not extrapolate far beyond the
+    footprint.  Every file and key above stays as it is, byte for byte; ``mosaic_filled.png`` (``J_filled`` through the function
+    that makes ``mosaic.png``: its own percentiles, or ``stretch``), ``mosaic_raw_filled.png`` and ``mosaic_filled_mask.png`` (255
+    measured, 128 filled, 0 empty) come next to them -- with a blend also ``mosaic_blend_filled.png`` and
+    ``mosaic_blend_raw_filled.png`` --, ``mosaic.pt`` gains ``J_filled, raw_filled, fill_level`` (``J_blend_filled,
+    raw_blend_filled``), ``fill`` and ``fill_levels``, and one more line is printed.  Not built: feathering by the distance to the
+    image border, multi-band blending."""
     from . import engine
     sfm.require_gpu(device, 'mosaic')
     images = [colmap_model[im] if isinstance(im, str) else im for im in images]
@@ -1431,6 +1440,11 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
             blend = engine.mosaic_blend_depth(blend)
         except ValueError as e:
             raise SystemExit(f'--mosaic-blend: {e}')
+    if fill is not None:
+        try:
+            fill = engine.mosaic_fill_reach(fill)
+        except ValueError as e:
+            raise SystemExit(f'--mosaic-fill: {e}')
     results_dir, output_dir = Path(results_dir), Path(output_dir)
     for image in images:   # before anything is decoded
         path = _consistency_file(results_dir, image)
@@ -1475,9 +1489,13 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
                 m.normalize()
             except ValueError as e:
                 raise SystemExit(f'--mosaic-blend: {e}')
+        if fill is not None:
+            m.fill(fill)
         out = m.result()
         picture = _mosaic_picture(out['J'], stretch)
         blend_picture = _mosaic_picture(out['J_blend'], stretch) if blend is not None else None
+        filled_picture = _mosaic_picture(out['J_filled'], stretch) if fill is not None else None
+        blend_filled_picture = _mosaic_picture(out['J_blend_filled'], stretch) if fill is not None and blend is not None else None
         out = {k: v.cpu() for k, v in out.items()}
     source = out['source']
     filled = source >= 0
@@ -1489,10 +1507,20 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
     if blend is not None:
         _save_png(PILImage.fromarray(blend_picture), output_dir / 'mosaic_blend.png')
         _save_png(PILImage.fromarray(out['raw_blend'].numpy()), output_dir / 'mosaic_blend_raw.png')
+    if fill is not None:
+        level = out['fill_level'].numpy()
+        _save_png(PILImage.fromarray(filled_picture), output_dir / 'mosaic_filled.png')
+        _save_png(PILImage.fromarray(out['raw_filled'].numpy()), output_dir / 'mosaic_raw_filled.png')
+        _save_png(PILImage.fromarray(np.where(level == 0, 255, np.where(level > 0, 128, 0)).astype(np.uint8)), output_dir / 'mosaic_filled_mask.png')
+        if blend is not None:
+            _save_png(PILImage.fromarray(blend_filled_picture), output_dir / 'mosaic_blend_filled.png')
+            _save_png(PILImage.fromarray(out['raw_blend_filled'].numpy()), output_dir / 'mosaic_blend_raw_filled.png')
     data = {**out, 'axes': m.axes.clone(), 'gsd': float(m.gsd), 'lo': torch.tensor([float(m.lo[0]), float(m.lo[1])], dtype=torch.float32),
             'images': [im.name for im in images], 'n_filled': n_filled, 'per_image': per_image}
     if blend is not None:
         data['blend'] = float(blend)
+    if fill is not None:
+        data['fill'], data['fill_levels'] = float(fill), int(m.fill_levels)
     torch.save(data, output_dir / 'mosaic.pt')
     top = int(per_image.argmax())
     print(f'mosaic of {len(images)} images: {Wm} x {Hm} cells of {float(m.gsd):.6g} m, {n_filled} filled '
@@ -1503,6 +1531,10 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
         total, most, several = int(samples.sum()), int(samples.max()), int((samples > 1).sum())
         print(f'mosaic blend of depth {float(blend):.6g} m: {total} samples, {total / max(1, n_filled):.2f} per filled cell on average, '
               f'{most} at most; {100.0 * several / max(1, n_filled):.1f} % of the filled cells blend more than one sample')
+    if fill is not None:
+        level = out['fill_level']
+        print(f'mosaic fill of {float(fill):.6g} m ({int(m.fill_levels)} levels): {int((level > 0).sum())} cells filled, '
+              f'{int((level < 0).sum())} left empty; deepest level {max(0, int(level.max()))}')
     return data
 
 
@@ -1553,13 +1585,17 @@ def _refuse_mode_flags(args, mode: str) -> None:
 
 
 def _refuse_mosaic_values(args, world: int = 1) -> None:
-    """The values of --mosaic-gsd and --mosaic-blend and the world size a mosaic takes, refused before any file is opened."""
+    """The values of --mosaic-gsd, --mosaic-blend and --mosaic-fill and the world size a mosaic takes, refused before any file is
+    opened."""
     gsd = getattr(args, 'mosaic_gsd', None)
     if gsd is not None and not (np.isfinite(gsd) and gsd > 0):
         raise SystemExit(f'--mosaic-gsd: G must be a finite size > 0 in metres, not {gsd}')
     blend = getattr(args, 'mosaic_blend', None)
     if blend is not None and not (np.isfinite(blend) and 1e-6 <= blend <= 1e6):
         raise SystemExit(f'--mosaic-blend: H must be a finite depth within [1e-06, 1e+06] metres, not {blend}')
+    fill = getattr(args, 'mosaic_fill', None)
+    if fill is not None and not (np.isfinite(fill) and 1e-6 <= fill <= 1e6):
+        raise SystemExit(f'--mosaic-fill: R must be a finite reach within [1e-06, 1e+06] metres, not {fill}')
     if world > 1:
         raise SystemExit(f'--mosaic: a world size of {world} is not supported yet: the four phases are separate entries of the library '
                          f'so that ranks can all-reduce bounds, keys and pixel words between them, but that all-reduce is not built; '
@@ -1591,6 +1627,8 @@ def parse_args(args: argparse.Namespace):
         raise SystemExit('--mosaic-gsd: only with --mosaic DIR')
     if mosaic_dir is None and getattr(args, 'mosaic_blend', None) is not None:
         raise SystemExit('--mosaic-blend: only with --mosaic DIR')
+    if mosaic_dir is None and getattr(args, 'mosaic_fill', None) is not None:
+        raise SystemExit('--mosaic-fill: only with --mosaic DIR')
     if mosaic_dir is not None:
         _refuse_mode_flags(args, '--mosaic')
         _refuse_mosaic_values(args, world)
@@ -1673,7 +1711,7 @@ def parse_args(args: argparse.Namespace):
     try:
         if mosaic_dir is not None:
             mosaic(images, colmap_model, mosaic_dir, args.output_dir, gsd=getattr(args, 'mosaic_gsd', None), stretch=stretch, device=device,
-                   blend=getattr(args, 'mosaic_blend', None))
+                   blend=getattr(args, 'mosaic_blend', None), fill=getattr(args, 'mosaic_fill', None))
         elif check is not None:
             if world > 1:   # the targets' records are gathered on rank 0
                 sdist.init_process_group()
@@ -1909,7 +1947,7 @@ def build_parser() -> argparse.ArgumentParser:
                           help='do not fit: drop every pixel of the images of the request that has a valid depth and a restored colour '
                                '(DIR/<name>.pt, as this tool and the reference write them) onto one plane grid that looks the way the '
                                'cameras look; the pixel seen through the least water wins its cell, nothing is blended and no hole is '
-                               'filled; writes mosaic.png, mosaic_raw.png, mosaic_source.png and mosaic.pt and prints the size and the cover')
+                               'filled (--mosaic-blend, --mosaic-fill); writes mosaic.png, mosaic_raw.png, mosaic_source.png and mosaic.pt and prints the size and the cover')
     p.extras.add_argument('--mosaic-gsd', type=float, metavar='G', default=argparse.SUPPRESS,
                           help='with --mosaic: metres per cell (twice the median pixel footprint of the images unless given)')
     p.extras.add_argument('--mosaic-blend', type=float, metavar='H', default=argparse.SUPPRESS,
@@ -1917,6 +1955,13 @@ def build_parser() -> argparse.ArgumentParser:
                                'max(1 - d / H, 0)^2 of the metres d of water it looked through beyond the cell\'s nearest view, summed in '
                                'fixed point (the same bits in any order); writes mosaic_blend.png and mosaic_blend_raw.png next to the '
                                'best-view files, which stay as they are, adds J_blend, raw_blend, weight, samples and blend to mosaic.pt '
+                               'and prints one more line')
+    p.extras.add_argument('--mosaic-fill', type=float, metavar='R', default=argparse.SUPPRESS,
+                          help='with --mosaic: also close the holes -- cells no pixel landed in -- up to R metres across, by a bounded '
+                               'push-pull over a pyramid of the grid (the same bits on every run); the mosaic is not extrapolated far beyond '
+                               'its footprint; writes mosaic_filled.png, mosaic_raw_filled.png and mosaic_filled_mask.png (255 measured, 128 '
+                               'filled, 0 empty; with --mosaic-blend also mosaic_blend_filled.png and mosaic_blend_raw_filled.png) next to the '
+                               'other files, which stay as they are, adds J_filled, raw_filled, fill_level, fill and fill_levels to mosaic.pt '
                                'and prints one more line')
     p.extras.add_argument('--common-stretch', action='store_true', default=argparse.SUPPRESS,
                           help='with --shared-water or --apply-water: stretch every <stem>_rgb.png between the SAME per-channel 1st '
