@@ -97,7 +97,7 @@ def mosaic(views, Js, axes, gsd, bounds=None):
         keep = (qs >= 0) & (qs < Wm) & (qt >= 0) & (qt < Hm)
         cell = qt[keep].to(torch.int64) * Wm + qs[keep].to(torch.int64)     # Tensor.long(): truncation
         zbits = z[keep].contiguous().view(torch.int32).to(torch.int64)
-        assert bool((zbits > 0).all())
+        assert bool((zbits >= 0).all())    # z >= +0: the bits order like the values (0 itself: a subnormal depth, whose squares underflow)
         rows.append(torch.stack([cell, zbits, torch.full_like(cell, i), p[keep]], dim=1))
     rows = torch.cat(rows).numpy()
     order = np.lexsort((rows[:, 3], rows[:, 2], rows[:, 1], rows[:, 0]))   # by cell, then (range bits, ordinal, pixel)

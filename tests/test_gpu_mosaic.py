@@ -23,8 +23,9 @@ DEV = 'cuda:0'
 _CASES = {}
 
 
-def restored_like(view, seed):
-    """Random float32 in (0, 1) with NaN patches: two rectangles with all channels NaN and about 2 % of the pixels with a NaN in one."""
+def restored_like(view, seed, device=DEV):
+    """Random float32 in (0, 1) with NaN patches: two rectangles with all channels NaN and about 2 % of the pixels with a NaN in one.
+    (``device``: where the image goes; test_mosaic_variants_host.py makes the same images on the CPU.)"""
     H, W = view.depth.shape
     g = torch.Generator().manual_seed(seed)
     J = torch.rand((H, W, 3), generator=g) * 0.98 + 0.01
@@ -35,7 +36,7 @@ def restored_like(view, seed):
     ch = torch.randint(0, 3, (H, W), generator=g)
     vv, uu = torch.nonzero(hit, as_tuple=True)
     J[vv, uu, ch[vv, uu]] = float('nan')
-    return J.to(DEV)
+    return J.to(device)
 
 
 def host_view(v):
