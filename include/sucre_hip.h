@@ -649,9 +649,28 @@ int sucre_view_consistency(int H, int W, int n_views, const sucre_view_t *target
  *                         samples_out (Hm,Wm) int32 = the count (2^31 - 1 when above).  Empty cells are not touched: the caller
  *                         fills the outputs first.  A filled cell has wsum >= 4096.
  * Checked before any launch as above, and: inv_h not finite or <= 0, a NULL or misaligned acc_dev or output, Hm Wm above 2^39.
+ *
+ * The feather: one more factor in the blend's weight, which falls to nothing towards the edge of an image's footprint -- its
+ * frame, a NaN patch of J, a hole of the depth map.  A pixel that takes part is a MEMBER of its image.  For a member (u, v) and a
+ * feather width of feather_px = F source pixels, 1..SUCRE_MOSAIC_FEATHER_MAX = 1024, in exact integers:
+ *   D2 = min over integer (u', v') that are non-members or lie outside [0,W) x [0,H) of (u - u')^2 + (v - v')^2
+ *   dist2 = min(D2, F^2), uint32; 0 for a non-member, >= 1 for a member (the frame just outside the image counts)
+ *   sucre_mosaic_feather_bytes  the bytes of feather_dev for these images (only H and W are read; 0 and an error for bad sizes):
+ *                         image i's dist2, row-major (H,W) uint32, starts at WORD 256 sum_(j<i) ceil(H_j W_j / 256); behind all the
+ *                         words, 4 bytes each, sits a uint16 scratch of as many entries: 6 bytes per pixel, images rounded up to 256
+ *   sucre_mosaic_feather  writes every image's dist2 (the words between two images are not written); two launches per 32
+ *                         images.  feather_dev: 4-byte aligned
+ *   sucre_mosaic_accumulate_feathered  sucre_mosaic_accumulate with, in float32, one IEEE operation per step,
+ *                         f = dist2 >= F^2 ? 1 : sqrtf((float)dist2) inv_F (inv_F = 1.0f / (float)F) and
+ *                         wq = (int)rintf(((t t) f) 4096), 0..4096; everything else as there, flags included.  The images are
+ *                         those of the sucre_mosaic_feather call that wrote feather_dev, in the same order, with the same F.
+ *                         A cell's winner has wq >= 4 (f >= 1/1024), so a filled cell has wsum >= 4 and a count >= 1; with
+ *                         F = 1 the words equal sucre_mosaic_accumulate's to the bit (every member has dist2 >= 1 = F^2).
+ * Checked before any launch as above, and: feather_px outside 1..1024, a NULL or misaligned feather_dev.
  */
 #define SUCRE_MOSAIC_PLAIN_ATOMIC 1u
 #define SUCRE_MOSAIC_ACC_WORDS 8
+#define SUCRE_MOSAIC_FEATHER_MAX 1024
 typedef struct sucre_mosaic_image {
     const float *depth;   /* (H,W) float32 */
     const uint8_t *rgb;   /* (H,W,3) uint8 */
@@ -680,6 +699,12 @@ int sucre_mosaic_accumulate(void *table_dev, int n_images, const sucre_mosaic_im
                             void *stream);
 int sucre_mosaic_normalize(const sucre_mosaic_grid_t *grid, const int64_t *acc_dev, float *J_out, uint8_t *raw_out, float *weight_out,
                            int32_t *samples_out, void *stream);
+size_t sucre_mosaic_feather_bytes(int n_images, const sucre_mosaic_image_t *images);
+int sucre_mosaic_feather(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int feather_px, void *feather_dev,
+                         void *stream);
+int sucre_mosaic_accumulate_feathered(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                                      const sucre_mosaic_grid_t *grid, const uint64_t *key_dev, float inv_h, int feather_px,
+                                      const void *feather_dev, int64_t *acc_dev, unsigned flags, void *stream);
 
 /*
  * ---- hole filling of the finished mosaic: a bounded push-pull over a pyramid of the grid ------------------------------------------

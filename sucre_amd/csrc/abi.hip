@@ -1008,6 +1008,53 @@ int sucre_mosaic_accumulate(void *table_dev, int n_images, const sucre_mosaic_im
                      "sucre_mosaic_accumulate");
 }
 
+static int check_feather_px(int feather_px) {
+    if (feather_px < 1 || feather_px > kFeatherMax) return fail(SUCRE_ERR_ARG, "feather_px=%d outside [1,%d]", feather_px, kFeatherMax);
+    return SUCRE_OK;
+}
+
+size_t sucre_mosaic_feather_bytes(int n_images, const sucre_mosaic_image_t *images) {
+    if (n_images < 1 || n_images > kMaxViews || !images) {
+        fail(SUCRE_ERR_ARG, "n_images=%d outside [1,%d], or images is NULL", n_images, kMaxViews);
+        return 0;
+    }
+    for (int i = 0; i < n_images; ++i) {
+        if (images[i].H < 1 || images[i].W < 1 || images[i].H > 32767 || images[i].W > 32767) {
+            fail(SUCRE_ERR_ARG, "image %d: invalid size %dx%d (need 1..32767)", i, images[i].W, images[i].H);
+            return 0;
+        }
+    }
+    return feather_bytes(n_images, images);
+}
+
+int sucre_mosaic_feather(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int feather_px, void *feather_dev,
+                         void *stream) {
+    if (int rc = check_mosaic_images(table_dev, n_images, images, 0)) return rc;
+    if (int rc = check_feather_px(feather_px)) return rc;
+    if (!feather_dev || !aligned(feather_dev, 4)) return fail(SUCRE_ERR_ARG, "feather_dev is NULL or not 4-byte aligned");
+    return check_hip(launch_mosaic_feather(table_dev, n_images, images, feather_px, feather_dev, static_cast<hipStream_t>(stream)),
+                     "sucre_mosaic_feather");
+}
+
+int sucre_mosaic_accumulate_feathered(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                                      const sucre_mosaic_grid_t *grid, const uint64_t *key_dev, float inv_h, int feather_px,
+                                      const void *feather_dev, int64_t *acc_dev, unsigned flags, void *stream) {
+    if (int rc = check_mosaic_images(table_dev, n_images, images, first_ordinal)) return rc;
+    MosaicGrid g;
+    if (int rc = check_mosaic_grid(grid, &g)) return rc;
+    if (!key_dev || !aligned(key_dev, 8)) return fail(SUCRE_ERR_ARG, "key_dev is NULL or not 8-byte aligned");
+    if (!std::isfinite(inv_h) || !(inv_h > 0.0f)) return fail(SUCRE_ERR_ARG, "inv_h=%g must be finite and > 0", (double)inv_h);
+    if (int rc = check_feather_px(feather_px)) return rc;
+    if (!feather_dev || !aligned(feather_dev, 4)) return fail(SUCRE_ERR_ARG, "feather_dev is NULL or not 4-byte aligned");
+    if (!acc_dev || !aligned(acc_dev, 8)) return fail(SUCRE_ERR_ARG, "acc_dev is NULL or not 8-byte aligned");
+    if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
+    return check_hip(launch_mosaic_accumulate_feathered((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) != 0, table_dev, n_images, images,
+                                                        first_ordinal, g, reinterpret_cast<const unsigned long long *>(key_dev), inv_h,
+                                                        feather_px, feather_dev, reinterpret_cast<unsigned long long *>(acc_dev),
+                                                        static_cast<hipStream_t>(stream)),
+                     "sucre_mosaic_accumulate_feathered");
+}
+
 int sucre_mosaic_normalize(const sucre_mosaic_grid_t *grid, const int64_t *acc_dev, float *J_out, uint8_t *raw_out, float *weight_out,
                            int32_t *samples_out, void *stream) {
     MosaicGrid g;

@@ -59,6 +59,35 @@
 // Measured on the shape above (profiles/mosaic_blend_time.txt; H = 0.5 m, 119 M samples): accumulate 23.8 ms with the run sums,
 // 47.7 ms with the plain atomics (7.5 against 58.2 ms at 1176 pixels per cell), against the splat's 0.87 ms in the same run -- a
 // sum can skip none of its atomics --; normalise 0.04 ms.
+//
+// The feather (sucre_mosaic_feather, sucre_mosaic_accumulate_feathered): one more factor in the blend's weight, which falls to
+// nothing towards the edge of an image's footprint -- the frame of the image, a NaN patch of J, a hole of the depth map -- so that
+// the blended colour no longer steps where a view ends.  A pixel is a MEMBER of its image when it takes part (mosaic_member, the
+// rule of mosaic_pixel: one function).  For a member (u, v) of an H x W image and a feather width of F source pixels, 1 <= F <= 1024:
+//   D2    = min over integer (u', v') that are non-members OR lie outside [0,W) x [0,H) of (u - u')^2 + (v - v')^2
+//   dist2 = min(D2, F^2)                           uint32; 0 for a non-member; >= 1 for a member (the frame just outside counts)
+// in exact integers, separably; integer min is order-free, so any schedule gives the same bits:
+//   columns  g(u,v) = min(F, distance along column u to the nearest non-member), rows -1 and H counting as non-members; uint16,
+//            0 for a non-member.  One lane per column walks down (reads depth and J, writes the distance to the one above) and
+//            then up (reads and lowers g alone); a wave's lanes touch consecutive addresses.  One launch per 32 images
+//   rows     dist2(u,v) = min(F^2, min over |dx| < F of dx^2 + g(u+dx, v)^2), a column outside the image having g = 0.  One lane
+//            per pixel, a workgroup per 256-column segment of a row; the segment and F - 1 columns of halo on each side are
+//            staged in LDS (256 + 2 x 1023 uint16 at most); each lane scans dx outwards and stops once dx^2 >= its best so far
+// The capped form is exact: a nearest non-member with |dx| < F and |dy| < F is found, any other one has D2 >= F^2.
+// THE BUFFER of one call (feather_bytes): image i's dist2 words, row-major H x W, start at word 256 sum_(j<i) ceil(H_j W_j / 256)
+// -- so the lane of mosaic_walk reads word blockIdx.x 256 + threadIdx.x behind its launch's first word: one coalesced load, no
+// pointer per image --; the uint16 g scratch sits behind all the words, image i's at the same index.  6 bytes per (padded) pixel.
+// The weight, float32, one IEEE operation per step (inv_F = float32(1) / float32(F), formed on the host):
+//   f  = dist2 >= F^2 ? 1.0f : sqrtf((float)dist2) inv_F
+//   wq = (int)rintf(((t t) f) 4096)                t as in the blend; 0 <= wq <= 4096
+// and everything after wq is the blend's: the Jq clamp, the eight words, the run sums, the 2^62 bound, the normalise pass.
+// EVERY FILLED CELL STILL HAS A BLEND: its winner has t = 1 and f >= 1 / F >= 1 / 1024, so wq >= 4, wsum > 0 and samples >= 1 --
+// which is why F stops at 1024 (a filled cell has wsum >= 4 here, not >= 4096).  F = 1 IS THE UNFEATHERED BLEND TO THE BIT: every
+// member has dist2 >= 1 = F^2, so f = 1 and (t t) 1.0f is t t.
+// Measured on the shape above in one run (tools/mosaic_feather_time.py, profiles/mosaic_feather_time.txt): the map 2.6 ms at F = 16
+// and 64, 3.1 ms at F = 1024, 2.2 ms of it the column pass (the floor at F = 1: one wave per 64 columns walks 1080 rows); the
+// feathered accumulate 23.8, 23.5 and 21.9 ms against 23.8 ms unfeathered.  Not built: the row pass's workgroup shortcut (a window
+// that holds only g = F writes F^2 at once).
 #pragma once
 #include "launch.h"
 
@@ -109,6 +138,23 @@ enum MosaicPhase { kMosaicBounds, kMosaicSplat, kMosaicSplatPlain, kMosaicResolv
 inline size_t mosaic_table_bytes(int n_images) { return align_up((size_t)n_images * sizeof(MosaicImage), 256); }
 inline uint64_t mosaic_blocks(int H, int W) { return ((uint64_t)H * (uint64_t)W + kMosaicBlockPx - 1) / kMosaicBlockPx; }
 
+constexpr int kFeatherMax = 1024;       // the widest feather (SUCRE_MOSAIC_FEATHER_MAX): the winner's wq stays >= 4
+static_assert(kFeatherMax == SUCRE_MOSAIC_FEATHER_MAX, "the widest feather is public");
+
+struct MosaicFeather {   // what a feathered accumulate launch reads (all zeros for an unfeathered one, which reads none of it)
+    const uint32_t *dist2;   // the first word of the launch's first image
+    uint32_t f2;             // F^2
+    float inv_f;             // 1 / F
+};
+
+// The words of the map of images[0 .. n), every image rounded up to whole workgroups; the g scratch holds as many uint16.
+inline size_t feather_words(int n_images, const sucre_mosaic_image_t *images) {
+    size_t words = 0;
+    for (int i = 0; i < n_images; ++i) words += (size_t)mosaic_blocks(images[i].H, images[i].W) * kMosaicBlockPx;
+    return words;
+}
+inline size_t feather_bytes(int n_images, const sucre_mosaic_image_t *images) { return feather_words(n_images, images) * 6; }
+
 // One phase over images[0 .. n): ceil(n / 32) launches (plus the table's set launches) on s.  Only the arguments of the phase
 // are read: bounds (kMosaicBounds), key (splat: written; resolve, gather: read), pix (resolve: written; gather: read), out (gather).
 hipError_t launch_mosaic(MosaicPhase phase, void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
@@ -121,5 +167,13 @@ hipError_t launch_mosaic_accumulate(bool plain, void *table, int n_images, const
                                     const MosaicGrid &grid, const unsigned long long *key, float inv_h, unsigned long long *acc,
                                     hipStream_t s);
 hipError_t launch_mosaic_normalize(const MosaicGrid &grid, const long long *acc, const MosaicBlend &out, hipStream_t s);
+
+// The feather's map of images[0 .. n) into `feather` (feather_bytes; two launches per 32 images, plus the table's), and the
+// accumulate phase that reads it (the same call's images in the same order; `feather` as the map's call left it).
+hipError_t launch_mosaic_feather(void *table, int n_images, const sucre_mosaic_image_t *images, int feather_px, void *feather,
+                                 hipStream_t s);
+hipError_t launch_mosaic_accumulate_feathered(bool plain, void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                                              const MosaicGrid &grid, const unsigned long long *key, float inv_h, int feather_px,
+                                              const void *feather, unsigned long long *acc, hipStream_t s);
 
 }  // namespace sucre

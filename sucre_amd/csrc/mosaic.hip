@@ -20,6 +20,12 @@ struct MosaicPixel {
     float J[3];
 };
 
+// Whether a pixel takes part, from its depth and its three restored channels: the one statement of the rule (the feather's column
+// pass forms its members with it too).
+__device__ __forceinline__ bool mosaic_member(float d, float J0, float J1, float J2) {
+    return d > 0.0f && J0 == J0 && J1 == J1 && J2 == J2;
+}
+
 __device__ __forceinline__ MosaicPixel mosaic_pixel(const MosaicImage *__restrict__ im, const float *Kinv, bool pin, const float *R,
                                                     const float *t, const float *axes, uint32_t p, uint32_t W) {
     MosaicPixel m;
@@ -27,7 +33,7 @@ __device__ __forceinline__ MosaicPixel mosaic_pixel(const MosaicImage *__restric
     const float d = global_ptr(im->depth)[p];
     const auto *pj = global_ptr(im->J) + (size_t)p * 3;
     m.J[0] = pj[0]; m.J[1] = pj[1]; m.J[2] = pj[2];
-    m.in = d > 0.0f && m.J[0] == m.J[0] && m.J[1] == m.J[1] && m.J[2] == m.J[2];
+    m.in = mosaic_member(d, m.J[0], m.J[1], m.J[2]);
     float cP[3], wP[3];
     unproject(Kinv, pin, (float)u, (float)v, d, cP);
     m.z = sqrtf(cP[0] * cP[0] + cP[1] * cP[1] + cP[2] * cP[2]);
@@ -159,10 +165,12 @@ __device__ __forceinline__ T run_sum(T x, int left) {
     return x;
 }
 
-template <bool kPlain>
+// kFeather: the weight takes one more factor, f of the pixel's capped squared border distance (mosaic.h, "The feather").  The
+// lane's word of the map sits where the lane sits in the launch: word blockIdx.x 256 + threadIdx.x of `feather.dist2`.
+template <bool kPlain, bool kFeather>
 __global__ __launch_bounds__(256) void mosaic_accumulate_kernel(const MosaicImage *__restrict__ table, int n_images, const MosaicGrid g,
                                                                 const unsigned long long *__restrict__ key, float inv_h,
-                                                                unsigned long long *__restrict__ acc) {
+                                                                unsigned long long *__restrict__ acc, const MosaicFeather feather) {
     const MosaicImage *__restrict__ im;
     uint32_t p;
     MosaicPixel m;
@@ -173,7 +181,13 @@ __global__ __launch_bounds__(256) void mosaic_accumulate_kernel(const MosaicImag
         const float zmin = __uint_as_float((uint32_t)(key[cell] >> 32));   // an unsplatted cell: NaN, and fmaxf gives weight 0
         const float d = m.z - zmin;
         const float t = fmaxf(1.0f - d * inv_h, 0.0f);
-        wq = (int32_t)rintf((t * t) * 4096.0f);
+        if constexpr (kFeather) {
+            const uint32_t d2 = global_ptr(feather.dist2)[(size_t)blockIdx.x * kMosaicBlockPx + threadIdx.x];
+            const float f = d2 >= feather.f2 ? 1.0f : sqrtf((float)d2) * feather.inv_f;
+            wq = (int32_t)rintf(((t * t) * f) * 4096.0f);
+        } else {
+            wq = (int32_t)rintf((t * t) * 4096.0f);
+        }
     }
     // (no lane leaves before the shuffles of the aggregated form)
     long long jq[3] = {0, 0, 0};
@@ -230,6 +244,62 @@ __global__ __launch_bounds__(256) void mosaic_normalize_kernel(size_t n_cells, c
     out.samples[cell] = count > 0x7fffffffll ? 0x7fffffff : (int32_t)count;
 }
 
+// ---- the feather (mosaic.h, "The feather"): the capped squared distance of every member to the nearest non-member ----
+
+// Columns: one lane per column walks down and then up; the lanes of a wave touch consecutive addresses of a row.  blockIdx.y: the
+// image of the launch; blockIdx.x: its 64-column strip (a workgroup past the image's width leaves).
+__global__ __launch_bounds__(64) void feather_columns_kernel(const MosaicImage *__restrict__ table, uint32_t F, uint16_t *__restrict__ g) {
+    const MosaicImage *__restrict__ im = table + blockIdx.y;
+    const uint32_t W = (uint32_t)im->W, H = (uint32_t)im->H, u = blockIdx.x * 64 + threadIdx.x;
+    if (u >= W) return;
+    const auto *depth = global_ptr(im->depth);
+    const auto *J = global_ptr(im->J);
+    uint16_t *__restrict__ gi = g + (size_t)im->block0 * kMosaicBlockPx;
+    uint32_t run = 0;   // rows since the last non-member, capped; the row above the image is one
+#pragma unroll 4
+    for (uint32_t v = 0; v < H; ++v) {
+        const size_t p = (size_t)v * W + u;
+        const bool in = mosaic_member(depth[p], J[p * 3], J[p * 3 + 1], J[p * 3 + 2]);
+        run = in ? (run < F ? run + 1 : F) : 0;
+        gi[p] = (uint16_t)run;
+    }
+    run = 0;            // and so is the row below it
+#pragma unroll 4
+    for (uint32_t v = H; v-- > 0;) {
+        const size_t p = (size_t)v * W + u;
+        const uint32_t down = gi[p];
+        run = down ? (run < F ? run + 1 : F) : 0;
+        if (run < down) gi[p] = (uint16_t)run;
+    }
+}
+
+// Rows: one lane per pixel, a workgroup per 256-column segment of a row (blockIdx.x: the segment, .y: the row, .z: the image; a
+// workgroup past the image leaves, all its lanes together).  The segment and its F - 1 columns of halo on either side are
+// staged in LDS, a column outside the image as 0; each lane then scans outwards and stops once dx^2 cannot improve its minimum.
+__global__ __launch_bounds__(256) void feather_rows_kernel(const MosaicImage *__restrict__ table, uint32_t F, const uint16_t *__restrict__ g,
+                                                           uint32_t *__restrict__ dist2) {
+    __shared__ uint16_t win[kMosaicBlockPx + 2 * (kFeatherMax - 1)];
+    const MosaicImage *__restrict__ im = table + blockIdx.z;
+    const uint32_t W = (uint32_t)im->W, H = (uint32_t)im->H, v = blockIdx.y, u0 = blockIdx.x * kMosaicBlockPx;
+    if (v >= H || u0 >= W) return;
+    const size_t row = (size_t)im->block0 * kMosaicBlockPx + (size_t)v * W;
+    const uint32_t halo = F - 1, n = kMosaicBlockPx + 2 * halo;
+    for (uint32_t i = threadIdx.x; i < n; i += kMosaicBlockPx) {
+        const uint32_t u = u0 + i - halo;   // wraps below 0: then it is not below W either
+        win[i] = u < W ? g[row + u] : (uint16_t)0;
+    }
+    __syncthreads();
+    const uint32_t u = u0 + threadIdx.x;
+    if (u >= W) return;
+    const uint32_t c = halo + threadIdx.x, g0 = win[c], F2 = F * F;
+    uint32_t best = g0 * g0 < F2 ? g0 * g0 : F2;
+    for (uint32_t dx = 1; dx < F && dx * dx < best; ++dx) {
+        const uint32_t a = win[c - dx], b = win[c + dx], m = a < b ? a : b, d = dx * dx + m * m;
+        best = d < best ? d : best;
+    }
+    dist2[row + u] = best;
+}
+
 template <int kPhase>
 static void mosaic_launch(uint32_t n_blocks, hipStream_t s, const MosaicImage *table, int n, const MosaicGrid &g, uint32_t *bounds,
                           unsigned long long *key, uint32_t *pix, const MosaicOut &out) {
@@ -282,8 +352,42 @@ hipError_t launch_mosaic_accumulate(bool plain, void *table, int n_images, const
                                     const MosaicGrid &grid, const unsigned long long *key, float inv_h, unsigned long long *acc,
                                     hipStream_t s) {
     mosaic_for_each_launch(table, n_images, images, first_ordinal, s, [&](uint32_t nb, const MosaicImage *entries, int nl) {
-        if (plain) hipLaunchKernelGGL((mosaic_accumulate_kernel<true>), dim3(nb), dim3(256), 0, s, entries, nl, grid, key, inv_h, acc);
-        else hipLaunchKernelGGL((mosaic_accumulate_kernel<false>), dim3(nb), dim3(256), 0, s, entries, nl, grid, key, inv_h, acc);
+        if (plain) hipLaunchKernelGGL((mosaic_accumulate_kernel<true, false>), dim3(nb), dim3(256), 0, s, entries, nl, grid, key, inv_h, acc, MosaicFeather{});
+        else hipLaunchKernelGGL((mosaic_accumulate_kernel<false, false>), dim3(nb), dim3(256), 0, s, entries, nl, grid, key, inv_h, acc, MosaicFeather{});
+    });
+    return hipGetLastError();
+}
+
+hipError_t launch_mosaic_feather(void *table, int n_images, const sucre_mosaic_image_t *images, int feather_px, void *feather,
+                                 hipStream_t s) {
+    auto *dist2 = static_cast<uint32_t *>(feather);
+    auto *g = reinterpret_cast<uint16_t *>(dist2 + feather_words(n_images, images));
+    size_t base = 0;   // words ahead of this launch's first image
+    int first = 0;     // that image
+    mosaic_for_each_launch(table, n_images, images, 0, s, [&](uint32_t nb, const MosaicImage *entries, int nl) {
+        int Hmax = 0, Wmax = 0;
+        for (int i = first; i < first + nl; ++i) {
+            Hmax = images[i].H > Hmax ? images[i].H : Hmax;
+            Wmax = images[i].W > Wmax ? images[i].W : Wmax;
+        }
+        hipLaunchKernelGGL(feather_columns_kernel, dim3((uint32_t)(Wmax + 63) / 64, (uint32_t)nl), dim3(64), 0, s, entries, (uint32_t)feather_px,
+                           g + base);
+        hipLaunchKernelGGL(feather_rows_kernel, dim3((uint32_t)(Wmax + kMosaicBlockPx - 1) / kMosaicBlockPx, (uint32_t)Hmax, (uint32_t)nl),
+                           dim3(256), 0, s, entries, (uint32_t)feather_px, g + base, dist2 + base);
+        base += (size_t)nb * kMosaicBlockPx;
+        first += nl;
+    });
+    return hipGetLastError();
+}
+
+hipError_t launch_mosaic_accumulate_feathered(bool plain, void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                                              const MosaicGrid &grid, const unsigned long long *key, float inv_h, int feather_px,
+                                              const void *feather, unsigned long long *acc, hipStream_t s) {
+    MosaicFeather f = {static_cast<const uint32_t *>(feather), (uint32_t)feather_px * (uint32_t)feather_px, 1.0f / (float)feather_px};
+    mosaic_for_each_launch(table, n_images, images, first_ordinal, s, [&](uint32_t nb, const MosaicImage *entries, int nl) {
+        if (plain) hipLaunchKernelGGL((mosaic_accumulate_kernel<true, true>), dim3(nb), dim3(256), 0, s, entries, nl, grid, key, inv_h, acc, f);
+        else hipLaunchKernelGGL((mosaic_accumulate_kernel<false, true>), dim3(nb), dim3(256), 0, s, entries, nl, grid, key, inv_h, acc, f);
+        f.dist2 += (size_t)nb * kMosaicBlockPx;
     });
     return hipGetLastError();
 }

@@ -1002,6 +1002,22 @@ def mosaic_blend_depth(blend) -> np.float32:
     return np.float32(H)
 
 
+MOSAIC_FEATHER_RANGE = (1, 1024)   # feather widths F a blend takes, source pixels (csrc/mosaic.h, "The feather")
+
+
+def mosaic_feather_px(feather) -> int:
+    """``feather`` as the feather width F in source pixels, or ValueError unless it is an integral number within
+    ``MOSAIC_FEATHER_RANGE``."""
+    try:
+        F = float(feather)
+    except (TypeError, ValueError):
+        F = float('nan')
+    if isinstance(feather, bool) or not (np.isfinite(F) and F == int(F) and MOSAIC_FEATHER_RANGE[0] <= F <= MOSAIC_FEATHER_RANGE[1]):
+        raise ValueError(f'mosaic feather width F must be an integer within [{MOSAIC_FEATHER_RANGE[0]}, {MOSAIC_FEATHER_RANGE[1]}] source pixels, '
+                         f'not {feather}')
+    return int(F)
+
+
 MOSAIC_FILL_RANGE = (1e-6, 1e6)    # fill reaches R a mosaic takes, metres
 
 
@@ -1053,7 +1069,15 @@ class Mosaic:
     Hole filling: ``fill(R)`` once ``gather`` (with a blend: ``normalize`` too) is through -- a bounded push-pull over a pyramid of
     the grid (csrc/fill.h) that closes every hole up to ``R`` metres across and reaches at most ``3 x 2^L`` cells beyond the
     footprint; ``result()`` then also holds ``J_filled``, ``raw_filled`` and ``fill_level`` (with a blend ``J_blend_filled`` and
-    ``raw_blend_filled``).  The other outputs are not touched."""
+    ``raw_blend_filled``).  The other outputs are not touched.
+
+    The feather: ``begin(blend=H, feather=F)`` -- every sample's weight takes one more factor, ``min(sqrt(dist2) / F, 1)`` of the
+    sample's distance in source pixels to the nearest pixel of its image that does not take part or lies outside it (csrc/mosaic.h,
+    "The feather"), so the blend no longer steps where a view's footprint ends.  ``accumulate`` then forms the batch's exact integer
+    map on the device first, in a buffer sized to the largest batch seen; ``J_blend``, ``raw_blend``, ``weight`` and ``samples`` are
+    the feathered ones, ``result()`` holds ``feather`` (= F), and ``feather_counts`` (int64 x 2, device) counts the pixels that took
+    part within F pixels of an edge and all of them.  ``feather_map(views, Js, F)`` returns the maps themselves; it needs no
+    ``begin``."""
 
     def __init__(self, axes, gsd, device):
         _lib.load()
@@ -1078,6 +1102,7 @@ class Mosaic:
         self._out = None
         self.blend = self.inv_h = self.acc = None
         self._blend_out = None
+        self.feather = self.feather_counts = self._feather_buf = None
         self.fill_reach = self.fill_levels = self.pyramid = None
         self._fill_out = None
 
@@ -1120,11 +1145,16 @@ class Mosaic:
         bits = np.where(k & 0x80000000, k & 0x7fffffff, ~k).astype(np.uint32)   # key_value of csrc/order_key.h
         return tuple(bits.view(np.float32).tolist())
 
-    def begin(self, bounds=None, blend=None):
+    def begin(self, bounds=None, blend=None, feather=None):
         """Fixes the grid and allocates; ``blend``: the blend depth H in metres (``MOSAIC_BLEND_RANGE``) -- a pixel whose range
-        exceeds its cell's smallest one by d gets the weight ``max(1 - d / H, 0)^2`` -- or None for the best view alone."""
+        exceeds its cell's smallest one by d gets the weight ``max(1 - d / H, 0)^2`` -- or None for the best view alone;
+        ``feather``: with a blend, the feather width F in source pixels (``MOSAIC_FEATHER_RANGE``), or None for none."""
         if blend is not None:
             blend = mosaic_blend_depth(blend)   # before anything is allocated
+        if feather is not None:
+            feather = mosaic_feather_px(feather)
+            if blend is None:
+                raise ValueError('Mosaic.begin: a feather is a factor of the blend\'s weight; give the blend depth too (blend=H)')
         if bounds is None:
             bounds = self.bounds()
             if bounds is None:
@@ -1152,6 +1182,9 @@ class Mosaic:
                      'range': torch.full((Hm, Wm), nan, dtype=torch.float32, device=dev)}
         self.blend, self.inv_h, self.acc, self._blend_out = blend, None, None, None
         self.fill_reach = self.fill_levels = self.pyramid = self._fill_out = None
+        self.feather, self.feather_counts, self._feather_buf = feather, None, None
+        if feather is not None:
+            self.feather_counts = torch.zeros(2, dtype=torch.int64, device=dev)
         if blend is not None:
             self.inv_h = np.float32(1) / blend
             self.acc = torch.zeros((Hm * Wm, _lib.MOSAIC_ACC_WORDS), dtype=torch.int64, device=dev)
@@ -1198,14 +1231,57 @@ class Mosaic:
 
     def accumulate(self, views: list, Js: list, first_ordinal: int, plain: bool = False) -> None:
         """Adds the images' weighted samples to ``acc``.  Valid once ``splat`` has seen every image (``key`` holds every cell's
-        smallest range then).  ``plain``: eight atomics per pixel instead of eight per run of a wave's lanes (the same ``acc``)."""
+        smallest range then).  ``plain``: eight atomics per pixel instead of eight per run of a wave's lanes (the same ``acc``).
+        With a feather the batch's map is formed first (``sucre_mosaic_feather``) and the feathered phase reads it."""
         self._blending('accumulate')
         arr, n, table, _ = self._images(views, Js)
+        if self.feather is not None:
+            with torch.cuda.device(self.device):
+                self._feather_buf, words = self._feather_pass(arr, n, table, self.feather, self._feather_buf)
+                if len({tuple(d2.shape) for d2 in words}) == 1:   # one size: the maps as one strided tensor, two reductions
+                    H, W = words[0].shape
+                    pitch = -(-(H * W) // _lib.MOSAIC_BLOCK_PX) * _lib.MOSAIC_BLOCK_PX
+                    words = [torch.as_strided(words[0], (n, H * W), (pitch, 1))]
+                for d2 in words:
+                    self.feather_counts += torch.stack([((d2 > 0) & (d2 < self.feather ** 2)).sum(), (d2 > 0).sum()])
+                _lib.check(_lib.load().sucre_mosaic_accumulate_feathered(
+                    C.c_void_p(table.data_ptr()), n, arr, int(first_ordinal), C.byref(self.grid), C.c_void_p(self.key.data_ptr()),
+                    C.c_float(float(self.inv_h)), self.feather, C.c_void_p(self._feather_buf.data_ptr()), C.c_void_p(self.acc.data_ptr()),
+                    _lib.MOSAIC_PLAIN_ATOMIC if plain else 0, _stream_ptr()))
+            return
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().sucre_mosaic_accumulate(C.c_void_p(table.data_ptr()), n, arr, int(first_ordinal), C.byref(self.grid),
                                                            C.c_void_p(self.key.data_ptr()), C.c_float(float(self.inv_h)),
                                                            C.c_void_p(self.acc.data_ptr()), _lib.MOSAIC_PLAIN_ATOMIC if plain else 0,
                                                            _stream_ptr()))
+
+    @staticmethod
+    def _feather_pass(arr, n: int, table, F: int, buf=None):
+        """Enqueues ``sucre_mosaic_feather`` over the images of ``arr`` into ``buf`` (a new buffer when None or too small) and
+        returns the buffer and, per image, the (H,W) int32 view of its ``dist2`` words in it."""
+        lib = _lib.load()
+        n_bytes = lib.sucre_mosaic_feather_bytes(n, arr)
+        if n_bytes == 0:
+            raise _lib.SucreError(f'sucre_mosaic_feather_bytes: {lib.sucre_last_error().decode()}')
+        if buf is None or buf.numel() < n_bytes:
+            buf = torch.empty(n_bytes, dtype=torch.uint8, device=table.device)    # (4-byte aligned: the allocator's blocks are)
+        _lib.check(lib.sucre_mosaic_feather(C.c_void_p(table.data_ptr()), n, arr, int(F), C.c_void_p(buf.data_ptr()), _stream_ptr()))
+        words = buf[:n_bytes // 6 * 4].view(torch.int32)   # the dist2 words; the uint16 scratch sits behind them
+        maps, at = [], 0
+        for e in arr:
+            maps.append(words[at:at + e.H * e.W].view(e.H, e.W))
+            at += -(-(e.H * e.W) // _lib.MOSAIC_BLOCK_PX) * _lib.MOSAIC_BLOCK_PX
+        return buf, maps
+
+    def feather_map(self, views: list, Js: list, F) -> list:
+        """Per image the (H,W) int32 ``dist2`` of csrc/mosaic.h, "The feather": ``min(D2, F^2)`` with D2 the squared distance in
+        pixels from a pixel that takes part to the nearest one that does not or lies outside the image; 0 for a pixel that does
+        not take part.  Needs no ``begin``; only enqueues (reading a map waits for it)."""
+        F = mosaic_feather_px(F)
+        arr, n, table, _ = self._images(views, Js)
+        with torch.cuda.device(self.device):
+            _, maps = self._feather_pass(arr, n, table, F)
+        return [m.clone() for m in maps]
 
     def normalize(self, check: bool = True) -> None:
         """The per-cell pass from ``acc`` to the four blended outputs; waits for it, and raises ValueError when a cell holds
@@ -1268,17 +1344,20 @@ class Mosaic:
         (Hm,Wm,3) float32 (NaN), ``raw_blend`` (Hm,Wm,3) uint8 (0), ``weight`` (Hm,Wm) float32 -- the sum of the samples' weights,
         each at most 1 -- (0) and ``samples`` (Hm,Wm) int32 (0), complete once ``normalize`` has run.  After ``fill`` also
         ``J_filled`` (Hm,Wm,3) float32 (NaN: still empty), ``raw_filled`` (Hm,Wm,3) uint8 (0), ``fill_level`` (Hm,Wm) int32 (-1)
-        and, with a blend, ``J_blend_filled`` and ``raw_blend_filled``."""
+        and, with a blend, ``J_blend_filled`` and ``raw_blend_filled``.  With a feather also ``feather``, the width F (an int)."""
         self._begun('result')
         out = {**self._out, **self._blend_out} if self.blend is not None else dict(self._out)
+        if self.feather is not None:
+            out['feather'] = self.feather
         return {**out, **self._fill_out} if self._fill_out is not None else out
 
 
 def mosaic_of(views: list, Js: list, axes, gsd, bounds=None, batch: int = 32, plain_atomic: bool = False, blend=None,
-              fill=None) -> 'Mosaic':
+              fill=None, feather=None) -> 'Mosaic':
     """All four phases over device-resident ``views`` / ``Js`` (ordinal = position in the list), ``batch`` images per call; with
     ``blend`` (the blend depth H, metres) the accumulate phase and the normalise pass after them (``plain_atomic``: both the
-    splat and the accumulate phase in their plain forms); with ``fill`` (the reach R, metres) the hole filling after all of them."""
+    splat and the accumulate phase in their plain forms), with ``feather`` (the width F, source pixels; only with ``blend``) the
+    feathered one; with ``fill`` (the reach R, metres) the hole filling after all of them."""
     views, Js = list(views), list(Js)
     if not views:
         raise ValueError('mosaic_of: no view')
@@ -1288,12 +1367,16 @@ def mosaic_of(views: list, Js: list, axes, gsd, bounds=None, batch: int = 32, pl
         mosaic_blend_depth(blend)   # before anything is allocated
     if fill is not None:
         mosaic_fill_reach(fill)
+    if feather is not None:
+        mosaic_feather_px(feather)
+        if blend is None:
+            raise ValueError('mosaic_of: a feather is a factor of the blend\'s weight; give the blend depth too (blend=H)')
     m = Mosaic(axes, gsd, views[0].depth.device)
     chunks = [(i, views[i:i + batch], Js[i:i + batch]) for i in range(0, len(views), batch)]
     if bounds is None:
         for _, v, J in chunks:
             m.add_bounds(v, J)
-    m.begin(bounds, blend=blend)
+    m.begin(bounds, blend=blend, feather=feather)
     for i, v, J in chunks:
         m.splat(v, J, i, plain_atomic=plain_atomic)
     for i, v, J in chunks:

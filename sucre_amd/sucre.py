@@ -1400,7 +1400,7 @@ def _mosaic_picture(J: Tensor, stretch) -> np.ndarray:
 
 
 def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, output_dir: Path, gsd: float | None = None, axes=None,
-           stretch=None, device: str = 'cuda', blend: float | None = None, fill: float | None = None) -> dict:
+           stretch=None, device: str = 'cuda', blend: float | None = None, fill: float | None = None, feather: int | None = None) -> dict:
     """One picture of the seabed from a finished restoration: every pixel of ``images`` (``sfm.Image`` objects or names of
     ``colmap_model``; at most ``engine.MAX_VIEWS``, ordinal = position) with a valid depth and a restored colour --
     ``results_dir / <name>.pt``, key ``J`` -- is dropped onto the plane grid ``axes`` (``mosaic_axes`` unless given) of ``gsd``
@@ -1424,8 +1424,15 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
     that makes ``mosaic.png``: its own percentiles, or ``stretch``), ``mosaic_raw_filled.png`` and ``mosaic_filled_mask.png`` (255
     measured, 128 filled, 0 empty) come next to them -- with a blend also ``mosaic_blend_filled.png`` and
     ``mosaic_blend_raw_filled.png`` --, ``mosaic.pt`` gains ``J_filled, raw_filled, fill_level`` (``J_blend_filled,
-    raw_blend_filled``), ``fill`` and ``fill_levels``, and one more line is printed.  Not built: feathering by the distance to the
-    image border, multi-band blending."""
+    raw_blend_filled``), ``fill`` and ``fill_levels``, and one more line is printed.
+
+    ``feather``: with ``blend``, a feather width F in source pixels (``engine.MOSAIC_FEATHER_RANGE``).  Every sample's weight then
+    takes one more factor, ``min(sqrt(dist2) / F, 1)`` of its distance to the nearest pixel of its image that does not take part or
+    lies outside it -- an exact integer map made on the device per batch (csrc/mosaic.h, "The feather") --, so the blend fades
+    out towards the edge of every footprint, NaN patch and depth hole and does not step there.  The blended files and keys are then
+    the feathered ones (a fill fills from them); the best-view ones stay as they are, byte for byte; ``mosaic.pt`` gains
+    ``feather`` and one more line is printed after the blend's (its share "within F px of an edge" is counted over the pixels that
+    take part, ``engine.Mosaic.feather_counts``, whether or not their weight rounds to nothing).  Not built: multi-band blending."""
     from . import engine
     sfm.require_gpu(device, 'mosaic')
     images = [colmap_model[im] if isinstance(im, str) else im for im in images]
@@ -1445,6 +1452,13 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
             fill = engine.mosaic_fill_reach(fill)
         except ValueError as e:
             raise SystemExit(f'--mosaic-fill: {e}')
+    if feather is not None:
+        if blend is None:
+            raise SystemExit('--mosaic-feather: only with --mosaic-blend H')
+        try:
+            feather = engine.mosaic_feather_px(feather)
+        except ValueError as e:
+            raise SystemExit(f'--mosaic-feather: {e}')
     results_dir, output_dir = Path(results_dir), Path(output_dir)
     for image in images:   # before anything is decoded
         path = _consistency_file(results_dir, image)
@@ -1478,7 +1492,7 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
         for _, batch in batches:
             m.add_bounds(*resident(batch))
         try:
-            Hm, Wm = m.begin(blend=blend)
+            Hm, Wm = m.begin(blend=blend, feather=feather)
         except ValueError as e:
             raise SystemExit(f'--mosaic: {e}')
         for phase in (m.splat, m.resolve, m.gather) + ((m.accumulate,) if blend is not None else ()):
@@ -1496,7 +1510,7 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
         blend_picture = _mosaic_picture(out['J_blend'], stretch) if blend is not None else None
         filled_picture = _mosaic_picture(out['J_filled'], stretch) if fill is not None else None
         blend_filled_picture = _mosaic_picture(out['J_blend_filled'], stretch) if fill is not None and blend is not None else None
-        out = {k: v.cpu() for k, v in out.items()}
+        out = {k: v.cpu() if torch.is_tensor(v) else v for k, v in out.items()}
     source = out['source']
     filled = source >= 0
     n_filled, n_cells = int(filled.sum()), Hm * Wm
@@ -1531,6 +1545,10 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
         total, most, several = int(samples.sum()), int(samples.max()), int((samples > 1).sum())
         print(f'mosaic blend of depth {float(blend):.6g} m: {total} samples, {total / max(1, n_filled):.2f} per filled cell on average, '
               f'{most} at most; {100.0 * several / max(1, n_filled):.1f} % of the filled cells blend more than one sample')
+    if feather is not None:
+        near, part = (int(x) for x in m.feather_counts.cpu())
+        print(f'mosaic feather of {feather} px: {100.0 * near / max(1, part):.1f} % of the samples within {feather} px of an edge; '
+              f'smallest weight sum in a filled cell {float(out["weight"][out["samples"] > 0].min()) if n_filled else 0.0:.6g}')
     if fill is not None:
         level = out['fill_level']
         print(f'mosaic fill of {float(fill):.6g} m ({int(m.fill_levels)} levels): {int((level > 0).sum())} cells filled, '
@@ -1577,6 +1595,19 @@ _MODE_REFUSES = {   # mode -> (flag, why), in the order they are looked at
 }
 
 
+_ONLY_WITH = [   # (flag, the flag it needs, that one's value), in the order they are looked at
+    ('--mosaic-gsd', '--mosaic', 'DIR'), ('--mosaic-blend', '--mosaic', 'DIR'), ('--mosaic-fill', '--mosaic', 'DIR'),
+    ('--mosaic-feather', '--mosaic-blend', 'H'),
+]
+
+
+def _refuse_lone_flags(args) -> None:
+    """The flags of ``_ONLY_WITH`` given without the flag they go with, refused before any file is opened."""
+    for flag, needs, value in _ONLY_WITH:
+        if getattr(args, flag[2:].replace('-', '_'), None) is not None and getattr(args, needs[2:].replace('-', '_'), None) is None:
+            raise SystemExit(f'{flag}: only with {needs} {value}')
+
+
 def _refuse_mode_flags(args, mode: str) -> None:
     """What ``mode`` (--mosaic, --check-consistency, --apply-water) does not combine with, refused before any file is opened."""
     for flag, why in _MODE_REFUSES[mode]:
@@ -1585,8 +1616,8 @@ def _refuse_mode_flags(args, mode: str) -> None:
 
 
 def _refuse_mosaic_values(args, world: int = 1) -> None:
-    """The values of --mosaic-gsd, --mosaic-blend and --mosaic-fill and the world size a mosaic takes, refused before any file is
-    opened."""
+    """The values of --mosaic-gsd, --mosaic-blend, --mosaic-fill and --mosaic-feather and the world size a mosaic takes, refused
+    before any file is opened."""
     gsd = getattr(args, 'mosaic_gsd', None)
     if gsd is not None and not (np.isfinite(gsd) and gsd > 0):
         raise SystemExit(f'--mosaic-gsd: G must be a finite size > 0 in metres, not {gsd}')
@@ -1596,6 +1627,9 @@ def _refuse_mosaic_values(args, world: int = 1) -> None:
     fill = getattr(args, 'mosaic_fill', None)
     if fill is not None and not (np.isfinite(fill) and 1e-6 <= fill <= 1e6):
         raise SystemExit(f'--mosaic-fill: R must be a finite reach within [1e-06, 1e+06] metres, not {fill}')
+    feather = getattr(args, 'mosaic_feather', None)
+    if feather is not None and not (np.isfinite(feather) and feather == int(feather) and 1 <= feather <= 1024):
+        raise SystemExit(f'--mosaic-feather: F must be an integer within [1, 1024] source pixels, not {feather:g}')
     if world > 1:
         raise SystemExit(f'--mosaic: a world size of {world} is not supported yet: the four phases are separate entries of the library '
                          f'so that ranks can all-reduce bounds, keys and pixel words between them, but that all-reduce is not built; '
@@ -1623,12 +1657,7 @@ def parse_args(args: argparse.Namespace):
     apply = getattr(args, 'apply_water', None)
     check = getattr(args, 'check_consistency', None)
     mosaic_dir = getattr(args, 'mosaic', None)
-    if mosaic_dir is None and getattr(args, 'mosaic_gsd', None) is not None:
-        raise SystemExit('--mosaic-gsd: only with --mosaic DIR')
-    if mosaic_dir is None and getattr(args, 'mosaic_blend', None) is not None:
-        raise SystemExit('--mosaic-blend: only with --mosaic DIR')
-    if mosaic_dir is None and getattr(args, 'mosaic_fill', None) is not None:
-        raise SystemExit('--mosaic-fill: only with --mosaic DIR')
+    _refuse_lone_flags(args)
     if mosaic_dir is not None:
         _refuse_mode_flags(args, '--mosaic')
         _refuse_mosaic_values(args, world)
@@ -1711,7 +1740,8 @@ def parse_args(args: argparse.Namespace):
     try:
         if mosaic_dir is not None:
             mosaic(images, colmap_model, mosaic_dir, args.output_dir, gsd=getattr(args, 'mosaic_gsd', None), stretch=stretch, device=device,
-                   blend=getattr(args, 'mosaic_blend', None), fill=getattr(args, 'mosaic_fill', None))
+                   blend=getattr(args, 'mosaic_blend', None), fill=getattr(args, 'mosaic_fill', None),
+                   feather=getattr(args, 'mosaic_feather', None))
         elif check is not None:
             if world > 1:   # the targets' records are gathered on rank 0
                 sdist.init_process_group()
@@ -1963,6 +1993,12 @@ def build_parser() -> argparse.ArgumentParser:
                                'filled, 0 empty; with --mosaic-blend also mosaic_blend_filled.png and mosaic_blend_raw_filled.png) next to the '
                                'other files, which stay as they are, adds J_filled, raw_filled, fill_level, fill and fill_levels to mosaic.pt '
                                'and prints one more line')
+    p.extras.add_argument('--mosaic-feather', type=float, metavar='F', default=argparse.SUPPRESS,
+                          help='with --mosaic-blend: also weight every pixel by its distance to the edge of its image\'s footprint -- the '
+                               'image border, a NaN patch of the restored image, a hole of the depth map --, rising from nothing at the edge '
+                               'to the full weight F source pixels inside (an integer, 1..1024; an exact distance map made on the device), '
+                               'so the blend does not step where a view ends; the blended files and keys are then the feathered ones, the '
+                               'best-view ones stay as they are; adds feather to mosaic.pt and prints one more line')
     p.extras.add_argument('--common-stretch', action='store_true', default=argparse.SUPPRESS,
                           help='with --shared-water or --apply-water: stretch every <stem>_rgb.png between the SAME per-channel 1st '
                                'and 99th percentile, those of the valid pixels of all images of the request pooled (all ranks), '
