@@ -992,25 +992,38 @@ int sucre_mosaic_gather(void *table_dev, int n_images, const sucre_mosaic_image_
                                    const_cast<uint32_t *>(pix_dev), out, static_cast<hipStream_t>(stream)), "sucre_mosaic_gather");
 }
 
-int sucre_mosaic_accumulate(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
-                            const sucre_mosaic_grid_t *grid, const uint64_t *key_dev, float inv_h, int64_t *acc_dev, unsigned flags,
-                            void *stream) {
+static int check_feather_px(int feather_px) {
+    if (feather_px < 1 || feather_px > kFeatherMax) return fail(SUCRE_ERR_ARG, "feather_px=%d outside [1,%d]", feather_px, kFeatherMax);
+    return SUCRE_OK;
+}
+
+// What the two accumulate entries check, in this order, and launch; `feathered`: feather_px and feather_dev are read.
+static int mosaic_accumulate(const char *entry, bool feathered, void *table_dev, int n_images, const sucre_mosaic_image_t *images,
+                             int first_ordinal, const sucre_mosaic_grid_t *grid, const uint64_t *key_dev, float inv_h, int feather_px,
+                             const void *feather_dev, int64_t *acc_dev, unsigned flags, void *stream) {
     if (int rc = check_mosaic_images(table_dev, n_images, images, first_ordinal)) return rc;
     MosaicGrid g;
     if (int rc = check_mosaic_grid(grid, &g)) return rc;
     if (!key_dev || !aligned(key_dev, 8)) return fail(SUCRE_ERR_ARG, "key_dev is NULL or not 8-byte aligned");
     if (!std::isfinite(inv_h) || !(inv_h > 0.0f)) return fail(SUCRE_ERR_ARG, "inv_h=%g must be finite and > 0", (double)inv_h);
+    MosaicFeather f = {};
+    if (feathered) {
+        if (int rc = check_feather_px(feather_px)) return rc;
+        if (!feather_dev || !aligned(feather_dev, 4)) return fail(SUCRE_ERR_ARG, "feather_dev is NULL or not 4-byte aligned");
+        f = {static_cast<const uint32_t *>(feather_dev), (uint32_t)feather_px * (uint32_t)feather_px, 1.0f / (float)feather_px};
+    }
     if (!acc_dev || !aligned(acc_dev, 8)) return fail(SUCRE_ERR_ARG, "acc_dev is NULL or not 8-byte aligned");
     if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
     return check_hip(launch_mosaic_accumulate((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) != 0, table_dev, n_images, images, first_ordinal, g,
-                                              reinterpret_cast<const unsigned long long *>(key_dev), inv_h,
-                                              reinterpret_cast<unsigned long long *>(acc_dev), static_cast<hipStream_t>(stream)),
-                     "sucre_mosaic_accumulate");
+                                              reinterpret_cast<const unsigned long long *>(key_dev), inv_h, feathered ? &f : nullptr,
+                                              reinterpret_cast<unsigned long long *>(acc_dev), static_cast<hipStream_t>(stream)), entry);
 }
 
-static int check_feather_px(int feather_px) {
-    if (feather_px < 1 || feather_px > kFeatherMax) return fail(SUCRE_ERR_ARG, "feather_px=%d outside [1,%d]", feather_px, kFeatherMax);
-    return SUCRE_OK;
+int sucre_mosaic_accumulate(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                            const sucre_mosaic_grid_t *grid, const uint64_t *key_dev, float inv_h, int64_t *acc_dev, unsigned flags,
+                            void *stream) {
+    return mosaic_accumulate("sucre_mosaic_accumulate", false, table_dev, n_images, images, first_ordinal, grid, key_dev, inv_h, 0, nullptr,
+                             acc_dev, flags, stream);
 }
 
 size_t sucre_mosaic_feather_bytes(int n_images, const sucre_mosaic_image_t *images) {
@@ -1039,20 +1052,8 @@ int sucre_mosaic_feather(void *table_dev, int n_images, const sucre_mosaic_image
 int sucre_mosaic_accumulate_feathered(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
                                       const sucre_mosaic_grid_t *grid, const uint64_t *key_dev, float inv_h, int feather_px,
                                       const void *feather_dev, int64_t *acc_dev, unsigned flags, void *stream) {
-    if (int rc = check_mosaic_images(table_dev, n_images, images, first_ordinal)) return rc;
-    MosaicGrid g;
-    if (int rc = check_mosaic_grid(grid, &g)) return rc;
-    if (!key_dev || !aligned(key_dev, 8)) return fail(SUCRE_ERR_ARG, "key_dev is NULL or not 8-byte aligned");
-    if (!std::isfinite(inv_h) || !(inv_h > 0.0f)) return fail(SUCRE_ERR_ARG, "inv_h=%g must be finite and > 0", (double)inv_h);
-    if (int rc = check_feather_px(feather_px)) return rc;
-    if (!feather_dev || !aligned(feather_dev, 4)) return fail(SUCRE_ERR_ARG, "feather_dev is NULL or not 4-byte aligned");
-    if (!acc_dev || !aligned(acc_dev, 8)) return fail(SUCRE_ERR_ARG, "acc_dev is NULL or not 8-byte aligned");
-    if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
-    return check_hip(launch_mosaic_accumulate_feathered((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) != 0, table_dev, n_images, images,
-                                                        first_ordinal, g, reinterpret_cast<const unsigned long long *>(key_dev), inv_h,
-                                                        feather_px, feather_dev, reinterpret_cast<unsigned long long *>(acc_dev),
-                                                        static_cast<hipStream_t>(stream)),
-                     "sucre_mosaic_accumulate_feathered");
+    return mosaic_accumulate("sucre_mosaic_accumulate_feathered", true, table_dev, n_images, images, first_ordinal, grid, key_dev, inv_h,
+                             feather_px, feather_dev, acc_dev, flags, stream);
 }
 
 int sucre_mosaic_normalize(const sucre_mosaic_grid_t *grid, const int64_t *acc_dev, float *J_out, uint8_t *raw_out, float *weight_out,

@@ -161,19 +161,16 @@ hipError_t launch_mosaic(MosaicPhase phase, void *table, int n_images, const suc
                          const MosaicGrid &grid, uint32_t *bounds, unsigned long long *key, uint32_t *pix, const MosaicOut &out,
                          hipStream_t s);
 
-// The blend's accumulate phase over images[0 .. n) (the same launches as a phase above; key: read, acc: added to) and its
-// per-cell pass (one launch).
-hipError_t launch_mosaic_accumulate(bool plain, void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
-                                    const MosaicGrid &grid, const unsigned long long *key, float inv_h, unsigned long long *acc,
-                                    hipStream_t s);
-hipError_t launch_mosaic_normalize(const MosaicGrid &grid, const long long *acc, const MosaicBlend &out, hipStream_t s);
-
-// The feather's map of images[0 .. n) into `feather` (feather_bytes; two launches per 32 images, plus the table's), and the
-// accumulate phase that reads it (the same call's images in the same order; `feather` as the map's call left it).
+// The feather's map of images[0 .. n) into `feather` (feather_bytes; two launches per 32 images, plus the table's).
 hipError_t launch_mosaic_feather(void *table, int n_images, const sucre_mosaic_image_t *images, int feather_px, void *feather,
                                  hipStream_t s);
-hipError_t launch_mosaic_accumulate_feathered(bool plain, void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
-                                              const MosaicGrid &grid, const unsigned long long *key, float inv_h, int feather_px,
-                                              const void *feather, unsigned long long *acc, hipStream_t s);
+
+// The blend's accumulate phase over images[0 .. n) (the same launches as a phase above; key: read, acc: added to) and its
+// per-cell pass (one launch).  `feather`: NULL, or what a feathered phase reads -- dist2 the map as launch_mosaic_feather left it
+// for the same call's images in the same order.
+hipError_t launch_mosaic_accumulate(bool plain, void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                                    const MosaicGrid &grid, const unsigned long long *key, float inv_h, const MosaicFeather *feather,
+                                    unsigned long long *acc, hipStream_t s);
+hipError_t launch_mosaic_normalize(const MosaicGrid &grid, const long long *acc, const MosaicBlend &out, hipStream_t s);
 
 }  // namespace sucre

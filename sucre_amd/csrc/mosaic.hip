@@ -349,11 +349,18 @@ hipError_t launch_mosaic(MosaicPhase phase, void *table, int n_images, const suc
 }
 
 hipError_t launch_mosaic_accumulate(bool plain, void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
-                                    const MosaicGrid &grid, const unsigned long long *key, float inv_h, unsigned long long *acc,
-                                    hipStream_t s) {
+                                    const MosaicGrid &grid, const unsigned long long *key, float inv_h, const MosaicFeather *feather,
+                                    unsigned long long *acc, hipStream_t s) {
+    MosaicFeather f = feather ? *feather : MosaicFeather{};
     mosaic_for_each_launch(table, n_images, images, first_ordinal, s, [&](uint32_t nb, const MosaicImage *entries, int nl) {
-        if (plain) hipLaunchKernelGGL((mosaic_accumulate_kernel<true, false>), dim3(nb), dim3(256), 0, s, entries, nl, grid, key, inv_h, acc, MosaicFeather{});
-        else hipLaunchKernelGGL((mosaic_accumulate_kernel<false, false>), dim3(nb), dim3(256), 0, s, entries, nl, grid, key, inv_h, acc, MosaicFeather{});
+        if (!feather) {
+            if (plain) hipLaunchKernelGGL((mosaic_accumulate_kernel<true, false>), dim3(nb), dim3(256), 0, s, entries, nl, grid, key, inv_h, acc, f);
+            else hipLaunchKernelGGL((mosaic_accumulate_kernel<false, false>), dim3(nb), dim3(256), 0, s, entries, nl, grid, key, inv_h, acc, f);
+            return;
+        }
+        if (plain) hipLaunchKernelGGL((mosaic_accumulate_kernel<true, true>), dim3(nb), dim3(256), 0, s, entries, nl, grid, key, inv_h, acc, f);
+        else hipLaunchKernelGGL((mosaic_accumulate_kernel<false, true>), dim3(nb), dim3(256), 0, s, entries, nl, grid, key, inv_h, acc, f);
+        f.dist2 += (size_t)nb * kMosaicBlockPx;   // the map of the next launch's first image
     });
     return hipGetLastError();
 }
@@ -376,18 +383,6 @@ hipError_t launch_mosaic_feather(void *table, int n_images, const sucre_mosaic_i
                            dim3(256), 0, s, entries, (uint32_t)feather_px, g + base, dist2 + base);
         base += (size_t)nb * kMosaicBlockPx;
         first += nl;
-    });
-    return hipGetLastError();
-}
-
-hipError_t launch_mosaic_accumulate_feathered(bool plain, void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
-                                              const MosaicGrid &grid, const unsigned long long *key, float inv_h, int feather_px,
-                                              const void *feather, unsigned long long *acc, hipStream_t s) {
-    MosaicFeather f = {static_cast<const uint32_t *>(feather), (uint32_t)feather_px * (uint32_t)feather_px, 1.0f / (float)feather_px};
-    mosaic_for_each_launch(table, n_images, images, first_ordinal, s, [&](uint32_t nb, const MosaicImage *entries, int nl) {
-        if (plain) hipLaunchKernelGGL((mosaic_accumulate_kernel<true, true>), dim3(nb), dim3(256), 0, s, entries, nl, grid, key, inv_h, acc, f);
-        else hipLaunchKernelGGL((mosaic_accumulate_kernel<false, true>), dim3(nb), dim3(256), 0, s, entries, nl, grid, key, inv_h, acc, f);
-        f.dist2 += (size_t)nb * kMosaicBlockPx;
     });
     return hipGetLastError();
 }

@@ -989,47 +989,75 @@ def mosaic_max_cells() -> int:
 
 MOSAIC_BLEND_RANGE = (1e-6, 1e6)   # blend depths H a mosaic takes, metres
 MOSAIC_MAX_SAMPLES = 1 << 20       # samples of one cell from which the blend's int64 sums may pass 2^62 (csrc/mosaic.h)
+MOSAIC_FILL_RANGE = (1e-6, 1e6)    # fill reaches R a mosaic takes, metres
+MOSAIC_FEATHER_RANGE = (1, 1024)   # feather widths F a blend takes, source pixels (csrc/mosaic.h, "The feather")
+MOSAIC_VALUES = {   # field of MosaicOptions -> (what it is, range, integral, unit, type of the checked value), in the order checked
+    'blend': ('blend depth H', MOSAIC_BLEND_RANGE, False, 'metres', np.float32),
+    'fill': ('fill reach R', MOSAIC_FILL_RANGE, False, 'metres', float),
+    'feather': ('feather width F', MOSAIC_FEATHER_RANGE, True, 'source pixels', int),
+}
+
+
+def _mosaic_refusal(field: str, text: str) -> ValueError:
+    """A ValueError whose ``field`` tells a caller which of its flags to name: the field of ``MosaicOptions`` at fault, or 'grid'
+    where ``Mosaic.begin`` finds no grid to make."""
+    e = ValueError(text)
+    e.field = field
+    return e
+
+
+def _mosaic_value(field: str, value):
+    """``value`` as ``MOSAIC_VALUES[field]`` describes it, or ValueError unless it is finite, within the range and, where the table
+    says so, an integral number and no bool."""
+    what, (lo, hi), integral, unit, kind = MOSAIC_VALUES[field]
+    try:
+        x = float(value)
+    except (TypeError, ValueError):
+        x = float('nan')
+    # The comparison is in float64.  A value that has the checked type already -- the float32 H of a checked record on its way
+    # through begin -- meets the ends as that type holds them, so that float32(1e-6), which lies below 1e-6, passes a second check.
+    if type(value) is kind:
+        lo, hi = kind(lo), kind(hi)
+    ok = bool(np.isfinite(x)) and float(lo) <= x <= float(hi)
+    if ok and integral:
+        ok = not isinstance(value, bool) and x == int(x)
+    if not ok:
+        raise _mosaic_refusal(field, f'mosaic {what} must be {"an integer" if integral else "finite and"} within [{lo:g}, {hi:g}] {unit}, '
+                                     f'not {value}')
+    return kind(x)
 
 
 def mosaic_blend_depth(blend) -> np.float32:
     """``blend`` as the float32 blend depth H, or ValueError unless it is finite and within ``MOSAIC_BLEND_RANGE``."""
-    try:
-        H = float(blend)
-    except (TypeError, ValueError):
-        H = float('nan')
-    if not (np.isfinite(H) and MOSAIC_BLEND_RANGE[0] <= H <= MOSAIC_BLEND_RANGE[1]):
-        raise ValueError(f'mosaic blend depth H must be finite and within [{MOSAIC_BLEND_RANGE[0]:g}, {MOSAIC_BLEND_RANGE[1]:g}] metres, not {blend}')
-    return np.float32(H)
-
-
-MOSAIC_FEATHER_RANGE = (1, 1024)   # feather widths F a blend takes, source pixels (csrc/mosaic.h, "The feather")
+    return _mosaic_value('blend', blend)
 
 
 def mosaic_feather_px(feather) -> int:
     """``feather`` as the feather width F in source pixels, or ValueError unless it is an integral number within
     ``MOSAIC_FEATHER_RANGE``."""
-    try:
-        F = float(feather)
-    except (TypeError, ValueError):
-        F = float('nan')
-    if isinstance(feather, bool) or not (np.isfinite(F) and F == int(F) and MOSAIC_FEATHER_RANGE[0] <= F <= MOSAIC_FEATHER_RANGE[1]):
-        raise ValueError(f'mosaic feather width F must be an integer within [{MOSAIC_FEATHER_RANGE[0]}, {MOSAIC_FEATHER_RANGE[1]}] source pixels, '
-                         f'not {feather}')
-    return int(F)
-
-
-MOSAIC_FILL_RANGE = (1e-6, 1e6)    # fill reaches R a mosaic takes, metres
+    return _mosaic_value('feather', feather)
 
 
 def mosaic_fill_reach(fill) -> float:
     """``fill`` as the reach R in metres, or ValueError unless it is finite and within ``MOSAIC_FILL_RANGE``."""
-    try:
-        R = float(fill)
-    except (TypeError, ValueError):
-        R = float('nan')
-    if not (np.isfinite(R) and MOSAIC_FILL_RANGE[0] <= R <= MOSAIC_FILL_RANGE[1]):
-        raise ValueError(f'mosaic fill reach R must be finite and within [{MOSAIC_FILL_RANGE[0]:g}, {MOSAIC_FILL_RANGE[1]:g}] metres, not {fill}')
-    return R
+    return _mosaic_value('fill', fill)
+
+
+@dataclass(frozen=True)
+class MosaicOptions:
+    """What a mosaic can be asked for beyond the best view: ``blend``, the blend depth H in metres; ``feather``, with a blend, the
+    feather width F in source pixels; ``fill``, the reach R in metres of the hole filling.  None: not asked for."""
+    blend: float = None
+    feather: int = None
+    fill: float = None
+
+    def checked(self, who: str = 'MosaicOptions') -> 'MosaicOptions':
+        """The record with float32 H, int F and float R.  ValueError (``field``: the option at fault) for a value ``MOSAIC_VALUES``
+        does not take -- blend, fill, feather in this order -- and then for a feather without a blend, in the name of ``who``."""
+        values = {f: None if getattr(self, f) is None else _mosaic_value(f, getattr(self, f)) for f in MOSAIC_VALUES}
+        if values['feather'] is not None and values['blend'] is None:
+            raise _mosaic_refusal('feather', f'{who}: a feather is a factor of the blend\'s weight; give the blend depth too (blend=H)')
+        return MosaicOptions(**values)
 
 
 def mosaic_fill_levels(R, gsd, Hm: int, Wm: int) -> int:
@@ -1051,13 +1079,36 @@ def mosaic_cells(lo: float, hi: float, gsd: float) -> int:
         return int((np.float32(hi) - np.float32(lo)) / np.float32(gsd)) + 1
 
 
+_NAN = float('nan')
+MOSAIC_OUTPUTS = {   # key of Mosaic.result() -> (group, trailing shape, dtype, value of an empty cell, PNG of --mosaic, how it is made)
+    # groups: 'best' (the best view; begin), 'blend' (begin with a blend), 'fill' (fill), 'blend_fill' (fill with a blend).  An
+    # empty value of None: the kernel writes every cell.  How: 'stretch' (sucre._mosaic_picture), 'bytes', 'source', 'mask'.
+    'J': ('best', (3,), torch.float32, _NAN, 'mosaic.png', 'stretch'),
+    'raw': ('best', (3,), torch.uint8, 0, 'mosaic_raw.png', 'bytes'),
+    'source': ('best', (), torch.int32, -1, 'mosaic_source.png', 'source'),
+    'pixel': ('best', (), torch.int32, -1, None, None),
+    'range': ('best', (), torch.float32, _NAN, None, None),
+    'J_blend': ('blend', (3,), torch.float32, _NAN, 'mosaic_blend.png', 'stretch'),
+    'raw_blend': ('blend', (3,), torch.uint8, 0, 'mosaic_blend_raw.png', 'bytes'),
+    'weight': ('blend', (), torch.float32, 0, None, None),
+    'samples': ('blend', (), torch.int32, 0, None, None),
+    'fill_level': ('fill', (), torch.int32, None, 'mosaic_filled_mask.png', 'mask'),
+    'J_filled': ('fill', (3,), torch.float32, None, 'mosaic_filled.png', 'stretch'),
+    'raw_filled': ('fill', (3,), torch.uint8, None, 'mosaic_raw_filled.png', 'bytes'),
+    'J_blend_filled': ('blend_fill', (3,), torch.float32, None, 'mosaic_blend_filled.png', 'stretch'),
+    'raw_blend_filled': ('blend_fill', (3,), torch.uint8, None, 'mosaic_blend_raw_filled.png', 'bytes'),
+}
+
+
 class Mosaic:
     """The seabed mosaic (``sucre_mosaic_*``, csrc/mosaic.h) phase by phase, in the style of ``PoolSelect``: every pixel with a
     valid depth and a restored colour without NaN is dropped onto the grid ``axes`` (3,3 float32, rows e1, e2, e3) x ``gsd`` metres
-    per cell, and the pixel with the smallest (range bits, ordinal, pixel index) wins its cell.  ``add_bounds(views, Js)`` any number
+    per cell, and the pixel with the smallest (range bits, ordinal, pixel index) wins its cell.  ``run(batches, options)`` drives
+    every phase below in its order (``mosaic_of`` and ``sucre.mosaic`` go through it); by hand: ``add_bounds(views, Js)`` any number
     of times; ``begin(bounds=None)`` -- waits for the bounds (or takes the caller's ``(lo_s, lo_t, hi_s, hi_t)``; pixels outside
     are dropped), allocates and returns ``(Hm, Wm)``; then ``splat``, ``resolve`` and ``gather``, each over ALL the images (in any
-    batches, every batch with the ordinal of its first image) before the next phase starts; ``result()``.  ``views``:
+    batches, every batch with the ordinal of its first image) before the next phase starts; ``result()``, whose keys, shapes,
+    dtypes and empty values are the rows of ``MOSAIC_OUTPUTS``.  ``views``:
     ``DeviceView`` with uint8 colours; ``Js``: their (H,W,3) float32 device images.  The words a later all-reduce over ranks would
     combine are tensors: ``bounds_words`` (int32 x 4), ``key`` (int64, min), ``pix`` (int32 bit patterns of uint32, unsigned min).
 
@@ -1099,12 +1150,10 @@ class Mosaic:
         self.Hm = self.Wm = None
         self.lo = self.hi = None
         self.key = self.pix = None
-        self._out = None
+        self._out = {}   # the outputs allocated so far, in the order of MOSAIC_OUTPUTS
         self.blend = self.inv_h = self.acc = None
-        self._blend_out = None
         self.feather = self.feather_counts = self._feather_buf = None
         self.fill_reach = self.fill_levels = self.pyramid = None
-        self._fill_out = None
 
     def _images(self, views: list, Js: list):
         views, Js = list(views), list(Js)
@@ -1131,11 +1180,24 @@ class Mosaic:
         table = torch.empty(_lib.load().sucre_mosaic_table_bytes(len(views)), dtype=torch.uint8, device=self.device)
         return arr, len(views), table, keep
 
-    def add_bounds(self, views: list, Js: list) -> None:
-        arr, n, table, _ = self._images(views, Js)
+    def _walk(self, entry: str, images, *rest) -> None:
+        """One entry of the library that walks images, on the current stream: ``entry(table, n, images, *rest, stream)`` with
+        ``images`` as ``_images`` returns them and the tensors of ``rest`` as their addresses."""
+        arr, n, table, _ = images
+        rest = [C.c_void_p(x.data_ptr()) if torch.is_tensor(x) else x for x in rest]
         with torch.cuda.device(self.device):
-            _lib.check(_lib.load().sucre_mosaic_bounds(C.c_void_p(table.data_ptr()), n, arr, self._axes_c,
-                                                       C.c_void_p(self.bounds_words.data_ptr()), _stream_ptr()))
+            _lib.check(getattr(_lib.load(), entry)(C.c_void_p(table.data_ptr()), n, arr, *rest, _stream_ptr()))
+
+    def _allocate(self, group: str) -> None:
+        """The outputs of ``group`` (``MOSAIC_OUTPUTS``), every cell empty."""
+        for key, (of, tail, dtype, empty, _, _) in MOSAIC_OUTPUTS.items():
+            if of == group:
+                shape = (self.Hm, self.Wm) + tail
+                self._out[key] = torch.empty(shape, dtype=dtype, device=self.device) if empty is None \
+                    else torch.full(shape, empty, dtype=dtype, device=self.device)
+
+    def add_bounds(self, views: list, Js: list) -> None:
+        self._walk('sucre_mosaic_bounds', self._images(views, Js), self._axes_c, self.bounds_words)
 
     def bounds(self):
         """``(lo_s, lo_t, hi_s, hi_t)`` float32 of what ``add_bounds`` has seen (waits for it), or None when no pixel took part."""
@@ -1149,24 +1211,20 @@ class Mosaic:
         """Fixes the grid and allocates; ``blend``: the blend depth H in metres (``MOSAIC_BLEND_RANGE``) -- a pixel whose range
         exceeds its cell's smallest one by d gets the weight ``max(1 - d / H, 0)^2`` -- or None for the best view alone;
         ``feather``: with a blend, the feather width F in source pixels (``MOSAIC_FEATHER_RANGE``), or None for none."""
-        if blend is not None:
-            blend = mosaic_blend_depth(blend)   # before anything is allocated
-        if feather is not None:
-            feather = mosaic_feather_px(feather)
-            if blend is None:
-                raise ValueError('Mosaic.begin: a feather is a factor of the blend\'s weight; give the blend depth too (blend=H)')
+        options = MosaicOptions(blend=blend, feather=feather).checked('Mosaic.begin')   # before anything is allocated
+        blend, feather = options.blend, options.feather
         if bounds is None:
             bounds = self.bounds()
             if bounds is None:
-                raise ValueError('Mosaic.begin: no pixel takes part (no valid depth with a restored colour), so there are no bounds')
+                raise _mosaic_refusal('grid', 'Mosaic.begin: no pixel takes part (no valid depth with a restored colour), so there are no bounds')
         lo_s, lo_t, hi_s, hi_t = (np.float32(x) for x in bounds)
         if not all(np.isfinite(x) for x in (lo_s, lo_t, hi_s, hi_t)) or hi_s < lo_s or hi_t < lo_t:
-            raise ValueError(f'Mosaic.begin: bounds {tuple(float(x) for x in (lo_s, lo_t, hi_s, hi_t))} are not finite and ordered')
+            raise _mosaic_refusal('grid', f'Mosaic.begin: bounds {tuple(float(x) for x in (lo_s, lo_t, hi_s, hi_t))} are not finite and ordered')
         Wm, Hm = mosaic_cells(lo_s, hi_s, self.gsd), mosaic_cells(lo_t, hi_t, self.gsd)
         limit = mosaic_max_cells()
         if Wm * Hm > limit or max(Wm, Hm) > 1 << 24:   # before anything is allocated
-            raise ValueError(f'mosaic of {Wm} x {Hm} cells of {float(self.gsd):.6g} m: more than the {limit} cells allowed '
-                             f'(SUCRE_MOSAIC_MAX_CELLS); give a coarser grid with --mosaic-gsd')
+            raise _mosaic_refusal('grid', f'mosaic of {Wm} x {Hm} cells of {float(self.gsd):.6g} m: more than the {limit} cells allowed '
+                                          f'(SUCRE_MOSAIC_MAX_CELLS); give a coarser grid with --mosaic-gsd')
         self.Hm, self.Wm, self.lo, self.hi = Hm, Wm, (lo_s, lo_t), (hi_s, hi_t)
         g = _lib.MosaicGrid()
         g.axes, g.gsd, g.lo_s, g.lo_t, g.Hm, g.Wm = self._axes_c, float(self.gsd), float(lo_s), float(lo_t), Hm, Wm
@@ -1174,24 +1232,17 @@ class Mosaic:
         dev = self.device
         self.key = torch.full((Hm * Wm,), -1, dtype=torch.int64, device=dev)    # all ones: empty
         self.pix = torch.full((Hm * Wm,), -1, dtype=torch.int32, device=dev)
-        nan = float('nan')
-        self._out = {'J': torch.full((Hm, Wm, 3), nan, dtype=torch.float32, device=dev),
-                     'raw': torch.zeros((Hm, Wm, 3), dtype=torch.uint8, device=dev),
-                     'source': torch.full((Hm, Wm), -1, dtype=torch.int32, device=dev),
-                     'pixel': torch.full((Hm, Wm), -1, dtype=torch.int32, device=dev),
-                     'range': torch.full((Hm, Wm), nan, dtype=torch.float32, device=dev)}
-        self.blend, self.inv_h, self.acc, self._blend_out = blend, None, None, None
-        self.fill_reach = self.fill_levels = self.pyramid = self._fill_out = None
+        self._out = {}
+        self._allocate('best')
+        self.blend, self.inv_h, self.acc = blend, None, None
+        self.fill_reach = self.fill_levels = self.pyramid = None
         self.feather, self.feather_counts, self._feather_buf = feather, None, None
         if feather is not None:
             self.feather_counts = torch.zeros(2, dtype=torch.int64, device=dev)
         if blend is not None:
             self.inv_h = np.float32(1) / blend
             self.acc = torch.zeros((Hm * Wm, _lib.MOSAIC_ACC_WORDS), dtype=torch.int64, device=dev)
-            self._blend_out = {'J_blend': torch.full((Hm, Wm, 3), nan, dtype=torch.float32, device=dev),
-                               'raw_blend': torch.zeros((Hm, Wm, 3), dtype=torch.uint8, device=dev),
-                               'weight': torch.zeros((Hm, Wm), dtype=torch.float32, device=dev),
-                               'samples': torch.zeros((Hm, Wm), dtype=torch.int32, device=dev)}
+            self._allocate('blend')
         return Hm, Wm
 
     def _begun(self, what: str) -> None:
@@ -1200,29 +1251,17 @@ class Mosaic:
 
     def splat(self, views: list, Js: list, first_ordinal: int, plain_atomic: bool = False) -> None:
         self._begun('splat')
-        arr, n, table, _ = self._images(views, Js)
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().sucre_mosaic_splat(C.c_void_p(table.data_ptr()), n, arr, int(first_ordinal), C.byref(self.grid),
-                                                      C.c_void_p(self.key.data_ptr()), _lib.MOSAIC_PLAIN_ATOMIC if plain_atomic else 0,
-                                                      _stream_ptr()))
+        self._walk('sucre_mosaic_splat', self._images(views, Js), int(first_ordinal), C.byref(self.grid), self.key,
+                   _lib.MOSAIC_PLAIN_ATOMIC if plain_atomic else 0)
 
     def resolve(self, views: list, Js: list, first_ordinal: int) -> None:
         self._begun('resolve')
-        arr, n, table, _ = self._images(views, Js)
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().sucre_mosaic_resolve(C.c_void_p(table.data_ptr()), n, arr, int(first_ordinal), C.byref(self.grid),
-                                                        C.c_void_p(self.key.data_ptr()), C.c_void_p(self.pix.data_ptr()), _stream_ptr()))
+        self._walk('sucre_mosaic_resolve', self._images(views, Js), int(first_ordinal), C.byref(self.grid), self.key, self.pix)
 
     def gather(self, views: list, Js: list, first_ordinal: int) -> None:
         self._begun('gather')
-        arr, n, table, _ = self._images(views, Js)
-        o = self._out
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().sucre_mosaic_gather(C.c_void_p(table.data_ptr()), n, arr, int(first_ordinal), C.byref(self.grid),
-                                                       C.c_void_p(self.key.data_ptr()), C.c_void_p(self.pix.data_ptr()),
-                                                       C.c_void_p(o['J'].data_ptr()), C.c_void_p(o['raw'].data_ptr()),
-                                                       C.c_void_p(o['source'].data_ptr()), C.c_void_p(o['pixel'].data_ptr()),
-                                                       C.c_void_p(o['range'].data_ptr()), _stream_ptr()))
+        self._walk('sucre_mosaic_gather', self._images(views, Js), int(first_ordinal), C.byref(self.grid), self.key, self.pix,
+                   *(self._out[k] for k in ('J', 'raw', 'source', 'pixel', 'range')))
 
     def _blending(self, what: str) -> None:
         self._begun(what)
@@ -1234,38 +1273,32 @@ class Mosaic:
         smallest range then).  ``plain``: eight atomics per pixel instead of eight per run of a wave's lanes (the same ``acc``).
         With a feather the batch's map is formed first (``sucre_mosaic_feather``) and the feathered phase reads it."""
         self._blending('accumulate')
-        arr, n, table, _ = self._images(views, Js)
-        if self.feather is not None:
-            with torch.cuda.device(self.device):
-                self._feather_buf, words = self._feather_pass(arr, n, table, self.feather, self._feather_buf)
-                if len({tuple(d2.shape) for d2 in words}) == 1:   # one size: the maps as one strided tensor, two reductions
-                    H, W = words[0].shape
-                    pitch = -(-(H * W) // _lib.MOSAIC_BLOCK_PX) * _lib.MOSAIC_BLOCK_PX
-                    words = [torch.as_strided(words[0], (n, H * W), (pitch, 1))]
-                for d2 in words:
-                    self.feather_counts += torch.stack([((d2 > 0) & (d2 < self.feather ** 2)).sum(), (d2 > 0).sum()])
-                _lib.check(_lib.load().sucre_mosaic_accumulate_feathered(
-                    C.c_void_p(table.data_ptr()), n, arr, int(first_ordinal), C.byref(self.grid), C.c_void_p(self.key.data_ptr()),
-                    C.c_float(float(self.inv_h)), self.feather, C.c_void_p(self._feather_buf.data_ptr()), C.c_void_p(self.acc.data_ptr()),
-                    _lib.MOSAIC_PLAIN_ATOMIC if plain else 0, _stream_ptr()))
-            return
+        images = self._images(views, Js)
+        head = (int(first_ordinal), C.byref(self.grid), self.key, C.c_float(float(self.inv_h)))
+        tail = (self.acc, _lib.MOSAIC_PLAIN_ATOMIC if plain else 0)
+        if self.feather is None:
+            return self._walk('sucre_mosaic_accumulate', images, *head, *tail)
+        self._feather_buf, words = self._feather_pass(images, self.feather, self._feather_buf)
         with torch.cuda.device(self.device):
-            _lib.check(_lib.load().sucre_mosaic_accumulate(C.c_void_p(table.data_ptr()), n, arr, int(first_ordinal), C.byref(self.grid),
-                                                           C.c_void_p(self.key.data_ptr()), C.c_float(float(self.inv_h)),
-                                                           C.c_void_p(self.acc.data_ptr()), _lib.MOSAIC_PLAIN_ATOMIC if plain else 0,
-                                                           _stream_ptr()))
+            if len({tuple(d2.shape) for d2 in words}) == 1:   # one size: the maps as one strided tensor, two reductions
+                H, W = words[0].shape
+                pitch = -(-(H * W) // _lib.MOSAIC_BLOCK_PX) * _lib.MOSAIC_BLOCK_PX
+                words = [torch.as_strided(words[0], (len(words), H * W), (pitch, 1))]
+            for d2 in words:
+                self.feather_counts += torch.stack([((d2 > 0) & (d2 < self.feather ** 2)).sum(), (d2 > 0).sum()])
+        self._walk('sucre_mosaic_accumulate_feathered', images, *head, self.feather, self._feather_buf, *tail)
 
-    @staticmethod
-    def _feather_pass(arr, n: int, table, F: int, buf=None):
-        """Enqueues ``sucre_mosaic_feather`` over the images of ``arr`` into ``buf`` (a new buffer when None or too small) and
-        returns the buffer and, per image, the (H,W) int32 view of its ``dist2`` words in it."""
+    def _feather_pass(self, images, F: int, buf=None):
+        """Enqueues ``sucre_mosaic_feather`` over ``images`` (as ``_images`` returns them) into ``buf`` (a new buffer when None or
+        too small) and returns the buffer and, per image, the (H,W) int32 view of its ``dist2`` words in it."""
+        arr, n, table, _ = images
         lib = _lib.load()
         n_bytes = lib.sucre_mosaic_feather_bytes(n, arr)
         if n_bytes == 0:
             raise _lib.SucreError(f'sucre_mosaic_feather_bytes: {lib.sucre_last_error().decode()}')
         if buf is None or buf.numel() < n_bytes:
-            buf = torch.empty(n_bytes, dtype=torch.uint8, device=table.device)    # (4-byte aligned: the allocator's blocks are)
-        _lib.check(lib.sucre_mosaic_feather(C.c_void_p(table.data_ptr()), n, arr, int(F), C.c_void_p(buf.data_ptr()), _stream_ptr()))
+            buf = torch.empty(n_bytes, dtype=torch.uint8, device=self.device)    # (4-byte aligned: the allocator's blocks are)
+        self._walk('sucre_mosaic_feather', images, int(F), buf)
         words = buf[:n_bytes // 6 * 4].view(torch.int32)   # the dist2 words; the uint16 scratch sits behind them
         maps, at = [], 0
         for e in arr:
@@ -1278,9 +1311,7 @@ class Mosaic:
         pixels from a pixel that takes part to the nearest one that does not or lies outside the image; 0 for a pixel that does
         not take part.  Needs no ``begin``; only enqueues (reading a map waits for it)."""
         F = mosaic_feather_px(F)
-        arr, n, table, _ = self._images(views, Js)
-        with torch.cuda.device(self.device):
-            _, maps = self._feather_pass(arr, n, table, F)
+        _, maps = self._feather_pass(self._images(views, Js), F)
         return [m.clone() for m in maps]
 
     def normalize(self, check: bool = True) -> None:
@@ -1288,7 +1319,7 @@ class Mosaic:
         ``MOSAIC_MAX_SAMPLES`` = 2^20 samples or more (its 64-bit sums may have wrapped).  ``check=False`` only enqueues the
         pass (for measurements: the caller looks at ``samples`` itself)."""
         self._blending('normalize')
-        o = self._blend_out
+        o = self._out
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().sucre_mosaic_normalize(C.byref(self.grid), C.c_void_p(self.acc.data_ptr()),
                                                           C.c_void_p(o['J_blend'].data_ptr()), C.c_void_p(o['raw_blend'].data_ptr()),
@@ -1298,8 +1329,8 @@ class Mosaic:
             return
         most = int(o['samples'].max())
         if most >= MOSAIC_MAX_SAMPLES:
-            raise ValueError(f'mosaic blend: a cell holds {most} samples, and from {MOSAIC_MAX_SAMPLES} on its 64-bit sums may overflow; '
-                             f'give a finer grid with --mosaic-gsd')
+            raise _mosaic_refusal('blend', f'mosaic blend: a cell holds {most} samples, and from {MOSAIC_MAX_SAMPLES} on its 64-bit sums '
+                                           f'may overflow; give a finer grid with --mosaic-gsd')
 
     def fill(self, R) -> int:
         """Closes the holes up to ``R`` metres across (``MOSAIC_FILL_RANGE``; ValueError before anything is allocated) and returns
@@ -1311,7 +1342,7 @@ class Mosaic:
         the phases before it have seen every image: called earlier on a begun mosaic it fills from the grid as it stands then
         (from an empty grid: nothing, every cell -1)."""
         self._begun('fill')
-        R = mosaic_fill_reach(R)
+        R = mosaic_fill_reach(R)   # (not through a MosaicOptions: there None is "no fill", here it is a value to refuse)
         L = mosaic_fill_levels(R, self.gsd, self.Hm, self.Wm)
         lib, dev, Hm, Wm = _lib.load(), self.device, self.Hm, self.Wm
         n_bytes = lib.sucre_mosaic_fill_bytes(Hm, Wm, L)
@@ -1319,23 +1350,20 @@ class Mosaic:
             raise _lib.SucreError(f'sucre_mosaic_fill_bytes: {lib.sucre_last_error().decode()}')
         self.fill_reach, self.fill_levels = R, L
         self.pyramid = torch.empty(n_bytes, dtype=torch.uint8, device=dev)    # (256-byte aligned: the allocator's blocks are)
-        pairs = [('J', 'raw', 'J_filled', 'raw_filled')]
+        pairs = [('fill', 'J', 'raw', 'J_filled', 'raw_filled')]
         if self.blend is not None:
-            pairs.append(('J_blend', 'raw_blend', 'J_blend_filled', 'raw_blend_filled'))
-        src = {**self._out, **(self._blend_out or {})}
-        self._fill_out = {'fill_level': torch.empty((Hm, Wm), dtype=torch.int32, device=dev)}
+            pairs.append(('blend_fill', 'J_blend', 'raw_blend', 'J_blend_filled', 'raw_blend_filled'))
+        o = self._out
         with torch.cuda.device(dev):
-            for J, raw, J_to, raw_to in pairs:
+            for group, J, raw, J_to, raw_to in pairs:
+                self._allocate(group)
                 # (the blend's own levels are not a result: a blended colour is always finite, a best-view one need not be)
-                level = self._fill_out['fill_level'] if J == 'J' else torch.empty_like(self._fill_out['fill_level'])
-                self._fill_out[J_to] = torch.empty((Hm, Wm, 3), dtype=torch.float32, device=dev)
-                self._fill_out[raw_to] = torch.empty((Hm, Wm, 3), dtype=torch.uint8, device=dev)
-                base = (Hm, Wm, L, C.c_void_p(src[J].data_ptr()), C.c_void_p(src[raw].data_ptr()), C.c_void_p(src['source'].data_ptr()),
+                level = o['fill_level'] if group == 'fill' else torch.empty_like(o['fill_level'])
+                base = (Hm, Wm, L, C.c_void_p(o[J].data_ptr()), C.c_void_p(o[raw].data_ptr()), C.c_void_p(o['source'].data_ptr()),
                         C.c_void_p(self.pyramid.data_ptr()))
                 _lib.check(lib.sucre_mosaic_fill_pull(*base, _stream_ptr()))
-                _lib.check(lib.sucre_mosaic_fill_push(*base, C.c_void_p(self._fill_out[J_to].data_ptr()),
-                                                      C.c_void_p(self._fill_out[raw_to].data_ptr()), C.c_void_p(level.data_ptr()),
-                                                      _stream_ptr()))
+                _lib.check(lib.sucre_mosaic_fill_push(*base, C.c_void_p(o[J_to].data_ptr()), C.c_void_p(o[raw_to].data_ptr()),
+                                                      C.c_void_p(level.data_ptr()), _stream_ptr()))
         return L
 
     def result(self) -> dict:
@@ -1346,50 +1374,48 @@ class Mosaic:
         ``J_filled`` (Hm,Wm,3) float32 (NaN: still empty), ``raw_filled`` (Hm,Wm,3) uint8 (0), ``fill_level`` (Hm,Wm) int32 (-1)
         and, with a blend, ``J_blend_filled`` and ``raw_blend_filled``.  With a feather also ``feather``, the width F (an int)."""
         self._begun('result')
-        out = {**self._out, **self._blend_out} if self.blend is not None else dict(self._out)
-        if self.feather is not None:
-            out['feather'] = self.feather
-        return {**out, **self._fill_out} if self._fill_out is not None else out
+        def of(*groups):
+            return {key: t for key, t in self._out.items() if MOSAIC_OUTPUTS[key][0] in groups}
+        return {**of('best', 'blend'), **({} if self.feather is None else {'feather': self.feather}), **of('fill', 'blend_fill')}
+
+    def run(self, batches, options: MosaicOptions = MosaicOptions(), bounds=None, plain_atomic: bool = False) -> 'Mosaic':
+        """Every phase over every batch, in the one order there is: the bounds (unless ``bounds`` is given), ``begin``, ``splat``,
+        ``resolve`` and ``gather``; with a blend ``accumulate`` and then ``normalize``; with a fill ``fill``.  ``batches``: a
+        sequence of ``(first_ordinal, load)``, ``load()`` returning the batch's ``(views, Js)`` -- called once per phase, so a
+        caller may hold only some of the images at a time; ``options``: as ``MosaicOptions.checked`` returns them;
+        ``plain_atomic``: both the splat and the accumulate phase in their plain forms.  Returns the mosaic."""
+        batches = list(batches)
+        if bounds is None:
+            for _, load in batches:
+                self.add_bounds(*load())
+        self.begin(bounds, blend=options.blend, feather=options.feather)
+        phases = [(self.splat, {'plain_atomic': plain_atomic}), (self.resolve, {}), (self.gather, {})]
+        if options.blend is not None:
+            phases.append((self.accumulate, {'plain': plain_atomic}))
+        for phase, kw in phases:
+            for first, load in batches:
+                phase(*load(), first, **kw)
+        if options.blend is not None:
+            self.normalize()
+        if options.fill is not None:
+            self.fill(options.fill)
+        return self
 
 
 def mosaic_of(views: list, Js: list, axes, gsd, bounds=None, batch: int = 32, plain_atomic: bool = False, blend=None,
               fill=None, feather=None) -> 'Mosaic':
-    """All four phases over device-resident ``views`` / ``Js`` (ordinal = position in the list), ``batch`` images per call; with
+    """``Mosaic.run`` over device-resident ``views`` / ``Js`` (ordinal = position in the list), ``batch`` images per call; with
     ``blend`` (the blend depth H, metres) the accumulate phase and the normalise pass after them (``plain_atomic``: both the
     splat and the accumulate phase in their plain forms), with ``feather`` (the width F, source pixels; only with ``blend``) the
-    feathered one; with ``fill`` (the reach R, metres) the hole filling after all of them."""
+    feathered one; with ``fill`` (the reach R, metres) the hole filling after all of them (``MosaicOptions``)."""
     views, Js = list(views), list(Js)
     if not views:
         raise ValueError('mosaic_of: no view')
     if len(views) > MAX_VIEWS:
         raise ValueError(f'mosaic_of: {len(views)} images, at most {MAX_VIEWS}')
-    if blend is not None:
-        mosaic_blend_depth(blend)   # before anything is allocated
-    if fill is not None:
-        mosaic_fill_reach(fill)
-    if feather is not None:
-        mosaic_feather_px(feather)
-        if blend is None:
-            raise ValueError('mosaic_of: a feather is a factor of the blend\'s weight; give the blend depth too (blend=H)')
-    m = Mosaic(axes, gsd, views[0].depth.device)
-    chunks = [(i, views[i:i + batch], Js[i:i + batch]) for i in range(0, len(views), batch)]
-    if bounds is None:
-        for _, v, J in chunks:
-            m.add_bounds(v, J)
-    m.begin(bounds, blend=blend, feather=feather)
-    for i, v, J in chunks:
-        m.splat(v, J, i, plain_atomic=plain_atomic)
-    for i, v, J in chunks:
-        m.resolve(v, J, i)
-    for i, v, J in chunks:
-        m.gather(v, J, i)
-    if blend is not None:
-        for i, v, J in chunks:
-            m.accumulate(v, J, i, plain=plain_atomic)
-        m.normalize()
-    if fill is not None:
-        m.fill(fill)
-    return m
+    options = MosaicOptions(blend=blend, feather=feather, fill=fill).checked('mosaic_of')   # before anything is allocated
+    batches = [(i, lambda i=i: (views[i:i + batch], Js[i:i + batch])) for i in range(0, len(views), batch)]
+    return Mosaic(axes, gsd, views[0].depth.device).run(batches, options, bounds, plain_atomic)
 
 
 def device_views_from_scene(scene, device='cuda') -> list[DeviceView]:

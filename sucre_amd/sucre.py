@@ -1379,6 +1379,11 @@ def mosaic_source_picture(source: np.ndarray) -> np.ndarray:
     return out
 
 
+def mosaic_fill_mask(level: np.ndarray) -> np.ndarray:
+    """(Hm,Wm) uint8 of a mosaic's ``fill_level``: 255 measured, 128 filled, 0 empty."""
+    return np.where(level == 0, 255, np.where(level > 0, 128, 0)).astype(np.uint8)
+
+
 def _mosaic_picture(J: Tensor, stretch) -> np.ndarray:
     """(Hm,Wm,3) uint8 of a mosaic's ``J`` on the device: the fixed ``stretch`` when given, ``plot_J``'s own percentiles over the
     filled cells otherwise."""
@@ -1399,16 +1404,35 @@ def _mosaic_picture(J: Tensor, stretch) -> np.ndarray:
     return np.uint8(J * 255)
 
 
+_MOSAIC_FLAG = {'grid': '--mosaic', 'blend': '--mosaic-blend', 'fill': '--mosaic-fill', 'feather': '--mosaic-feather'}
+
+
+def _mosaic_refused(e: ValueError, fields=tuple(_MOSAIC_FLAG)) -> BaseException:
+    """The SystemExit that names the flag of the ``field`` of an engine's mosaic refusal; ``e`` itself when it has none of ``fields``."""
+    field = getattr(e, 'field', None)
+    return SystemExit(f'{_MOSAIC_FLAG[field]}: {e}') if field in fields else e
+
+
+_MOSAIC_PNG = {   # how a row of engine.MOSAIC_OUTPUTS becomes its PNG: (the output on the device, the stretch) -> uint8 array
+    'stretch': _mosaic_picture,
+    'bytes': lambda t, stretch: t.cpu().numpy(),
+    'source': lambda t, stretch: mosaic_source_picture(t.cpu().numpy()),
+    'mask': lambda t, stretch: mosaic_fill_mask(t.cpu().numpy()),
+}
+
+
 def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, output_dir: Path, gsd: float | None = None, axes=None,
            stretch=None, device: str = 'cuda', blend: float | None = None, fill: float | None = None, feather: int | None = None) -> dict:
     """One picture of the seabed from a finished restoration: every pixel of ``images`` (``sfm.Image`` objects or names of
     ``colmap_model``; at most ``engine.MAX_VIEWS``, ordinal = position) with a valid depth and a restored colour --
     ``results_dir / <name>.pt``, key ``J`` -- is dropped onto the plane grid ``axes`` (``mosaic_axes`` unless given) of ``gsd``
     metres per cell (``mosaic_default_gsd`` unless given; printed), and the pixel seen through the least water wins its cell
-    (``engine.Mosaic``; csrc/mosaic.h).  Holes stay empty unless ``fill`` is given.  Every file is checked before any image is decoded.  The
+    (``engine.Mosaic``; csrc/mosaic.h).  Holes stay empty unless ``fill`` is given.  Every file is checked before any image is decoded.
+    ``blend``, ``feather`` and ``fill`` are checked as one ``engine.MosaicOptions``; the images are cut into batches here (at most
+    ``MOSAIC_IMAGES_PER_CALL``, and what fits the cache together) and ``engine.Mosaic.run`` takes every phase over every batch.  The
     restored images stay on the device across the four phases within ``consistency_cache_budget`` and are read again per phase
-    otherwise: the same bits either way.  Writes ``mosaic.png`` (``plot_J``'s stretch over the filled cells, or the fixed
-    ``stretch``), ``mosaic_raw.png``, ``mosaic_source.png`` (``mosaic_source_picture``) and ``mosaic.pt`` (``J, raw, source, pixel,
+    otherwise: the same bits either way.  The PNGs are those of the rows of ``engine.MOSAIC_OUTPUTS``.  Writes ``mosaic.png``
+    (``plot_J``'s stretch over the filled cells, or the fixed ``stretch``), ``mosaic_raw.png``, ``mosaic_source.png`` (``mosaic_source_picture``) and ``mosaic.pt`` (``J, raw, source, pixel,
     range, axes, gsd, lo, images, n_filled, per_image``), prints one line and returns the dictionary of ``mosaic.pt``.
 
     ``blend``: a blend depth H in metres (``engine.MOSAIC_BLEND_RANGE``).  One more pass over the batches then sums, per cell, ALL
@@ -1442,23 +1466,13 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
         raise SystemExit(f'--mosaic: {len(images)} images in the request, at most {engine.MAX_VIEWS} go into one mosaic')
     if stretch is not None:
         stretch = check_stretch(stretch)
-    if blend is not None:
-        try:
-            blend = engine.mosaic_blend_depth(blend)
-        except ValueError as e:
-            raise SystemExit(f'--mosaic-blend: {e}')
-    if fill is not None:
-        try:
-            fill = engine.mosaic_fill_reach(fill)
-        except ValueError as e:
-            raise SystemExit(f'--mosaic-fill: {e}')
-    if feather is not None:
-        if blend is None:
+    try:
+        options = engine.MosaicOptions(blend=blend, feather=feather, fill=fill).checked()
+    except ValueError as e:
+        if e.field == 'feather' and blend is None:
             raise SystemExit('--mosaic-feather: only with --mosaic-blend H')
-        try:
-            feather = engine.mosaic_feather_px(feather)
-        except ValueError as e:
-            raise SystemExit(f'--mosaic-feather: {e}')
+        raise _mosaic_refused(e)
+    blend, feather, fill = options.blend, options.feather, options.fill
     results_dir, output_dir = Path(results_dir), Path(output_dir)
     for image in images:   # before anything is decoded
         path = _consistency_file(results_dir, image)
@@ -1488,47 +1502,24 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
             gsd = mosaic_default_gsd(depths, [float(im.camera.K[0, 0]) for im in images])
             del depths
             print(f'--mosaic: ground sample distance {float(gsd):.6g} m (twice the median pixel footprint; --mosaic-gsd sets it).')
-        m = engine.Mosaic(axes, gsd, device)
-        for _, batch in batches:
-            m.add_bounds(*resident(batch))
         try:
-            Hm, Wm = m.begin(blend=blend, feather=feather)
+            m = engine.Mosaic(axes, gsd, device).run([(first, lambda batch=batch: resident(batch)) for first, batch in batches], options)
         except ValueError as e:
-            raise SystemExit(f'--mosaic: {e}')
-        for phase in (m.splat, m.resolve, m.gather) + ((m.accumulate,) if blend is not None else ()):
-            for first, batch in batches:
-                phase(*resident(batch), first)
-        if blend is not None:
-            try:
-                m.normalize()
-            except ValueError as e:
-                raise SystemExit(f'--mosaic-blend: {e}')
-        if fill is not None:
-            m.fill(fill)
+            # Two refusals of the run belong to a flag: begin's of the grid (--mosaic) and normalize's of a cell's sample count
+            # (--mosaic-blend).  The options were checked above, so begin and fill have nothing left to refuse in them; every other
+            # ValueError (of a view, of a restored image) passes as it is.
+            raise _mosaic_refused(e, ('grid', 'blend'))
         out = m.result()
-        picture = _mosaic_picture(out['J'], stretch)
-        blend_picture = _mosaic_picture(out['J_blend'], stretch) if blend is not None else None
-        filled_picture = _mosaic_picture(out['J_filled'], stretch) if fill is not None else None
-        blend_filled_picture = _mosaic_picture(out['J_blend_filled'], stretch) if fill is not None and blend is not None else None
+        pictures = [(png, _MOSAIC_PNG[how](out[key], stretch)) for key, (_, _, _, _, png, how) in engine.MOSAIC_OUTPUTS.items()
+                    if png is not None and key in out]
         out = {k: v.cpu() if torch.is_tensor(v) else v for k, v in out.items()}
+    Hm, Wm = m.Hm, m.Wm
     source = out['source']
     filled = source >= 0
     n_filled, n_cells = int(filled.sum()), Hm * Wm
     per_image = torch.bincount(source[filled].to(torch.int64), minlength=len(images))
-    _save_png(PILImage.fromarray(picture), output_dir / 'mosaic.png')
-    _save_png(PILImage.fromarray(out['raw'].numpy()), output_dir / 'mosaic_raw.png')
-    _save_png(PILImage.fromarray(mosaic_source_picture(source.numpy())), output_dir / 'mosaic_source.png')
-    if blend is not None:
-        _save_png(PILImage.fromarray(blend_picture), output_dir / 'mosaic_blend.png')
-        _save_png(PILImage.fromarray(out['raw_blend'].numpy()), output_dir / 'mosaic_blend_raw.png')
-    if fill is not None:
-        level = out['fill_level'].numpy()
-        _save_png(PILImage.fromarray(filled_picture), output_dir / 'mosaic_filled.png')
-        _save_png(PILImage.fromarray(out['raw_filled'].numpy()), output_dir / 'mosaic_raw_filled.png')
-        _save_png(PILImage.fromarray(np.where(level == 0, 255, np.where(level > 0, 128, 0)).astype(np.uint8)), output_dir / 'mosaic_filled_mask.png')
-        if blend is not None:
-            _save_png(PILImage.fromarray(blend_filled_picture), output_dir / 'mosaic_blend_filled.png')
-            _save_png(PILImage.fromarray(out['raw_blend_filled'].numpy()), output_dir / 'mosaic_blend_raw_filled.png')
+    for png, picture in pictures:
+        _save_png(PILImage.fromarray(picture), output_dir / png)
     data = {**out, 'axes': m.axes.clone(), 'gsd': float(m.gsd), 'lo': torch.tensor([float(m.lo[0]), float(m.lo[1])], dtype=torch.float32),
             'images': [im.name for im in images], 'n_filled': n_filled, 'per_image': per_image}
     if blend is not None:
@@ -1621,15 +1612,12 @@ def _refuse_mosaic_values(args, world: int = 1) -> None:
     gsd = getattr(args, 'mosaic_gsd', None)
     if gsd is not None and not (np.isfinite(gsd) and gsd > 0):
         raise SystemExit(f'--mosaic-gsd: G must be a finite size > 0 in metres, not {gsd}')
-    blend = getattr(args, 'mosaic_blend', None)
-    if blend is not None and not (np.isfinite(blend) and 1e-6 <= blend <= 1e6):
-        raise SystemExit(f'--mosaic-blend: H must be a finite depth within [1e-06, 1e+06] metres, not {blend}')
-    fill = getattr(args, 'mosaic_fill', None)
-    if fill is not None and not (np.isfinite(fill) and 1e-6 <= fill <= 1e6):
-        raise SystemExit(f'--mosaic-fill: R must be a finite reach within [1e-06, 1e+06] metres, not {fill}')
-    feather = getattr(args, 'mosaic_feather', None)
-    if feather is not None and not (np.isfinite(feather) and feather == int(feather) and 1 <= feather <= 1024):
-        raise SystemExit(f'--mosaic-feather: F must be an integer within [1, 1024] source pixels, not {feather:g}')
+    from . import engine
+    for field, letter, kind, last in (('blend', 'H', 'a finite depth', '{}'), ('fill', 'R', 'a finite reach', '{}'), ('feather', 'F', 'an integer', '{:g}')):
+        value = getattr(args, 'mosaic_' + field, None)
+        _, (lo, hi), integral, unit, _ = engine.MOSAIC_VALUES[field]
+        if value is not None and not (np.isfinite(value) and lo <= value <= hi and (not integral or value == int(value))):
+            raise SystemExit(f'{_MOSAIC_FLAG[field]}: {letter} must be {kind} within [{lo:g}, {hi:g}] {unit}, not {last.format(value)}')
     if world > 1:
         raise SystemExit(f'--mosaic: a world size of {world} is not supported yet: the four phases are separate entries of the library '
                          f'so that ranks can all-reduce bounds, keys and pixel words between them, but that all-reduce is not built; '
