@@ -663,14 +663,43 @@ int sucre_view_consistency(int H, int W, int n_views, const sucre_view_t *target
  *   sucre_mosaic_accumulate_feathered  sucre_mosaic_accumulate with, in float32, one IEEE operation per step,
  *                         f = dist2 >= F^2 ? 1 : sqrtf((float)dist2) inv_F (inv_F = 1.0f / (float)F) and
  *                         wq = (int)rintf(((t t) f) 4096), 0..4096; everything else as there, flags included.  The images are
- *                         those of the sucre_mosaic_feather call that wrote feather_dev, in the same order, with the same F.
+ *                         those of the sucre_mosaic_feather call that wrote feather_dev, in the same order, with this F or a
+ *                         larger one (dist2 = min(D2, F'^2) with F' >= F gives the same dist2 >= F^2 and the same root below it).
  *                         A cell's winner has wq >= 4 (f >= 1/1024), so a filled cell has wsum >= 4 and a count >= 1; with
  *                         F = 1 the words equal sucre_mosaic_accumulate's to the bit (every member has dist2 >= 1 = F^2).
  * Checked before any launch as above, and: feather_px outside 1..1024, a NULL or misaligned feather_dev.
+ *
+ * The bands: a multi-band blend.  Every image is split, in source space, into K detail bands D_0 .. D_(K-1) and a residual S_K,
+ * K in 1..SUCRE_MOSAIC_BANDS_MAX = 6; the caller accumulates every band with sucre_mosaic_accumulate(_feathered) -- the band as the
+ * images' J, signed values included -- into an accumulator of its own, the finer the band the smaller its blend depth, and one
+ * pass over the cells adds the blended bands.  The members of an image are the pixels that take part.  Float32, one IEEE
+ * operation per step:
+ *   S_0 = min(max(J, -1024), 1024) at members (the accumulate's clamp; an infinity becomes finite)
+ *   level j -> j+1, s = 2^j, with a(u,v) = S_j at a member and +0.0f elsewhere and outside the image, m the same with 1 and 0:
+ *     Nh(u,v) = (a(u-s,v) + 2 a(u,v)) + a(u+s,v),  N(u,v) = (Nh(u,v-s) + 2 Nh(u,v)) + Nh(u,v+s);  Ah, A likewise in integers (A: 0..16)
+ *     S_(j+1) = N / (float)A (a member has A >= 4);  D_j = S_j - S_(j+1)
+ *   at a non-member every S and D is the NaN 0x7fc00000 in all three channels: the members of every band are the members of J.
+ *   sucre_mosaic_band_bytes  the bytes of ONE band buffer for these images (only H and W are read; 0 and an error for bad sizes):
+ *                         image i's (H,W,3) float32 block starts at PIXEL 256 sum_(j<i) ceil(H_j W_j / 256), 12 bytes per pixel
+ *                         (the feather map's placement); the pixels between two images are not written
+ *   sucre_mosaic_band_split  one level: writes S_(level+1) to S_out and D_level to D_out.  level = 0: S_in is NULL and the images'
+ *                         depth and J are read; level >= 1: S_in is the S_out of the level before (a NaN marks a non-member;
+ *                         depth and J are not read).  S_in, S_out and D_out are three buffers of sucre_mosaic_band_bytes that do
+ *                         not overlap.  One launch per 32 images (plus the table's); only enqueues: nothing is allocated, nothing
+ *                         copied from the host
+ *   sucre_mosaic_band_combine  acc_bands_dev: n_bands = K + 1 accumulators of sucre_mosaic_accumulate's layout, (n_bands, Hm Wm, 8)
+ *                         int64, band j at slice j and the residual last.  One pass over the cells, no image read; for a cell
+ *                         whose residual has word 7 > 0: B_j = (float)(((double)acc_j,c / (double)wsum_j) 2^-20), the quotient of
+ *                         sucre_mosaic_normalize, and J_out (Hm,Wm,3) float32 = (..((B_K + B_(K-1)) + B_(K-2)) ..) + B_0, coarse
+ *                         to fine.  Empty cells are not touched.  Every filled cell has wsum_j >= 4 in every band: its winner
+ *                         has d = 0, so t = 1 whatever the band's blend depth, and f >= 1/1024.
+ * Checked before any launch as above, and: level outside 0..5, S_in given at level 0 or NULL above it, a NULL or misaligned S_out
+ * or D_out, buffers that overlap, n_bands outside 2..7, a NULL or misaligned acc_bands_dev or J_out, Hm Wm above 2^39.
  */
 #define SUCRE_MOSAIC_PLAIN_ATOMIC 1u
 #define SUCRE_MOSAIC_ACC_WORDS 8
 #define SUCRE_MOSAIC_FEATHER_MAX 1024
+#define SUCRE_MOSAIC_BANDS_MAX 6
 typedef struct sucre_mosaic_image {
     const float *depth;   /* (H,W) float32 */
     const uint8_t *rgb;   /* (H,W,3) uint8 */
@@ -705,6 +734,10 @@ int sucre_mosaic_feather(void *table_dev, int n_images, const sucre_mosaic_image
 int sucre_mosaic_accumulate_feathered(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
                                       const sucre_mosaic_grid_t *grid, const uint64_t *key_dev, float inv_h, int feather_px,
                                       const void *feather_dev, int64_t *acc_dev, unsigned flags, void *stream);
+size_t sucre_mosaic_band_bytes(int n_images, const sucre_mosaic_image_t *images);
+int sucre_mosaic_band_split(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int level, const float *S_in, float *S_out,
+                            float *D_out, void *stream);
+int sucre_mosaic_band_combine(const sucre_mosaic_grid_t *grid, int n_bands, const int64_t *acc_bands_dev, float *J_out, void *stream);
 
 /*
  * ---- hole filling of the finished mosaic: a bounded push-pull over a pyramid of the grid ------------------------------------------

@@ -30,6 +30,7 @@ MOSAIC_PLAIN_ATOMIC = 1     # SUCRE_MOSAIC_PLAIN_ATOMIC: sucre_mosaic_splat with
 #                             sucre_mosaic_accumulate with eight atomics per pixel instead of eight per run of a wave's lanes
 MOSAIC_ACC_WORDS = 8        # SUCRE_MOSAIC_ACC_WORDS: int64 words per cell of the blend's accumulator
 MOSAIC_FEATHER_MAX = 1024   # SUCRE_MOSAIC_FEATHER_MAX: the widest feather, source pixels
+MOSAIC_BANDS_MAX = 6         # SUCRE_MOSAIC_BANDS_MAX: the most detail bands of a multi-band blend
 MOSAIC_BLOCK_PX = 256       # kMosaicBlockPx of csrc/mosaic.h: an image's words of the feather map start at a multiple of it
 POOL_MAX_IMAGES = 4096    # kPoolMaxImages of csrc/pool.h: images per sucre_pool_select_pass call
 POOL_MAX_RANKS = 8
@@ -171,6 +172,9 @@ SIGNATURES = {
     'sucre_mosaic_feather': (_i, [_vp, _i, C.POINTER(MosaicImage), _i, _vp, _vp]),
     'sucre_mosaic_accumulate_feathered': (_i, [_vp, _i, C.POINTER(MosaicImage), _i, C.POINTER(MosaicGrid), _vp, C.c_float, _i, _vp, _vp,
                                                C.c_uint, _vp]),
+    'sucre_mosaic_band_bytes': (C.c_size_t, [_i, C.POINTER(MosaicImage)]),
+    'sucre_mosaic_band_split': (_i, [_vp, _i, C.POINTER(MosaicImage), _i, _vp, _vp, _vp, _vp]),
+    'sucre_mosaic_band_combine': (_i, [C.POINTER(MosaicGrid), _i, _vp, _vp, _vp]),
     'sucre_mosaic_fill_bytes': (C.c_size_t, [_i, _i, _i]),
     'sucre_mosaic_fill_pull': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'sucre_mosaic_fill_push': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

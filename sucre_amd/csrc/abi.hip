@@ -11,6 +11,7 @@
 #include "invert.h"
 #include "launch.h"
 #include "mosaic.h"
+#include "bands.h"
 #include "pool.h"
 
 namespace sucre {
@@ -1068,6 +1069,52 @@ int sucre_mosaic_normalize(const sucre_mosaic_grid_t *grid, const int64_t *acc_d
     MosaicBlend out = {J_out, raw_out, weight_out, samples_out};
     return check_hip(launch_mosaic_normalize(g, reinterpret_cast<const long long *>(acc_dev), out, static_cast<hipStream_t>(stream)),
                      "sucre_mosaic_normalize");
+}
+
+/* ---- multi-band blend: the band stack of every image and the per-cell sum of the blended bands (bands.h) ---- */
+
+size_t sucre_mosaic_band_bytes(int n_images, const sucre_mosaic_image_t *images) {
+    if (n_images < 1 || n_images > kMaxViews || !images) {
+        fail(SUCRE_ERR_ARG, "n_images=%d outside [1,%d], or images is NULL", n_images, kMaxViews);
+        return 0;
+    }
+    for (int i = 0; i < n_images; ++i) {
+        if (images[i].H < 1 || images[i].W < 1 || images[i].H > 32767 || images[i].W > 32767) {
+            fail(SUCRE_ERR_ARG, "image %d: invalid size %dx%d (need 1..32767)", i, images[i].W, images[i].H);
+            return 0;
+        }
+    }
+    return band_bytes(n_images, images);
+}
+
+int sucre_mosaic_band_split(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int level, const float *S_in, float *S_out,
+                            float *D_out, void *stream) {
+    if (int rc = check_mosaic_images(table_dev, n_images, images, 0)) return rc;
+    if (level < 0 || level >= kBandsMax) return fail(SUCRE_ERR_ARG, "level=%d outside [0,%d]", level, kBandsMax - 1);
+    if (level == 0 && S_in) return fail(SUCRE_ERR_ARG, "level 0 reads the images: S_in must be NULL");
+    if (level > 0 && (!S_in || !aligned(S_in, 4))) return fail(SUCRE_ERR_ARG, "S_in is NULL or not 4-byte aligned");
+    if (!S_out || !D_out || !aligned(S_out, 4) || !aligned(D_out, 4)) return fail(SUCRE_ERR_ARG, "S_out / D_out is NULL or not 4-byte aligned");
+    // three different buffers of band_bytes each: no two of them may overlap
+    const size_t n_bytes = band_bytes(n_images, images);
+    const auto overlap = [n_bytes](const void *a, const void *b) {
+        const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+        return a && b && x < y + n_bytes && y < x + n_bytes;
+    };
+    if (overlap(S_in, S_out) || overlap(S_in, D_out) || overlap(S_out, D_out))
+        return fail(SUCRE_ERR_ARG, "S_in / S_out / D_out overlap: a level reads its neighbours' S_in while it writes");
+    return check_hip(launch_band_split(table_dev, n_images, images, level, S_in, S_out, D_out, static_cast<hipStream_t>(stream)),
+                     "sucre_mosaic_band_split");
+}
+
+int sucre_mosaic_band_combine(const sucre_mosaic_grid_t *grid, int n_bands, const int64_t *acc_bands_dev, float *J_out, void *stream) {
+    MosaicGrid g;
+    if (int rc = check_mosaic_grid(grid, &g)) return rc;
+    if ((uint64_t)g.Hm * (uint64_t)g.Wm > (1ull << 39)) return fail(SUCRE_ERR_ARG, "mosaic of %dx%d cells: one pass takes 2^39 cells", g.Wm, g.Hm);
+    if (n_bands < 2 || n_bands > kBandsMax + 1) return fail(SUCRE_ERR_ARG, "n_bands=%d outside [2,%d]", n_bands, kBandsMax + 1);
+    if (!acc_bands_dev || !aligned(acc_bands_dev, 8)) return fail(SUCRE_ERR_ARG, "acc_bands_dev is NULL or not 8-byte aligned");
+    if (!J_out || !aligned(J_out, 4)) return fail(SUCRE_ERR_ARG, "J_out is NULL or not 4-byte aligned");
+    return check_hip(launch_band_combine(g, n_bands, reinterpret_cast<const long long *>(acc_bands_dev), J_out,
+                                         static_cast<hipStream_t>(stream)), "sucre_mosaic_band_combine");
 }
 
 /* ---- hole filling of the finished mosaic: a bounded push-pull over a pyramid of the grid (fill.h) ---- */

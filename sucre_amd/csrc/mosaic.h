@@ -167,10 +167,49 @@ hipError_t launch_mosaic_feather(void *table, int n_images, const sucre_mosaic_i
 
 // The blend's accumulate phase over images[0 .. n) (the same launches as a phase above; key: read, acc: added to) and its
 // per-cell pass (one launch).  `feather`: NULL, or what a feathered phase reads -- dist2 the map as launch_mosaic_feather left it
-// for the same call's images in the same order.
+// for the same call's images in the same order, made with this F or a larger one (bands.h blends every band from one map).
 hipError_t launch_mosaic_accumulate(bool plain, void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
                                     const MosaicGrid &grid, const unsigned long long *key, float inv_h, const MosaicFeather *feather,
                                     unsigned long long *acc, hipStream_t s);
 hipError_t launch_mosaic_normalize(const MosaicGrid &grid, const long long *acc, const MosaicBlend &out, hipStream_t s);
+
+// ---- what every translation unit that walks images shares (mosaic.hip, bands.hip): one copy of each ----
+
+// Whether a pixel takes part, from its depth and its three restored channels: the one statement of the rule (the feather's column
+// pass and the band split form their members with it too).
+__device__ __forceinline__ bool mosaic_member(float d, float J0, float J1, float J2) {
+    return d > 0.0f && J0 == J0 && J1 == J1 && J2 == J2;
+}
+
+// The image of this workgroup: the last one whose first workgroup is not behind blockIdx.x (wave-uniform: scalar loads).
+__device__ __forceinline__ const MosaicImage *mosaic_block_image(const MosaicImage *__restrict__ table, int n_images) {
+    int lo = 0, hi = n_images - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[mid].block0 <= blockIdx.x) lo = mid;
+        else hi = mid - 1;
+    }
+    return table + lo;
+}
+
+// A blended colour from its fixed-point sum and weight sum: the quotient of the normalise pass and of the band combine.
+__device__ __forceinline__ float mosaic_quotient(long long acc, long long wsum) {
+    return (float)(((double)acc / (double)wsum) * 0x1p-20);
+}
+
+// The table entries of images[l0 .. l0 + nl), one launch's, written to entries[l0 ..) by set launches on s (by value: nothing is
+// copied from the host); returns the workgroups of that launch (the caller has checked that every launch's grid fits).
+uint32_t mosaic_set_launch(MosaicImage *entries, int l0, int nl, const sucre_mosaic_image_t *images, int first_ordinal, hipStream_t s);
+
+// The launches of one phase over images[0 .. n): per 32 images, the table's set launches, then launch(workgroups, table, images).
+template <typename Launch>
+static void mosaic_for_each_launch(void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal, hipStream_t s,
+                                   Launch launch) {
+    auto *entries = static_cast<MosaicImage *>(table);
+    for (int l0 = 0; l0 < n_images; l0 += kMosaicLaunch) {
+        const int nl = n_images - l0 < kMosaicLaunch ? n_images - l0 : kMosaicLaunch;
+        launch(mosaic_set_launch(entries, l0, nl, images, first_ordinal, s), entries + l0, nl);
+    }
+}
 
 }  // namespace sucre

@@ -20,12 +20,6 @@ struct MosaicPixel {
     float J[3];
 };
 
-// Whether a pixel takes part, from its depth and its three restored channels: the one statement of the rule (the feather's column
-// pass forms its members with it too).
-__device__ __forceinline__ bool mosaic_member(float d, float J0, float J1, float J2) {
-    return d > 0.0f && J0 == J0 && J1 == J1 && J2 == J2;
-}
-
 __device__ __forceinline__ MosaicPixel mosaic_pixel(const MosaicImage *__restrict__ im, const float *Kinv, bool pin, const float *R,
                                                     const float *t, const float *axes, uint32_t p, uint32_t W) {
     MosaicPixel m;
@@ -66,14 +60,7 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t x) {
 // image's last pixel and for a pixel that does not take part.
 __device__ __forceinline__ bool mosaic_walk(const MosaicImage *__restrict__ table, int n_images, const MosaicGrid &g,
                                             const MosaicImage *__restrict__ *image, uint32_t *pixel, MosaicPixel *m) {
-    // the image of this workgroup: the last one whose first workgroup is not behind blockIdx.x (wave-uniform: scalar loads)
-    int lo = 0, hi = n_images - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (table[mid].block0 <= blockIdx.x) lo = mid;
-        else hi = mid - 1;
-    }
-    const MosaicImage *__restrict__ im = table + lo;
+    const MosaicImage *__restrict__ im = mosaic_block_image(table, n_images);
     const uint32_t W = (uint32_t)im->W, n_px = (uint32_t)im->H * W;   // H, W <= 32767: below 2^30
     const uint32_t p = (blockIdx.x - im->block0) * kMosaicBlockPx + threadIdx.x;
     const bool inside = p < n_px;
@@ -237,7 +224,7 @@ __global__ __launch_bounds__(256) void mosaic_normalize_kernel(size_t n_cells, c
     if (count <= 0) return;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        out.J[cell * 3 + c] = (float)(((double)a[c] / (double)wsum) * 0x1p-20);
+        out.J[cell * 3 + c] = mosaic_quotient(a[c], wsum);
         out.raw[cell * 3 + c] = (uint8_t)((2 * a[3 + c] + wsum) / (2 * wsum));
     }
     out.weight[cell] = (float)((double)wsum * 0x1p-12);
@@ -306,31 +293,24 @@ static void mosaic_launch(uint32_t n_blocks, hipStream_t s, const MosaicImage *t
     hipLaunchKernelGGL((mosaic_kernel<kPhase>), dim3(n_blocks), dim3(256), 0, s, table, n, g, bounds, key, pix, out);
 }
 
-// The launches of one phase over images[0 .. n): per 32 images, the table's set launches, then launch(workgroups, table, images).
-template <typename Launch>
-static void mosaic_for_each_launch(void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal, hipStream_t s,
-                                   Launch launch) {
-    auto *entries = static_cast<MosaicImage *>(table);
-    for (int l0 = 0; l0 < n_images; l0 += kMosaicLaunch) {
-        const int nl = n_images - l0 < kMosaicLaunch ? n_images - l0 : kMosaicLaunch;
-        uint64_t block0 = 0;   // per launch: the caller has checked that every launch's grid fits
-        for (int i0 = l0; i0 < l0 + nl; i0 += kMosaicSet) {
-            MosaicEntries src = {};
-            const int n = l0 + nl - i0 < kMosaicSet ? l0 + nl - i0 : kMosaicSet;
-            for (int j = 0; j < n; ++j) {
-                const sucre_mosaic_image_t &im = images[i0 + j];
-                MosaicImage &e = src.e[j];
-                e.depth = im.depth; e.rgb = im.rgb; e.J = im.J; e.H = im.H; e.W = im.W;
-                for (int q = 0; q < 9; ++q) { e.Kinv[q] = im.Kinv[q]; e.R[q] = im.R[q]; }
-                for (int q = 0; q < 3; ++q) e.t[q] = im.t[q];
-                e.block0 = (uint32_t)block0;
-                e.ordinal = first_ordinal + i0 + j;
-                block0 += mosaic_blocks(im.H, im.W);
-            }
-            hipLaunchKernelGGL(mosaic_set_kernel, dim3(1), dim3(64), 0, s, entries + i0, src, n);
+uint32_t mosaic_set_launch(MosaicImage *entries, int l0, int nl, const sucre_mosaic_image_t *images, int first_ordinal, hipStream_t s) {
+    uint64_t block0 = 0;
+    for (int i0 = l0; i0 < l0 + nl; i0 += kMosaicSet) {
+        MosaicEntries src = {};
+        const int n = l0 + nl - i0 < kMosaicSet ? l0 + nl - i0 : kMosaicSet;
+        for (int j = 0; j < n; ++j) {
+            const sucre_mosaic_image_t &im = images[i0 + j];
+            MosaicImage &e = src.e[j];
+            e.depth = im.depth; e.rgb = im.rgb; e.J = im.J; e.H = im.H; e.W = im.W;
+            for (int q = 0; q < 9; ++q) { e.Kinv[q] = im.Kinv[q]; e.R[q] = im.R[q]; }
+            for (int q = 0; q < 3; ++q) e.t[q] = im.t[q];
+            e.block0 = (uint32_t)block0;
+            e.ordinal = first_ordinal + i0 + j;
+            block0 += mosaic_blocks(im.H, im.W);
         }
-        launch((uint32_t)block0, entries + l0, nl);
+        hipLaunchKernelGGL(mosaic_set_kernel, dim3(1), dim3(64), 0, s, entries + i0, src, n);
     }
+    return (uint32_t)block0;
 }
 
 hipError_t launch_mosaic(MosaicPhase phase, void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,

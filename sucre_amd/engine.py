@@ -983,7 +983,8 @@ def mosaic_max_cells() -> int:
     """Cells a mosaic may have: SUCRE_MOSAIC_MAX_CELLS, 2^27 unless set (37 bytes per cell: key, pixel word and the five outputs;
     124 with a blend: 64 more for the accumulator's eight int64 words and 23 for the four blended outputs; a fill adds at most 30:
     19 for its three outputs and up to 11 for the pyramid, 32-byte records on a third as many cells -- 49 with a blend, whose two
-    filled outputs take 15 and whose own levels 4)."""
+    filled outputs take 15 and whose own levels 4; a multi-band blend of K bands adds 64 (K + 1) + 12: its K + 1 accumulators and
+    ``J_multiband`` -- and 19 more with a fill, ``J_multiband_filled`` and the pass's levels and dropped raw picture)."""
     return int(os.environ.get('SUCRE_MOSAIC_MAX_CELLS', 1 << 27))
 
 
@@ -991,6 +992,7 @@ MOSAIC_BLEND_RANGE = (1e-6, 1e6)   # blend depths H a mosaic takes, metres
 MOSAIC_MAX_SAMPLES = 1 << 20       # samples of one cell from which the blend's int64 sums may pass 2^62 (csrc/mosaic.h)
 MOSAIC_FILL_RANGE = (1e-6, 1e6)    # fill reaches R a mosaic takes, metres
 MOSAIC_FEATHER_RANGE = (1, 1024)   # feather widths F a blend takes, source pixels (csrc/mosaic.h, "The feather")
+MOSAIC_BANDS_RANGE = (1, 6)        # detail bands K a multi-band blend takes (csrc/bands.h): filter steps 1 .. 2^(K-1) source pixels
 MOSAIC_VALUES = {   # field of MosaicOptions -> (what it is, range, integral, unit, type of the checked value), in the order checked
     'blend': ('blend depth H', MOSAIC_BLEND_RANGE, False, 'metres', np.float32),
     'fill': ('fill reach R', MOSAIC_FILL_RANGE, False, 'metres', float),
@@ -1006,10 +1008,14 @@ def _mosaic_refusal(field: str, text: str) -> ValueError:
     return e
 
 
-def _mosaic_value(field: str, value):
-    """``value`` as ``MOSAIC_VALUES[field]`` describes it, or ValueError unless it is finite, within the range and, where the table
-    says so, an integral number and no bool."""
-    what, (lo, hi), integral, unit, kind = MOSAIC_VALUES[field]
+_MOSAIC_BANDS = ('band count K', MOSAIC_BANDS_RANGE, True, 'bands', int)   # a row like MOSAIC_VALUES': the band count travels beside
+#                                                                            the options record, not inside it
+
+
+def _mosaic_value(field: str, value, row=None):
+    """``value`` as ``MOSAIC_VALUES[field]`` (or ``row``) describes it, or ValueError unless it is finite, within the range and,
+    where the table says so, an integral number and no bool."""
+    what, (lo, hi), integral, unit, kind = MOSAIC_VALUES[field] if row is None else row
     try:
         x = float(value)
     except (TypeError, ValueError):
@@ -1041,6 +1047,34 @@ def mosaic_feather_px(feather) -> int:
 def mosaic_fill_reach(fill) -> float:
     """``fill`` as the reach R in metres, or ValueError unless it is finite and within ``MOSAIC_FILL_RANGE``."""
     return _mosaic_value('fill', fill)
+
+
+def mosaic_band_count(bands) -> int:
+    """``bands`` as the number K of detail bands of a multi-band blend, or ValueError (``field``: 'bands') unless it is an integral
+    number, no bool, within ``MOSAIC_BANDS_RANGE``."""
+    return _mosaic_value('bands', bands, _MOSAIC_BANDS)
+
+
+def mosaic_bands_checked(bands, blend, who: str):
+    """None, or K as ``mosaic_band_count`` returns it; ValueError (``field``: 'bands') for bands without a blend, in the name of ``who``."""
+    if bands is None:
+        return None
+    bands = mosaic_band_count(bands)
+    if blend is None:
+        raise _mosaic_refusal('bands', f'{who}: the bands are blended with the blend\'s weights; give the blend depth too (blend=H)')
+    return bands
+
+
+def mosaic_band_plan(H, F, K) -> list:
+    """The ``K + 1`` pairs ``(H_j, F_j)`` a multi-band blend of blend depth ``H``, feather ``F`` (None: none) and ``K`` detail bands
+    blends its bands with, detail band 0 (the finest) first and the residual last: the residual takes the user's ``(H, F)``, detail
+    band j ``H_j = max(float32(H) 2^(j-K), float32(1e-6))`` -- an exact scaling: the transition halves with every finer band -- and
+    ``F_j = max(F >> (K - j), 1)``.  ``H_j``: np.float32; ``F_j``: int, or None without a feather."""
+    H, K = mosaic_blend_depth(H), mosaic_band_count(K)
+    F = None if F is None else mosaic_feather_px(F)
+    floor = np.float32(1e-6)
+    plan = [(max(np.float32(H * np.float32(2.0 ** (j - K))), floor), None if F is None else max(F >> (K - j), 1)) for j in range(K)]
+    return plan + [(H, F)]
 
 
 @dataclass(frozen=True)
@@ -1081,8 +1115,9 @@ def mosaic_cells(lo: float, hi: float, gsd: float) -> int:
 
 _NAN = float('nan')
 MOSAIC_OUTPUTS = {   # key of Mosaic.result() -> (group, trailing shape, dtype, value of an empty cell, PNG of --mosaic, how it is made)
-    # groups: 'best' (the best view; begin), 'blend' (begin with a blend), 'fill' (fill), 'blend_fill' (fill with a blend).  An
-    # empty value of None: the kernel writes every cell.  How: 'stretch' (sucre._mosaic_picture), 'bytes', 'source', 'mask'.
+    # groups: 'best' (the best view; begin), 'blend' (begin with a blend), 'bands' (begin with bands), 'fill' (fill), 'blend_fill'
+    # (fill with a blend), 'bands_fill' (fill with bands).  An empty value of None: the kernel writes every cell.  How: 'stretch'
+    # (sucre._mosaic_picture), 'bytes', 'source', 'mask'.
     'J': ('best', (3,), torch.float32, _NAN, 'mosaic.png', 'stretch'),
     'raw': ('best', (3,), torch.uint8, 0, 'mosaic_raw.png', 'bytes'),
     'source': ('best', (), torch.int32, -1, 'mosaic_source.png', 'source'),
@@ -1092,11 +1127,13 @@ MOSAIC_OUTPUTS = {   # key of Mosaic.result() -> (group, trailing shape, dtype, 
     'raw_blend': ('blend', (3,), torch.uint8, 0, 'mosaic_blend_raw.png', 'bytes'),
     'weight': ('blend', (), torch.float32, 0, None, None),
     'samples': ('blend', (), torch.int32, 0, None, None),
+    'J_multiband': ('bands', (3,), torch.float32, _NAN, 'mosaic_multiband.png', 'stretch'),
     'fill_level': ('fill', (), torch.int32, None, 'mosaic_filled_mask.png', 'mask'),
     'J_filled': ('fill', (3,), torch.float32, None, 'mosaic_filled.png', 'stretch'),
     'raw_filled': ('fill', (3,), torch.uint8, None, 'mosaic_raw_filled.png', 'bytes'),
     'J_blend_filled': ('blend_fill', (3,), torch.float32, None, 'mosaic_blend_filled.png', 'stretch'),
     'raw_blend_filled': ('blend_fill', (3,), torch.uint8, None, 'mosaic_blend_raw_filled.png', 'bytes'),
+    'J_multiband_filled': ('bands_fill', (3,), torch.float32, None, 'mosaic_multiband_filled.png', 'stretch'),
 }
 
 
@@ -1128,7 +1165,16 @@ class Mosaic:
     map on the device first, in a buffer sized to the largest batch seen; ``J_blend``, ``raw_blend``, ``weight`` and ``samples`` are
     the feathered ones, ``result()`` holds ``feather`` (= F), and ``feather_counts`` (int64 x 2, device) counts the pixels that took
     part within F pixels of an edge and all of them.  ``feather_map(views, Js, F)`` returns the maps themselves; it needs no
-    ``begin``."""
+    ``begin``.
+
+    The bands: ``begin(blend=H, bands=K)`` -- a multi-band blend next to the blend (csrc/bands.h).  Every image is split in source
+    space into K detail bands and a residual (``band_stack``); band j is blended by the blend's own accumulate with
+    ``mosaic_band_plan(H, F, K)[j]`` into slice j of ``acc_bands`` ((K + 1, Hm Wm, 8) int64, zeros; the residual last, its words
+    3..7 equal to ``acc``'s), so the low frequencies of a cell are the consensus of every view and the fine detail comes from the
+    nearest one.  ``accumulate_bands`` over ALL the images once ``splat`` has seen every one of them -- every image is loaded once
+    for all its bands --, then ``combine_bands()``; ``result()`` then holds ``J_multiband`` and ``bands`` (= K), after ``fill`` also
+    ``J_multiband_filled``.  ``acc``, ``feather_counts`` and every other output are not touched.  Three band buffers of 12 bytes per
+    pixel of the largest batch are held."""
 
     def __init__(self, axes, gsd, device):
         _lib.load()
@@ -1154,6 +1200,7 @@ class Mosaic:
         self.blend = self.inv_h = self.acc = None
         self.feather = self.feather_counts = self._feather_buf = None
         self.fill_reach = self.fill_levels = self.pyramid = None
+        self.bands = self.band_plan = self.acc_bands = self._band_bufs = None
 
     def _images(self, views: list, Js: list):
         views, Js = list(views), list(Js)
@@ -1207,12 +1254,14 @@ class Mosaic:
         bits = np.where(k & 0x80000000, k & 0x7fffffff, ~k).astype(np.uint32)   # key_value of csrc/order_key.h
         return tuple(bits.view(np.float32).tolist())
 
-    def begin(self, bounds=None, blend=None, feather=None):
+    def begin(self, bounds=None, blend=None, feather=None, bands=None):
         """Fixes the grid and allocates; ``blend``: the blend depth H in metres (``MOSAIC_BLEND_RANGE``) -- a pixel whose range
         exceeds its cell's smallest one by d gets the weight ``max(1 - d / H, 0)^2`` -- or None for the best view alone;
-        ``feather``: with a blend, the feather width F in source pixels (``MOSAIC_FEATHER_RANGE``), or None for none."""
+        ``feather``: with a blend, the feather width F in source pixels (``MOSAIC_FEATHER_RANGE``), or None for none; ``bands``:
+        with a blend, the number K of detail bands of the multi-band blend (``MOSAIC_BANDS_RANGE``), or None for none."""
         options = MosaicOptions(blend=blend, feather=feather).checked('Mosaic.begin')   # before anything is allocated
         blend, feather = options.blend, options.feather
+        bands = mosaic_bands_checked(bands, blend, 'Mosaic.begin')
         if bounds is None:
             bounds = self.bounds()
             if bounds is None:
@@ -1243,6 +1292,11 @@ class Mosaic:
             self.inv_h = np.float32(1) / blend
             self.acc = torch.zeros((Hm * Wm, _lib.MOSAIC_ACC_WORDS), dtype=torch.int64, device=dev)
             self._allocate('blend')
+        self.bands, self.band_plan, self.acc_bands, self._band_bufs = bands, None, None, None
+        if bands is not None:
+            self.band_plan = mosaic_band_plan(blend, feather, bands)
+            self.acc_bands = torch.zeros((bands + 1, Hm * Wm, _lib.MOSAIC_ACC_WORDS), dtype=torch.int64, device=dev)
+            self._allocate('bands')
         return Hm, Wm
 
     def _begun(self, what: str) -> None:
@@ -1314,6 +1368,89 @@ class Mosaic:
         _, maps = self._feather_pass(self._images(views, Js), F)
         return [m.clone() for m in maps]
 
+    def _band_buffers(self, images, bufs=None):
+        """Three float32 buffers of one band each for ``images`` (``sucre_mosaic_band_bytes``; ``bufs`` when they are large enough)
+        and, per image, the index of its first pixel in them."""
+        arr, n, _, _ = images
+        lib = _lib.load()
+        n_bytes = lib.sucre_mosaic_band_bytes(n, arr)
+        if n_bytes == 0:
+            raise _lib.SucreError(f'sucre_mosaic_band_bytes: {lib.sucre_last_error().decode()}')
+        if bufs is None or bufs[0].numel() * 4 < n_bytes:
+            bufs = [torch.empty(n_bytes // 4, dtype=torch.float32, device=self.device) for _ in range(3)]
+        first, at = [], 0
+        for e in arr:
+            first.append(at)
+            at += -(-(e.H * e.W) // _lib.MOSAIC_BLOCK_PX) * _lib.MOSAIC_BLOCK_PX
+        return bufs, first
+
+    def _band_levels(self, images, K: int, bufs):
+        """Enqueues the K levels of ``sucre_mosaic_band_split`` over ``images``, S ping-ponging between ``bufs[0]`` and ``bufs[1]``,
+        and yields after each ``(j, buffer)``: the detail band D_j in ``bufs[2]`` for j < K, then ``(K, the buffer of S_K)``.  A
+        yielded buffer is overwritten by the next level: the caller enqueues what reads it before it goes on."""
+        S, D = bufs[:2], bufs[2]
+        for level in range(K):
+            self._walk('sucre_mosaic_band_split', images, level, None if level == 0 else S[(level - 1) % 2], S[level % 2], D)
+            yield level, D
+        yield K, S[(K - 1) % 2]
+
+    def band_stack(self, views: list, Js: list, K) -> list:
+        """Per image the K + 1 (H,W,3) float32 tensors ``D_0 .. D_(K-1), S_K`` of csrc/bands.h: the detail bands of an a-trous
+        ``[1, 2, 1]`` filter normalised over the pixels that take part, finest first, and the residual; NaN at a pixel that does not
+        take part.  Needs no ``begin``; only enqueues (reading a band waits for it)."""
+        K = mosaic_band_count(K)
+        images = self._images(views, Js)
+        bufs, first = self._band_buffers(images)
+        stacks = [[] for _ in first]
+        for _, buf in self._band_levels(images, K, bufs):
+            for stack, e, at in zip(stacks, images[0], first):
+                stack.append(buf[at * 3:(at + e.H * e.W) * 3].view(e.H, e.W, 3).clone())
+        return stacks
+
+    def _banding(self, what: str) -> None:
+        self._blending(what)
+        if self.bands is None:
+            raise ValueError(f'Mosaic.{what}: begin() was not given a band count, so there are no bands to blend')
+
+    def _accumulate_band(self, images, first, j: int, buf, first_ordinal: int, flags: int, feather_buf) -> None:
+        """Band ``j`` of ``images`` -- in ``buf``, image i's block at pixel ``first[i]`` -- into slice ``j`` of ``acc_bands``: the
+        accumulate entry with the band as the images' J and ``band_plan[j]``; ``feather_buf``: a map of these images made at
+        ``F_j`` or wider (not read without a feather)."""
+        arr, n, table, keep = images
+        band = (_lib.MosaicImage * n)()
+        C.memmove(band, arr, C.sizeof(band))
+        for e, at in zip(band, first):
+            e.J = buf.data_ptr() + at * 12
+        H_j, F_j = self.band_plan[j]
+        head = (int(first_ordinal), C.byref(self.grid), self.key, C.c_float(float(np.float32(1) / H_j)))
+        if F_j is None:
+            return self._walk('sucre_mosaic_accumulate', (band, n, table, keep), *head, self.acc_bands[j], flags)
+        self._walk('sucre_mosaic_accumulate_feathered', (band, n, table, keep), *head, F_j, feather_buf, self.acc_bands[j], flags)
+
+    def accumulate_bands(self, views: list, Js: list, first_ordinal: int, plain: bool = False) -> None:
+        """Splits the images into their band stacks and adds every band's weighted samples to its slice of ``acc_bands``: the
+        blend's accumulate entry (the feathered one with a feather) with the band as the images' J and the band's
+        ``(H_j, F_j)`` of ``band_plan``.  Valid once ``splat`` has seen every image.  With a feather the batch's map is formed once,
+        at the user's F and from the true J, and every band reads it: ``dist2 = min(D2, F^2)`` tells ``dist2 >= F_j^2`` and holds
+        every root below it for any ``F_j <= F``.  ``plain``: as ``accumulate``.  ``acc`` and ``feather_counts`` are not touched."""
+        self._banding('accumulate_bands')
+        images = self._images(views, Js)
+        self._band_bufs, first = self._band_buffers(images, self._band_bufs)
+        if self.feather is not None:
+            self._feather_buf, _ = self._feather_pass(images, self.feather, self._feather_buf)
+        flags = _lib.MOSAIC_PLAIN_ATOMIC if plain else 0
+        for j, buf in self._band_levels(images, self.bands, self._band_bufs):
+            self._accumulate_band(images, first, j, buf, first_ordinal, flags, self._feather_buf)
+
+    def combine_bands(self) -> None:
+        """The per-cell pass from ``acc_bands`` to ``J_multiband``: every band's quotient as ``normalize`` forms the blend's, added
+        in float32 from the residual to the finest band.  Valid once ``accumulate_bands`` has seen every image (``normalize`` has
+        checked the sample bound: the residual's counts are the blend's); only enqueues."""
+        self._banding('combine_bands')
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().sucre_mosaic_band_combine(C.byref(self.grid), self.bands + 1, C.c_void_p(self.acc_bands.data_ptr()),
+                                                             C.c_void_p(self._out['J_multiband'].data_ptr()), _stream_ptr()))
+
     def normalize(self, check: bool = True) -> None:
         """The per-cell pass from ``acc`` to the four blended outputs; waits for it, and raises ValueError when a cell holds
         ``MOSAIC_MAX_SAMPLES`` = 2^20 samples or more (its 64-bit sums may have wrapped).  ``check=False`` only enqueues the
@@ -1338,7 +1475,8 @@ class Mosaic:
         has run.  ``J_filled`` / ``raw_filled`` are ``J`` / ``raw`` with every cell without a source (``source < 0``) replaced by
         the pyramid's value where one reaches it (``fill_level``: 0 measured, 1..L the coarsest level a filled cell drew on, -1
         still empty; NaN and 0 there); with a blend ``J_blend_filled`` / ``raw_blend_filled`` come from ``J_blend`` / ``raw_blend``
-        and the same ``source`` through the same pyramid buffer.  Only enqueues.  Like the other phases it cannot tell whether
+        and the same ``source`` through the same pyramid buffer, with bands ``J_multiband_filled`` from ``J_multiband`` and
+        ``raw_blend`` likewise (that pass's raw picture is dropped: there is no multi-band raw mosaic).  Only enqueues.  Like the other phases it cannot tell whether
         the phases before it have seen every image: called earlier on a begun mosaic it fills from the grid as it stands then
         (from an empty grid: nothing, every cell -1)."""
         self._begun('fill')
@@ -1353,16 +1491,19 @@ class Mosaic:
         pairs = [('fill', 'J', 'raw', 'J_filled', 'raw_filled')]
         if self.blend is not None:
             pairs.append(('blend_fill', 'J_blend', 'raw_blend', 'J_blend_filled', 'raw_blend_filled'))
+        if self.bands is not None:
+            pairs.append(('bands_fill', 'J_multiband', 'raw_blend', 'J_multiband_filled', None))
         o = self._out
         with torch.cuda.device(dev):
             for group, J, raw, J_to, raw_to in pairs:
                 self._allocate(group)
                 # (the blend's own levels are not a result: a blended colour is always finite, a best-view one need not be)
                 level = o['fill_level'] if group == 'fill' else torch.empty_like(o['fill_level'])
+                raw_filled = torch.empty_like(o[raw]) if raw_to is None else o[raw_to]
                 base = (Hm, Wm, L, C.c_void_p(o[J].data_ptr()), C.c_void_p(o[raw].data_ptr()), C.c_void_p(o['source'].data_ptr()),
                         C.c_void_p(self.pyramid.data_ptr()))
                 _lib.check(lib.sucre_mosaic_fill_pull(*base, _stream_ptr()))
-                _lib.check(lib.sucre_mosaic_fill_push(*base, C.c_void_p(o[J_to].data_ptr()), C.c_void_p(o[raw_to].data_ptr()),
+                _lib.check(lib.sucre_mosaic_fill_push(*base, C.c_void_p(o[J_to].data_ptr()), C.c_void_p(raw_filled.data_ptr()),
                                                       C.c_void_p(level.data_ptr()), _stream_ptr()))
         return L
 
@@ -1372,15 +1513,19 @@ class Mosaic:
         (Hm,Wm,3) float32 (NaN), ``raw_blend`` (Hm,Wm,3) uint8 (0), ``weight`` (Hm,Wm) float32 -- the sum of the samples' weights,
         each at most 1 -- (0) and ``samples`` (Hm,Wm) int32 (0), complete once ``normalize`` has run.  After ``fill`` also
         ``J_filled`` (Hm,Wm,3) float32 (NaN: still empty), ``raw_filled`` (Hm,Wm,3) uint8 (0), ``fill_level`` (Hm,Wm) int32 (-1)
-        and, with a blend, ``J_blend_filled`` and ``raw_blend_filled``.  With a feather also ``feather``, the width F (an int)."""
+        and, with a blend, ``J_blend_filled`` and ``raw_blend_filled``.  With a feather also ``feather``, the width F (an int).  With
+        bands also ``J_multiband`` (Hm,Wm,3) float32 (NaN), complete once ``combine_bands`` has run, and ``bands``, the count K (an
+        int); after ``fill`` also ``J_multiband_filled``."""
         self._begun('result')
         def of(*groups):
             return {key: t for key, t in self._out.items() if MOSAIC_OUTPUTS[key][0] in groups}
-        return {**of('best', 'blend'), **({} if self.feather is None else {'feather': self.feather}), **of('fill', 'blend_fill')}
+        return {**of('best', 'blend', 'bands'), **({} if self.feather is None else {'feather': self.feather}),
+                **({} if self.bands is None else {'bands': self.bands}), **of('fill', 'blend_fill', 'bands_fill')}
 
-    def run(self, batches, options: MosaicOptions = MosaicOptions(), bounds=None, plain_atomic: bool = False) -> 'Mosaic':
+    def run(self, batches, options: MosaicOptions = MosaicOptions(), bounds=None, plain_atomic: bool = False, bands=None) -> 'Mosaic':
         """Every phase over every batch, in the one order there is: the bounds (unless ``bounds`` is given), ``begin``, ``splat``,
-        ``resolve`` and ``gather``; with a blend ``accumulate`` and then ``normalize``; with a fill ``fill``.  ``batches``: a
+        ``resolve`` and ``gather``; with a blend ``accumulate`` and then ``normalize``; with ``bands`` (the count K of a multi-band
+        blend, beside the options record; only with a blend) ``accumulate_bands`` and then ``combine_bands``; with a fill ``fill``.  ``batches``: a
         sequence of ``(first_ordinal, load)``, ``load()`` returning the batch's ``(views, Js)`` -- called once per phase, so a
         caller may hold only some of the images at a time; ``options``: as ``MosaicOptions.checked`` returns them;
         ``plain_atomic``: both the splat and the accumulate phase in their plain forms.  Returns the mosaic."""
@@ -1388,7 +1533,8 @@ class Mosaic:
         if bounds is None:
             for _, load in batches:
                 self.add_bounds(*load())
-        self.begin(bounds, blend=options.blend, feather=options.feather)
+        bands = mosaic_bands_checked(bands, options.blend, 'Mosaic.run')
+        self.begin(bounds, blend=options.blend, feather=options.feather, **({} if bands is None else {'bands': bands}))
         phases = [(self.splat, {'plain_atomic': plain_atomic}), (self.resolve, {}), (self.gather, {})]
         if options.blend is not None:
             phases.append((self.accumulate, {'plain': plain_atomic}))
@@ -1397,25 +1543,31 @@ class Mosaic:
                 phase(*load(), first, **kw)
         if options.blend is not None:
             self.normalize()
+        if bands is not None:
+            for first, load in batches:
+                self.accumulate_bands(*load(), first, plain=plain_atomic)
+            self.combine_bands()
         if options.fill is not None:
             self.fill(options.fill)
         return self
 
 
 def mosaic_of(views: list, Js: list, axes, gsd, bounds=None, batch: int = 32, plain_atomic: bool = False, blend=None,
-              fill=None, feather=None) -> 'Mosaic':
+              fill=None, feather=None, bands=None) -> 'Mosaic':
     """``Mosaic.run`` over device-resident ``views`` / ``Js`` (ordinal = position in the list), ``batch`` images per call; with
     ``blend`` (the blend depth H, metres) the accumulate phase and the normalise pass after them (``plain_atomic``: both the
     splat and the accumulate phase in their plain forms), with ``feather`` (the width F, source pixels; only with ``blend``) the
-    feathered one; with ``fill`` (the reach R, metres) the hole filling after all of them (``MosaicOptions``)."""
+    feathered one; with ``bands`` (the count K of detail bands; only with ``blend``) the multi-band blend after them; with ``fill``
+    (the reach R, metres) the hole filling after all of them (``MosaicOptions``)."""
     views, Js = list(views), list(Js)
     if not views:
         raise ValueError('mosaic_of: no view')
     if len(views) > MAX_VIEWS:
         raise ValueError(f'mosaic_of: {len(views)} images, at most {MAX_VIEWS}')
     options = MosaicOptions(blend=blend, feather=feather, fill=fill).checked('mosaic_of')   # before anything is allocated
+    bands = mosaic_bands_checked(bands, options.blend, 'mosaic_of')
     batches = [(i, lambda i=i: (views[i:i + batch], Js[i:i + batch])) for i in range(0, len(views), batch)]
-    return Mosaic(axes, gsd, views[0].depth.device).run(batches, options, bounds, plain_atomic)
+    return Mosaic(axes, gsd, views[0].depth.device).run(batches, options, bounds, plain_atomic, **({} if bands is None else {'bands': bands}))
 
 
 def device_views_from_scene(scene, device='cuda') -> list[DeviceView]:

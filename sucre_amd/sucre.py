@@ -1404,7 +1404,8 @@ def _mosaic_picture(J: Tensor, stretch) -> np.ndarray:
     return np.uint8(J * 255)
 
 
-_MOSAIC_FLAG = {'grid': '--mosaic', 'blend': '--mosaic-blend', 'fill': '--mosaic-fill', 'feather': '--mosaic-feather'}
+_MOSAIC_FLAG = {'grid': '--mosaic', 'blend': '--mosaic-blend', 'fill': '--mosaic-fill', 'feather': '--mosaic-feather',
+                'bands': '--mosaic-bands'}
 
 
 def _mosaic_refused(e: ValueError, fields=tuple(_MOSAIC_FLAG)) -> BaseException:
@@ -1422,7 +1423,8 @@ _MOSAIC_PNG = {   # how a row of engine.MOSAIC_OUTPUTS becomes its PNG: (the out
 
 
 def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, output_dir: Path, gsd: float | None = None, axes=None,
-           stretch=None, device: str = 'cuda', blend: float | None = None, fill: float | None = None, feather: int | None = None) -> dict:
+           stretch=None, device: str = 'cuda', blend: float | None = None, fill: float | None = None, feather: int | None = None,
+           bands: int | None = None) -> dict:
     """One picture of the seabed from a finished restoration: every pixel of ``images`` (``sfm.Image`` objects or names of
     ``colmap_model``; at most ``engine.MAX_VIEWS``, ordinal = position) with a valid depth and a restored colour --
     ``results_dir / <name>.pt``, key ``J`` -- is dropped onto the plane grid ``axes`` (``mosaic_axes`` unless given) of ``gsd``
@@ -1456,7 +1458,17 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
     out towards the edge of every footprint, NaN patch and depth hole and does not step there.  The blended files and keys are then
     the feathered ones (a fill fills from them); the best-view ones stay as they are, byte for byte; ``mosaic.pt`` gains
     ``feather`` and one more line is printed after the blend's (its share "within F px of an edge" is counted over the pixels that
-    take part, ``engine.Mosaic.feather_counts``, whether or not their weight rounds to nothing).  Not built: multi-band blending."""
+    take part, ``engine.Mosaic.feather_counts``, whether or not their weight rounds to nothing).
+
+    ``bands``: with ``blend``, the number K of detail bands (``engine.MOSAIC_BANDS_RANGE``) of a multi-band blend next to the blend.
+    Every image is split in source space into K detail bands and a residual (csrc/bands.h), one more pass over the batches
+    blends every band with the blend's own fixed-point sums -- the residual with ``(H, F)``, every finer band with half the depth
+    and half the feather of the one before (``engine.mosaic_band_plan``) --, and a pass over the cells adds them: the colour of the
+    blend with the detail of the best view.  Every file and key above stays as it is, byte for byte; ``mosaic_multiband.png``
+    (``J_multiband`` through the function that makes ``mosaic.png``) comes next to them -- with a fill also
+    ``mosaic_multiband_filled.png`` --, ``mosaic.pt`` gains ``J_multiband`` (``J_multiband_filled``), ``bands`` and ``band_plan``,
+    the list of ``(H_j, F_j)``, and one more line is printed after the blend's and the feather's.  Not built: a multi-band raw
+    mosaic."""
     from . import engine
     sfm.require_gpu(device, 'mosaic')
     images = [colmap_model[im] if isinstance(im, str) else im for im in images]
@@ -1473,6 +1485,12 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
             raise SystemExit('--mosaic-feather: only with --mosaic-blend H')
         raise _mosaic_refused(e)
     blend, feather, fill = options.blend, options.feather, options.fill
+    try:
+        bands = None if bands is None else engine.mosaic_band_count(bands)
+    except ValueError as e:
+        raise _mosaic_refused(e)
+    if bands is not None and blend is None:
+        raise SystemExit('--mosaic-bands: only with --mosaic-blend H')
     results_dir, output_dir = Path(results_dir), Path(output_dir)
     for image in images:   # before anything is decoded
         path = _consistency_file(results_dir, image)
@@ -1503,7 +1521,8 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
             del depths
             print(f'--mosaic: ground sample distance {float(gsd):.6g} m (twice the median pixel footprint; --mosaic-gsd sets it).')
         try:
-            m = engine.Mosaic(axes, gsd, device).run([(first, lambda batch=batch: resident(batch)) for first, batch in batches], options)
+            m = engine.Mosaic(axes, gsd, device).run([(first, lambda batch=batch: resident(batch)) for first, batch in batches], options,
+                                                     **({} if bands is None else {'bands': bands}))
         except ValueError as e:
             # Two refusals of the run belong to a flag: begin's of the grid (--mosaic) and normalize's of a cell's sample count
             # (--mosaic-blend).  The options were checked above, so begin and fill have nothing left to refuse in them; every other
@@ -1526,6 +1545,8 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
         data['blend'] = float(blend)
     if fill is not None:
         data['fill'], data['fill_levels'] = float(fill), int(m.fill_levels)
+    if bands is not None:
+        data['band_plan'] = [(float(h), f) for h, f in m.band_plan]
     torch.save(data, output_dir / 'mosaic.pt')
     top = int(per_image.argmax())
     print(f'mosaic of {len(images)} images: {Wm} x {Hm} cells of {float(m.gsd):.6g} m, {n_filled} filled '
@@ -1540,6 +1561,12 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
         near, part = (int(x) for x in m.feather_counts.cpu())
         print(f'mosaic feather of {feather} px: {100.0 * near / max(1, part):.1f} % of the samples within {feather} px of an edge; '
               f'smallest weight sum in a filled cell {float(out["weight"][out["samples"] > 0].min()) if n_filled else 0.0:.6g}')
+    if bands is not None:
+        diff = (out['J_multiband'].double() - out['J_blend'].double())[filled]
+        rms = diff.pow(2).mean(dim=0).sqrt().tolist() if n_filled else [0.0] * 3
+        print(f'mosaic multi-band blend of {bands} bands: depths {" ".join(f"{float(h):.6g}" for h, _ in m.band_plan)} m, feathers '
+              f'{" ".join("-" if f is None else str(f) for _, f in m.band_plan)} px; RMS difference from the blend '
+              f'R {rms[0]:.6g} G {rms[1]:.6g} B {rms[2]:.6g}')
     if fill is not None:
         level = out['fill_level']
         print(f'mosaic fill of {float(fill):.6g} m ({int(m.fill_levels)} levels): {int((level > 0).sum())} cells filled, '
@@ -1588,7 +1615,7 @@ _MODE_REFUSES = {   # mode -> (flag, why), in the order they are looked at
 
 _ONLY_WITH = [   # (flag, the flag it needs, that one's value), in the order they are looked at
     ('--mosaic-gsd', '--mosaic', 'DIR'), ('--mosaic-blend', '--mosaic', 'DIR'), ('--mosaic-fill', '--mosaic', 'DIR'),
-    ('--mosaic-feather', '--mosaic-blend', 'H'),
+    ('--mosaic-feather', '--mosaic-blend', 'H'), ('--mosaic-bands', '--mosaic-blend', 'H'),
 ]
 
 
@@ -1607,8 +1634,8 @@ def _refuse_mode_flags(args, mode: str) -> None:
 
 
 def _refuse_mosaic_values(args, world: int = 1) -> None:
-    """The values of --mosaic-gsd, --mosaic-blend, --mosaic-fill and --mosaic-feather and the world size a mosaic takes, refused
-    before any file is opened."""
+    """The values of --mosaic-gsd, --mosaic-blend, --mosaic-fill, --mosaic-feather and --mosaic-bands and the world size a mosaic
+    takes, refused before any file is opened."""
     gsd = getattr(args, 'mosaic_gsd', None)
     if gsd is not None and not (np.isfinite(gsd) and gsd > 0):
         raise SystemExit(f'--mosaic-gsd: G must be a finite size > 0 in metres, not {gsd}')
@@ -1618,6 +1645,10 @@ def _refuse_mosaic_values(args, world: int = 1) -> None:
         _, (lo, hi), integral, unit, _ = engine.MOSAIC_VALUES[field]
         if value is not None and not (np.isfinite(value) and lo <= value <= hi and (not integral or value == int(value))):
             raise SystemExit(f'{_MOSAIC_FLAG[field]}: {letter} must be {kind} within [{lo:g}, {hi:g}] {unit}, not {last.format(value)}')
+    bands = getattr(args, 'mosaic_bands', None)
+    lo, hi = engine.MOSAIC_BANDS_RANGE
+    if bands is not None and not (np.isfinite(bands) and lo <= bands <= hi and bands == int(bands)):
+        raise SystemExit(f'{_MOSAIC_FLAG["bands"]}: K must be an integer within [{lo:g}, {hi:g}] bands, not {bands:g}')
     if world > 1:
         raise SystemExit(f'--mosaic: a world size of {world} is not supported yet: the four phases are separate entries of the library '
                          f'so that ranks can all-reduce bounds, keys and pixel words between them, but that all-reduce is not built; '
@@ -1729,7 +1760,7 @@ def parse_args(args: argparse.Namespace):
         if mosaic_dir is not None:
             mosaic(images, colmap_model, mosaic_dir, args.output_dir, gsd=getattr(args, 'mosaic_gsd', None), stretch=stretch, device=device,
                    blend=getattr(args, 'mosaic_blend', None), fill=getattr(args, 'mosaic_fill', None),
-                   feather=getattr(args, 'mosaic_feather', None))
+                   feather=getattr(args, 'mosaic_feather', None), bands=getattr(args, 'mosaic_bands', None))
         elif check is not None:
             if world > 1:   # the targets' records are gathered on rank 0
                 sdist.init_process_group()
@@ -1987,6 +2018,13 @@ def build_parser() -> argparse.ArgumentParser:
                                'to the full weight F source pixels inside (an integer, 1..1024; an exact distance map made on the device), '
                                'so the blend does not step where a view ends; the blended files and keys are then the feathered ones, the '
                                'best-view ones stay as they are; adds feather to mosaic.pt and prints one more line')
+    p.extras.add_argument('--mosaic-bands', type=float, metavar='K', default=argparse.SUPPRESS,
+                          help='with --mosaic-blend: also a multi-band blend -- every image is split into K detail bands (an integer, '
+                               '1..6) and a residual, the residual is blended with the depth H (and the feather F), every finer band with '
+                               'half the depth and half the feather of the one before, and the blended bands are added: the colour of the '
+                               'blend with the detail of the best view; writes mosaic_multiband.png (with --mosaic-fill also '
+                               'mosaic_multiband_filled.png) next to the other files, which stay as they are, adds J_multiband, bands and '
+                               'band_plan to mosaic.pt and prints one more line')
     p.extras.add_argument('--common-stretch', action='store_true', default=argparse.SUPPRESS,
                           help='with --shared-water or --apply-water: stretch every <stem>_rgb.png between the SAME per-channel 1st '
                                'and 99th percentile, those of the valid pixels of all images of the request pooled (all ranks), '
