@@ -695,6 +695,23 @@ int sucre_view_consistency(int H, int W, int n_views, const sucre_view_t *target
  *                         has d = 0, so t = 1 whatever the band's blend depth, and f >= 1/1024.
  * Checked before any launch as above, and: level outside 0..5, S_in given at level 0 or NULL above it, a NULL or misaligned S_out
  * or D_out, buffers that overlap, n_bands outside 2..7, a NULL or misaligned acc_bands_dev or J_out, Hm Wm above 2^39.
+ *
+ * The surface test: a per-cell top height along e3 (row 2 of the axes; it looks the way the cameras look, so smaller is higher),
+ * and the samples too far below it taken out of every later phase.  For a pixel that takes part and has a cell, a_n = dot3(e3, wP)
+ * with the wP its plane coordinates are formed from; top[cell] is the smallest a_n of the cell, kept as the order-preserving
+ * uint32 image of its bits (k = bits ^ 0x80000000 for a_n >= +0, ~bits below; -0.0 lies below +0.0; all ones: empty).
+ *   sucre_mosaic_surface  top_dev[cell] (uint32) = min k over the pixels of the cell; the caller starts it at all ones.  One pass
+ *                         over ALL images, any split into calls, before sucre_mosaic_cull.  flags: SUCRE_MOSAIC_PLAIN_ATOMIC --
+ *                         the atomic min for every pixel instead of loading the word first (the same top_dev)
+ *   sucre_mosaic_cull     J_out: a buffer of sucre_mosaic_band_bytes for these images, in that layout.  A pixel that takes part and
+ *                         is not culled -- culled: it has a cell, the cell's top is not all ones and a_n - top > tol, one float32
+ *                         subtraction and one comparison -- gets its J copied bit for bit; every other pixel of an image gets
+ *                         the NaN 0x7fc00000 in all three channels; the pixels between two images are not written.  The caller
+ *                         hands the other entries J_out's blocks as the images' J: a culled pixel takes part in nothing.
+ *                         culled_dev (uint32 per cell, or NULL): a culled sample adds 1 to its cell.  counts_dev (uint64 x 2, or
+ *                         NULL): adds the culled samples and the samples with a cell.  Only enqueues
+ * Checked before any launch as above, and: a NULL or misaligned top_dev or J_out, a misaligned culled_dev or counts_dev, tol not
+ * finite or <= 0, a J_out that overlaps an image's J, unknown flags.
  */
 #define SUCRE_MOSAIC_PLAIN_ATOMIC 1u
 #define SUCRE_MOSAIC_ACC_WORDS 8
@@ -738,6 +755,11 @@ size_t sucre_mosaic_band_bytes(int n_images, const sucre_mosaic_image_t *images)
 int sucre_mosaic_band_split(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int level, const float *S_in, float *S_out,
                             float *D_out, void *stream);
 int sucre_mosaic_band_combine(const sucre_mosaic_grid_t *grid, int n_bands, const int64_t *acc_bands_dev, float *J_out, void *stream);
+int sucre_mosaic_surface(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                         const sucre_mosaic_grid_t *grid, uint32_t *top_dev, unsigned flags, void *stream);
+int sucre_mosaic_cull(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                      const sucre_mosaic_grid_t *grid, const uint32_t *top_dev, float tol, float *J_out, uint32_t *culled_dev,
+                      uint64_t *counts_dev, void *stream);
 
 /*
  * ---- hole filling of the finished mosaic: a bounded push-pull over a pyramid of the grid ------------------------------------------

@@ -13,6 +13,7 @@
 #include "mosaic.h"
 #include "bands.h"
 #include "pool.h"
+#include "surface.h"
 
 namespace sucre {
 
@@ -1115,6 +1116,41 @@ int sucre_mosaic_band_combine(const sucre_mosaic_grid_t *grid, int n_bands, cons
     if (!J_out || !aligned(J_out, 4)) return fail(SUCRE_ERR_ARG, "J_out is NULL or not 4-byte aligned");
     return check_hip(launch_band_combine(g, n_bands, reinterpret_cast<const long long *>(acc_bands_dev), J_out,
                                          static_cast<hipStream_t>(stream)), "sucre_mosaic_band_combine");
+}
+
+/* ---- surface test of the mosaic: the per-cell top height along e3 and the samples too far below it (surface.h) ---- */
+
+int sucre_mosaic_surface(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                         const sucre_mosaic_grid_t *grid, uint32_t *top_dev, unsigned flags, void *stream) {
+    if (int rc = check_mosaic_images(table_dev, n_images, images, first_ordinal)) return rc;
+    MosaicGrid g;
+    if (int rc = check_mosaic_grid(grid, &g)) return rc;
+    if (!top_dev || !aligned(top_dev, 4)) return fail(SUCRE_ERR_ARG, "top_dev is NULL or not 4-byte aligned");
+    if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
+    return check_hip(launch_mosaic_surface((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) != 0, table_dev, n_images, images, first_ordinal, g, top_dev,
+                                           static_cast<hipStream_t>(stream)), "sucre_mosaic_surface");
+}
+
+int sucre_mosaic_cull(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                      const sucre_mosaic_grid_t *grid, const uint32_t *top_dev, float tol, float *J_out, uint32_t *culled_dev,
+                      uint64_t *counts_dev, void *stream) {
+    if (int rc = check_mosaic_images(table_dev, n_images, images, first_ordinal)) return rc;
+    MosaicGrid g;
+    if (int rc = check_mosaic_grid(grid, &g)) return rc;
+    if (!top_dev || !aligned(top_dev, 4)) return fail(SUCRE_ERR_ARG, "top_dev is NULL or not 4-byte aligned");
+    if (!std::isfinite(tol) || !(tol > 0.0f)) return fail(SUCRE_ERR_ARG, "tol=%g must be finite and > 0", (double)tol);
+    if (!J_out || !aligned(J_out, 4)) return fail(SUCRE_ERR_ARG, "J_out is NULL or not 4-byte aligned");
+    if (culled_dev && !aligned(culled_dev, 4)) return fail(SUCRE_ERR_ARG, "culled_dev is not 4-byte aligned");
+    if (counts_dev && !aligned(counts_dev, 8)) return fail(SUCRE_ERR_ARG, "counts_dev is not 8-byte aligned");
+    // J_out is a buffer of its own: a lane reads its pixel of an image's J and writes it somewhere else in J_out
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(J_out), o1 = o0 + band_bytes(n_images, images);
+    for (int i = 0; i < n_images; ++i) {
+        const uintptr_t j0 = reinterpret_cast<uintptr_t>(images[i].J), j1 = j0 + (size_t)images[i].H * (size_t)images[i].W * 12;
+        if (j0 < o1 && o0 < j1) return fail(SUCRE_ERR_ARG, "image %d: J_out overlaps the image's J", i);
+    }
+    const MosaicCull out = {culled_dev, reinterpret_cast<unsigned long long *>(counts_dev)};
+    return check_hip(launch_mosaic_cull(table_dev, n_images, images, first_ordinal, g, top_dev, tol, J_out, out,
+                                        static_cast<hipStream_t>(stream)), "sucre_mosaic_cull");
 }
 
 /* ---- hole filling of the finished mosaic: a bounded push-pull over a pyramid of the grid (fill.h) ---- */

@@ -1,6 +1,7 @@
 // Seabed mosaic of restored images (sucre_mosaic_*): a best-view ortho splat.  Every pixel of every image is dropped onto a
 // plane grid; the pixel seen through the LEAST water wins its cell.  No float atomics: the optional blend
-// ("The blend" below) sums in fixed point.  Cells no pixel lands in stay empty here; closing them is fill.h.
+// ("The blend" below) sums in fixed point.  Cells no pixel lands in stay empty here; closing them is fill.h.  Range alone decides
+// here; a test of the samples' height along e3 ahead of every phase, which hands the phases a culled copy of J, is surface.h.
 //
 // A pixel p = v W + u of image i (its ordinal: the position in the request) TAKES PART when d > 0 and J[p] holds no NaN in any
 // channel (plot_J's rule, sucre.py:86-87).  Then, all in float32 with explicit FMAs (the library is built with
@@ -187,6 +188,18 @@ __device__ __forceinline__ const MosaicImage *mosaic_block_image(const MosaicIma
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
         if (table[mid].block0 <= blockIdx.x) lo = mid;
+        else hi = mid - 1;
+    }
+    return table + lo;
+}
+
+// The same for a kernel whose workgroups each walk several of the grid's 256-pixel blocks: the image of `block`.  A second copy on
+// purpose: handing blockIdx.x to this form moves the loop's entry branches in every existing kernel, and their code stays as it is.
+__device__ __forceinline__ const MosaicImage *mosaic_block_image_at(const MosaicImage *__restrict__ table, int n_images, uint32_t block) {
+    int lo = 0, hi = n_images - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[mid].block0 <= block) lo = mid;
         else hi = mid - 1;
     }
     return table + lo;

@@ -1,6 +1,5 @@
 // Seabed mosaic of restored images for gfx950 (sucre_mosaic_*; the description: mosaic.h).
-#include "mosaic.h"
-#include "match_pixel.h"
+#include "mosaic_walk.h"
 #include "order_key.h"
 
 namespace sucre {
@@ -10,71 +9,6 @@ struct MosaicEntries { MosaicImage e[kMosaicSet]; };
 // Entries of the table handed over by value: the library performs no host-to-device copy (invert_set_kernel's way).
 __global__ void mosaic_set_kernel(MosaicImage *dst, const MosaicEntries src, int n) {
     if ((int)threadIdx.x < n) dst[threadIdx.x] = src.e[threadIdx.x];
-}
-
-// What every phase needs to know about one pixel, formed by every phase with these very operations.
-struct MosaicPixel {
-    bool in;          // takes part (d > 0, no NaN in J)
-    float z;          // its range
-    float a_s, a_t;   // its plane coordinates
-    float J[3];
-};
-
-__device__ __forceinline__ MosaicPixel mosaic_pixel(const MosaicImage *__restrict__ im, const float *Kinv, bool pin, const float *R,
-                                                    const float *t, const float *axes, uint32_t p, uint32_t W) {
-    MosaicPixel m;
-    const uint32_t v = p / W, u = p - v * W;
-    const float d = global_ptr(im->depth)[p];
-    const auto *pj = global_ptr(im->J) + (size_t)p * 3;
-    m.J[0] = pj[0]; m.J[1] = pj[1]; m.J[2] = pj[2];
-    m.in = mosaic_member(d, m.J[0], m.J[1], m.J[2]);
-    float cP[3], wP[3];
-    unproject(Kinv, pin, (float)u, (float)v, d, cP);
-    m.z = sqrtf(cP[0] * cP[0] + cP[1] * cP[1] + cP[2] * cP[2]);
-    rigid(R, t, cP, wP);
-    m.a_s = dot3(axes + 0, wP[0], wP[1], wP[2]);
-    m.a_t = dot3(axes + 3, wP[0], wP[1], wP[2]);
-    return m;
-}
-
-// The pixel's cell, or false when it falls outside the grid (caller-given bounds) or its coordinates are not numbers.
-__device__ __forceinline__ bool mosaic_cell(const MosaicGrid &g, const MosaicPixel &m, size_t *cell) {
-    const float qs = (m.a_s - g.lo_s) / g.gsd, qt = (m.a_t - g.lo_t) / g.gsd;
-    if (!(qs >= 0.0f && qs < (float)g.Wm && qt >= 0.0f && qt < (float)g.Hm)) return false;
-    const int col = (int)qs, row = (int)qt;
-    if (col >= g.Wm || row >= g.Hm) return false;   // (float)Wm may round up above 2^24: never index past the grid
-    *cell = (size_t)row * (size_t)g.Wm + (size_t)col;
-    return true;
-}
-
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t y = (uint32_t)__shfl_xor((int)x, o);
-        x = y < x ? y : x;
-    }
-    return x;
-}
-
-// The walk of every phase: the workgroup's image, the lane's pixel and what mosaic_pixel says of it.  False for a lane past the
-// image's last pixel and for a pixel that does not take part.
-__device__ __forceinline__ bool mosaic_walk(const MosaicImage *__restrict__ table, int n_images, const MosaicGrid &g,
-                                            const MosaicImage *__restrict__ *image, uint32_t *pixel, MosaicPixel *m) {
-    const MosaicImage *__restrict__ im = mosaic_block_image(table, n_images);
-    const uint32_t W = (uint32_t)im->W, n_px = (uint32_t)im->H * W;   // H, W <= 32767: below 2^30
-    const uint32_t p = (blockIdx.x - im->block0) * kMosaicBlockPx + threadIdx.x;
-    const bool inside = p < n_px;
-    float Kinv[9], R[9], t[3];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) { Kinv[i] = im->Kinv[i]; R[i] = im->R[i]; }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) t[i] = im->t[i];
-    const bool pin = pinhole_form(Kinv);
-    *m = MosaicPixel{};
-    if (inside) *m = mosaic_pixel(im, Kinv, pin, R, t, g.axes, p, W);
-    *image = im;
-    *pixel = p;
-    return inside && m->in;
 }
 
 template <int kPhase>

@@ -984,7 +984,8 @@ def mosaic_max_cells() -> int:
     124 with a blend: 64 more for the accumulator's eight int64 words and 23 for the four blended outputs; a fill adds at most 30:
     19 for its three outputs and up to 11 for the pyramid, 32-byte records on a third as many cells -- 49 with a blend, whose two
     filled outputs take 15 and whose own levels 4; a multi-band blend of K bands adds 64 (K + 1) + 12: its K + 1 accumulators and
-    ``J_multiband`` -- and 19 more with a fill, ``J_multiband_filled`` and the pass's levels and dropped raw picture)."""
+    ``J_multiband`` -- and 19 more with a fill, ``J_multiband_filled`` and the pass's levels and dropped raw picture; a surface test
+    adds 12: the ``top`` word, ``surface`` and ``culled``)."""
     return int(os.environ.get('SUCRE_MOSAIC_MAX_CELLS', 1 << 27))
 
 
@@ -1010,6 +1011,10 @@ def _mosaic_refusal(field: str, text: str) -> ValueError:
 
 _MOSAIC_BANDS = ('band count K', MOSAIC_BANDS_RANGE, True, 'bands', int)   # a row like MOSAIC_VALUES': the band count travels beside
 #                                                                            the options record, not inside it
+
+
+MOSAIC_SURFACE_RANGE = (1e-6, 1e6)   # surface tolerances T a mosaic takes, metres (csrc/surface.h)
+_MOSAIC_SURFACE = ('surface tolerance T', MOSAIC_SURFACE_RANGE, False, 'metres', np.float32)   # beside the record, as the band count
 
 
 def _mosaic_value(field: str, value, row=None):
@@ -1053,6 +1058,12 @@ def mosaic_band_count(bands) -> int:
     """``bands`` as the number K of detail bands of a multi-band blend, or ValueError (``field``: 'bands') unless it is an integral
     number, no bool, within ``MOSAIC_BANDS_RANGE``."""
     return _mosaic_value('bands', bands, _MOSAIC_BANDS)
+
+
+def mosaic_surface_tol(surface) -> np.float32:
+    """``surface`` as the float32 tolerance T of the surface test in metres, or ValueError (``field``: 'surface') unless it is finite
+    and within ``MOSAIC_SURFACE_RANGE``."""
+    return _mosaic_value('surface', surface, _MOSAIC_SURFACE)
 
 
 def mosaic_bands_checked(bands, blend, who: str):
@@ -1128,6 +1139,8 @@ MOSAIC_OUTPUTS = {   # key of Mosaic.result() -> (group, trailing shape, dtype, 
     'weight': ('blend', (), torch.float32, 0, None, None),
     'samples': ('blend', (), torch.int32, 0, None, None),
     'J_multiband': ('bands', (3,), torch.float32, _NAN, 'mosaic_multiband.png', 'stretch'),
+    'surface': ('surface', (), torch.float32, _NAN, 'mosaic_surface.png', 'height'),
+    'culled': ('surface', (), torch.int32, 0, 'mosaic_culled.png', 'count'),
     'fill_level': ('fill', (), torch.int32, None, 'mosaic_filled_mask.png', 'mask'),
     'J_filled': ('fill', (3,), torch.float32, None, 'mosaic_filled.png', 'stretch'),
     'raw_filled': ('fill', (3,), torch.uint8, None, 'mosaic_raw_filled.png', 'bytes'),
@@ -1174,7 +1187,18 @@ class Mosaic:
     nearest one.  ``accumulate_bands`` over ALL the images once ``splat`` has seen every one of them -- every image is loaded once
     for all its bands --, then ``combine_bands()``; ``result()`` then holds ``J_multiband`` and ``bands`` (= K), after ``fill`` also
     ``J_multiband_filled``.  ``acc``, ``feather_counts`` and every other output are not touched.  Three band buffers of 12 bytes per
-    pixel of the largest batch are held."""
+    pixel of the largest batch are held.
+
+    The surface test: ``begin(surface=T)`` -- T in metres (``MOSAIC_SURFACE_RANGE``; csrc/surface.h).  ``top`` (int32 bit patterns of
+    uint32, all ones: empty) holds per cell the order key of the smallest coordinate along e3, the highest sample, of all the
+    pixels that take part; it is the tensor a later all-reduce (unsigned min) over ranks would combine, next to ``key`` and
+    ``pix``.  ``add_surface(views, Js, first_ordinal)`` over ALL the images, after ``begin`` and before ``splat``; from then on
+    ``splat``, ``resolve``, ``gather``, ``accumulate`` and ``accumulate_bands`` see, through ``culled_images``, a copy of every
+    ``J`` with NaN where a sample lies more than T below its cell's top: such a sample takes part in nothing.  The grid is that of
+    all the pixels that take part, and the set of filled cells does not change.  ``result()`` then holds ``surface`` ((Hm,Wm)
+    float32, the top's coordinate along e3 -- smaller is higher --, NaN: empty), ``culled`` ((Hm,Wm) int32, the samples culled per
+    cell) and ``surface_tol`` (= T, a float); ``surface_counts`` (int64 x 2, device) counts the culled samples and the samples with
+    a cell.  One buffer of 12 bytes per padded pixel of the largest batch is held."""
 
     def __init__(self, axes, gsd, device):
         _lib.load()
@@ -1201,6 +1225,7 @@ class Mosaic:
         self.feather = self.feather_counts = self._feather_buf = None
         self.fill_reach = self.fill_levels = self.pyramid = None
         self.bands = self.band_plan = self.acc_bands = self._band_bufs = None
+        self.surface = self.top = self.surface_counts = self._cull_buf = self._held = None
 
     def _images(self, views: list, Js: list):
         views, Js = list(views), list(Js)
@@ -1254,14 +1279,16 @@ class Mosaic:
         bits = np.where(k & 0x80000000, k & 0x7fffffff, ~k).astype(np.uint32)   # key_value of csrc/order_key.h
         return tuple(bits.view(np.float32).tolist())
 
-    def begin(self, bounds=None, blend=None, feather=None, bands=None):
+    def begin(self, bounds=None, blend=None, feather=None, bands=None, surface=None):
         """Fixes the grid and allocates; ``blend``: the blend depth H in metres (``MOSAIC_BLEND_RANGE``) -- a pixel whose range
         exceeds its cell's smallest one by d gets the weight ``max(1 - d / H, 0)^2`` -- or None for the best view alone;
         ``feather``: with a blend, the feather width F in source pixels (``MOSAIC_FEATHER_RANGE``), or None for none; ``bands``:
-        with a blend, the number K of detail bands of the multi-band blend (``MOSAIC_BANDS_RANGE``), or None for none."""
+        with a blend, the number K of detail bands of the multi-band blend (``MOSAIC_BANDS_RANGE``), or None for none;
+        ``surface``: the tolerance T in metres of the surface test (``MOSAIC_SURFACE_RANGE``), or None for none."""
         options = MosaicOptions(blend=blend, feather=feather).checked('Mosaic.begin')   # before anything is allocated
         blend, feather = options.blend, options.feather
         bands = mosaic_bands_checked(bands, blend, 'Mosaic.begin')
+        surface = None if surface is None else mosaic_surface_tol(surface)
         if bounds is None:
             bounds = self.bounds()
             if bounds is None:
@@ -1297,25 +1324,75 @@ class Mosaic:
             self.band_plan = mosaic_band_plan(blend, feather, bands)
             self.acc_bands = torch.zeros((bands + 1, Hm * Wm, _lib.MOSAIC_ACC_WORDS), dtype=torch.int64, device=dev)
             self._allocate('bands')
+        self.surface, self.top, self.surface_counts, self._cull_buf, self._held = surface, None, None, None, None
+        if surface is not None:
+            self.top = torch.full((Hm * Wm,), -1, dtype=torch.int32, device=dev)    # all ones: empty
+            self.surface_counts = torch.zeros(2, dtype=torch.int64, device=dev)
+            self._allocate('surface')
         return Hm, Wm
 
     def _begun(self, what: str) -> None:
         if self.grid is None:
             raise ValueError(f'Mosaic.{what}: begin() comes first (it fixes the grid)')
 
+    def _surfaced(self, what: str) -> None:
+        self._begun(what)
+        if self.surface is None:
+            raise ValueError(f'Mosaic.{what}: begin() was not given a surface tolerance, so there is no surface to test against')
+
+    def add_surface(self, views: list, Js: list, first_ordinal: int, plain_atomic: bool = False) -> None:
+        """Lowers ``top`` to the highest sample of every cell the images reach.  Over ALL the images, in any batches, after
+        ``begin`` and before ``splat``.  ``plain_atomic``: the atomic min for every pixel, without the load that filters them."""
+        self._surfaced('add_surface')
+        self._walk('sucre_mosaic_surface', self._images(views, Js), int(first_ordinal), C.byref(self.grid), self.top,
+                   _lib.MOSAIC_PLAIN_ATOMIC if plain_atomic else 0)
+
+    def culled_images(self, views: list, Js: list, first_ordinal: int, count: bool = False) -> list:
+        """The batch's ``Js`` as the phases after the surface test see them: per image an (H,W,3) float32 copy of ``J`` with NaN in
+        every channel of a pixel that does not take part or lies more than T below its cell's top (``sucre_mosaic_cull``).  Valid
+        once ``add_surface`` has seen every image.  The images are views into ONE transient buffer, sized to the largest batch
+        seen (12 bytes per pixel, every image rounded up to 256 pixels): the next call overwrites them.  ``count``: the culled
+        samples are added to ``culled`` and ``surface_counts`` -- to be asked for in one phase alone, so that every sample is
+        counted once (``splat`` does).  Only enqueues."""
+        self._surfaced('culled_images')
+        images = self._images(views, Js)
+        arr, n, _, _ = images
+        lib = _lib.load()
+        n_bytes = lib.sucre_mosaic_band_bytes(n, arr)
+        if n_bytes == 0:
+            raise _lib.SucreError(f'sucre_mosaic_band_bytes: {lib.sucre_last_error().decode()}')
+        if self._cull_buf is None or self._cull_buf.numel() * 4 < n_bytes:
+            self._cull_buf = torch.empty(n_bytes // 4, dtype=torch.float32, device=self.device)
+        buf = self._cull_buf
+        self._walk('sucre_mosaic_cull', images, int(first_ordinal), C.byref(self.grid), self.top, C.c_float(float(self.surface)), buf,
+                   self._out['culled'] if count else None, self.surface_counts if count else None)
+        out, at = [], 0
+        for e in arr:
+            out.append(buf[at * 3:(at + e.H * e.W) * 3].view(e.H, e.W, 3))
+            at += -(-(e.H * e.W) // _lib.MOSAIC_BLOCK_PX) * _lib.MOSAIC_BLOCK_PX
+        return out
+
+    def _phase_images(self, views: list, Js: list, first_ordinal: int, count: bool = False):
+        """``_images`` for a phase after the surface test: of the culled ``Js`` when a surface was begun (of the ones ``run`` holds
+        when a single batch is the whole request: culled once, the same bits)."""
+        if self.surface is None:
+            return self._images(views, Js)
+        return self._images(views, self.culled_images(views, Js, first_ordinal, count) if self._held is None else self._held)
+
     def splat(self, views: list, Js: list, first_ordinal: int, plain_atomic: bool = False) -> None:
         self._begun('splat')
-        self._walk('sucre_mosaic_splat', self._images(views, Js), int(first_ordinal), C.byref(self.grid), self.key,
-                   _lib.MOSAIC_PLAIN_ATOMIC if plain_atomic else 0)
+        self._walk('sucre_mosaic_splat', self._phase_images(views, Js, first_ordinal, count=True), int(first_ordinal), C.byref(self.grid),
+                   self.key, _lib.MOSAIC_PLAIN_ATOMIC if plain_atomic else 0)
 
     def resolve(self, views: list, Js: list, first_ordinal: int) -> None:
         self._begun('resolve')
-        self._walk('sucre_mosaic_resolve', self._images(views, Js), int(first_ordinal), C.byref(self.grid), self.key, self.pix)
+        self._walk('sucre_mosaic_resolve', self._phase_images(views, Js, first_ordinal), int(first_ordinal), C.byref(self.grid), self.key,
+                   self.pix)
 
     def gather(self, views: list, Js: list, first_ordinal: int) -> None:
         self._begun('gather')
-        self._walk('sucre_mosaic_gather', self._images(views, Js), int(first_ordinal), C.byref(self.grid), self.key, self.pix,
-                   *(self._out[k] for k in ('J', 'raw', 'source', 'pixel', 'range')))
+        self._walk('sucre_mosaic_gather', self._phase_images(views, Js, first_ordinal), int(first_ordinal), C.byref(self.grid), self.key,
+                   self.pix, *(self._out[k] for k in ('J', 'raw', 'source', 'pixel', 'range')))
 
     def _blending(self, what: str) -> None:
         self._begun(what)
@@ -1327,7 +1404,7 @@ class Mosaic:
         smallest range then).  ``plain``: eight atomics per pixel instead of eight per run of a wave's lanes (the same ``acc``).
         With a feather the batch's map is formed first (``sucre_mosaic_feather``) and the feathered phase reads it."""
         self._blending('accumulate')
-        images = self._images(views, Js)
+        images = self._phase_images(views, Js, first_ordinal)
         head = (int(first_ordinal), C.byref(self.grid), self.key, C.c_float(float(self.inv_h)))
         tail = (self.acc, _lib.MOSAIC_PLAIN_ATOMIC if plain else 0)
         if self.feather is None:
@@ -1434,7 +1511,7 @@ class Mosaic:
         at the user's F and from the true J, and every band reads it: ``dist2 = min(D2, F^2)`` tells ``dist2 >= F_j^2`` and holds
         every root below it for any ``F_j <= F``.  ``plain``: as ``accumulate``.  ``acc`` and ``feather_counts`` are not touched."""
         self._banding('accumulate_bands')
-        images = self._images(views, Js)
+        images = self._phase_images(views, Js, first_ordinal)
         self._band_bufs, first = self._band_buffers(images, self._band_bufs)
         if self.feather is not None:
             self._feather_buf, _ = self._feather_pass(images, self.feather, self._feather_buf)
@@ -1515,50 +1592,71 @@ class Mosaic:
         ``J_filled`` (Hm,Wm,3) float32 (NaN: still empty), ``raw_filled`` (Hm,Wm,3) uint8 (0), ``fill_level`` (Hm,Wm) int32 (-1)
         and, with a blend, ``J_blend_filled`` and ``raw_blend_filled``.  With a feather also ``feather``, the width F (an int).  With
         bands also ``J_multiband`` (Hm,Wm,3) float32 (NaN), complete once ``combine_bands`` has run, and ``bands``, the count K (an
-        int); after ``fill`` also ``J_multiband_filled``."""
+        int); after ``fill`` also ``J_multiband_filled``.  With a surface test also ``surface`` (Hm,Wm) float32 (NaN) -- the value of
+        ``top`` as it stands, complete once ``add_surface`` has seen every image --, ``culled`` (Hm,Wm) int32 (0), complete once
+        ``splat`` has, and ``surface_tol``, the tolerance T (a float, the float32 value)."""
         self._begun('result')
+        if self.surface is not None:   # key_value of csrc/order_key.h, per cell
+            k = self.top
+            bits = torch.where(k < 0, k & 0x7fffffff, ~k).view(torch.float32)
+            self._out['surface'].copy_(torch.where(k == -1, torch.full_like(bits, _NAN), bits).view(self.Hm, self.Wm))
         def of(*groups):
             return {key: t for key, t in self._out.items() if MOSAIC_OUTPUTS[key][0] in groups}
-        return {**of('best', 'blend', 'bands'), **({} if self.feather is None else {'feather': self.feather}),
-                **({} if self.bands is None else {'bands': self.bands}), **of('fill', 'blend_fill', 'bands_fill')}
+        return {**of('best', 'blend', 'bands', 'surface'), **({} if self.feather is None else {'feather': self.feather}),
+                **({} if self.bands is None else {'bands': self.bands}),
+                **({} if self.surface is None else {'surface_tol': float(self.surface)}), **of('fill', 'blend_fill', 'bands_fill')}
 
-    def run(self, batches, options: MosaicOptions = MosaicOptions(), bounds=None, plain_atomic: bool = False, bands=None) -> 'Mosaic':
-        """Every phase over every batch, in the one order there is: the bounds (unless ``bounds`` is given), ``begin``, ``splat``,
+    def run(self, batches, options: MosaicOptions = MosaicOptions(), bounds=None, plain_atomic: bool = False, bands=None,
+            surface=None) -> 'Mosaic':
+        """Every phase over every batch, in the one order there is: the bounds (unless ``bounds`` is given), ``begin``; with
+        ``surface`` (the tolerance T of the surface test, beside the options record) ``add_surface``; ``splat``,
         ``resolve`` and ``gather``; with a blend ``accumulate`` and then ``normalize``; with ``bands`` (the count K of a multi-band
         blend, beside the options record; only with a blend) ``accumulate_bands`` and then ``combine_bands``; with a fill ``fill``.  ``batches``: a
         sequence of ``(first_ordinal, load)``, ``load()`` returning the batch's ``(views, Js)`` -- called once per phase, so a
         caller may hold only some of the images at a time; ``options``: as ``MosaicOptions.checked`` returns them;
-        ``plain_atomic``: both the splat and the accumulate phase in their plain forms.  Returns the mosaic."""
+        ``plain_atomic``: the surface, the splat and the accumulate phase in their plain forms.  With a surface test every phase
+        culls its batch anew, unless one batch is the whole request: that one is culled once.  Returns the mosaic."""
         batches = list(batches)
         if bounds is None:
             for _, load in batches:
                 self.add_bounds(*load())
         bands = mosaic_bands_checked(bands, options.blend, 'Mosaic.run')
-        self.begin(bounds, blend=options.blend, feather=options.feather, **({} if bands is None else {'bands': bands}))
-        phases = [(self.splat, {'plain_atomic': plain_atomic}), (self.resolve, {}), (self.gather, {})]
-        if options.blend is not None:
-            phases.append((self.accumulate, {'plain': plain_atomic}))
-        for phase, kw in phases:
+        self.begin(bounds, blend=options.blend, feather=options.feather, **({} if bands is None else {'bands': bands}),
+                   **({} if surface is None else {'surface': surface}))
+        if surface is not None:
             for first, load in batches:
-                phase(*load(), first, **kw)
-        if options.blend is not None:
-            self.normalize()
-        if bands is not None:
-            for first, load in batches:
-                self.accumulate_bands(*load(), first, plain=plain_atomic)
-            self.combine_bands()
+                self.add_surface(*load(), first, plain_atomic=plain_atomic)
+            if len(batches) == 1:
+                first, load = batches[0]
+                self._held = self.culled_images(*load(), first, count=True)
+        try:
+            phases = [(self.splat, {'plain_atomic': plain_atomic}), (self.resolve, {}), (self.gather, {})]
+            if options.blend is not None:
+                phases.append((self.accumulate, {'plain': plain_atomic}))
+            for phase, kw in phases:
+                for first, load in batches:
+                    phase(*load(), first, **kw)
+            if options.blend is not None:
+                self.normalize()
+            if bands is not None:
+                for first, load in batches:
+                    self.accumulate_bands(*load(), first, plain=plain_atomic)
+                self.combine_bands()
+        finally:
+            self._held = None
         if options.fill is not None:
             self.fill(options.fill)
         return self
 
 
 def mosaic_of(views: list, Js: list, axes, gsd, bounds=None, batch: int = 32, plain_atomic: bool = False, blend=None,
-              fill=None, feather=None, bands=None) -> 'Mosaic':
+              fill=None, feather=None, bands=None, surface=None) -> 'Mosaic':
     """``Mosaic.run`` over device-resident ``views`` / ``Js`` (ordinal = position in the list), ``batch`` images per call; with
     ``blend`` (the blend depth H, metres) the accumulate phase and the normalise pass after them (``plain_atomic``: both the
     splat and the accumulate phase in their plain forms), with ``feather`` (the width F, source pixels; only with ``blend``) the
     feathered one; with ``bands`` (the count K of detail bands; only with ``blend``) the multi-band blend after them; with ``fill``
-    (the reach R, metres) the hole filling after all of them (``MosaicOptions``)."""
+    (the reach R, metres) the hole filling after all of them (``MosaicOptions``); with ``surface`` (the tolerance T, metres) the
+    surface test ahead of the splat (csrc/surface.h)."""
     views, Js = list(views), list(Js)
     if not views:
         raise ValueError('mosaic_of: no view')
@@ -1566,8 +1664,10 @@ def mosaic_of(views: list, Js: list, axes, gsd, bounds=None, batch: int = 32, pl
         raise ValueError(f'mosaic_of: {len(views)} images, at most {MAX_VIEWS}')
     options = MosaicOptions(blend=blend, feather=feather, fill=fill).checked('mosaic_of')   # before anything is allocated
     bands = mosaic_bands_checked(bands, options.blend, 'mosaic_of')
+    surface = None if surface is None else mosaic_surface_tol(surface)
     batches = [(i, lambda i=i: (views[i:i + batch], Js[i:i + batch])) for i in range(0, len(views), batch)]
-    return Mosaic(axes, gsd, views[0].depth.device).run(batches, options, bounds, plain_atomic, **({} if bands is None else {'bands': bands}))
+    return Mosaic(axes, gsd, views[0].depth.device).run(batches, options, bounds, plain_atomic, **({} if bands is None else {'bands': bands}),
+                                                        **({} if surface is None else {'surface': surface}))
 
 
 def device_views_from_scene(scene, device='cuda') -> list[DeviceView]:

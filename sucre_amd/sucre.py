@@ -1384,6 +1384,25 @@ def mosaic_fill_mask(level: np.ndarray) -> np.ndarray:
     return np.where(level == 0, 255, np.where(level > 0, 128, 0)).astype(np.uint8)
 
 
+def mosaic_surface_picture(surface: np.ndarray) -> np.ndarray:
+    """(Hm,Wm) uint8 of a mosaic's ``surface``: a filled cell (no NaN) gets ``1 + rint(254 (smax - s) / (smax - smin))`` in float64
+    over the filled cells -- the highest ground, the smallest coordinate along the view axis, is white --, 255 when the surface is
+    flat; an empty cell 0."""
+    s = np.asarray(surface, dtype=np.float64)
+    filled = ~np.isnan(s)
+    out = np.zeros(s.shape, np.uint8)
+    if filled.any():
+        smin, smax = s[filled].min(), s[filled].max()
+        out[filled] = 255 if smax == smin else (1 + np.rint(254.0 * (smax - s[filled]) / (smax - smin))).astype(np.uint8)
+    return out
+
+
+def mosaic_culled_picture(culled: np.ndarray) -> np.ndarray:
+    """(Hm,Wm) uint8 of a mosaic's ``culled``: ``255 culled // max(1, culled.max())``."""
+    c = np.asarray(culled).astype(np.int64)
+    return (255 * c // max(1, int(c.max(initial=0)))).astype(np.uint8)
+
+
 def _mosaic_picture(J: Tensor, stretch) -> np.ndarray:
     """(Hm,Wm,3) uint8 of a mosaic's ``J`` on the device: the fixed ``stretch`` when given, ``plot_J``'s own percentiles over the
     filled cells otherwise."""
@@ -1405,7 +1424,7 @@ def _mosaic_picture(J: Tensor, stretch) -> np.ndarray:
 
 
 _MOSAIC_FLAG = {'grid': '--mosaic', 'blend': '--mosaic-blend', 'fill': '--mosaic-fill', 'feather': '--mosaic-feather',
-                'bands': '--mosaic-bands'}
+                'bands': '--mosaic-bands', 'surface': '--mosaic-surface'}
 
 
 def _mosaic_refused(e: ValueError, fields=tuple(_MOSAIC_FLAG)) -> BaseException:
@@ -1419,12 +1438,14 @@ _MOSAIC_PNG = {   # how a row of engine.MOSAIC_OUTPUTS becomes its PNG: (the out
     'bytes': lambda t, stretch: t.cpu().numpy(),
     'source': lambda t, stretch: mosaic_source_picture(t.cpu().numpy()),
     'mask': lambda t, stretch: mosaic_fill_mask(t.cpu().numpy()),
+    'height': lambda t, stretch: mosaic_surface_picture(t.cpu().numpy()),
+    'count': lambda t, stretch: mosaic_culled_picture(t.cpu().numpy()),
 }
 
 
 def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, output_dir: Path, gsd: float | None = None, axes=None,
            stretch=None, device: str = 'cuda', blend: float | None = None, fill: float | None = None, feather: int | None = None,
-           bands: int | None = None) -> dict:
+           bands: int | None = None, surface: float | None = None) -> dict:
     """One picture of the seabed from a finished restoration: every pixel of ``images`` (``sfm.Image`` objects or names of
     ``colmap_model``; at most ``engine.MAX_VIEWS``, ordinal = position) with a valid depth and a restored colour --
     ``results_dir / <name>.pt``, key ``J`` -- is dropped onto the plane grid ``axes`` (``mosaic_axes`` unless given) of ``gsd``
@@ -1468,7 +1489,17 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
     (``J_multiband`` through the function that makes ``mosaic.png``) comes next to them -- with a fill also
     ``mosaic_multiband_filled.png`` --, ``mosaic.pt`` gains ``J_multiband`` (``J_multiband_filled``), ``bands`` and ``band_plan``,
     the list of ``(H_j, F_j)``, and one more line is printed after the blend's and the feather's.  Not built: a multi-band raw
-    mosaic."""
+    mosaic.
+
+    ``surface``: a tolerance T in metres (``engine.MOSAIC_SURFACE_RANGE``) of a surface test ahead of every phase above
+    (csrc/surface.h).  One more pass over the batches finds, per cell, the highest sample along the mosaic's view axis ``e3`` -- the
+    smallest ``e3 . wP`` --, and a sample that lies more than T below its cell's top takes part in nothing: the lower of two
+    surfaces no longer wins a cell because a camera is close to it, and the blend no longer mixes two layers.  The grid and the set
+    of filled cells are those of a run without the flag, and a T that culls nothing leaves every file and key above as it is, byte
+    for byte.  ``mosaic_surface.png`` (``mosaic_surface_picture``: the height, highest ground white) and ``mosaic_culled.png``
+    (``mosaic_culled_picture``) come next to the other files, ``mosaic.pt`` gains ``surface``, ``culled`` and ``surface_tol``, and one
+    more line is printed after the mosaic's.  The surface is a plain minimum: one spurious high sample owns its cell.  Not built: a
+    robust (median) surface."""
     from . import engine
     sfm.require_gpu(device, 'mosaic')
     images = [colmap_model[im] if isinstance(im, str) else im for im in images]
@@ -1491,6 +1522,10 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
         raise _mosaic_refused(e)
     if bands is not None and blend is None:
         raise SystemExit('--mosaic-bands: only with --mosaic-blend H')
+    try:
+        surface = None if surface is None else engine.mosaic_surface_tol(surface)
+    except ValueError as e:
+        raise _mosaic_refused(e)
     results_dir, output_dir = Path(results_dir), Path(output_dir)
     for image in images:   # before anything is decoded
         path = _consistency_file(results_dir, image)
@@ -1522,7 +1557,8 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
             print(f'--mosaic: ground sample distance {float(gsd):.6g} m (twice the median pixel footprint; --mosaic-gsd sets it).')
         try:
             m = engine.Mosaic(axes, gsd, device).run([(first, lambda batch=batch: resident(batch)) for first, batch in batches], options,
-                                                     **({} if bands is None else {'bands': bands}))
+                                                     **({} if bands is None else {'bands': bands}),
+                                                     **({} if surface is None else {'surface': surface}))
         except ValueError as e:
             # Two refusals of the run belong to a flag: begin's of the grid (--mosaic) and normalize's of a cell's sample count
             # (--mosaic-blend).  The options were checked above, so begin and fill have nothing left to refuse in them; every other
@@ -1532,6 +1568,7 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
         pictures = [(png, _MOSAIC_PNG[how](out[key], stretch)) for key, (_, _, _, _, png, how) in engine.MOSAIC_OUTPUTS.items()
                     if png is not None and key in out]
         out = {k: v.cpu() if torch.is_tensor(v) else v for k, v in out.items()}
+        surface_counts = None if surface is None else [int(x) for x in m.surface_counts.cpu()]
     Hm, Wm = m.Hm, m.Wm
     source = out['source']
     filled = source >= 0
@@ -1552,6 +1589,13 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
     print(f'mosaic of {len(images)} images: {Wm} x {Hm} cells of {float(m.gsd):.6g} m, {n_filled} filled '
           f'({100.0 * n_filled / n_cells:.1f} %), {n_cells - n_filled} empty; largest share {images[top].name} '
           f'({100.0 * int(per_image[top]) / max(1, n_filled):.1f} %)')
+    if surface is not None:
+        tops = out['surface'][filled]
+        s0, s1 = (float(tops.min()), float(tops.max())) if n_filled else (0.0, 0.0)
+        gone, part = surface_counts
+        print(f'mosaic surface of {float(surface):.6g} m: top between {s0:.6g} and {s1:.6g} m along the view axis; {gone} of {part} samples '
+              f'({100.0 * gone / max(1, part):.1f} %) lie more than {float(surface):.6g} m below their cell\'s top, in '
+              f'{int((out["culled"] > 0).sum())} cells')
     if blend is not None:
         samples = out['samples'].to(torch.int64)
         total, most, several = int(samples.sum()), int(samples.max()), int((samples > 1).sum())
@@ -1615,7 +1659,7 @@ _MODE_REFUSES = {   # mode -> (flag, why), in the order they are looked at
 
 _ONLY_WITH = [   # (flag, the flag it needs, that one's value), in the order they are looked at
     ('--mosaic-gsd', '--mosaic', 'DIR'), ('--mosaic-blend', '--mosaic', 'DIR'), ('--mosaic-fill', '--mosaic', 'DIR'),
-    ('--mosaic-feather', '--mosaic-blend', 'H'), ('--mosaic-bands', '--mosaic-blend', 'H'),
+    ('--mosaic-feather', '--mosaic-blend', 'H'), ('--mosaic-bands', '--mosaic-blend', 'H'), ('--mosaic-surface', '--mosaic', 'DIR'),
 ]
 
 
@@ -1634,8 +1678,8 @@ def _refuse_mode_flags(args, mode: str) -> None:
 
 
 def _refuse_mosaic_values(args, world: int = 1) -> None:
-    """The values of --mosaic-gsd, --mosaic-blend, --mosaic-fill, --mosaic-feather and --mosaic-bands and the world size a mosaic
-    takes, refused before any file is opened."""
+    """The values of --mosaic-gsd, --mosaic-blend, --mosaic-fill, --mosaic-feather, --mosaic-bands and --mosaic-surface and the
+    world size a mosaic takes, refused before any file is opened."""
     gsd = getattr(args, 'mosaic_gsd', None)
     if gsd is not None and not (np.isfinite(gsd) and gsd > 0):
         raise SystemExit(f'--mosaic-gsd: G must be a finite size > 0 in metres, not {gsd}')
@@ -1649,6 +1693,10 @@ def _refuse_mosaic_values(args, world: int = 1) -> None:
     lo, hi = engine.MOSAIC_BANDS_RANGE
     if bands is not None and not (np.isfinite(bands) and lo <= bands <= hi and bands == int(bands)):
         raise SystemExit(f'{_MOSAIC_FLAG["bands"]}: K must be an integer within [{lo:g}, {hi:g}] bands, not {bands:g}')
+    tol = getattr(args, 'mosaic_surface', None)
+    lo, hi = engine.MOSAIC_SURFACE_RANGE
+    if tol is not None and not (np.isfinite(tol) and lo <= tol <= hi):
+        raise SystemExit(f'{_MOSAIC_FLAG["surface"]}: T must be a finite tolerance within [{lo:g}, {hi:g}] metres, not {tol}')
     if world > 1:
         raise SystemExit(f'--mosaic: a world size of {world} is not supported yet: the four phases are separate entries of the library '
                          f'so that ranks can all-reduce bounds, keys and pixel words between them, but that all-reduce is not built; '
@@ -1760,7 +1808,8 @@ def parse_args(args: argparse.Namespace):
         if mosaic_dir is not None:
             mosaic(images, colmap_model, mosaic_dir, args.output_dir, gsd=getattr(args, 'mosaic_gsd', None), stretch=stretch, device=device,
                    blend=getattr(args, 'mosaic_blend', None), fill=getattr(args, 'mosaic_fill', None),
-                   feather=getattr(args, 'mosaic_feather', None), bands=getattr(args, 'mosaic_bands', None))
+                   feather=getattr(args, 'mosaic_feather', None), bands=getattr(args, 'mosaic_bands', None),
+                   surface=getattr(args, 'mosaic_surface', None))
         elif check is not None:
             if world > 1:   # the targets' records are gathered on rank 0
                 sdist.init_process_group()
@@ -2025,6 +2074,12 @@ def build_parser() -> argparse.ArgumentParser:
                                'blend with the detail of the best view; writes mosaic_multiband.png (with --mosaic-fill also '
                                'mosaic_multiband_filled.png) next to the other files, which stay as they are, adds J_multiband, bands and '
                                'band_plan to mosaic.pt and prints one more line')
+    p.extras.add_argument('--mosaic-surface', type=float, metavar='T', default=argparse.SUPPRESS,
+                          help='with --mosaic: also a surface test -- per cell the highest sample along the mosaic\'s view axis is found '
+                               'first, and a sample that lies more than T metres below its cell\'s top takes part in nothing, so the lower '
+                               'of two surfaces neither wins a cell nor is blended into it; the grid and the filled cells stay those of a '
+                               'run without the flag; writes mosaic_surface.png (the height, highest ground white) and mosaic_culled.png '
+                               'next to the other files, adds surface, culled and surface_tol to mosaic.pt and prints one more line')
     p.extras.add_argument('--common-stretch', action='store_true', default=argparse.SUPPRESS,
                           help='with --shared-water or --apply-water: stretch every <stem>_rgb.png between the SAME per-channel 1st '
                                'and 99th percentile, those of the valid pixels of all images of the request pooled (all ranks), '
