@@ -712,8 +712,28 @@ int sucre_view_consistency(int H, int W, int n_views, const sucre_view_t *target
  *                         NULL): adds the culled samples and the samples with a cell.  Only enqueues
  * Checked before any launch as above, and: a NULL or misaligned top_dev or J_out, a misaligned culled_dev or counts_dev, tol not
  * finite or <= 0, a J_out that overlaps an image's J, unknown flags.
+ *
+ * The supported surface (csrc/support.h): the top above is a plain minimum, so one spurious high sample owns its cell.  Here the top
+ * of a cell is the highest level that at least M different images reach.  key64 = (uint64)k << 32 | ordinal, k as above; level 0 of
+ * a cell is the smallest key64 of its samples, level r the smallest among the samples whose ordinal is not the low word of one of
+ * its levels 0..r-1 (a view listed twice has two ordinals and counts twice; a height tie goes to the earlier image); a level that
+ * finds no sample stays all ones.  With n the levels of a cell that hold something and m = min(n_levels, n): top = the high word
+ * of level m-1 (all ones for n = 0), support = n, source = the low word of level m-1 (-1 for n = 0): a cell that fewer than
+ * n_levels images see rests on the lowest of its per-image tops.
+ *   sucre_mosaic_support         level `level` of rank_dev ((n_levels, Hm Wm) uint64; the caller starts it at all ones): one pass
+ *                                over ALL images, any split into calls, after level - 1 has seen them all.  flags:
+ *                                SUCRE_MOSAIC_PLAIN_ATOMIC -- the atomic min for every pixel (the same rank_dev)
+ *   sucre_mosaic_support_top     top_dev (uint32, the key format of sucre_mosaic_surface), support_out and source_out (int32, or
+ *                                NULL) of every cell from its n_levels words; reads no image
+ *   sucre_mosaic_cull_supported  sucre_mosaic_cull with a second side: with d = a_n - top (one float32 subtraction) a sample is
+ *                                culled below when d > tol and above when d < -tol; J_out as there.  culled_dev counts the
+ *                                samples culled below per cell, culled_above_dev those culled above (uint32, or NULL);
+ *                                counts_dev (uint64 x 3, or NULL): culled below, culled above, samples with a cell
+ * All three only enqueue.  Checked before any launch as above, and: n_levels outside 1..SUCRE_MOSAIC_SUPPORT_MAX, level outside
+ * 0..n_levels-1, a NULL or misaligned rank_dev or top_dev, misaligned support_out, source_out, culled_above_dev, Hm Wm above 2^39.
  */
 #define SUCRE_MOSAIC_PLAIN_ATOMIC 1u
+#define SUCRE_MOSAIC_SUPPORT_MAX 4
 #define SUCRE_MOSAIC_ACC_WORDS 8
 #define SUCRE_MOSAIC_FEATHER_MAX 1024
 #define SUCRE_MOSAIC_BANDS_MAX 6
@@ -760,6 +780,13 @@ int sucre_mosaic_surface(void *table_dev, int n_images, const sucre_mosaic_image
 int sucre_mosaic_cull(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
                       const sucre_mosaic_grid_t *grid, const uint32_t *top_dev, float tol, float *J_out, uint32_t *culled_dev,
                       uint64_t *counts_dev, void *stream);
+int sucre_mosaic_support(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                         const sucre_mosaic_grid_t *grid, int n_levels, int level, uint64_t *rank_dev, unsigned flags, void *stream);
+int sucre_mosaic_support_top(const sucre_mosaic_grid_t *grid, int n_levels, const uint64_t *rank_dev, uint32_t *top_dev,
+                             int32_t *support_out, int32_t *source_out, void *stream);
+int sucre_mosaic_cull_supported(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                                const sucre_mosaic_grid_t *grid, const uint32_t *top_dev, float tol, float *J_out,
+                                uint32_t *culled_dev, uint32_t *culled_above_dev, uint64_t *counts_dev, void *stream);
 
 /*
  * ---- hole filling of the finished mosaic: a bounded push-pull over a pyramid of the grid ------------------------------------------

@@ -177,6 +177,10 @@ SIGNATURES = {
     'sucre_mosaic_band_combine': (_i, [C.POINTER(MosaicGrid), _i, _vp, _vp, _vp]),
     'sucre_mosaic_surface': (_i, [_vp, _i, C.POINTER(MosaicImage), _i, C.POINTER(MosaicGrid), _vp, C.c_uint, _vp]),
     'sucre_mosaic_cull': (_i, [_vp, _i, C.POINTER(MosaicImage), _i, C.POINTER(MosaicGrid), _vp, C.c_float, _vp, _vp, _vp, _vp]),
+    'sucre_mosaic_support': (_i, [_vp, _i, C.POINTER(MosaicImage), _i, C.POINTER(MosaicGrid), _i, _i, _vp, C.c_uint, _vp]),
+    'sucre_mosaic_support_top': (_i, [C.POINTER(MosaicGrid), _i, _vp, _vp, _vp, _vp, _vp]),
+    'sucre_mosaic_cull_supported': (_i, [_vp, _i, C.POINTER(MosaicImage), _i, C.POINTER(MosaicGrid), _vp, C.c_float, _vp, _vp, _vp, _vp,
+                                         _vp]),
     'sucre_mosaic_fill_bytes': (C.c_size_t, [_i, _i, _i]),
     'sucre_mosaic_fill_pull': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'sucre_mosaic_fill_push': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

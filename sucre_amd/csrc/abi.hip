@@ -14,6 +14,7 @@
 #include "bands.h"
 #include "pool.h"
 #include "surface.h"
+#include "support.h"
 
 namespace sucre {
 
@@ -1151,6 +1152,63 @@ int sucre_mosaic_cull(void *table_dev, int n_images, const sucre_mosaic_image_t 
     const MosaicCull out = {culled_dev, reinterpret_cast<unsigned long long *>(counts_dev)};
     return check_hip(launch_mosaic_cull(table_dev, n_images, images, first_ordinal, g, top_dev, tol, J_out, out,
                                         static_cast<hipStream_t>(stream)), "sucre_mosaic_cull");
+}
+
+/* ---- view-supported surface: per-cell ranks of the per-image tops, the supported top, the two-sided cull (support.h) ---- */
+
+static int check_support_levels(int n_levels, const MosaicGrid &g) {
+    if (n_levels < 1 || n_levels > kSupportMax) return fail(SUCRE_ERR_ARG, "n_levels=%d outside [1,%d]", n_levels, kSupportMax);
+    if ((uint64_t)g.Hm * (uint64_t)g.Wm > (1ull << 39)) return fail(SUCRE_ERR_ARG, "mosaic of %dx%d cells: one pass takes 2^39 cells", g.Wm, g.Hm);
+    return SUCRE_OK;
+}
+
+int sucre_mosaic_support(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                         const sucre_mosaic_grid_t *grid, int n_levels, int level, uint64_t *rank_dev, unsigned flags, void *stream) {
+    if (int rc = check_mosaic_images(table_dev, n_images, images, first_ordinal)) return rc;
+    MosaicGrid g;
+    if (int rc = check_mosaic_grid(grid, &g)) return rc;
+    if (int rc = check_support_levels(n_levels, g)) return rc;
+    if (level < 0 || level >= n_levels) return fail(SUCRE_ERR_ARG, "level=%d outside [0,%d)", level, n_levels);
+    if (!rank_dev || !aligned(rank_dev, 8)) return fail(SUCRE_ERR_ARG, "rank_dev is NULL or not 8-byte aligned");
+    if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
+    return check_hip(launch_mosaic_support((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) != 0, table_dev, n_images, images, first_ordinal, g, level,
+                                           reinterpret_cast<unsigned long long *>(rank_dev), static_cast<hipStream_t>(stream)),
+                     "sucre_mosaic_support");
+}
+
+int sucre_mosaic_support_top(const sucre_mosaic_grid_t *grid, int n_levels, const uint64_t *rank_dev, uint32_t *top_dev,
+                             int32_t *support_out, int32_t *source_out, void *stream) {
+    MosaicGrid g;
+    if (int rc = check_mosaic_grid(grid, &g)) return rc;
+    if (int rc = check_support_levels(n_levels, g)) return rc;
+    if (!rank_dev || !aligned(rank_dev, 8)) return fail(SUCRE_ERR_ARG, "rank_dev is NULL or not 8-byte aligned");
+    if (!top_dev || !aligned(top_dev, 4)) return fail(SUCRE_ERR_ARG, "top_dev is NULL or not 4-byte aligned");
+    if (!aligned(support_out, 4) || !aligned(source_out, 4)) return fail(SUCRE_ERR_ARG, "support_out / source_out must be 4-byte aligned");
+    return check_hip(launch_mosaic_support_top(g, n_levels, reinterpret_cast<const unsigned long long *>(rank_dev), top_dev, support_out,
+                                               source_out, static_cast<hipStream_t>(stream)), "sucre_mosaic_support_top");
+}
+
+int sucre_mosaic_cull_supported(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                                const sucre_mosaic_grid_t *grid, const uint32_t *top_dev, float tol, float *J_out,
+                                uint32_t *culled_dev, uint32_t *culled_above_dev, uint64_t *counts_dev, void *stream) {
+    if (int rc = check_mosaic_images(table_dev, n_images, images, first_ordinal)) return rc;
+    MosaicGrid g;
+    if (int rc = check_mosaic_grid(grid, &g)) return rc;
+    if (!top_dev || !aligned(top_dev, 4)) return fail(SUCRE_ERR_ARG, "top_dev is NULL or not 4-byte aligned");
+    if (!std::isfinite(tol) || !(tol > 0.0f)) return fail(SUCRE_ERR_ARG, "tol=%g must be finite and > 0", (double)tol);
+    if (!J_out || !aligned(J_out, 4)) return fail(SUCRE_ERR_ARG, "J_out is NULL or not 4-byte aligned");
+    if (culled_dev && !aligned(culled_dev, 4)) return fail(SUCRE_ERR_ARG, "culled_dev is not 4-byte aligned");
+    if (culled_above_dev && !aligned(culled_above_dev, 4)) return fail(SUCRE_ERR_ARG, "culled_above_dev is not 4-byte aligned");
+    if (counts_dev && !aligned(counts_dev, 8)) return fail(SUCRE_ERR_ARG, "counts_dev is not 8-byte aligned");
+    // J_out is a buffer of its own, as sucre_mosaic_cull's
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(J_out), o1 = o0 + band_bytes(n_images, images);
+    for (int i = 0; i < n_images; ++i) {
+        const uintptr_t j0 = reinterpret_cast<uintptr_t>(images[i].J), j1 = j0 + (size_t)images[i].H * (size_t)images[i].W * 12;
+        if (j0 < o1 && o0 < j1) return fail(SUCRE_ERR_ARG, "image %d: J_out overlaps the image's J", i);
+    }
+    const MosaicCullSupported out = {culled_dev, culled_above_dev, reinterpret_cast<unsigned long long *>(counts_dev)};
+    return check_hip(launch_mosaic_cull_supported(table_dev, n_images, images, first_ordinal, g, top_dev, tol, J_out, out,
+                                                  static_cast<hipStream_t>(stream)), "sucre_mosaic_cull_supported");
 }
 
 /* ---- hole filling of the finished mosaic: a bounded push-pull over a pyramid of the grid (fill.h) ---- */

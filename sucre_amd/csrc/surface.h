@@ -21,7 +21,8 @@
 //   - A T that culls nothing leaves every output of the other phases identical bit for bit (the copy IS J at the members).
 // The feather then fades towards a culled region as it does towards a NaN patch: it is a seam.
 // THE SURFACE IS A PLAIN MINIMUM: one spurious high sample -- a fish, a bad depth -- owns its cell and culls the seabed under it
-// (the best view has the same weakness with the nearest sample).  Not built: a robust (median) surface.
+// (the best view has the same weakness with the nearest sample).  The remedy is support.h: the top that M different images reach,
+// and a cull on both sides of it; this file's two kernels stay as they are, and its M = 1 is this surface bit for bit.
 //
 // surface  the walk of mosaic.h (one lane per pixel, 32 images per launch): atomicMin(top[cell], order_key(a_n)), uint32 per cell,
 //          empty: all ones.  Unless SUCRE_MOSAIC_PLAIN_ATOMIC is given, top[cell] is loaded first and the atomic skipped when the

@@ -985,7 +985,8 @@ def mosaic_max_cells() -> int:
     19 for its three outputs and up to 11 for the pyramid, 32-byte records on a third as many cells -- 49 with a blend, whose two
     filled outputs take 15 and whose own levels 4; a multi-band blend of K bands adds 64 (K + 1) + 12: its K + 1 accumulators and
     ``J_multiband`` -- and 19 more with a fill, ``J_multiband_filled`` and the pass's levels and dropped raw picture; a surface test
-    adds 12: the ``top`` word, ``surface`` and ``culled``)."""
+    adds 12: the ``top`` word, ``surface`` and ``culled``; a support of M views 8 M + 16 more: the ``rank`` words, ``support``,
+    ``surface_source``, ``culled_above`` and ``surface_top``)."""
     return int(os.environ.get('SUCRE_MOSAIC_MAX_CELLS', 1 << 27))
 
 
@@ -1015,6 +1016,10 @@ _MOSAIC_BANDS = ('band count K', MOSAIC_BANDS_RANGE, True, 'bands', int)   # a r
 
 MOSAIC_SURFACE_RANGE = (1e-6, 1e6)   # surface tolerances T a mosaic takes, metres (csrc/surface.h)
 _MOSAIC_SURFACE = ('surface tolerance T', MOSAIC_SURFACE_RANGE, False, 'metres', np.float32)   # beside the record, as the band count
+
+
+MOSAIC_SUPPORT_RANGE = (1, 4)   # views M whose agreement a supported surface asks for (csrc/support.h)
+_MOSAIC_SUPPORT = ('supporting views M', MOSAIC_SUPPORT_RANGE, True, 'views', int)   # beside the record, as the surface tolerance
 
 
 def _mosaic_value(field: str, value, row=None):
@@ -1064,6 +1069,24 @@ def mosaic_surface_tol(surface) -> np.float32:
     """``surface`` as the float32 tolerance T of the surface test in metres, or ValueError (``field``: 'surface') unless it is finite
     and within ``MOSAIC_SURFACE_RANGE``."""
     return _mosaic_value('surface', surface, _MOSAIC_SURFACE)
+
+
+def mosaic_support_views(support) -> int:
+    """``support`` as the number M of views a supported surface rests on, or ValueError (``field``: 'support') unless it is an
+    integral number, no bool, within ``MOSAIC_SUPPORT_RANGE``."""
+    return _mosaic_value('support', support, _MOSAIC_SUPPORT)
+
+
+def mosaic_support_checked(support, surface, who: str):
+    """None, or M as ``mosaic_support_views`` returns it; ValueError (``field``: 'support') for a support without a surface
+    tolerance, in the name of ``who``."""
+    if support is None:
+        return None
+    support = mosaic_support_views(support)
+    if surface is None:
+        raise _mosaic_refusal('support', f'{who}: the support decides which top the surface test measures against; give the '
+                                         f'tolerance too (surface=T)')
+    return support
 
 
 def mosaic_bands_checked(bands, blend, who: str):
@@ -1127,8 +1150,9 @@ def mosaic_cells(lo: float, hi: float, gsd: float) -> int:
 _NAN = float('nan')
 MOSAIC_OUTPUTS = {   # key of Mosaic.result() -> (group, trailing shape, dtype, value of an empty cell, PNG of --mosaic, how it is made)
     # groups: 'best' (the best view; begin), 'blend' (begin with a blend), 'bands' (begin with bands), 'fill' (fill), 'blend_fill'
-    # (fill with a blend), 'bands_fill' (fill with bands).  An empty value of None: the kernel writes every cell.  How: 'stretch'
-    # (sucre._mosaic_picture), 'bytes', 'source', 'mask'.
+    # (fill with a blend), 'bands_fill' (fill with bands), 'surface' (begin with a surface tolerance), 'support' (begin with a
+    # support; the last rows: older rows keep their places).  An empty value of None: the kernel writes every cell.  How: 'stretch'
+    # (sucre._mosaic_picture), 'bytes', 'source', 'mask', 'height', 'count'.
     'J': ('best', (3,), torch.float32, _NAN, 'mosaic.png', 'stretch'),
     'raw': ('best', (3,), torch.uint8, 0, 'mosaic_raw.png', 'bytes'),
     'source': ('best', (), torch.int32, -1, 'mosaic_source.png', 'source'),
@@ -1147,6 +1171,10 @@ MOSAIC_OUTPUTS = {   # key of Mosaic.result() -> (group, trailing shape, dtype, 
     'J_blend_filled': ('blend_fill', (3,), torch.float32, None, 'mosaic_blend_filled.png', 'stretch'),
     'raw_blend_filled': ('blend_fill', (3,), torch.uint8, None, 'mosaic_blend_raw_filled.png', 'bytes'),
     'J_multiband_filled': ('bands_fill', (3,), torch.float32, None, 'mosaic_multiband_filled.png', 'stretch'),
+    'support': ('support', (), torch.int32, 0, None, None),
+    'surface_source': ('support', (), torch.int32, -1, None, None),
+    'culled_above': ('support', (), torch.int32, 0, 'mosaic_culled_above.png', 'count'),
+    'surface_top': ('support', (), torch.float32, _NAN, None, None),
 }
 
 
@@ -1198,7 +1226,20 @@ class Mosaic:
     all the pixels that take part, and the set of filled cells does not change.  ``result()`` then holds ``surface`` ((Hm,Wm)
     float32, the top's coordinate along e3 -- smaller is higher --, NaN: empty), ``culled`` ((Hm,Wm) int32, the samples culled per
     cell) and ``surface_tol`` (= T, a float); ``surface_counts`` (int64 x 2, device) counts the culled samples and the samples with
-    a cell.  One buffer of 12 bytes per padded pixel of the largest batch is held."""
+    a cell.  One buffer of 12 bytes per padded pixel of the largest batch is held.
+
+    The supported surface: ``begin(surface=T, support=M)`` -- M views (``MOSAIC_SUPPORT_RANGE``; csrc/support.h).  The plain
+    minimum lets one spurious high sample of one image own its cell; with a support the top of a cell is the highest level that M
+    different images reach (a view listed twice has two ordinals and counts twice), a cell seen by fewer than M images rests on the
+    lowest of its per-image tops, and a sample more than T ABOVE the top is culled like one more than T below it.  ``rank``
+    ((M, Hm Wm) int64, all ones: empty) holds per cell the M smallest per-image ``order key << 32 | ordinal``, one image each;
+    ``add_support(views, Js, first_ordinal, level)`` over ALL the images for level 0, then for level 1, ... (``add_surface`` is not
+    called), then ``finish_support()``, which writes ``top``; everything after that is the surface test's.  ``result()`` then also
+    holds ``support`` ((Hm,Wm) int32: the images that reach the cell, at most M; 0: empty), ``surface_source`` (int32: the ordinal
+    of the image whose top the cell rests on; -1), ``culled_above`` (int32), ``surface_top`` (float32: the plain minimum, level 0;
+    NaN) and ``surface_support`` (= M); ``surface`` is the supported top.  ``support_counts`` (int64 x 3, device): samples culled
+    below, culled above, samples with a cell; ``surface_counts`` is its first and last word.  With M = 1 every output of the
+    surface test keeps its bits."""
 
     def __init__(self, axes, gsd, device):
         _lib.load()
@@ -1226,6 +1267,7 @@ class Mosaic:
         self.fill_reach = self.fill_levels = self.pyramid = None
         self.bands = self.band_plan = self.acc_bands = self._band_bufs = None
         self.surface = self.top = self.surface_counts = self._cull_buf = self._held = None
+        self.support = self.rank = self.support_counts = None
 
     def _images(self, views: list, Js: list):
         views, Js = list(views), list(Js)
@@ -1279,16 +1321,18 @@ class Mosaic:
         bits = np.where(k & 0x80000000, k & 0x7fffffff, ~k).astype(np.uint32)   # key_value of csrc/order_key.h
         return tuple(bits.view(np.float32).tolist())
 
-    def begin(self, bounds=None, blend=None, feather=None, bands=None, surface=None):
+    def begin(self, bounds=None, blend=None, feather=None, bands=None, surface=None, support=None):
         """Fixes the grid and allocates; ``blend``: the blend depth H in metres (``MOSAIC_BLEND_RANGE``) -- a pixel whose range
         exceeds its cell's smallest one by d gets the weight ``max(1 - d / H, 0)^2`` -- or None for the best view alone;
         ``feather``: with a blend, the feather width F in source pixels (``MOSAIC_FEATHER_RANGE``), or None for none; ``bands``:
         with a blend, the number K of detail bands of the multi-band blend (``MOSAIC_BANDS_RANGE``), or None for none;
-        ``surface``: the tolerance T in metres of the surface test (``MOSAIC_SURFACE_RANGE``), or None for none."""
+        ``surface``: the tolerance T in metres of the surface test (``MOSAIC_SURFACE_RANGE``), or None for none; ``support``: with
+        a surface, the number M of views the top must rest on (``MOSAIC_SUPPORT_RANGE``), or None for the plain minimum."""
         options = MosaicOptions(blend=blend, feather=feather).checked('Mosaic.begin')   # before anything is allocated
         blend, feather = options.blend, options.feather
         bands = mosaic_bands_checked(bands, blend, 'Mosaic.begin')
         surface = None if surface is None else mosaic_surface_tol(surface)
+        support = mosaic_support_checked(support, surface, 'Mosaic.begin')
         if bounds is None:
             bounds = self.bounds()
             if bounds is None:
@@ -1300,7 +1344,9 @@ class Mosaic:
         limit = mosaic_max_cells()
         if Wm * Hm > limit or max(Wm, Hm) > 1 << 24:   # before anything is allocated
             raise _mosaic_refusal('grid', f'mosaic of {Wm} x {Hm} cells of {float(self.gsd):.6g} m: more than the {limit} cells allowed '
-                                          f'(SUCRE_MOSAIC_MAX_CELLS); give a coarser grid with --mosaic-gsd')
+                                          f'(SUCRE_MOSAIC_MAX_CELLS); give a coarser grid with --mosaic-gsd'
+                                          + ('' if support is None else f' (a support of {support} views holds {8 * support} more bytes per cell: '
+                                                                        f'the rank words)'))
         self.Hm, self.Wm, self.lo, self.hi = Hm, Wm, (lo_s, lo_t), (hi_s, hi_t)
         g = _lib.MosaicGrid()
         g.axes, g.gsd, g.lo_s, g.lo_t, g.Hm, g.Wm = self._axes_c, float(self.gsd), float(lo_s), float(lo_t), Hm, Wm
@@ -1329,6 +1375,12 @@ class Mosaic:
             self.top = torch.full((Hm * Wm,), -1, dtype=torch.int32, device=dev)    # all ones: empty
             self.surface_counts = torch.zeros(2, dtype=torch.int64, device=dev)
             self._allocate('surface')
+        self.support, self.rank, self.support_counts = support, None, None
+        if support is not None:
+            self.rank = torch.full((support, Hm * Wm), -1, dtype=torch.int64, device=dev)    # all ones: empty; 8 M bytes per cell
+            self.support_counts = torch.zeros(3, dtype=torch.int64, device=dev)
+            self.surface_counts = self.support_counts[::2]   # culled below, samples with a cell: the surface test's two, the same memory
+            self._allocate('support')
         return Hm, Wm
 
     def _begun(self, what: str) -> None:
@@ -1347,13 +1399,36 @@ class Mosaic:
         self._walk('sucre_mosaic_surface', self._images(views, Js), int(first_ordinal), C.byref(self.grid), self.top,
                    _lib.MOSAIC_PLAIN_ATOMIC if plain_atomic else 0)
 
+    def _supported(self, what: str) -> None:
+        self._surfaced(what)
+        if self.support is None:
+            raise ValueError(f'Mosaic.{what}: begin() was not given a support, so there are no ranks to fill')
+
+    def add_support(self, views: list, Js: list, first_ordinal: int, level: int, plain_atomic: bool = False) -> None:
+        """Lowers level ``level`` of ``rank`` (``sucre_mosaic_support``): the smallest ``order key << 32 | ordinal`` among the
+        samples of the images that hold none of the cell's levels below.  Over ALL the images, in any batches, for level 0, then
+        for level 1, ..., after ``begin`` and before ``finish_support``.  ``plain_atomic``: as ``add_surface``."""
+        self._supported('add_support')
+        self._walk('sucre_mosaic_support', self._images(views, Js), int(first_ordinal), C.byref(self.grid), int(self.support), int(level),
+                   self.rank, _lib.MOSAIC_PLAIN_ATOMIC if plain_atomic else 0)
+
+    def finish_support(self) -> None:
+        """``top``, ``support`` and ``surface_source`` of every cell from its ranks (``sucre_mosaic_support_top``), once
+        ``add_support`` has run every level over every image and before ``splat``.  Only enqueues."""
+        self._supported('finish_support')
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().sucre_mosaic_support_top(C.byref(self.grid), int(self.support), C.c_void_p(self.rank.data_ptr()),
+                                                            C.c_void_p(self.top.data_ptr()), C.c_void_p(self._out['support'].data_ptr()),
+                                                            C.c_void_p(self._out['surface_source'].data_ptr()), _stream_ptr()))
+
     def culled_images(self, views: list, Js: list, first_ordinal: int, count: bool = False) -> list:
         """The batch's ``Js`` as the phases after the surface test see them: per image an (H,W,3) float32 copy of ``J`` with NaN in
         every channel of a pixel that does not take part or lies more than T below its cell's top (``sucre_mosaic_cull``).  Valid
         once ``add_surface`` has seen every image.  The images are views into ONE transient buffer, sized to the largest batch
         seen (12 bytes per pixel, every image rounded up to 256 pixels): the next call overwrites them.  ``count``: the culled
         samples are added to ``culled`` and ``surface_counts`` -- to be asked for in one phase alone, so that every sample is
-        counted once (``splat`` does).  Only enqueues."""
+        counted once (``splat`` does).  With a support the cull has two sides (``sucre_mosaic_cull_supported``): a sample more than T
+        above its cell's supported top goes too, counted in ``culled_above`` and ``support_counts``.  Only enqueues."""
         self._surfaced('culled_images')
         images = self._images(views, Js)
         arr, n, _, _ = images
@@ -1364,8 +1439,13 @@ class Mosaic:
         if self._cull_buf is None or self._cull_buf.numel() * 4 < n_bytes:
             self._cull_buf = torch.empty(n_bytes // 4, dtype=torch.float32, device=self.device)
         buf = self._cull_buf
-        self._walk('sucre_mosaic_cull', images, int(first_ordinal), C.byref(self.grid), self.top, C.c_float(float(self.surface)), buf,
-                   self._out['culled'] if count else None, self.surface_counts if count else None)
+        if self.support is None:
+            self._walk('sucre_mosaic_cull', images, int(first_ordinal), C.byref(self.grid), self.top, C.c_float(float(self.surface)), buf,
+                       self._out['culled'] if count else None, self.surface_counts if count else None)
+        else:
+            self._walk('sucre_mosaic_cull_supported', images, int(first_ordinal), C.byref(self.grid), self.top,
+                       C.c_float(float(self.surface)), buf, self._out['culled'] if count else None,
+                       self._out['culled_above'] if count else None, self.support_counts if count else None)
         out, at = [], 0
         for e in arr:
             out.append(buf[at * 3:(at + e.H * e.W) * 3].view(e.H, e.W, 3))
@@ -1594,22 +1674,32 @@ class Mosaic:
         bands also ``J_multiband`` (Hm,Wm,3) float32 (NaN), complete once ``combine_bands`` has run, and ``bands``, the count K (an
         int); after ``fill`` also ``J_multiband_filled``.  With a surface test also ``surface`` (Hm,Wm) float32 (NaN) -- the value of
         ``top`` as it stands, complete once ``add_surface`` has seen every image --, ``culled`` (Hm,Wm) int32 (0), complete once
-        ``splat`` has, and ``surface_tol``, the tolerance T (a float, the float32 value)."""
+        ``splat`` has, and ``surface_tol``, the tolerance T (a float, the float32 value).  With a support ``surface`` is the
+        supported top, complete once ``finish_support`` has run, and the result also holds ``support`` (Hm,Wm) int32 (0),
+        ``surface_source`` (Hm,Wm) int32 (-1), ``culled_above`` (Hm,Wm) int32 (0), ``surface_top`` (Hm,Wm) float32 (NaN) -- the plain
+        minimum, the value of level 0 of ``rank`` -- and ``surface_support``, the count M (an int)."""
         self._begun('result')
-        if self.surface is not None:   # key_value of csrc/order_key.h, per cell
-            k = self.top
+        def heights(k):   # key_value of csrc/order_key.h, per cell; all ones: NaN
             bits = torch.where(k < 0, k & 0x7fffffff, ~k).view(torch.float32)
-            self._out['surface'].copy_(torch.where(k == -1, torch.full_like(bits, _NAN), bits).view(self.Hm, self.Wm))
+            return torch.where(k == -1, torch.full_like(bits, _NAN), bits).view(self.Hm, self.Wm)
+        if self.surface is not None:
+            self._out['surface'].copy_(heights(self.top))
+        if self.support is not None:
+            self._out['surface_top'].copy_(heights((self.rank[0] >> 32).to(torch.int32)))
         def of(*groups):
             return {key: t for key, t in self._out.items() if MOSAIC_OUTPUTS[key][0] in groups}
         return {**of('best', 'blend', 'bands', 'surface'), **({} if self.feather is None else {'feather': self.feather}),
                 **({} if self.bands is None else {'bands': self.bands}),
-                **({} if self.surface is None else {'surface_tol': float(self.surface)}), **of('fill', 'blend_fill', 'bands_fill')}
+                **({} if self.surface is None else {'surface_tol': float(self.surface)}),
+                **({} if self.support is None else {**of('support'), 'surface_support': int(self.support)}),
+                **of('fill', 'blend_fill', 'bands_fill')}
 
     def run(self, batches, options: MosaicOptions = MosaicOptions(), bounds=None, plain_atomic: bool = False, bands=None,
-            surface=None) -> 'Mosaic':
+            surface=None, support=None) -> 'Mosaic':
         """Every phase over every batch, in the one order there is: the bounds (unless ``bounds`` is given), ``begin``; with
-        ``surface`` (the tolerance T of the surface test, beside the options record) ``add_surface``; ``splat``,
+        ``surface`` (the tolerance T of the surface test, beside the options record) ``add_surface`` -- or, with ``support`` (the
+        count M of supporting views, beside the record too; only with a surface), ``add_support`` over every batch for level 0,
+        then for level 1, ... and ``finish_support``: M passes, and ``add_surface`` does not run --; ``splat``,
         ``resolve`` and ``gather``; with a blend ``accumulate`` and then ``normalize``; with ``bands`` (the count K of a multi-band
         blend, beside the options record; only with a blend) ``accumulate_bands`` and then ``combine_bands``; with a fill ``fill``.  ``batches``: a
         sequence of ``(first_ordinal, load)``, ``load()`` returning the batch's ``(views, Js)`` -- called once per phase, so a
@@ -1621,11 +1711,18 @@ class Mosaic:
             for _, load in batches:
                 self.add_bounds(*load())
         bands = mosaic_bands_checked(bands, options.blend, 'Mosaic.run')
+        support = mosaic_support_checked(support, surface, 'Mosaic.run')
         self.begin(bounds, blend=options.blend, feather=options.feather, **({} if bands is None else {'bands': bands}),
-                   **({} if surface is None else {'surface': surface}))
+                   **({} if surface is None else {'surface': surface}), **({} if support is None else {'support': support}))
         if surface is not None:
-            for first, load in batches:
-                self.add_surface(*load(), first, plain_atomic=plain_atomic)
+            if support is None:
+                for first, load in batches:
+                    self.add_surface(*load(), first, plain_atomic=plain_atomic)
+            else:
+                for level in range(support):
+                    for first, load in batches:
+                        self.add_support(*load(), first, level, plain_atomic=plain_atomic)
+                self.finish_support()
             if len(batches) == 1:
                 first, load = batches[0]
                 self._held = self.culled_images(*load(), first, count=True)
@@ -1650,13 +1747,14 @@ class Mosaic:
 
 
 def mosaic_of(views: list, Js: list, axes, gsd, bounds=None, batch: int = 32, plain_atomic: bool = False, blend=None,
-              fill=None, feather=None, bands=None, surface=None) -> 'Mosaic':
+              fill=None, feather=None, bands=None, surface=None, support=None) -> 'Mosaic':
     """``Mosaic.run`` over device-resident ``views`` / ``Js`` (ordinal = position in the list), ``batch`` images per call; with
     ``blend`` (the blend depth H, metres) the accumulate phase and the normalise pass after them (``plain_atomic``: both the
     splat and the accumulate phase in their plain forms), with ``feather`` (the width F, source pixels; only with ``blend``) the
     feathered one; with ``bands`` (the count K of detail bands; only with ``blend``) the multi-band blend after them; with ``fill``
     (the reach R, metres) the hole filling after all of them (``MosaicOptions``); with ``surface`` (the tolerance T, metres) the
-    surface test ahead of the splat (csrc/surface.h)."""
+    surface test ahead of the splat (csrc/surface.h), with ``support`` (the count M of views; only with ``surface``) against the
+    view-supported top instead of the plain minimum (csrc/support.h)."""
     views, Js = list(views), list(Js)
     if not views:
         raise ValueError('mosaic_of: no view')
@@ -1665,9 +1763,11 @@ def mosaic_of(views: list, Js: list, axes, gsd, bounds=None, batch: int = 32, pl
     options = MosaicOptions(blend=blend, feather=feather, fill=fill).checked('mosaic_of')   # before anything is allocated
     bands = mosaic_bands_checked(bands, options.blend, 'mosaic_of')
     surface = None if surface is None else mosaic_surface_tol(surface)
+    support = mosaic_support_checked(support, surface, 'mosaic_of')
     batches = [(i, lambda i=i: (views[i:i + batch], Js[i:i + batch])) for i in range(0, len(views), batch)]
     return Mosaic(axes, gsd, views[0].depth.device).run(batches, options, bounds, plain_atomic, **({} if bands is None else {'bands': bands}),
-                                                        **({} if surface is None else {'surface': surface}))
+                                                        **({} if surface is None else {'surface': surface}),
+                                                        **({} if support is None else {'support': support}))
 
 
 def device_views_from_scene(scene, device='cuda') -> list[DeviceView]:

@@ -1424,7 +1424,7 @@ def _mosaic_picture(J: Tensor, stretch) -> np.ndarray:
 
 
 _MOSAIC_FLAG = {'grid': '--mosaic', 'blend': '--mosaic-blend', 'fill': '--mosaic-fill', 'feather': '--mosaic-feather',
-                'bands': '--mosaic-bands', 'surface': '--mosaic-surface'}
+                'bands': '--mosaic-bands', 'surface': '--mosaic-surface', 'support': '--mosaic-support'}
 
 
 def _mosaic_refused(e: ValueError, fields=tuple(_MOSAIC_FLAG)) -> BaseException:
@@ -1445,7 +1445,7 @@ _MOSAIC_PNG = {   # how a row of engine.MOSAIC_OUTPUTS becomes its PNG: (the out
 
 def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, output_dir: Path, gsd: float | None = None, axes=None,
            stretch=None, device: str = 'cuda', blend: float | None = None, fill: float | None = None, feather: int | None = None,
-           bands: int | None = None, surface: float | None = None) -> dict:
+           bands: int | None = None, surface: float | None = None, support: int | None = None) -> dict:
     """One picture of the seabed from a finished restoration: every pixel of ``images`` (``sfm.Image`` objects or names of
     ``colmap_model``; at most ``engine.MAX_VIEWS``, ordinal = position) with a valid depth and a restored colour --
     ``results_dir / <name>.pt``, key ``J`` -- is dropped onto the plane grid ``axes`` (``mosaic_axes`` unless given) of ``gsd``
@@ -1498,8 +1498,18 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
     of filled cells are those of a run without the flag, and a T that culls nothing leaves every file and key above as it is, byte
     for byte.  ``mosaic_surface.png`` (``mosaic_surface_picture``: the height, highest ground white) and ``mosaic_culled.png``
     (``mosaic_culled_picture``) come next to the other files, ``mosaic.pt`` gains ``surface``, ``culled`` and ``surface_tol``, and one
-    more line is printed after the mosaic's.  The surface is a plain minimum: one spurious high sample owns its cell.  Not built: a
-    robust (median) surface."""
+    more line is printed after the mosaic's.  The surface is a plain minimum: one spurious high sample owns its cell; ``support``
+    is the remedy.
+
+    ``support``: with ``surface``, the number M of views (``engine.MOSAIC_SUPPORT_RANGE``) the top of a cell must rest on
+    (csrc/support.h): the highest level that at least M different images reach -- a view listed twice has two ordinals and counts
+    twice; a cell seen by fewer than M images rests on the lowest of its per-image tops --, found in M passes over the batches, and
+    a sample that stands more than T ABOVE it takes part in nothing either: a fish in one view's depth map no longer owns its cells.
+    The filled cells stay those of a run without the flag, and ``support=1`` is the surface test bit for bit.
+    ``mosaic_culled_above.png`` (``mosaic_culled_picture`` of ``culled_above``) comes next to the other files, ``mosaic.pt`` gains
+    ``support``, ``surface_source``, ``culled_above``, ``surface_top`` and ``surface_support``, ``surface`` is the supported top, and
+    one more line is printed after the surface's.  The limit: an error that M or more images share passes, and a real feature that
+    one image alone sees more than T above what M images agree on is removed.  Not built: the single-pass k-smallest form."""
     from . import engine
     sfm.require_gpu(device, 'mosaic')
     images = [colmap_model[im] if isinstance(im, str) else im for im in images]
@@ -1526,6 +1536,12 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
         surface = None if surface is None else engine.mosaic_surface_tol(surface)
     except ValueError as e:
         raise _mosaic_refused(e)
+    try:
+        support = None if support is None else engine.mosaic_support_views(support)
+    except ValueError as e:
+        raise _mosaic_refused(e)
+    if support is not None and surface is None:
+        raise SystemExit('--mosaic-support: only with --mosaic-surface T')
     results_dir, output_dir = Path(results_dir), Path(output_dir)
     for image in images:   # before anything is decoded
         path = _consistency_file(results_dir, image)
@@ -1558,7 +1574,8 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
         try:
             m = engine.Mosaic(axes, gsd, device).run([(first, lambda batch=batch: resident(batch)) for first, batch in batches], options,
                                                      **({} if bands is None else {'bands': bands}),
-                                                     **({} if surface is None else {'surface': surface}))
+                                                     **({} if surface is None else {'surface': surface}),
+                                                     **({} if support is None else {'support': support}))
         except ValueError as e:
             # Two refusals of the run belong to a flag: begin's of the grid (--mosaic) and normalize's of a cell's sample count
             # (--mosaic-blend).  The options were checked above, so begin and fill have nothing left to refuse in them; every other
@@ -1569,6 +1586,7 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
                     if png is not None and key in out]
         out = {k: v.cpu() if torch.is_tensor(v) else v for k, v in out.items()}
         surface_counts = None if surface is None else [int(x) for x in m.surface_counts.cpu()]
+        support_counts = None if support is None else [int(x) for x in m.support_counts.cpu()]
     Hm, Wm = m.Hm, m.Wm
     source = out['source']
     filled = source >= 0
@@ -1596,6 +1614,11 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
         print(f'mosaic surface of {float(surface):.6g} m: top between {s0:.6g} and {s1:.6g} m along the view axis; {gone} of {part} samples '
               f'({100.0 * gone / max(1, part):.1f} %) lie more than {float(surface):.6g} m below their cell\'s top, in '
               f'{int((out["culled"] > 0).sum())} cells')
+    if support is not None:
+        _, above, part = support_counts
+        print(f'mosaic support of {support} views: {int(((out["support"] < support) & filled).sum())} of {n_filled} filled cells rest on '
+              f'fewer than {support}; {above} of {part} samples ({100.0 * above / max(1, part):.1f} %) stand more than '
+              f'{float(surface):.6g} m above their cell\'s supported top, in {int((out["culled_above"] > 0).sum())} cells')
     if blend is not None:
         samples = out['samples'].to(torch.int64)
         total, most, several = int(samples.sum()), int(samples.max()), int((samples > 1).sum())
@@ -1659,7 +1682,8 @@ _MODE_REFUSES = {   # mode -> (flag, why), in the order they are looked at
 
 _ONLY_WITH = [   # (flag, the flag it needs, that one's value), in the order they are looked at
     ('--mosaic-gsd', '--mosaic', 'DIR'), ('--mosaic-blend', '--mosaic', 'DIR'), ('--mosaic-fill', '--mosaic', 'DIR'),
-    ('--mosaic-feather', '--mosaic-blend', 'H'), ('--mosaic-bands', '--mosaic-blend', 'H'), ('--mosaic-surface', '--mosaic', 'DIR'),
+    ('--mosaic-feather', '--mosaic-blend', 'H'), ('--mosaic-bands', '--mosaic-blend', 'H'), ('--mosaic-support', '--mosaic-surface', 'T'),
+    ('--mosaic-surface', '--mosaic', 'DIR'),
 ]
 
 
@@ -1678,8 +1702,8 @@ def _refuse_mode_flags(args, mode: str) -> None:
 
 
 def _refuse_mosaic_values(args, world: int = 1) -> None:
-    """The values of --mosaic-gsd, --mosaic-blend, --mosaic-fill, --mosaic-feather, --mosaic-bands and --mosaic-surface and the
-    world size a mosaic takes, refused before any file is opened."""
+    """The values of --mosaic-gsd, --mosaic-blend, --mosaic-fill, --mosaic-feather, --mosaic-bands, --mosaic-surface and
+    --mosaic-support and the world size a mosaic takes, refused before any file is opened."""
     gsd = getattr(args, 'mosaic_gsd', None)
     if gsd is not None and not (np.isfinite(gsd) and gsd > 0):
         raise SystemExit(f'--mosaic-gsd: G must be a finite size > 0 in metres, not {gsd}')
@@ -1697,6 +1721,10 @@ def _refuse_mosaic_values(args, world: int = 1) -> None:
     lo, hi = engine.MOSAIC_SURFACE_RANGE
     if tol is not None and not (np.isfinite(tol) and lo <= tol <= hi):
         raise SystemExit(f'{_MOSAIC_FLAG["surface"]}: T must be a finite tolerance within [{lo:g}, {hi:g}] metres, not {tol}')
+    views = getattr(args, 'mosaic_support', None)
+    lo, hi = engine.MOSAIC_SUPPORT_RANGE
+    if views is not None and not (np.isfinite(views) and lo <= views <= hi and views == int(views)):
+        raise SystemExit(f'{_MOSAIC_FLAG["support"]}: M must be an integer within [{lo:g}, {hi:g}] views, not {views:g}')
     if world > 1:
         raise SystemExit(f'--mosaic: a world size of {world} is not supported yet: the four phases are separate entries of the library '
                          f'so that ranks can all-reduce bounds, keys and pixel words between them, but that all-reduce is not built; '
@@ -1809,7 +1837,7 @@ def parse_args(args: argparse.Namespace):
             mosaic(images, colmap_model, mosaic_dir, args.output_dir, gsd=getattr(args, 'mosaic_gsd', None), stretch=stretch, device=device,
                    blend=getattr(args, 'mosaic_blend', None), fill=getattr(args, 'mosaic_fill', None),
                    feather=getattr(args, 'mosaic_feather', None), bands=getattr(args, 'mosaic_bands', None),
-                   surface=getattr(args, 'mosaic_surface', None))
+                   surface=getattr(args, 'mosaic_surface', None), support=getattr(args, 'mosaic_support', None))
         elif check is not None:
             if world > 1:   # the targets' records are gathered on rank 0
                 sdist.init_process_group()
@@ -2080,6 +2108,13 @@ def build_parser() -> argparse.ArgumentParser:
                                'of two surfaces neither wins a cell nor is blended into it; the grid and the filled cells stay those of a '
                                'run without the flag; writes mosaic_surface.png (the height, highest ground white) and mosaic_culled.png '
                                'next to the other files, adds surface, culled and surface_tol to mosaic.pt and prints one more line')
+    p.extras.add_argument('--mosaic-support', type=float, metavar='M', default=argparse.SUPPRESS,
+                          help='with --mosaic-surface: the top of a cell is the highest level that at least M different images reach '
+                               '(an integer, 1..4; a cell seen by fewer rests on the lowest of its per-image tops) instead of the plain '
+                               'minimum, and a sample more than T metres ABOVE it takes part in nothing either, so a fish or one bad depth '
+                               'patch in a single view no longer owns its cells; M = 1 is --mosaic-surface alone; writes '
+                               'mosaic_culled_above.png, adds support, surface_source, culled_above, surface_top and surface_support '
+                               'to mosaic.pt and prints one more line')
     p.extras.add_argument('--common-stretch', action='store_true', default=argparse.SUPPRESS,
                           help='with --shared-water or --apply-water: stretch every <stem>_rgb.png between the SAME per-channel 1st '
                                'and 99th percentile, those of the valid pixels of all images of the request pooled (all ranks), '
