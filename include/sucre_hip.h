@@ -731,8 +731,30 @@ int sucre_view_consistency(int H, int W, int n_views, const sucre_view_t *target
  *                                counts_dev (uint64 x 3, or NULL): culled below, culled above, samples with a cell
  * All three only enqueue.  Checked before any launch as above, and: n_levels outside 1..SUCRE_MOSAIC_SUPPORT_MAX, level outside
  * 0..n_levels-1, a NULL or misaligned rank_dev or top_dev, misaligned support_out, source_out, culled_above_dev, Hm Wm above 2^39.
+ *
+ * Per-image gain compensation (csrc/gains_mosaic.h): one gain per image and channel from the cells that two or more images share,
+ * by rounds of exact block-coordinate descent on sum (g_i J - m_cell)^2; the host solves between the passes.  The images' J are
+ * those the phases after the surface test see.  gains_dev: (n_ordinals, 3) float32, row = ordinal; sums_dev: (n_ordinals, 16) int64,
+ * row = ordinal, SUCRE_MOSAIC_GAIN_WORDS = 10 words used (rows padded to 128 bytes); the caller starts the sums at zero.
+ *   sucre_mosaic_gain_span   span_dev ((Hm Wm, 2) uint32; the caller starts every pair at all ones, 0): per cell the min and the max of
+ *                            the ordinals of the pixels that take part and have a cell; a cell is SHARED when min < max.  Once,
+ *                            over ALL images, any split into calls.  flags: SUCRE_MOSAIC_PLAIN_ATOMIC -- both atomics for every
+ *                            pixel instead of loading the words first (the same span_dev)
+ *   sucre_mosaic_gain_apply  J_out (sucre_mosaic_band_bytes for these images, that layout): J_c x gains[ordinal][c], one float32
+ *                            multiply, for every pixel of every image; a NaN stays a NaN.  An image's J may be its own block of
+ *                            J_out; it may not overlap J_out otherwise
+ *   sucre_mosaic_gain_sums   acc_dev: an accumulator of sucre_mosaic_accumulate over the gained images with inv_h = 0x1p-126f (every
+ *                            wq = 4096: the per-sample mean), complete for ALL images.  For a pixel that takes part, whose cell is
+ *                            shared, with q(x) = (int64)rintf(fminf(fmaxf(x, -8), 8) 16384), m_c = the quotient of
+ *                            sucre_mosaic_normalize of words c and 6: Xq = q(J_c), Mq = q(m_c), Rq = q(J_c gains[ordinal][c]) - Mq,
+ *                            and the image's row takes 1, Xq Mq x 3, Xq Xq x 3, Rq Rq x 3 (integer adds: any order, the same words).
+ *                            flags: SUCRE_MOSAIC_PLAIN_ATOMIC -- ten atomics per 256 pixels instead of ten per 8192 of an image
+ * All three only enqueue.  Checked before any launch as above, and: a NULL or misaligned span_dev (8 bytes), gains_dev, J_out, acc_dev
+ * or sums_dev (128 bytes), n_ordinals outside 1..4096 or below first_ordinal + n_images, an image of more than 2^26 pixels (its sums
+ * could pass 2^62), a J_out that overlaps an image's J without being it, unknown flags.
  */
 #define SUCRE_MOSAIC_PLAIN_ATOMIC 1u
+#define SUCRE_MOSAIC_GAIN_WORDS 10
 #define SUCRE_MOSAIC_SUPPORT_MAX 4
 #define SUCRE_MOSAIC_ACC_WORDS 8
 #define SUCRE_MOSAIC_FEATHER_MAX 1024
@@ -787,6 +809,13 @@ int sucre_mosaic_support_top(const sucre_mosaic_grid_t *grid, int n_levels, cons
 int sucre_mosaic_cull_supported(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
                                 const sucre_mosaic_grid_t *grid, const uint32_t *top_dev, float tol, float *J_out,
                                 uint32_t *culled_dev, uint32_t *culled_above_dev, uint64_t *counts_dev, void *stream);
+int sucre_mosaic_gain_span(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                           const sucre_mosaic_grid_t *grid, uint32_t *span_dev, unsigned flags, void *stream);
+int sucre_mosaic_gain_apply(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal, const float *gains_dev,
+                            int n_ordinals, float *J_out, void *stream);
+int sucre_mosaic_gain_sums(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                           const sucre_mosaic_grid_t *grid, const uint32_t *span_dev, const int64_t *acc_dev, const float *gains_dev,
+                           int n_ordinals, int64_t *sums_dev, unsigned flags, void *stream);
 
 /*
  * ---- hole filling of the finished mosaic: a bounded push-pull over a pyramid of the grid ------------------------------------------

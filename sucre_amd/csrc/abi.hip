@@ -15,6 +15,7 @@
 #include "pool.h"
 #include "surface.h"
 #include "support.h"
+#include "gains_mosaic.h"
 
 namespace sucre {
 
@@ -1209,6 +1210,66 @@ int sucre_mosaic_cull_supported(void *table_dev, int n_images, const sucre_mosai
     const MosaicCullSupported out = {culled_dev, culled_above_dev, reinterpret_cast<unsigned long long *>(counts_dev)};
     return check_hip(launch_mosaic_cull_supported(table_dev, n_images, images, first_ordinal, g, top_dev, tol, J_out, out,
                                                   static_cast<hipStream_t>(stream)), "sucre_mosaic_cull_supported");
+}
+
+/* ---- per-image gain compensation of the mosaic: the span of ordinals per cell, J x gain, the ten sums per image (gains_mosaic.h) ---- */
+
+// The rows of gains_dev (and sums_dev) the call's ordinals index: all of them must exist.
+static int check_gain_rows(int n_images, int first_ordinal, int n_ordinals) {
+    if (n_ordinals < 1 || n_ordinals > kMaxViews) return fail(SUCRE_ERR_ARG, "n_ordinals=%d outside [1,%d]", n_ordinals, kMaxViews);
+    if (first_ordinal + n_images > n_ordinals)
+        return fail(SUCRE_ERR_ARG, "ordinals %d..%d outside the %d rows of the gain table", first_ordinal, first_ordinal + n_images - 1, n_ordinals);
+    return SUCRE_OK;
+}
+
+int sucre_mosaic_gain_span(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                           const sucre_mosaic_grid_t *grid, uint32_t *span_dev, unsigned flags, void *stream) {
+    if (int rc = check_mosaic_images(table_dev, n_images, images, first_ordinal)) return rc;
+    MosaicGrid g;
+    if (int rc = check_mosaic_grid(grid, &g)) return rc;
+    if (!span_dev || !aligned(span_dev, 8)) return fail(SUCRE_ERR_ARG, "span_dev is NULL or not 8-byte aligned");
+    if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
+    return check_hip(launch_mosaic_gain_span((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) != 0, table_dev, n_images, images, first_ordinal, g, span_dev,
+                                             static_cast<hipStream_t>(stream)), "sucre_mosaic_gain_span");
+}
+
+int sucre_mosaic_gain_apply(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal, const float *gains_dev,
+                            int n_ordinals, float *J_out, void *stream) {
+    if (int rc = check_mosaic_images(table_dev, n_images, images, first_ordinal)) return rc;
+    if (int rc = check_gain_rows(n_images, first_ordinal, n_ordinals)) return rc;
+    if (!gains_dev || !aligned(gains_dev, 4)) return fail(SUCRE_ERR_ARG, "gains_dev is NULL or not 4-byte aligned");
+    if (!J_out || !aligned(J_out, 4)) return fail(SUCRE_ERR_ARG, "J_out is NULL or not 4-byte aligned");
+    // an image's J is its own block of J_out (a lane reads and writes its own pixel alone) or lies outside J_out altogether
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(J_out), o1 = o0 + band_bytes(n_images, images);
+    uint64_t at = 0;   // pixels ahead of the image's block
+    for (int i = 0; i < n_images; ++i) {
+        const uintptr_t j0 = reinterpret_cast<uintptr_t>(images[i].J), j1 = j0 + (size_t)images[i].H * (size_t)images[i].W * 12;
+        if (j0 != o0 + at * 12 && j0 < o1 && o0 < j1) return fail(SUCRE_ERR_ARG, "image %d: J_out overlaps the image's J without being it", i);
+        at += mosaic_blocks(images[i].H, images[i].W) * kMosaicBlockPx;
+    }
+    return check_hip(launch_mosaic_gain_apply(table_dev, n_images, images, first_ordinal, gains_dev, J_out, static_cast<hipStream_t>(stream)),
+                     "sucre_mosaic_gain_apply");
+}
+
+int sucre_mosaic_gain_sums(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                           const sucre_mosaic_grid_t *grid, const uint32_t *span_dev, const int64_t *acc_dev, const float *gains_dev,
+                           int n_ordinals, int64_t *sums_dev, unsigned flags, void *stream) {
+    if (int rc = check_mosaic_images(table_dev, n_images, images, first_ordinal)) return rc;
+    MosaicGrid g;
+    if (int rc = check_mosaic_grid(grid, &g)) return rc;
+    if (int rc = check_gain_rows(n_images, first_ordinal, n_ordinals)) return rc;
+    for (int i = 0; i < n_images; ++i)
+        if ((uint64_t)images[i].H * (uint64_t)images[i].W > kGainMaxPixels)
+            return fail(SUCRE_ERR_ARG, "image %d: %dx%d pixels, more than the 2^26 whose sums stay below 2^62", i, images[i].W, images[i].H);
+    if (!span_dev || !aligned(span_dev, 8)) return fail(SUCRE_ERR_ARG, "span_dev is NULL or not 8-byte aligned");
+    if (!acc_dev || !aligned(acc_dev, 8)) return fail(SUCRE_ERR_ARG, "acc_dev is NULL or not 8-byte aligned");
+    if (!gains_dev || !aligned(gains_dev, 4)) return fail(SUCRE_ERR_ARG, "gains_dev is NULL or not 4-byte aligned");
+    if (!sums_dev || !aligned(sums_dev, 128)) return fail(SUCRE_ERR_ARG, "sums_dev is NULL or not 128-byte aligned");
+    if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
+    return check_hip(launch_mosaic_gain_sums((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) != 0, table_dev, n_images, images, first_ordinal, g, span_dev,
+                                             reinterpret_cast<const long long *>(acc_dev), gains_dev,
+                                             reinterpret_cast<unsigned long long *>(sums_dev), static_cast<hipStream_t>(stream)),
+                     "sucre_mosaic_gain_sums");
 }
 
 /* ---- hole filling of the finished mosaic: a bounded push-pull over a pyramid of the grid (fill.h) ---- */

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 import os
 import threading
 from dataclasses import dataclass
@@ -986,7 +987,8 @@ def mosaic_max_cells() -> int:
     filled outputs take 15 and whose own levels 4; a multi-band blend of K bands adds 64 (K + 1) + 12: its K + 1 accumulators and
     ``J_multiband`` -- and 19 more with a fill, ``J_multiband_filled`` and the pass's levels and dropped raw picture; a surface test
     adds 12: the ``top`` word, ``surface`` and ``culled``; a support of M views 8 M + 16 more: the ``rank`` words, ``support``,
-    ``surface_source``, ``culled_above`` and ``surface_top``)."""
+    ``surface_source``, ``culled_above`` and ``surface_top``; a gain compensation adds 72: the ``span`` pair and the
+    reference accumulator ``acc_gain``, eight int64 words of its own)."""
     return int(os.environ.get('SUCRE_MOSAIC_MAX_CELLS', 1 << 27))
 
 
@@ -1020,6 +1022,14 @@ _MOSAIC_SURFACE = ('surface tolerance T', MOSAIC_SURFACE_RANGE, False, 'metres',
 
 MOSAIC_SUPPORT_RANGE = (1, 4)   # views M whose agreement a supported surface asks for (csrc/support.h)
 _MOSAIC_SUPPORT = ('supporting views M', MOSAIC_SUPPORT_RANGE, True, 'views', int)   # beside the record, as the surface tolerance
+
+
+MOSAIC_GAIN_ROUNDS_RANGE = (1, 64)      # rounds R of the per-image gain compensation (csrc/gains_mosaic.h)
+MOSAIC_GAIN_LIMIT_RANGE = (1.0, 16.0)   # limits L a gain is clamped to: 1/L <= g <= L
+MOSAIC_GAIN_LIMIT = 2.0                 # the limit unless one is given
+MOSAIC_GAIN_MAX_PIXELS = 1 << 26        # pixels of one image from which the gain sums' int64 words may pass 2^62
+_MOSAIC_GAINS = ('gain rounds R', MOSAIC_GAIN_ROUNDS_RANGE, True, 'rounds', int)   # beside the record, as the supporting views
+_MOSAIC_GAIN_LIMIT = ('gain limit L', MOSAIC_GAIN_LIMIT_RANGE, False, 'times', float)
 
 
 def _mosaic_value(field: str, value, row=None):
@@ -1087,6 +1097,65 @@ def mosaic_support_checked(support, surface, who: str):
         raise _mosaic_refusal('support', f'{who}: the support decides which top the surface test measures against; give the '
                                          f'tolerance too (surface=T)')
     return support
+
+
+def mosaic_gain_rounds(gains) -> int:
+    """``gains`` as the number R of rounds of the gain compensation, or ValueError (``field``: 'gains') unless it is an integral
+    number, no bool, within ``MOSAIC_GAIN_ROUNDS_RANGE``."""
+    return _mosaic_value('gains', gains, _MOSAIC_GAINS)
+
+
+def mosaic_gain_limit(gain_limit) -> float:
+    """``gain_limit`` as the limit L of a gain, or ValueError (``field``: 'gain_limit') unless it is finite and within
+    ``MOSAIC_GAIN_LIMIT_RANGE``."""
+    return _mosaic_value('gain_limit', gain_limit, _MOSAIC_GAIN_LIMIT)
+
+
+def mosaic_gains_checked(gains, gain_limit, who: str):
+    """``(None, None)``, or ``(R, L)`` as ``mosaic_gain_rounds`` and ``mosaic_gain_limit`` return them (L: ``MOSAIC_GAIN_LIMIT``
+    unless given); ValueError (``field``: 'gain_limit') for a limit without rounds, in the name of ``who``."""
+    if gain_limit is not None:
+        gain_limit = mosaic_gain_limit(gain_limit)
+    if gains is None:
+        if gain_limit is not None:
+            raise _mosaic_refusal('gain_limit', f'{who}: the limit clamps the gains the rounds find; give the rounds too (gains=R)')
+        return None, None
+    return mosaic_gain_rounds(gains), MOSAIC_GAIN_LIMIT if gain_limit is None else gain_limit
+
+
+def mosaic_gain_solve(sums, G, limit):
+    """One solve of the gain compensation (csrc/gains_mosaic.h) on the host, in float64: ``sums`` (n, 10) integers -- per image the
+    sample count n_i, ``sum Xq Mq`` x 3, ``sum Xq Xq`` x 3 (the last three words are not read) --, ``G`` (n, 3) the gains of the pass
+    that made them, ``limit`` L.  Per channel: ``g_i = float(A) / float(B)`` where ``n_i > 0``, ``A > 0`` and ``B > 0``, otherwise
+    the gain the image had; over the images with ``n_i > 0`` ``s = fsum(float(n_i) g_i) / fsum(float(n_i))`` and ``g_i / s`` -- the
+    gauge: the overlap-weighted mean gain is 1 --; then ``min(max(g_i, 1 / L), L)``, then float32.  An image with ``n_i = 0`` keeps
+    exactly 1.  Returns (n, 3) float32 (numpy)."""
+    sums = [[int(x) for x in row] for row in np.asarray(sums).tolist()]
+    old = np.asarray(G, dtype=np.float32).reshape(len(sums), 3)
+    L = float(limit)
+    lo = 1.0 / L
+    out = np.ones((len(sums), 3), np.float32)
+    seen = [i for i, row in enumerate(sums) if row[0] > 0]
+    n_all = math.fsum(float(sums[i][0]) for i in seen)
+    for c in range(3):
+        g = {}
+        for i in seen:
+            A, B = sums[i][1 + c], sums[i][4 + c]
+            g[i] = float(A) / float(B) if A > 0 and B > 0 else float(old[i, c])
+        if not seen:
+            continue
+        s = math.fsum(float(sums[i][0]) * g[i] for i in seen) / n_all
+        for i in seen:
+            out[i, c] = np.float32(min(max(g[i] / s if s > 0 else g[i], lo), L))
+    return out
+
+
+def mosaic_gain_rms(sums) -> list:
+    """``[sqrt(sum_i word(7 + c) / sum_i word 0) / 16384 for c in 0..2]`` of one pass's ``sums`` (n, 10), Python integers under a
+    float64 root; zeros when no sample lies in a shared cell."""
+    rows = [[int(x) for x in row] for row in np.asarray(sums).tolist()]
+    n = sum(row[0] for row in rows)
+    return [math.sqrt(sum(row[7 + c] for row in rows) / n) / 16384.0 if n else 0.0 for c in range(3)]
 
 
 def mosaic_bands_checked(bands, blend, who: str):
@@ -1239,7 +1308,25 @@ class Mosaic:
     of the image whose top the cell rests on; -1), ``culled_above`` (int32), ``surface_top`` (float32: the plain minimum, level 0;
     NaN) and ``surface_support`` (= M); ``surface`` is the supported top.  ``support_counts`` (int64 x 3, device): samples culled
     below, culled above, samples with a cell; ``surface_counts`` is its first and last word.  With M = 1 every output of the
-    surface test keeps its bits."""
+    surface test keeps its bits.
+
+    The gain compensation: ``begin(gains=R, gain_limit=L)`` -- R rounds (``MOSAIC_GAIN_ROUNDS_RANGE``), every gain within
+    ``[1 / L, L]`` (``MOSAIC_GAIN_LIMIT_RANGE``; ``MOSAIC_GAIN_LIMIT`` unless given; csrc/gains_mosaic.h).  One gain per image and
+    channel, from the cells that two or more images share, so that the images agree on the colour of the same seabed before
+    anything is resolved or blended.  ``begin`` allocates ``span`` ((Hm Wm, 2) int32 bit patterns of uint32: min and max ordinal per
+    cell; all ones, 0: empty), ``acc_gain`` ((Hm Wm, 8) int64, the reference pass's accumulator, a tensor of its own: 64 bytes per
+    cell besides the blend's ``acc``), ``gain_table`` ((n, 3) float32, ones) and ``gain_sums_words`` ((R + 1, n, 16) int64, ten words
+    used) -- the last two at the first pass, which learns n, the images of the request, from its batches.  ``add_span(views, Js,
+    first_ordinal)`` over ALL the images once ``splat`` has seen them all; then R times ``gain_pass(batches)`` and ``solve_gains()``,
+    and one more ``gain_pass`` that measures the final state (by hand a pass is ``begin_gain_pass(n)``, ``add_gain_reference`` over
+    ALL the images, then ``add_gain_sums`` over ALL of them, then ``end_gain_pass()``).  From the first pass on ``resolve``,
+    ``gather``, ``accumulate`` and ``accumulate_bands`` see, through ``gained_images``, every (culled) ``J`` times its image's gain.
+    ``span``, ``acc_gain`` and the sums are the tensors a later all-reduce (min / max, sum, sum) over ranks would combine.
+    ``result()`` then also holds ``gains`` (n,3) float32, ``gain_sums`` (passes so far, n, 10) int64, ``gain_rms`` (passes, 3)
+    float64 -- row r: the RMS disagreement in the shared cells at the gains entering pass r --, ``gain_overlap`` (n,) int64 -- the
+    samples of every image in shared cells --, ``gain_rounds`` (= R) and ``gain_limit`` (= L).  One more buffer of 12 bytes per
+    padded pixel of the largest batch is held.  A finite positive gain makes and removes no NaN, so every output that is not a
+    ``J`` keeps its bits, and L = 1 keeps every output's."""
 
     def __init__(self, axes, gsd, device):
         _lib.load()
@@ -1268,6 +1355,11 @@ class Mosaic:
         self.bands = self.band_plan = self.acc_bands = self._band_bufs = None
         self.surface = self.top = self.surface_counts = self._cull_buf = self._held = None
         self.support = self.rank = self.support_counts = None
+        self.gains = self.gain_limit = self.span = self.acc_gain = self.gain_table = self.gain_sums_words = self._gain_buf = None
+        self._gain_passes = 0
+        self._gain_open = False
+        self._splatted = False
+        self._held_gained = None
 
     def _images(self, views: list, Js: list):
         views, Js = list(views), list(Js)
@@ -1321,14 +1413,17 @@ class Mosaic:
         bits = np.where(k & 0x80000000, k & 0x7fffffff, ~k).astype(np.uint32)   # key_value of csrc/order_key.h
         return tuple(bits.view(np.float32).tolist())
 
-    def begin(self, bounds=None, blend=None, feather=None, bands=None, surface=None, support=None):
+    def begin(self, bounds=None, blend=None, feather=None, bands=None, surface=None, support=None, gains=None, gain_limit=None):
         """Fixes the grid and allocates; ``blend``: the blend depth H in metres (``MOSAIC_BLEND_RANGE``) -- a pixel whose range
         exceeds its cell's smallest one by d gets the weight ``max(1 - d / H, 0)^2`` -- or None for the best view alone;
         ``feather``: with a blend, the feather width F in source pixels (``MOSAIC_FEATHER_RANGE``), or None for none; ``bands``:
         with a blend, the number K of detail bands of the multi-band blend (``MOSAIC_BANDS_RANGE``), or None for none;
         ``surface``: the tolerance T in metres of the surface test (``MOSAIC_SURFACE_RANGE``), or None for none; ``support``: with
-        a surface, the number M of views the top must rest on (``MOSAIC_SUPPORT_RANGE``), or None for the plain minimum."""
+        a surface, the number M of views the top must rest on (``MOSAIC_SUPPORT_RANGE``), or None for the plain minimum;
+        ``gains``: the rounds R of the per-image gain compensation (``MOSAIC_GAIN_ROUNDS_RANGE``), or None for none;
+        ``gain_limit``: with ``gains``, the limit L of a gain (``MOSAIC_GAIN_LIMIT_RANGE``), ``MOSAIC_GAIN_LIMIT`` unless given."""
         options = MosaicOptions(blend=blend, feather=feather).checked('Mosaic.begin')   # before anything is allocated
+        gains, gain_limit = mosaic_gains_checked(gains, gain_limit, 'Mosaic.begin')
         blend, feather = options.blend, options.feather
         bands = mosaic_bands_checked(bands, blend, 'Mosaic.begin')
         surface = None if surface is None else mosaic_surface_tol(surface)
@@ -1381,6 +1476,12 @@ class Mosaic:
             self.support_counts = torch.zeros(3, dtype=torch.int64, device=dev)
             self.surface_counts = self.support_counts[::2]   # culled below, samples with a cell: the surface test's two, the same memory
             self._allocate('support')
+        self.gains, self.gain_limit = gains, gain_limit
+        self.span = self.acc_gain = self.gain_table = self.gain_sums_words = self._gain_buf = None
+        self._gain_passes, self._gain_open, self._splatted, self._held_gained = 0, False, False, None
+        if gains is not None:
+            self.span = torch.tensor([-1, 0], dtype=torch.int32, device=dev).repeat(Hm * Wm, 1)    # all ones, 0: empty; 8 bytes per cell
+            self.acc_gain = torch.zeros((Hm * Wm, _lib.MOSAIC_ACC_WORDS), dtype=torch.int64, device=dev)   # 64 bytes per cell
         return Hm, Wm
 
     def _begun(self, what: str) -> None:
@@ -1452,15 +1553,171 @@ class Mosaic:
             at += -(-(e.H * e.W) // _lib.MOSAIC_BLOCK_PX) * _lib.MOSAIC_BLOCK_PX
         return out
 
-    def _phase_images(self, views: list, Js: list, first_ordinal: int, count: bool = False):
-        """``_images`` for a phase after the surface test: of the culled ``Js`` when a surface was begun (of the ones ``run`` holds
-        when a single batch is the whole request: culled once, the same bits)."""
+    def _culled(self, views: list, Js: list, first_ordinal: int, count: bool = False) -> list:
+        """The batch's ``Js`` as the phases after the surface test see them, gains apart: the culled ones when a surface was begun
+        (the ones ``run`` holds when a single batch is the whole request: culled once, the same bits)."""
         if self.surface is None:
-            return self._images(views, Js)
-        return self._images(views, self.culled_images(views, Js, first_ordinal, count) if self._held is None else self._held)
+            return Js
+        return self.culled_images(views, Js, first_ordinal, count) if self._held is None else self._held
+
+    def _phase_images(self, views: list, Js: list, first_ordinal: int, count: bool = False):
+        """``_images`` for a phase after the surface test: of the culled ``Js`` when a surface was begun, and, once a gain pass has
+        run, of those times their gains (``gained_images``; of the ones ``run`` holds when a single batch is the whole request)."""
+        if self._gain_passes == 0:
+            return self._images(views, self._culled(views, Js, first_ordinal, count))
+        return self._images(views, self.gained_images(views, Js, first_ordinal) if self._held_gained is None else self._held_gained)
+
+    # ---- the gain compensation (csrc/gains_mosaic.h) ----
+
+    def _gaining(self, what: str) -> None:
+        self._begun(what)
+        if self.gains is None:
+            raise ValueError(f'Mosaic.{what}: begin() was not given gain rounds, so there are no gains to find')
+
+    def _spanned(self, what: str) -> None:
+        self._gaining(what)
+        if self._splatted is False:
+            raise ValueError(f'Mosaic.{what}: splat() comes first (the reference pass reads every cell\'s smallest range)')
+
+    def add_span(self, views: list, Js: list, first_ordinal: int, plain_atomic: bool = False) -> None:
+        """Lowers and raises ``span`` to the smallest and the largest ordinal of the samples of every cell the images reach
+        (``sucre_mosaic_gain_span``).  Over ALL the images, in any batches, once ``splat`` has seen every image and before the first
+        gain pass.  ``plain_atomic``: both atomics for every pixel, without the loads that filter them."""
+        self._spanned('add_span')
+        self._walk('sucre_mosaic_gain_span', self._images(views, self._culled(views, Js, first_ordinal)), int(first_ordinal),
+                   C.byref(self.grid), self.span, _lib.MOSAIC_PLAIN_ATOMIC if plain_atomic else 0)
+
+    def _apply_gains(self, views: list, Jc: list, first_ordinal: int) -> list:
+        """``Jc`` times the gains of their ordinals (``sucre_mosaic_gain_apply``) as views into the ONE transient buffer
+        ``_gain_buf``, sized to the largest batch seen: the next call overwrites them."""
+        images = self._images(views, Jc)
+        arr, n, _, _ = images
+        if int(first_ordinal) + n > self.gain_table.shape[0]:
+            raise ValueError(f'Mosaic: ordinals {int(first_ordinal)}..{int(first_ordinal) + n - 1} but the gain table holds '
+                             f'{self.gain_table.shape[0]} images (begin_gain_pass fixes the count)')
+        lib = _lib.load()
+        n_bytes = lib.sucre_mosaic_band_bytes(n, arr)
+        if n_bytes == 0:
+            raise _lib.SucreError(f'sucre_mosaic_band_bytes: {lib.sucre_last_error().decode()}')
+        if self._gain_buf is None or self._gain_buf.numel() * 4 < n_bytes:
+            self._gain_buf = torch.empty(n_bytes // 4, dtype=torch.float32, device=self.device)
+        buf = self._gain_buf
+        self._walk('sucre_mosaic_gain_apply', images, int(first_ordinal), self.gain_table, int(self.gain_table.shape[0]), buf)
+        out, at = [], 0
+        for e in arr:
+            out.append(buf[at * 3:(at + e.H * e.W) * 3].view(e.H, e.W, 3))
+            at += -(-(e.H * e.W) // _lib.MOSAIC_BLOCK_PX) * _lib.MOSAIC_BLOCK_PX
+        return out
+
+    def gained_images(self, views: list, Js: list, first_ordinal: int) -> list:
+        """The batch's ``Js`` as the phases after the gain compensation see them: per image the (H,W,3) float32 culled ``J`` (``J``
+        itself without a surface test) times the image's gain, one float32 multiply per channel; a NaN stays a NaN.  Valid once a
+        gain pass has begun (the gain table exists then).  Views into one transient buffer; only enqueues."""
+        self._gaining('gained_images')
+        if self.gain_table is None:
+            raise ValueError('Mosaic.gained_images: no gain pass has begun, so there is no gain table yet')
+        return self._apply_gains(views, self._culled(views, Js, first_ordinal), first_ordinal)
+
+    def begin_gain_pass(self, n_images: int) -> None:
+        """Opens a pass at the gains as they stand: zeroes ``acc_gain``; the first one allocates ``gain_table`` (ones) and
+        ``gain_sums_words`` for ``n_images``, the images of the whole request."""
+        self._spanned('begin_gain_pass')
+        if self._gain_passes > self.gains:
+            raise ValueError(f'Mosaic.begin_gain_pass: the {self.gains} rounds and the measuring pass have run')
+        if self.gain_table is None:
+            n = int(n_images)
+            if not 1 <= n <= MAX_VIEWS:
+                raise ValueError(f'Mosaic.begin_gain_pass: {n} images, need 1..{MAX_VIEWS}')
+            self.gain_table = torch.ones((n, 3), dtype=torch.float32, device=self.device)
+            self.gain_sums_words = torch.zeros((self.gains + 1, n, _lib.MOSAIC_GAIN_ROW_WORDS), dtype=torch.int64, device=self.device)
+        elif int(n_images) != self.gain_table.shape[0]:
+            raise ValueError(f'Mosaic.begin_gain_pass: {int(n_images)} images, but the first pass saw {self.gain_table.shape[0]}')
+        self.acc_gain.zero_()
+        self._gain_open = True
+
+    def _in_gain_pass(self, what: str) -> None:
+        self._gaining(what)
+        if not self._gain_open:
+            raise ValueError(f'Mosaic.{what}: begin_gain_pass() comes first')
+
+    def add_gain_reference(self, views: list, Js: list, first_ordinal: int, plain: bool = False) -> None:
+        """The reference of the open pass: the blend's accumulate over the gained images into ``acc_gain`` with the smallest normal
+        float32 as ``inv_h``, so that every sample weighs 4096 -- the per-sample mean.  Over ALL the images before ``add_gain_sums``."""
+        self._in_gain_pass('add_gain_reference')
+        Jg = self._apply_gains(views, self._culled(views, Js, first_ordinal), first_ordinal)
+        self._walk('sucre_mosaic_accumulate', self._images(views, Jg), int(first_ordinal), C.byref(self.grid), self.key,
+                   C.c_float(2.0 ** -126), self.acc_gain, _lib.MOSAIC_PLAIN_ATOMIC if plain else 0)
+
+    def check_gain_reference(self) -> None:
+        """Waits for the reference and raises ValueError (``field``: 'gains') when a cell holds ``MOSAIC_MAX_SAMPLES`` = 2^20 samples
+        or more (its 64-bit sums may have wrapped).  ``gain_pass`` calls it in the first pass: the counts do not change after it."""
+        self._gaining('check_gain_reference')
+        most = int(self.acc_gain[:, 7].max())
+        if most >= MOSAIC_MAX_SAMPLES:
+            raise _mosaic_refusal('gains', f'mosaic gains: a cell holds {most} samples, and from {MOSAIC_MAX_SAMPLES} on its 64-bit sums '
+                                           f'may overflow; give a finer grid with --mosaic-gsd')
+
+    def add_gain_sums(self, views: list, Js: list, first_ordinal: int, plain: bool = False) -> None:
+        """The ten sums per image of the open pass (``sucre_mosaic_gain_sums``) over the un-gained (culled) images, once
+        ``add_gain_reference`` has seen every image.  An image of more than ``MOSAIC_GAIN_MAX_PIXELS`` pixels is refused before any
+        launch.  ``plain``: one set of atomics per 256 pixels (the same words)."""
+        self._in_gain_pass('add_gain_sums')
+        for v in views:
+            H, W = v.depth.shape
+            if H * W > MOSAIC_GAIN_MAX_PIXELS:
+                raise _mosaic_refusal('gains', f'mosaic gains: {v.name or "a view"} has {W} x {H} pixels, more than the '
+                                               f'{MOSAIC_GAIN_MAX_PIXELS} whose 64-bit sums stay below 2^62')
+        images = self._images(views, self._culled(views, Js, first_ordinal))
+        if int(first_ordinal) + images[1] > self.gain_table.shape[0]:
+            raise ValueError(f'Mosaic.add_gain_sums: ordinals {int(first_ordinal)}..{int(first_ordinal) + images[1] - 1} but the gain '
+                             f'table holds {self.gain_table.shape[0]} images')
+        self._walk('sucre_mosaic_gain_sums', images, int(first_ordinal), C.byref(self.grid), self.span, self.acc_gain, self.gain_table,
+                   int(self.gain_table.shape[0]), self.gain_sums_words[self._gain_passes], _lib.MOSAIC_PLAIN_ATOMIC if plain else 0)
+
+    def end_gain_pass(self) -> None:
+        """Closes the open pass: its sums are row ``passes so far`` of ``gain_sums``."""
+        self._in_gain_pass('end_gain_pass')
+        self._gain_open = False
+        self._gain_passes += 1
+
+    def gain_pass(self, batches, plain: bool = False) -> None:
+        """One whole pass at the gains as they stand over ``batches`` (as ``run`` takes them): ``begin_gain_pass``, the reference
+        over every batch, in the first pass ``check_gain_reference``, the sums over every batch, ``end_gain_pass``."""
+        batches = list(batches)
+        self._spanned('gain_pass')
+        if self.gain_table is None:   # the first pass learns the images of the request
+            self.begin_gain_pass(max(first + len(load()[0]) for first, load in batches))
+        else:
+            self.begin_gain_pass(self.gain_table.shape[0])
+        for first, load in batches:
+            self.add_gain_reference(*load(), first, plain=plain)
+        if self._gain_passes == 0:
+            self.check_gain_reference()
+        for first, load in batches:
+            self.add_gain_sums(*load(), first, plain=plain)
+        self.end_gain_pass()
+
+    def gain_sums(self) -> torch.Tensor:
+        """(passes so far, n, 10) int64 on the device: the sums of every closed pass."""
+        self._gaining('gain_sums')
+        if self.gain_sums_words is None:
+            raise ValueError('Mosaic.gain_sums: no gain pass has begun')
+        return self.gain_sums_words[:self._gain_passes, :, :_lib.MOSAIC_GAIN_WORDS].contiguous()
+
+    def solve_gains(self) -> torch.Tensor:
+        """The gains of the next pass from the sums of the last closed one (``mosaic_gain_solve``, on the host: waits); returns the
+        (n,3) float32 device table."""
+        self._gaining('solve_gains')
+        if self._gain_passes == 0 or self._gain_open:
+            raise ValueError('Mosaic.solve_gains: a whole gain pass comes first (gain_pass, or begin_gain_pass .. end_gain_pass)')
+        sums = self.gain_sums_words[self._gain_passes - 1, :, :_lib.MOSAIC_GAIN_WORDS].cpu().numpy()
+        solved = mosaic_gain_solve(sums, self.gain_table.cpu().numpy(), self.gain_limit)
+        self.gain_table.copy_(torch.from_numpy(solved))
+        return self.gain_table
 
     def splat(self, views: list, Js: list, first_ordinal: int, plain_atomic: bool = False) -> None:
         self._begun('splat')
+        self._splatted = True
         self._walk('sucre_mosaic_splat', self._phase_images(views, Js, first_ordinal, count=True), int(first_ordinal), C.byref(self.grid),
                    self.key, _lib.MOSAIC_PLAIN_ATOMIC if plain_atomic else 0)
 
@@ -1677,7 +1934,9 @@ class Mosaic:
         ``splat`` has, and ``surface_tol``, the tolerance T (a float, the float32 value).  With a support ``surface`` is the
         supported top, complete once ``finish_support`` has run, and the result also holds ``support`` (Hm,Wm) int32 (0),
         ``surface_source`` (Hm,Wm) int32 (-1), ``culled_above`` (Hm,Wm) int32 (0), ``surface_top`` (Hm,Wm) float32 (NaN) -- the plain
-        minimum, the value of level 0 of ``rank`` -- and ``surface_support``, the count M (an int)."""
+        minimum, the value of level 0 of ``rank`` -- and ``surface_support``, the count M (an int).  With a gain compensation also, after
+        every other key, ``gains`` (n,3) float32, ``gain_sums`` (passes, n, 10) int64, ``gain_rms`` (passes, 3) float64 (CPU),
+        ``gain_overlap`` (n,) int64, ``gain_rounds`` (= R, an int) and ``gain_limit`` (= L, a float)."""
         self._begun('result')
         def heights(k):   # key_value of csrc/order_key.h, per cell; all ones: NaN
             bits = torch.where(k < 0, k & 0x7fffffff, ~k).view(torch.float32)
@@ -1692,10 +1951,23 @@ class Mosaic:
                 **({} if self.bands is None else {'bands': self.bands}),
                 **({} if self.surface is None else {'surface_tol': float(self.surface)}),
                 **({} if self.support is None else {**of('support'), 'surface_support': int(self.support)}),
-                **of('fill', 'blend_fill', 'bands_fill')}
+                **of('fill', 'blend_fill', 'bands_fill'), **self._gain_result()}
+
+    def _gain_result(self) -> dict:
+        """The keys of ``result()`` that a gain compensation adds (none without one); waits for the sums."""
+        if self.gains is None:
+            return {}
+        n = 0 if self.gain_table is None else self.gain_table.shape[0]
+        sums = torch.zeros((0, n, _lib.MOSAIC_GAIN_WORDS), dtype=torch.int64, device=self.device) if n == 0 else self.gain_sums()
+        host = sums.cpu().numpy()
+        rms = torch.tensor([mosaic_gain_rms(p) for p in host], dtype=torch.float64).reshape(len(host), 3)
+        overlap = sums[-1, :, 0].clone() if len(host) else torch.zeros(n, dtype=torch.int64, device=self.device)
+        gains = torch.ones((0, 3), dtype=torch.float32, device=self.device) if n == 0 else self.gain_table.clone()
+        return {'gains': gains, 'gain_sums': sums, 'gain_rms': rms, 'gain_overlap': overlap, 'gain_rounds': int(self.gains),
+                'gain_limit': float(self.gain_limit)}
 
     def run(self, batches, options: MosaicOptions = MosaicOptions(), bounds=None, plain_atomic: bool = False, bands=None,
-            surface=None, support=None) -> 'Mosaic':
+            surface=None, support=None, gains=None, gain_limit=None) -> 'Mosaic':
         """Every phase over every batch, in the one order there is: the bounds (unless ``bounds`` is given), ``begin``; with
         ``surface`` (the tolerance T of the surface test, beside the options record) ``add_surface`` -- or, with ``support`` (the
         count M of supporting views, beside the record too; only with a surface), ``add_support`` over every batch for level 0,
@@ -1705,15 +1977,21 @@ class Mosaic:
         sequence of ``(first_ordinal, load)``, ``load()`` returning the batch's ``(views, Js)`` -- called once per phase, so a
         caller may hold only some of the images at a time; ``options``: as ``MosaicOptions.checked`` returns them;
         ``plain_atomic``: the surface, the splat and the accumulate phase in their plain forms.  With a surface test every phase
-        culls its batch anew, unless one batch is the whole request: that one is culled once.  Returns the mosaic."""
+        culls its batch anew, unless one batch is the whole request: that one is culled once.  With ``gains`` (the rounds R of the
+        gain compensation, beside the record; ``gain_limit``: its limit L) the splat is followed by ``add_span`` over every batch,
+        R times ``gain_pass`` and ``solve_gains``, and one more ``gain_pass`` that measures the final state; resolve, gather,
+        accumulate and the bands then see the gained images -- applied anew per phase and batch, unless one batch is the whole
+        request: that one is gained once and held.  Returns the mosaic."""
         batches = list(batches)
         if bounds is None:
             for _, load in batches:
                 self.add_bounds(*load())
         bands = mosaic_bands_checked(bands, options.blend, 'Mosaic.run')
         support = mosaic_support_checked(support, surface, 'Mosaic.run')
+        gains, gain_limit = mosaic_gains_checked(gains, gain_limit, 'Mosaic.run')
         self.begin(bounds, blend=options.blend, feather=options.feather, **({} if bands is None else {'bands': bands}),
-                   **({} if surface is None else {'surface': surface}), **({} if support is None else {'support': support}))
+                   **({} if surface is None else {'surface': surface}), **({} if support is None else {'support': support}),
+                   **({} if gains is None else {'gains': gains, 'gain_limit': gain_limit}))
         if surface is not None:
             if support is None:
                 for first, load in batches:
@@ -1727,7 +2005,19 @@ class Mosaic:
                 first, load = batches[0]
                 self._held = self.culled_images(*load(), first, count=True)
         try:
-            phases = [(self.splat, {'plain_atomic': plain_atomic}), (self.resolve, {}), (self.gather, {})]
+            for first, load in batches:
+                self.splat(*load(), first, plain_atomic=plain_atomic)
+            if gains is not None:
+                for first, load in batches:
+                    self.add_span(*load(), first, plain_atomic=plain_atomic)
+                for _ in range(gains):
+                    self.gain_pass(batches, plain=plain_atomic)
+                    self.solve_gains()
+                self.gain_pass(batches, plain=plain_atomic)
+                if len(batches) == 1:
+                    first, load = batches[0]
+                    self._held_gained = self.gained_images(*load(), first)
+            phases = [(self.resolve, {}), (self.gather, {})]
             if options.blend is not None:
                 phases.append((self.accumulate, {'plain': plain_atomic}))
             for phase, kw in phases:
@@ -1740,21 +2030,22 @@ class Mosaic:
                     self.accumulate_bands(*load(), first, plain=plain_atomic)
                 self.combine_bands()
         finally:
-            self._held = None
+            self._held = self._held_gained = None
         if options.fill is not None:
             self.fill(options.fill)
         return self
 
 
 def mosaic_of(views: list, Js: list, axes, gsd, bounds=None, batch: int = 32, plain_atomic: bool = False, blend=None,
-              fill=None, feather=None, bands=None, surface=None, support=None) -> 'Mosaic':
+              fill=None, feather=None, bands=None, surface=None, support=None, gains=None, gain_limit=None) -> 'Mosaic':
     """``Mosaic.run`` over device-resident ``views`` / ``Js`` (ordinal = position in the list), ``batch`` images per call; with
     ``blend`` (the blend depth H, metres) the accumulate phase and the normalise pass after them (``plain_atomic``: both the
     splat and the accumulate phase in their plain forms), with ``feather`` (the width F, source pixels; only with ``blend``) the
     feathered one; with ``bands`` (the count K of detail bands; only with ``blend``) the multi-band blend after them; with ``fill``
     (the reach R, metres) the hole filling after all of them (``MosaicOptions``); with ``surface`` (the tolerance T, metres) the
     surface test ahead of the splat (csrc/surface.h), with ``support`` (the count M of views; only with ``surface``) against the
-    view-supported top instead of the plain minimum (csrc/support.h)."""
+    view-supported top instead of the plain minimum (csrc/support.h); with ``gains`` (the rounds R) the per-image gain compensation
+    between the splat and the resolve (csrc/gains_mosaic.h), every gain within ``[1 / gain_limit, gain_limit]``."""
     views, Js = list(views), list(Js)
     if not views:
         raise ValueError('mosaic_of: no view')
@@ -1764,10 +2055,12 @@ def mosaic_of(views: list, Js: list, axes, gsd, bounds=None, batch: int = 32, pl
     bands = mosaic_bands_checked(bands, options.blend, 'mosaic_of')
     surface = None if surface is None else mosaic_surface_tol(surface)
     support = mosaic_support_checked(support, surface, 'mosaic_of')
+    gains, gain_limit = mosaic_gains_checked(gains, gain_limit, 'mosaic_of')
     batches = [(i, lambda i=i: (views[i:i + batch], Js[i:i + batch])) for i in range(0, len(views), batch)]
     return Mosaic(axes, gsd, views[0].depth.device).run(batches, options, bounds, plain_atomic, **({} if bands is None else {'bands': bands}),
                                                         **({} if surface is None else {'surface': surface}),
-                                                        **({} if support is None else {'support': support}))
+                                                        **({} if support is None else {'support': support}),
+                                                        **({} if gains is None else {'gains': gains, 'gain_limit': gain_limit}))
 
 
 def device_views_from_scene(scene, device='cuda') -> list[DeviceView]:

@@ -1424,7 +1424,8 @@ def _mosaic_picture(J: Tensor, stretch) -> np.ndarray:
 
 
 _MOSAIC_FLAG = {'grid': '--mosaic', 'blend': '--mosaic-blend', 'fill': '--mosaic-fill', 'feather': '--mosaic-feather',
-                'bands': '--mosaic-bands', 'surface': '--mosaic-surface', 'support': '--mosaic-support'}
+                'bands': '--mosaic-bands', 'surface': '--mosaic-surface', 'support': '--mosaic-support', 'gains': '--mosaic-gains',
+                'gain_limit': '--mosaic-gain-limit'}
 
 
 def _mosaic_refused(e: ValueError, fields=tuple(_MOSAIC_FLAG)) -> BaseException:
@@ -1445,7 +1446,8 @@ _MOSAIC_PNG = {   # how a row of engine.MOSAIC_OUTPUTS becomes its PNG: (the out
 
 def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, output_dir: Path, gsd: float | None = None, axes=None,
            stretch=None, device: str = 'cuda', blend: float | None = None, fill: float | None = None, feather: int | None = None,
-           bands: int | None = None, surface: float | None = None, support: int | None = None) -> dict:
+           bands: int | None = None, surface: float | None = None, support: int | None = None, gains: int | None = None,
+           gain_limit: float | None = None) -> dict:
     """One picture of the seabed from a finished restoration: every pixel of ``images`` (``sfm.Image`` objects or names of
     ``colmap_model``; at most ``engine.MAX_VIEWS``, ordinal = position) with a valid depth and a restored colour --
     ``results_dir / <name>.pt``, key ``J`` -- is dropped onto the plane grid ``axes`` (``mosaic_axes`` unless given) of ``gsd``
@@ -1509,7 +1511,16 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
     ``mosaic_culled_above.png`` (``mosaic_culled_picture`` of ``culled_above``) comes next to the other files, ``mosaic.pt`` gains
     ``support``, ``surface_source``, ``culled_above``, ``surface_top`` and ``surface_support``, ``surface`` is the supported top, and
     one more line is printed after the surface's.  The limit: an error that M or more images share passes, and a real feature that
-    one image alone sees more than T above what M images agree on is removed.  Not built: the single-pass k-smallest form."""
+    one image alone sees more than T above what M images agree on is removed.  Not built: the single-pass k-smallest form.
+
+    ``gains``: the rounds R (``engine.MOSAIC_GAIN_ROUNDS_RANGE``) of a per-image gain compensation between the splat and every later
+    phase (csrc/gains_mosaic.h): one gain per image and channel, found from the cells that two or more images share, so that images
+    restored with a water model each agree on the colour of the same seabed; ``gain_limit``: with ``gains``, the limit L
+    (``engine.MOSAIC_GAIN_LIMIT_RANGE``, ``engine.MOSAIC_GAIN_LIMIT`` unless given) -- every gain lies within [1 / L, L].  Every file
+    and key that is not a ``J`` stays as it is, byte for byte; every ``J`` is that of a run without the flag on the images times
+    their gains; ``mosaic.pt`` gains ``gains``, ``gain_sums``, ``gain_rms``, ``gain_overlap``, ``gain_rounds`` and ``gain_limit``, and
+    one more line is printed after the mosaic's and the surface's.  The rounds remove what overlapping images disagree on; a slow
+    drift along a chain of N images needs on the order of N^2 rounds and is not what the flag is for."""
     from . import engine
     sfm.require_gpu(device, 'mosaic')
     images = [colmap_model[im] if isinstance(im, str) else im for im in images]
@@ -1542,6 +1553,12 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
         raise _mosaic_refused(e)
     if support is not None and surface is None:
         raise SystemExit('--mosaic-support: only with --mosaic-surface T')
+    if gain_limit is not None and gains is None:
+        raise SystemExit('--mosaic-gain-limit: only with --mosaic-gains R')
+    try:
+        gains, gain_limit = engine.mosaic_gains_checked(gains, gain_limit, 'mosaic')
+    except ValueError as e:
+        raise _mosaic_refused(e)
     results_dir, output_dir = Path(results_dir), Path(output_dir)
     for image in images:   # before anything is decoded
         path = _consistency_file(results_dir, image)
@@ -1575,12 +1592,13 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
             m = engine.Mosaic(axes, gsd, device).run([(first, lambda batch=batch: resident(batch)) for first, batch in batches], options,
                                                      **({} if bands is None else {'bands': bands}),
                                                      **({} if surface is None else {'surface': surface}),
-                                                     **({} if support is None else {'support': support}))
+                                                     **({} if support is None else {'support': support}),
+                                                     **({} if gains is None else {'gains': gains, 'gain_limit': gain_limit}))
         except ValueError as e:
-            # Two refusals of the run belong to a flag: begin's of the grid (--mosaic) and normalize's of a cell's sample count
-            # (--mosaic-blend).  The options were checked above, so begin and fill have nothing left to refuse in them; every other
+            # Three refusals of the run belong to a flag: begin's of the grid (--mosaic), normalize's of a cell's sample count
+            # (--mosaic-blend) and the gain passes' of a cell's sample count or an image's size (--mosaic-gains).  The options were checked above, so begin and fill have nothing left to refuse in them; every other
             # ValueError (of a view, of a restored image) passes as it is.
-            raise _mosaic_refused(e, ('grid', 'blend'))
+            raise _mosaic_refused(e, ('grid', 'blend', 'gains'))
         out = m.result()
         pictures = [(png, _MOSAIC_PNG[how](out[key], stretch)) for key, (_, _, _, _, png, how) in engine.MOSAIC_OUTPUTS.items()
                     if png is not None and key in out]
@@ -1619,6 +1637,16 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
         print(f'mosaic support of {support} views: {int(((out["support"] < support) & filled).sum())} of {n_filled} filled cells rest on '
               f'fewer than {support}; {above} of {part} samples ({100.0 * above / max(1, part):.1f} %) stand more than '
               f'{float(surface):.6g} m above their cell\'s supported top, in {int((out["culled_above"] > 0).sum())} cells')
+    if gains is not None:
+        g, rms, overlap = out['gains'].double(), out['gain_rms'], out['gain_overlap']
+        far = (g.log().abs().max(dim=1).values * (overlap > 0)).argmax() if len(images) else 0
+        lo, hi = np.float32(1.0 / gain_limit), np.float32(gain_limit)
+        clipped = 0 if gain_limit == 1.0 else int((((out['gains'] == float(lo)) | (out['gains'] == float(hi))) & (overlap > 0)[:, None]).sum())
+        print(f'mosaic gains of {gains} rounds (limit {gain_limit:.6g}): {int((overlap > 0).sum())} of {len(images)} images share a cell with '
+              f'another; RMS disagreement in shared cells '
+              + ' '.join(f'{ch} {float(rms[0, c]):.6g} -> {float(rms[-1, c]):.6g}' for c, ch in enumerate('RGB'))
+              + f'; largest correction {images[int(far)].name} (gain R {float(g[far, 0]):.6g} G {float(g[far, 1]):.6g} B {float(g[far, 2]):.6g}); '
+              f'{clipped} values clipped')
     if blend is not None:
         samples = out['samples'].to(torch.int64)
         total, most, several = int(samples.sum()), int(samples.max()), int((samples > 1).sum())
@@ -1682,8 +1710,9 @@ _MODE_REFUSES = {   # mode -> (flag, why), in the order they are looked at
 
 _ONLY_WITH = [   # (flag, the flag it needs, that one's value), in the order they are looked at
     ('--mosaic-gsd', '--mosaic', 'DIR'), ('--mosaic-blend', '--mosaic', 'DIR'), ('--mosaic-fill', '--mosaic', 'DIR'),
-    ('--mosaic-feather', '--mosaic-blend', 'H'), ('--mosaic-bands', '--mosaic-blend', 'H'), ('--mosaic-support', '--mosaic-surface', 'T'),
-    ('--mosaic-surface', '--mosaic', 'DIR'),
+    ('--mosaic-feather', '--mosaic-blend', 'H'), ('--mosaic-bands', '--mosaic-blend', 'H'),
+    ('--mosaic-gain-limit', '--mosaic-gains', 'R'), ('--mosaic-gains', '--mosaic', 'DIR'),
+    ('--mosaic-support', '--mosaic-surface', 'T'), ('--mosaic-surface', '--mosaic', 'DIR'),
 ]
 
 
@@ -1702,8 +1731,8 @@ def _refuse_mode_flags(args, mode: str) -> None:
 
 
 def _refuse_mosaic_values(args, world: int = 1) -> None:
-    """The values of --mosaic-gsd, --mosaic-blend, --mosaic-fill, --mosaic-feather, --mosaic-bands, --mosaic-surface and
-    --mosaic-support and the world size a mosaic takes, refused before any file is opened."""
+    """The values of --mosaic-gsd, --mosaic-blend, --mosaic-fill, --mosaic-feather, --mosaic-bands, --mosaic-surface,
+    --mosaic-support, --mosaic-gains and --mosaic-gain-limit and the world size a mosaic takes, refused before any file is opened."""
     gsd = getattr(args, 'mosaic_gsd', None)
     if gsd is not None and not (np.isfinite(gsd) and gsd > 0):
         raise SystemExit(f'--mosaic-gsd: G must be a finite size > 0 in metres, not {gsd}')
@@ -1725,6 +1754,14 @@ def _refuse_mosaic_values(args, world: int = 1) -> None:
     lo, hi = engine.MOSAIC_SUPPORT_RANGE
     if views is not None and not (np.isfinite(views) and lo <= views <= hi and views == int(views)):
         raise SystemExit(f'{_MOSAIC_FLAG["support"]}: M must be an integer within [{lo:g}, {hi:g}] views, not {views:g}')
+    rounds = getattr(args, 'mosaic_gains', None)
+    lo, hi = engine.MOSAIC_GAIN_ROUNDS_RANGE
+    if rounds is not None and not (np.isfinite(rounds) and lo <= rounds <= hi and rounds == int(rounds)):
+        raise SystemExit(f'{_MOSAIC_FLAG["gains"]}: R must be an integer within [{lo:g}, {hi:g}] rounds, not {rounds:g}')
+    limit = getattr(args, 'mosaic_gain_limit', None)
+    lo, hi = engine.MOSAIC_GAIN_LIMIT_RANGE
+    if limit is not None and not (np.isfinite(limit) and lo <= limit <= hi):
+        raise SystemExit(f'{_MOSAIC_FLAG["gain_limit"]}: L must be a finite limit within [{lo:g}, {hi:g}] times, not {limit}')
     if world > 1:
         raise SystemExit(f'--mosaic: a world size of {world} is not supported yet: the four phases are separate entries of the library '
                          f'so that ranks can all-reduce bounds, keys and pixel words between them, but that all-reduce is not built; '
@@ -1837,7 +1874,8 @@ def parse_args(args: argparse.Namespace):
             mosaic(images, colmap_model, mosaic_dir, args.output_dir, gsd=getattr(args, 'mosaic_gsd', None), stretch=stretch, device=device,
                    blend=getattr(args, 'mosaic_blend', None), fill=getattr(args, 'mosaic_fill', None),
                    feather=getattr(args, 'mosaic_feather', None), bands=getattr(args, 'mosaic_bands', None),
-                   surface=getattr(args, 'mosaic_surface', None), support=getattr(args, 'mosaic_support', None))
+                   surface=getattr(args, 'mosaic_surface', None), support=getattr(args, 'mosaic_support', None),
+                   gains=getattr(args, 'mosaic_gains', None), gain_limit=getattr(args, 'mosaic_gain_limit', None))
         elif check is not None:
             if world > 1:   # the targets' records are gathered on rank 0
                 sdist.init_process_group()
@@ -2115,6 +2153,16 @@ def build_parser() -> argparse.ArgumentParser:
                                'patch in a single view no longer owns its cells; M = 1 is --mosaic-surface alone; writes '
                                'mosaic_culled_above.png, adds support, surface_source, culled_above, surface_top and surface_support '
                                'to mosaic.pt and prints one more line')
+    p.extras.add_argument('--mosaic-gains', type=float, metavar='R', default=argparse.SUPPRESS,
+                          help='with --mosaic: also a per-image gain compensation -- R rounds (an integer, 1..64) find one gain per '
+                               'image and channel from the cells that two or more images share, so that images restored with a water '
+                               'model each agree on the colour of the same seabed before anything is resolved or blended (fixed-point '
+                               'sums: the same bits in any order); every file that is not a picture of J stays as it is; removes seams '
+                               'between overlapping images, not a slow drift along a long chain; adds gains, gain_sums, gain_rms, '
+                               'gain_overlap, gain_rounds and gain_limit to mosaic.pt and prints one more line')
+    p.extras.add_argument('--mosaic-gain-limit', type=float, metavar='L', default=argparse.SUPPRESS,
+                          help='with --mosaic-gains: every gain is kept within [1/L, L] (1..16; 2 unless given; 1 leaves every file as '
+                               'it is without the flag)')
     p.extras.add_argument('--common-stretch', action='store_true', default=argparse.SUPPRESS,
                           help='with --shared-water or --apply-water: stretch every <stem>_rgb.png between the SAME per-channel 1st '
                                'and 99th percentile, those of the valid pixels of all images of the request pooled (all ranks), '
