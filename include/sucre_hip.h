@@ -752,9 +752,31 @@ int sucre_view_consistency(int H, int W, int n_views, const sucre_view_t *target
  * All three only enqueue.  Checked before any launch as above, and: a NULL or misaligned span_dev (8 bytes), gains_dev, J_out, acc_dev
  * or sums_dev (128 bytes), n_ordinals outside 1..4096 or below first_ordinal + n_images, an image of more than 2^26 pixels (its sums
  * could pass 2^62), a J_out that overlaps an image's J without being it, unknown flags.
+ *
+ * The direct solve of the gain compensation (csrc/gains_direct.h): the rounds' objective solved exactly, once.  Integer state only.
+ * slot_ord_dev: (Hm Wm, SUCRE_MOSAIC_GAIN_SLOTS = 8) uint32, the caller starts every word at all ones (free); slot_sum_dev:
+ * (Hm Wm, 8, 4) int64 -- n, sum Xq x 3 --, slot_over_dev: (Hm Wm) uint32, pairs_dev: (n_ordinals, n_ordinals, 4) int64, diag_dev:
+ * (n_ordinals, 16) int64, 4 words used; the caller starts all of these at zero.
+ *   sucre_mosaic_gain_slots  after the span, over ALL images, any split into calls: a sample of a shared cell takes the cell's slot
+ *                            that holds its ordinal, or claims the first free one, and adds 1 and Xq_c = q(J_c); a sample that finds
+ *                            all eight held by other images sets slot_over[cell] = 1.  Which slot an image holds depends on
+ *                            arrival (sort a cell's slots by ordinal); the slots of a cell with slot_over set hold nothing to read.
+ *                            flags: SUCRE_MOSAIC_PLAIN_ATOMIC -- every sample for itself, without the run sums of a wave's lanes
+ *   sucre_mosaic_gain_pairs  once, after the slots: for every shared cell with slot_over 0, N = sum n_a, and for every pair of held
+ *                            slots a <= b with i = min, j = max of their ordinals: pairs[i][j][c] += llrint(((double)S_a,c
+ *                            (double)S_b,c) / (double)N) for c in 0..2, pairs[i][j][3] += 1.  table_entries: the size of a
+ *                            workgroup's LDS table of pair sums, a power of two up to 512, 0 for 512 (any size: the same words).
+ *                            flags: SUCRE_MOSAIC_PLAIN_ATOMIC -- global atomics per cell and pair, no table
+ *   sucre_mosaic_gain_diag   after the slots, over ALL images: the image's row takes 1 and Xq Xq x 3 for every sample in a shared
+ *                            cell with slot_over 0.  flags: SUCRE_MOSAIC_PLAIN_ATOMIC -- four atomics per 256 pixels
+ * All three only enqueue.  Checked before any launch as above, and: a NULL or misaligned span_dev (8 bytes), slot_ord_dev (4),
+ * slot_sum_dev (8), slot_over_dev (4), pairs_dev (8) or diag_dev (128), n_ordinals outside 1..4096, a table_entries that is no such
+ * power of two, a grid of 2^43 cells or more (pairs: its workgroups of 4096 cells must fit a launch), an image of more than 2^26
+ * pixels (diag), unknown flags.
  */
 #define SUCRE_MOSAIC_PLAIN_ATOMIC 1u
 #define SUCRE_MOSAIC_GAIN_WORDS 10
+#define SUCRE_MOSAIC_GAIN_SLOTS 8
 #define SUCRE_MOSAIC_SUPPORT_MAX 4
 #define SUCRE_MOSAIC_ACC_WORDS 8
 #define SUCRE_MOSAIC_FEATHER_MAX 1024
@@ -816,6 +838,15 @@ int sucre_mosaic_gain_apply(void *table_dev, int n_images, const sucre_mosaic_im
 int sucre_mosaic_gain_sums(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
                            const sucre_mosaic_grid_t *grid, const uint32_t *span_dev, const int64_t *acc_dev, const float *gains_dev,
                            int n_ordinals, int64_t *sums_dev, unsigned flags, void *stream);
+int sucre_mosaic_gain_slots(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                            const sucre_mosaic_grid_t *grid, const uint32_t *span_dev, uint32_t *slot_ord_dev, int64_t *slot_sum_dev,
+                            uint32_t *slot_over_dev, unsigned flags, void *stream);
+int sucre_mosaic_gain_pairs(const sucre_mosaic_grid_t *grid, const uint32_t *span_dev, const uint32_t *slot_ord_dev,
+                            const int64_t *slot_sum_dev, const uint32_t *slot_over_dev, int n_ordinals, int64_t *pairs_dev, int table_entries,
+                            unsigned flags, void *stream);
+int sucre_mosaic_gain_diag(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                           const sucre_mosaic_grid_t *grid, const uint32_t *span_dev, const uint32_t *slot_over_dev, int n_ordinals,
+                           int64_t *diag_dev, unsigned flags, void *stream);
 
 /*
  * ---- hole filling of the finished mosaic: a bounded push-pull over a pyramid of the grid ------------------------------------------

@@ -16,6 +16,7 @@
 #include "surface.h"
 #include "support.h"
 #include "gains_mosaic.h"
+#include "gains_direct.h"
 
 namespace sucre {
 
@@ -1270,6 +1271,68 @@ int sucre_mosaic_gain_sums(void *table_dev, int n_images, const sucre_mosaic_ima
                                              reinterpret_cast<const long long *>(acc_dev), gains_dev,
                                              reinterpret_cast<unsigned long long *>(sums_dev), static_cast<hipStream_t>(stream)),
                      "sucre_mosaic_gain_sums");
+}
+
+/* ---- the direct solve of the gain compensation: a cell's slots, the pair sums, the diag (gains_direct.h) ---- */
+
+static int check_gain_slot_state(const uint32_t *span_dev, const void *slot_ord_dev, const void *slot_sum_dev, const void *slot_over_dev,
+                                 bool need_slots) {
+    if (!span_dev || !aligned(span_dev, 8)) return fail(SUCRE_ERR_ARG, "span_dev is NULL or not 8-byte aligned");
+    if (need_slots && (!slot_ord_dev || !aligned(slot_ord_dev, 4))) return fail(SUCRE_ERR_ARG, "slot_ord_dev is NULL or not 4-byte aligned");
+    if (need_slots && (!slot_sum_dev || !aligned(slot_sum_dev, 8))) return fail(SUCRE_ERR_ARG, "slot_sum_dev is NULL or not 8-byte aligned");
+    if (!slot_over_dev || !aligned(slot_over_dev, 4)) return fail(SUCRE_ERR_ARG, "slot_over_dev is NULL or not 4-byte aligned");
+    return SUCRE_OK;
+}
+
+int sucre_mosaic_gain_slots(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                            const sucre_mosaic_grid_t *grid, const uint32_t *span_dev, uint32_t *slot_ord_dev, int64_t *slot_sum_dev,
+                            uint32_t *slot_over_dev, unsigned flags, void *stream) {
+    if (int rc = check_mosaic_images(table_dev, n_images, images, first_ordinal)) return rc;
+    MosaicGrid g;
+    if (int rc = check_mosaic_grid(grid, &g)) return rc;
+    if (int rc = check_gain_slot_state(span_dev, slot_ord_dev, slot_sum_dev, slot_over_dev, true)) return rc;
+    if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
+    return check_hip(launch_mosaic_gain_slots((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) != 0, table_dev, n_images, images, first_ordinal, g, span_dev,
+                                              slot_ord_dev, reinterpret_cast<unsigned long long *>(slot_sum_dev), slot_over_dev,
+                                              static_cast<hipStream_t>(stream)), "sucre_mosaic_gain_slots");
+}
+
+int sucre_mosaic_gain_pairs(const sucre_mosaic_grid_t *grid, const uint32_t *span_dev, const uint32_t *slot_ord_dev,
+                            const int64_t *slot_sum_dev, const uint32_t *slot_over_dev, int n_ordinals, int64_t *pairs_dev, int table_entries,
+                            unsigned flags, void *stream) {
+    MosaicGrid g;
+    if (int rc = check_mosaic_grid(grid, &g)) return rc;
+    // ceil(cells / kPairTileCells) workgroups must stay within the 2^31 - 1 of a launch
+    if ((uint64_t)g.Hm * (uint64_t)g.Wm >= (1ull << 43)) return fail(SUCRE_ERR_ARG, "mosaic of %dx%d cells: the pairs take fewer than 2^43", g.Wm, g.Hm);
+    if (int rc = check_gain_slot_state(span_dev, slot_ord_dev, slot_sum_dev, slot_over_dev, true)) return rc;
+    if (n_ordinals < 1 || n_ordinals > kMaxViews) return fail(SUCRE_ERR_ARG, "n_ordinals=%d outside [1,%d]", n_ordinals, kMaxViews);
+    if (!pairs_dev || !aligned(pairs_dev, 8)) return fail(SUCRE_ERR_ARG, "pairs_dev is NULL or not 8-byte aligned");
+    if (table_entries == 0) table_entries = kPairTableMax;
+    if (table_entries < 1 || table_entries > kPairTableMax || (table_entries & (table_entries - 1)))
+        return fail(SUCRE_ERR_ARG, "table_entries=%d is not 0 or a power of two within [1,%d]", table_entries, kPairTableMax);
+    if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
+    return check_hip(launch_mosaic_gain_pairs((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) != 0, g, span_dev, slot_ord_dev,
+                                              reinterpret_cast<const long long *>(slot_sum_dev), slot_over_dev, n_ordinals,
+                                              reinterpret_cast<unsigned long long *>(pairs_dev), table_entries, static_cast<hipStream_t>(stream)),
+                     "sucre_mosaic_gain_pairs");
+}
+
+int sucre_mosaic_gain_diag(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                           const sucre_mosaic_grid_t *grid, const uint32_t *span_dev, const uint32_t *slot_over_dev, int n_ordinals,
+                           int64_t *diag_dev, unsigned flags, void *stream) {
+    if (int rc = check_mosaic_images(table_dev, n_images, images, first_ordinal)) return rc;
+    MosaicGrid g;
+    if (int rc = check_mosaic_grid(grid, &g)) return rc;
+    if (int rc = check_gain_rows(n_images, first_ordinal, n_ordinals)) return rc;
+    for (int i = 0; i < n_images; ++i)
+        if ((uint64_t)images[i].H * (uint64_t)images[i].W > kGainMaxPixels)
+            return fail(SUCRE_ERR_ARG, "image %d: %dx%d pixels, more than the 2^26 whose sums stay below 2^62", i, images[i].W, images[i].H);
+    if (int rc = check_gain_slot_state(span_dev, nullptr, nullptr, slot_over_dev, false)) return rc;
+    if (!diag_dev || !aligned(diag_dev, 128)) return fail(SUCRE_ERR_ARG, "diag_dev is NULL or not 128-byte aligned");
+    if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
+    return check_hip(launch_mosaic_gain_diag((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) != 0, table_dev, n_images, images, first_ordinal, g, span_dev,
+                                             slot_over_dev, reinterpret_cast<unsigned long long *>(diag_dev), static_cast<hipStream_t>(stream)),
+                     "sucre_mosaic_gain_diag");
 }
 
 /* ---- hole filling of the finished mosaic: a bounded push-pull over a pyramid of the grid (fill.h) ---- */

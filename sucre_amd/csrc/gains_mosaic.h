@@ -11,7 +11,7 @@
 // over the image's samples in shared cells.  One ROUND is one such pair; the host solves (engine.mosaic_gain_solve, float64) and
 // fixes the gauge -- the overlap-weighted mean gain is 1 -- and the limit, 1/L <= g <= L.  The rounds are a Jacobi-style
 // relaxation: what overlapping images disagree on (the seams) goes in a few rounds; a slow drift along a chain of N images takes
-// on the order of N^2 rounds and is not what this is for.
+// on the order of N^2 rounds and is not what this is for: gains_direct.h solves the same objective exactly, once, for that.
 //
 // Every kernel takes the image's J as the phases after the surface test see it (the culled copy when there is one), walks as
 // mosaic.h's phases do (mosaic_walk.h: one lane per pixel, 32 images per launch, ordinal = first_ordinal + index) and forms a
@@ -63,9 +63,8 @@
 // reused accumulate is 92 % of a round, as expected.  Three rounds and the measuring pass: 116 ms on this survey, whose RMS
 // disagreement in the shared cells falls from 0.034 / 0.031 / 0.031 to 0.015 / 0.0041 / 0.0035 (R / G / B; factors 0.9 .. 1.1).
 // Not built: run sums of adjacent lanes ahead of the span's atomics (a wave's lanes share cells; it would take the max side's
-// (image, cell) atomics down by the pixels per cell and image); a direct pairwise least-squares solve (per-pair sums need n^2
-// words and a cell's pair list; the rounds need 10 n); a 4-word reference pass (the reference reuses the blend's accumulate and
-// pays for its three raw-colour words); multi-rank mosaics -- span (min / max), the reference accumulator (sum) and the sums
+// (image, cell) atomics down by the pixels per cell and image); a 4-word reference pass (the reference reuses the blend's
+// accumulate and pays for its three raw-colour words); multi-rank mosaics -- span (min / max), the reference accumulator (sum) and the sums
 // (sum) are the tensors an all-reduce would combine.
 #pragma once
 #include "mosaic.h"
@@ -80,6 +79,33 @@ constexpr uint64_t kGainMaxPixels = 1ull << 26;   // H W of an image the sums ta
 // The float32 clamp / quantise of the sums: one IEEE operation per step; a NaN comes out as -8 (fmaxf drops it), an infinity as +-8.
 __device__ __forceinline__ long long gain_quantise(float x) {
     return (long long)rintf(fminf(fmaxf(x, -8.0f), 8.0f) * 16384.0f);
+}
+
+__device__ __forceinline__ long long wave_sum_i64(long long x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+    return x;
+}
+
+// The workgroup's kWords sums into the row of `ordinal`, and the lanes' registers back to zero.  Every lane of the workgroup calls it.
+// (The ten sums of a pass, and the four words per image of the direct solve's diag, gains_direct.h.)
+template <int kWords>
+__device__ __forceinline__ void gain_flush(long long (&w)[kWords], long long (&part)[4][kWords], int ordinal,
+                                           unsigned long long *__restrict__ sums) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < kWords; ++i) {
+        const long long x = wave_sum_i64(w[i]);
+        if (lane == 0) part[wave][i] = x;
+        w[i] = 0;
+    }
+    __syncthreads();
+    if (threadIdx.x < kWords) {
+        const int i = threadIdx.x;
+        const long long x = (part[0][i] + part[1][i]) + (part[2][i] + part[3][i]);
+        if (x) __hip_atomic_fetch_add(sums + (size_t)ordinal * kGainRowWords + i, (unsigned long long)x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();   // part is written again by the next flush
 }
 
 // The span pass over images[0 .. n): the launches of a phase of mosaic.h; span: lowered / raised.

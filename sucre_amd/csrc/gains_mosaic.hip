@@ -39,31 +39,6 @@ __global__ __launch_bounds__(256) void mosaic_gain_apply_kernel(const MosaicImag
     o[0] = j0 * g0; o[1] = j1 * g1; o[2] = j2 * g2;
 }
 
-__device__ __forceinline__ long long wave_sum_i64(long long x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    return x;
-}
-
-// The workgroup's ten sums into the row of `ordinal`, and the lanes' registers back to zero.  Every lane of the workgroup calls it.
-__device__ __forceinline__ void gain_flush(long long (&w)[kGainWords], long long (&part)[4][kGainWords], int ordinal,
-                                           unsigned long long *__restrict__ sums) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < kGainWords; ++i) {
-        const long long x = wave_sum_i64(w[i]);
-        if (lane == 0) part[wave][i] = x;
-        w[i] = 0;
-    }
-    __syncthreads();
-    if (threadIdx.x < kGainWords) {
-        const int i = threadIdx.x;
-        const long long x = (part[0][i] + part[1][i]) + (part[2][i] + part[3][i]);
-        if (x) __hip_atomic_fetch_add(sums + (size_t)ordinal * kGainRowWords + i, (unsigned long long)x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();   // part is written again by the next flush
-}
-
 // kPlain: a workgroup per 256-pixel block, one set of atomics each.  Otherwise a workgroup walks kGainSumBlocks consecutive blocks
 // and flushes when the image changes (the block's image is workgroup-uniform) and at the end.
 template <bool kPlain>

@@ -74,18 +74,6 @@ __global__ __launch_bounds__(256) void mosaic_kernel(const MosaicImage *__restri
 
 // ---- the blend (mosaic.h, "The blend"): fixed-point sums per cell, then one pass over the cells ----
 
-// Suffix sum over the lane's run: after the step with offset o, x holds the sum over lanes lane .. min(lane + 2 o, end of run) - 1.
-// `left`: lanes from this one to the end of its run, this one included.
-template <typename T>
-__device__ __forceinline__ T run_sum(T x, int left) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T y = __shfl_down(x, o);
-        if (o < left) x += y;
-    }
-    return x;
-}
-
 // kFeather: the weight takes one more factor, f of the pixel's capped squared border distance (mosaic.h, "The feather").  The
 // lane's word of the map sits where the lane sits in the launch: word blockIdx.x 256 + threadIdx.x of `feather.dist2`.
 template <bool kPlain, bool kFeather>

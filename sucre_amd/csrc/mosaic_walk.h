@@ -52,6 +52,18 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t x) {
     return x;
 }
 
+// Suffix sum over the lane's run: after the step with offset o, x holds the sum over lanes lane .. min(lane + 2 o, end of run) - 1.
+// `left`: lanes from this one to the end of its run, this one included.  (The blend's accumulate and the direct gain solve's slots.)
+template <typename T>
+__device__ __forceinline__ T run_sum(T x, int left) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T y = __shfl_down(x, o);
+        if (o < left) x += y;
+    }
+    return x;
+}
+
 // The walk of every phase: the workgroup's image, the lane's pixel and what mosaic_pixel says of it.  False for a lane past the
 // image's last pixel and for a pixel that does not take part.
 __device__ __forceinline__ bool mosaic_walk(const MosaicImage *__restrict__ table, int n_images, const MosaicGrid &g,

@@ -1030,6 +1030,10 @@ MOSAIC_GAIN_LIMIT = 2.0                 # the limit unless one is given
 MOSAIC_GAIN_MAX_PIXELS = 1 << 26        # pixels of one image from which the gain sums' int64 words may pass 2^62
 _MOSAIC_GAINS = ('gain rounds R', MOSAIC_GAIN_ROUNDS_RANGE, True, 'rounds', int)   # beside the record, as the supporting views
 _MOSAIC_GAIN_LIMIT = ('gain limit L', MOSAIC_GAIN_LIMIT_RANGE, False, 'times', float)
+MOSAIC_GAIN_SOLVES = ('rounds', 'direct')   # how the first round's gains are found (csrc/gains_direct.h: 'direct')
+MOSAIC_GAIN_PRIOR = 2.0 ** -20              # mu of the direct solve: the weight of (g - 1)^2 against the data term
+MOSAIC_GAIN_DIRECT_CELL_BYTES = 292         # the direct solve's slots: 32 + 256 + 4 bytes per cell
+MOSAIC_GAIN_DIRECT_MEMORY = 0.8             # the share of the free device memory the direct solve's state may take
 
 
 def _mosaic_value(field: str, value, row=None):
@@ -1148,6 +1152,108 @@ def mosaic_gain_solve(sums, G, limit):
         for i in seen:
             out[i, c] = np.float32(min(max(g[i] / s if s > 0 else g[i], lo), L))
     return out
+
+
+def _device_free_bytes(device) -> int:
+    """The free memory of ``device`` in bytes, as the driver reports it now."""
+    with torch.cuda.device(device):
+        return int(torch.cuda.mem_get_info()[0])
+
+
+def mosaic_gain_solve_checked(gain_solve, gains, who: str):
+    """None for the rounds alone (``gain_solve`` None or 'rounds'), or 'direct'; ValueError (``field``: 'gain_solve') for any other
+    value, and for a solve without rounds (``gains`` None), in the name of ``who``."""
+    if gain_solve is None:
+        return None
+    if not isinstance(gain_solve, str) or gain_solve not in MOSAIC_GAIN_SOLVES:
+        raise _mosaic_refusal('gain_solve', f'mosaic gain solve must be one of {" or ".join(MOSAIC_GAIN_SOLVES)}, not {gain_solve!r}')
+    if gains is None:
+        raise _mosaic_refusal('gain_solve', f'{who}: the solve finds the gains of the first round; give the rounds too (gains=R)')
+    return 'direct' if gain_solve == 'direct' else None
+
+
+def mosaic_gain_pair_matrix(pairs, word: int) -> np.ndarray:
+    """Word ``word`` of ``pairs`` -- (n, n, 4) integers, the upper triangle as ``sucre_mosaic_gain_pairs`` leaves it -- as the
+    symmetric (n, n) float64 matrix (an int64 becomes the nearest float64, as ``float()`` of the integer would)."""
+    upper = np.triu(np.asarray(pairs)[:, :, word].astype(np.int64))
+    return upper.astype(np.float64) + np.triu(upper, 1).T.astype(np.float64)
+
+
+def mosaic_gain_direct_unclamped(pairs, diag, prior=MOSAIC_GAIN_PRIOR):
+    """The solution of the direct solve's normal equations before gauge and clamp: ``(x, kept)``, ``x`` (n, 3) float64 -- per
+    channel, over the images with ``n_i > 0`` and ``Q_i > 0``, the ``g`` of ``(A + mu diag(Q)) g = mu Q`` (``A_ii = Q_i - P_ii``,
+    ``A_ij = -P_ij``) by ``numpy.linalg.solve``; NaN for every other image --, ``kept`` the channels whose solve raises or returns
+    a gain that is not finite and positive (their column is NaN)."""
+    diag = np.asarray(diag).astype(np.int64).reshape(-1, 4)
+    mu = float(prior)
+    x = np.full((len(diag), 3), np.nan, np.float64)
+    kept = []
+    for c in range(3):
+        act = np.nonzero((diag[:, 0] > 0) & (diag[:, 1 + c] > 0))[0]
+        if len(act) == 0:
+            continue
+        Q = diag[act, 1 + c].astype(np.float64)
+        M = -mosaic_gain_pair_matrix(pairs, c)[np.ix_(act, act)]
+        M[np.diag_indices(len(act))] += Q * (1.0 + mu)
+        try:
+            g = np.linalg.solve(M, mu * Q)
+        except np.linalg.LinAlgError:
+            g = None
+        if g is None or not bool(np.all(np.isfinite(g) & (g > 0))):
+            kept.append(c)
+            continue
+        x[act, c] = g
+    return x, kept
+
+
+def mosaic_gain_solve_direct(pairs, diag, G, limit, prior=MOSAIC_GAIN_PRIOR):
+    """The direct solve of the gain compensation (csrc/gains_direct.h) on the host, in float64: ``pairs`` (n, n, 4) integers, the
+    upper triangle -- per pair of images ``P_ij`` x 3 and the cells they share --, ``diag`` (n, 4) integers -- per image the sample
+    count n_i and ``Q_i = sum Xq Xq`` x 3 --, ``G`` (n, 3) the gains the images have, ``limit`` L, ``prior`` mu.  Per channel, over the
+    images with ``n_i > 0`` and ``Q_i > 0``: ``A_ii = Q_i - P_ii``, ``A_ij = -P_ij``, and ``(A + mu diag(Q)) g = mu Q`` by
+    ``numpy.linalg.solve`` (``mosaic_gain_direct_unclamped``) -- the minimum of ``g^T A g + mu sum Q_i (g_i - 1)^2``; A alone is
+    singular exactly when the images can be made to agree, and the prior pulls a group of images that shares nothing with the rest
+    towards 1.  A channel whose solve raises or returns a gain that is not finite and positive keeps the gains it had, untouched,
+    and is reported.  Then the gauge of ``mosaic_gain_solve`` -- over the images with ``n_i > 0`` the n-weighted ``fsum`` mean is 1 --,
+    the clamp to ``[1 / L, L]`` and float32.  What an image outside the solve keeps: one with ``n_i = 0`` keeps the gain it had, to
+    the bit (it is in no shared cell that counts, and outside the gauge); one with ``n_i > 0`` and ``Q_i = 0`` enters the gauge
+    with the gain it had, as an image whose sums are not positive does in ``mosaic_gain_solve``, and so comes out as that gain
+    over the gauge's mean, clamped.  Returns ``(gains (n, 3) float32 (numpy), kept)``, ``kept`` the list of the reported channels."""
+    x, kept = mosaic_gain_direct_unclamped(pairs, diag, prior)
+    counts = np.asarray(diag).astype(np.int64).reshape(-1, 4)[:, 0]
+    old = np.asarray(G, dtype=np.float32).reshape(len(counts), 3)
+    L = float(limit)
+    lo = 1.0 / L
+    out = old.copy()
+    seen = np.nonzero(counts > 0)[0].tolist()
+    if not seen:
+        return out, kept
+    weight = [float(counts[i]) for i in seen]
+    n_all = math.fsum(weight)
+    for c in range(3):
+        if c in kept:
+            continue
+        g = [float(old[i, c]) if np.isnan(x[i, c]) else float(x[i, c]) for i in seen]
+        s = math.fsum(w * gi for w, gi in zip(weight, g)) / n_all
+        for i, gi in zip(seen, g):
+            out[i, c] = np.float32(min(max(gi / s if s > 0 else gi, lo), L))
+    return out, kept
+
+
+def mosaic_gain_groups(pairs, diag) -> int:
+    """The connected groups of the overlap graph: over the images with ``diag[i][0] > 0``, joined where ``pairs[i][j][3] > 0``
+    (a breadth-first walk over the boolean adjacency: every image's row is read once)."""
+    live = np.asarray(diag).astype(np.int64).reshape(-1, 4)[:, 0] > 0
+    adj = mosaic_gain_pair_matrix(pairs, 3) > 0
+    todo, groups = live.copy(), 0
+    while todo.any():
+        groups += 1
+        front = np.zeros_like(todo)
+        front[np.argmax(todo)] = True
+        while front.any():
+            todo &= ~front
+            front = adj[front].any(axis=0) & todo
+    return groups
 
 
 def mosaic_gain_rms(sums) -> list:
@@ -1326,7 +1432,20 @@ class Mosaic:
     float64 -- row r: the RMS disagreement in the shared cells at the gains entering pass r --, ``gain_overlap`` (n,) int64 -- the
     samples of every image in shared cells --, ``gain_rounds`` (= R) and ``gain_limit`` (= L).  One more buffer of 12 bytes per
     padded pixel of the largest batch is held.  A finite positive gain makes and removes no NaN, so every output that is not a
-    ``J`` keeps its bits, and L = 1 keeps every output's."""
+    ``J`` keeps its bits, and L = 1 keeps every output's.
+
+    The direct solve: ``begin(gains=R, gain_solve='direct')`` (csrc/gains_direct.h) -- the rounds' objective solved exactly, once,
+    in place of the first round's solve: what a drift along a chain of images takes the rounds on the order of N^2 rounds for.  After
+    the first pass ``add_gain_slots(views, Js, first_ordinal)`` over ALL the images (the first call allocates ``slot_ord``
+    ((Hm Wm, 8) int32 bit patterns, all ones: free), ``slot_sum`` ((Hm Wm, 8, 4) int64), ``slot_over`` ((Hm Wm,) int32),
+    ``gain_pairs_words`` ((n, n, 4) int64) and ``gain_diag_words`` ((n, 16) int64, four words used): 292 bytes per cell and
+    32 n^2 + 128 n, refused beyond ``MOSAIC_GAIN_DIRECT_MEMORY`` of the free device memory before any of it is allocated), then
+    ``gain_pairs()``, then ``add_gain_diag`` over ALL the images, then ``solve_gains_direct()`` (``mosaic_gain_solve_direct``, on the
+    host).  ``result()`` then also holds ``gain_solve`` ('direct'), ``gain_direct`` (n,3) float32 -- the table that solve produced --,
+    ``gain_pair_index`` (P,2) int32 and ``gain_pair_words`` (P,4) int64 -- the pairs i <= j with a shared cell, ascending: P_ij x 3
+    and the cells --, ``gain_diag`` (n,4) int64, ``gain_excluded_cells`` -- shared cells that more than 8 images reach, left out --,
+    ``gain_shared_cells`` -- all the shared cells --, ``gain_kept`` -- the channels (0..2) that kept their gains because their system
+    has no finite positive solution --, ``gain_components`` -- connected groups of the overlap graph -- and ``gain_prior``.  ``gain_rms[1]`` shows what the solve achieved."""
 
     def __init__(self, axes, gsd, device):
         _lib.load()
@@ -1360,6 +1479,9 @@ class Mosaic:
         self._gain_open = False
         self._splatted = False
         self._held_gained = None
+        self.gain_solve = self.slot_ord = self.slot_sum = self.slot_over = self.gain_pairs_words = self.gain_diag_words = None
+        self.gain_direct = self.gain_kept = None
+        self._paired = False
 
     def _images(self, views: list, Js: list):
         views, Js = list(views), list(Js)
@@ -1413,7 +1535,8 @@ class Mosaic:
         bits = np.where(k & 0x80000000, k & 0x7fffffff, ~k).astype(np.uint32)   # key_value of csrc/order_key.h
         return tuple(bits.view(np.float32).tolist())
 
-    def begin(self, bounds=None, blend=None, feather=None, bands=None, surface=None, support=None, gains=None, gain_limit=None):
+    def begin(self, bounds=None, blend=None, feather=None, bands=None, surface=None, support=None, gains=None, gain_limit=None,
+              gain_solve=None):
         """Fixes the grid and allocates; ``blend``: the blend depth H in metres (``MOSAIC_BLEND_RANGE``) -- a pixel whose range
         exceeds its cell's smallest one by d gets the weight ``max(1 - d / H, 0)^2`` -- or None for the best view alone;
         ``feather``: with a blend, the feather width F in source pixels (``MOSAIC_FEATHER_RANGE``), or None for none; ``bands``:
@@ -1421,9 +1544,12 @@ class Mosaic:
         ``surface``: the tolerance T in metres of the surface test (``MOSAIC_SURFACE_RANGE``), or None for none; ``support``: with
         a surface, the number M of views the top must rest on (``MOSAIC_SUPPORT_RANGE``), or None for the plain minimum;
         ``gains``: the rounds R of the per-image gain compensation (``MOSAIC_GAIN_ROUNDS_RANGE``), or None for none;
-        ``gain_limit``: with ``gains``, the limit L of a gain (``MOSAIC_GAIN_LIMIT_RANGE``), ``MOSAIC_GAIN_LIMIT`` unless given."""
+        ``gain_limit``: with ``gains``, the limit L of a gain (``MOSAIC_GAIN_LIMIT_RANGE``), ``MOSAIC_GAIN_LIMIT`` unless given;
+        ``gain_solve``: with ``gains``, 'direct' for the direct solve in place of the first round's (``MOSAIC_GAIN_SOLVES``), 'rounds'
+        or None for the rounds alone."""
         options = MosaicOptions(blend=blend, feather=feather).checked('Mosaic.begin')   # before anything is allocated
         gains, gain_limit = mosaic_gains_checked(gains, gain_limit, 'Mosaic.begin')
+        gain_solve = mosaic_gain_solve_checked(gain_solve, gains, 'Mosaic.begin')
         blend, feather = options.blend, options.feather
         bands = mosaic_bands_checked(bands, blend, 'Mosaic.begin')
         surface = None if surface is None else mosaic_surface_tol(surface)
@@ -1479,6 +1605,9 @@ class Mosaic:
         self.gains, self.gain_limit = gains, gain_limit
         self.span = self.acc_gain = self.gain_table = self.gain_sums_words = self._gain_buf = None
         self._gain_passes, self._gain_open, self._splatted, self._held_gained = 0, False, False, None
+        self.gain_solve = gain_solve
+        self.slot_ord = self.slot_sum = self.slot_over = self.gain_pairs_words = self.gain_diag_words = None
+        self.gain_direct, self.gain_kept, self._paired = None, None, False
         if gains is not None:
             self.span = torch.tensor([-1, 0], dtype=torch.int32, device=dev).repeat(Hm * Wm, 1)    # all ones, 0: empty; 8 bytes per cell
             self.acc_gain = torch.zeros((Hm * Wm, _lib.MOSAIC_ACC_WORDS), dtype=torch.int64, device=dev)   # 64 bytes per cell
@@ -1713,6 +1842,97 @@ class Mosaic:
         sums = self.gain_sums_words[self._gain_passes - 1, :, :_lib.MOSAIC_GAIN_WORDS].cpu().numpy()
         solved = mosaic_gain_solve(sums, self.gain_table.cpu().numpy(), self.gain_limit)
         self.gain_table.copy_(torch.from_numpy(solved))
+        return self.gain_table
+
+    # ---- the direct solve (csrc/gains_direct.h) ----
+
+    def _direct(self, what: str) -> None:
+        self._gaining(what)
+        if self.gain_solve != 'direct':
+            raise ValueError(f"Mosaic.{what}: begin() was not given gain_solve='direct'")
+        if self._gain_passes == 0 or self._gain_open:
+            raise ValueError(f'Mosaic.{what}: a whole gain pass comes first (it fixes the images of the request and checks the cells)')
+
+    def _begin_direct(self) -> None:
+        """Allocates the direct solve's state, or refuses (``field``: 'gain_solve') what does not fit into
+        ``MOSAIC_GAIN_DIRECT_MEMORY`` of the free device memory (``_device_free_bytes``), before any of it is allocated."""
+        n, cells = int(self.gain_table.shape[0]), self.Hm * self.Wm
+        need = MOSAIC_GAIN_DIRECT_CELL_BYTES * cells + 32 * n * n + 8 * _lib.MOSAIC_GAIN_ROW_WORDS * n
+        free = _device_free_bytes(self.device)
+        if need > MOSAIC_GAIN_DIRECT_MEMORY * free:
+            raise _mosaic_refusal('gain_solve', f'mosaic gain solve direct: {self.Wm} x {self.Hm} cells and {n} images need {need} bytes '
+                                                f'({MOSAIC_GAIN_DIRECT_CELL_BYTES} per cell, 32 per pair of images), more than '
+                                                f'{MOSAIC_GAIN_DIRECT_MEMORY:g} of the {free} free on the device; give a coarser grid with '
+                                                f'--mosaic-gsd, fewer than {n} images, or leave the solve to the rounds')
+        dev = self.device
+        self.slot_ord = torch.full((cells, _lib.MOSAIC_GAIN_CELL_IMAGES), -1, dtype=torch.int32, device=dev)    # all ones: free
+        self.slot_sum = torch.zeros((cells, _lib.MOSAIC_GAIN_CELL_IMAGES, 4), dtype=torch.int64, device=dev)
+        self.slot_over = torch.zeros((cells,), dtype=torch.int32, device=dev)
+        self.gain_pairs_words = torch.zeros((n, n, 4), dtype=torch.int64, device=dev)
+        self.gain_diag_words = torch.zeros((n, _lib.MOSAIC_GAIN_ROW_WORDS), dtype=torch.int64, device=dev)
+
+    def _direct_images(self, what: str, views: list, Js: list, first_ordinal: int):
+        images = self._images(views, self._culled(views, Js, first_ordinal))
+        if int(first_ordinal) + images[1] > self.gain_table.shape[0]:
+            raise ValueError(f'Mosaic.{what}: ordinals {int(first_ordinal)}..{int(first_ordinal) + images[1] - 1} but the gain '
+                             f'table holds {self.gain_table.shape[0]} images')
+        return images
+
+    def add_gain_slots(self, views: list, Js: list, first_ordinal: int, plain: bool = False) -> None:
+        """Per shared cell, the count and the colour sums of every image that reaches it (``sucre_mosaic_gain_slots``), over the
+        un-gained (culled) images.  Over ALL the images, in any batches, after the first gain pass and before ``gain_pairs``.
+        ``plain``: every sample for itself (the same words)."""
+        self._direct('add_gain_slots')
+        if self._paired:
+            raise ValueError('Mosaic.add_gain_slots: gain_pairs() has read the slots already')
+        images = self._direct_images('add_gain_slots', views, Js, first_ordinal)
+        if self.slot_ord is None:
+            self._begin_direct()
+        self._walk('sucre_mosaic_gain_slots', images, int(first_ordinal), C.byref(self.grid), self.span, self.slot_ord, self.slot_sum,
+                   self.slot_over, _lib.MOSAIC_PLAIN_ATOMIC if plain else 0)
+
+    def _slotted(self, what: str) -> None:
+        self._direct(what)
+        if self.slot_ord is None:
+            raise ValueError(f'Mosaic.{what}: add_gain_slots() over every image comes first')
+
+    def gain_pairs(self, plain: bool = False, table_entries: int = 0) -> None:
+        """The pair sums of every shared cell that did not overflow (``sucre_mosaic_gain_pairs``), once, when ``add_gain_slots`` has
+        seen every image.  ``plain``: global atomics per cell and pair; ``table_entries``: the size of a workgroup's table, a
+        power of two up to ``_lib.MOSAIC_GAIN_PAIR_TABLE``, 0 for that (the same words either way)."""
+        self._slotted('gain_pairs')
+        if self._paired:
+            raise ValueError('Mosaic.gain_pairs: the pairs have been added already')
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().sucre_mosaic_gain_pairs(C.byref(self.grid), *(C.c_void_p(x.data_ptr()) for x in (
+                self.span, self.slot_ord, self.slot_sum, self.slot_over)), int(self.gain_table.shape[0]),
+                C.c_void_p(self.gain_pairs_words.data_ptr()), int(table_entries), _lib.MOSAIC_PLAIN_ATOMIC if plain else 0, _stream_ptr()))
+        self._paired = True
+
+    def add_gain_diag(self, views: list, Js: list, first_ordinal: int, plain: bool = False) -> None:
+        """Per image the count and ``sum Xq Xq`` of its samples in shared cells that did not overflow (``sucre_mosaic_gain_diag``),
+        over the un-gained (culled) images, once ``add_gain_slots`` has seen every image.  ``plain``: one set of atomics per 256 pixels."""
+        self._slotted('add_gain_diag')
+        images = self._direct_images('add_gain_diag', views, Js, first_ordinal)
+        self._walk('sucre_mosaic_gain_diag', images, int(first_ordinal), C.byref(self.grid), self.span, self.slot_over,
+                   int(self.gain_table.shape[0]), self.gain_diag_words, _lib.MOSAIC_PLAIN_ATOMIC if plain else 0)
+
+    def gain_diag(self) -> torch.Tensor:
+        """(n, 4) int64 on the device: per image n_i and ``sum Xq Xq`` x 3."""
+        self._slotted('gain_diag')
+        return self.gain_diag_words[:, :4].contiguous()
+
+    def solve_gains_direct(self) -> torch.Tensor:
+        """The gains of the next pass from the pairs and the diag (``mosaic_gain_solve_direct``, on the host: waits), in place of
+        ``solve_gains`` after the first pass; returns the (n,3) float32 device table.  ``gain_kept``: the channels that kept
+        their gains."""
+        self._slotted('solve_gains_direct')
+        if not self._paired:
+            raise ValueError('Mosaic.solve_gains_direct: gain_pairs() and add_gain_diag() over every image come first')
+        solved, kept = mosaic_gain_solve_direct(self.gain_pairs_words.cpu().numpy(), self.gain_diag().cpu().numpy(),
+                                                self.gain_table.cpu().numpy(), self.gain_limit)
+        self.gain_table.copy_(torch.from_numpy(solved))
+        self.gain_direct, self.gain_kept = self.gain_table.clone(), kept
         return self.gain_table
 
     def splat(self, views: list, Js: list, first_ordinal: int, plain_atomic: bool = False) -> None:
@@ -1964,10 +2184,25 @@ class Mosaic:
         overlap = sums[-1, :, 0].clone() if len(host) else torch.zeros(n, dtype=torch.int64, device=self.device)
         gains = torch.ones((0, 3), dtype=torch.float32, device=self.device) if n == 0 else self.gain_table.clone()
         return {'gains': gains, 'gain_sums': sums, 'gain_rms': rms, 'gain_overlap': overlap, 'gain_rounds': int(self.gains),
-                'gain_limit': float(self.gain_limit)}
+                'gain_limit': float(self.gain_limit), **self._gain_direct_result()}
+
+    def _gain_direct_result(self) -> dict:
+        """The keys of ``result()`` that a direct solve adds (none before ``solve_gains_direct``); waits."""
+        if self.gain_direct is None:
+            return {}
+        pairs, diag = self.gain_pairs_words.cpu(), self.gain_diag().cpu()
+        index = (pairs[:, :, 3] > 0).nonzero()      # ascending (i, j); only the upper triangle is written
+        span = self.span.cpu().numpy().view(np.uint32)
+        shared = span[:, 0] < span[:, 1]
+        excluded = int((shared & (self.slot_over.cpu().numpy() != 0)).sum())
+        dev = self.device
+        return {'gain_solve': 'direct', 'gain_direct': self.gain_direct.clone(), 'gain_pair_index': index.to(torch.int32).to(dev),
+                'gain_pair_words': pairs[index[:, 0], index[:, 1]].contiguous().to(dev), 'gain_diag': diag.to(dev), 'gain_excluded_cells': excluded,
+                'gain_shared_cells': int(shared.sum()), 'gain_kept': [int(c) for c in self.gain_kept],
+                'gain_components': mosaic_gain_groups(pairs.numpy(), diag.numpy()), 'gain_prior': float(MOSAIC_GAIN_PRIOR)}
 
     def run(self, batches, options: MosaicOptions = MosaicOptions(), bounds=None, plain_atomic: bool = False, bands=None,
-            surface=None, support=None, gains=None, gain_limit=None) -> 'Mosaic':
+            surface=None, support=None, gains=None, gain_limit=None, gain_solve=None) -> 'Mosaic':
         """Every phase over every batch, in the one order there is: the bounds (unless ``bounds`` is given), ``begin``; with
         ``surface`` (the tolerance T of the surface test, beside the options record) ``add_surface`` -- or, with ``support`` (the
         count M of supporting views, beside the record too; only with a surface), ``add_support`` over every batch for level 0,
@@ -1981,7 +2216,9 @@ class Mosaic:
         gain compensation, beside the record; ``gain_limit``: its limit L) the splat is followed by ``add_span`` over every batch,
         R times ``gain_pass`` and ``solve_gains``, and one more ``gain_pass`` that measures the final state; resolve, gather,
         accumulate and the bands then see the gained images -- applied anew per phase and batch, unless one batch is the whole
-        request: that one is gained once and held.  Returns the mosaic."""
+        request: that one is gained once and held.  With ``gain_solve='direct'`` the first pass is followed by ``add_gain_slots``
+        over every batch, ``gain_pairs``, ``add_gain_diag`` over every batch and ``solve_gains_direct`` in place of the first
+        ``solve_gains`` (csrc/gains_direct.h); 'rounds' and None: the rounds alone.  Returns the mosaic."""
         batches = list(batches)
         if bounds is None:
             for _, load in batches:
@@ -1989,9 +2226,11 @@ class Mosaic:
         bands = mosaic_bands_checked(bands, options.blend, 'Mosaic.run')
         support = mosaic_support_checked(support, surface, 'Mosaic.run')
         gains, gain_limit = mosaic_gains_checked(gains, gain_limit, 'Mosaic.run')
+        gain_solve = mosaic_gain_solve_checked(gain_solve, gains, 'Mosaic.run')
         self.begin(bounds, blend=options.blend, feather=options.feather, **({} if bands is None else {'bands': bands}),
                    **({} if surface is None else {'surface': surface}), **({} if support is None else {'support': support}),
-                   **({} if gains is None else {'gains': gains, 'gain_limit': gain_limit}))
+                   **({} if gains is None else {'gains': gains, 'gain_limit': gain_limit}),
+                   **({} if gain_solve is None else {'gain_solve': gain_solve}))
         if surface is not None:
             if support is None:
                 for first, load in batches:
@@ -2010,9 +2249,17 @@ class Mosaic:
             if gains is not None:
                 for first, load in batches:
                     self.add_span(*load(), first, plain_atomic=plain_atomic)
-                for _ in range(gains):
+                for r in range(gains):
                     self.gain_pass(batches, plain=plain_atomic)
-                    self.solve_gains()
+                    if r == 0 and gain_solve == 'direct':
+                        for first, load in batches:
+                            self.add_gain_slots(*load(), first, plain=plain_atomic)
+                        self.gain_pairs(plain=plain_atomic)
+                        for first, load in batches:
+                            self.add_gain_diag(*load(), first, plain=plain_atomic)
+                        self.solve_gains_direct()
+                    else:
+                        self.solve_gains()
                 self.gain_pass(batches, plain=plain_atomic)
                 if len(batches) == 1:
                     first, load = batches[0]
@@ -2037,7 +2284,8 @@ class Mosaic:
 
 
 def mosaic_of(views: list, Js: list, axes, gsd, bounds=None, batch: int = 32, plain_atomic: bool = False, blend=None,
-              fill=None, feather=None, bands=None, surface=None, support=None, gains=None, gain_limit=None) -> 'Mosaic':
+              fill=None, feather=None, bands=None, surface=None, support=None, gains=None, gain_limit=None,
+              gain_solve=None) -> 'Mosaic':
     """``Mosaic.run`` over device-resident ``views`` / ``Js`` (ordinal = position in the list), ``batch`` images per call; with
     ``blend`` (the blend depth H, metres) the accumulate phase and the normalise pass after them (``plain_atomic``: both the
     splat and the accumulate phase in their plain forms), with ``feather`` (the width F, source pixels; only with ``blend``) the
@@ -2045,7 +2293,9 @@ def mosaic_of(views: list, Js: list, axes, gsd, bounds=None, batch: int = 32, pl
     (the reach R, metres) the hole filling after all of them (``MosaicOptions``); with ``surface`` (the tolerance T, metres) the
     surface test ahead of the splat (csrc/surface.h), with ``support`` (the count M of views; only with ``surface``) against the
     view-supported top instead of the plain minimum (csrc/support.h); with ``gains`` (the rounds R) the per-image gain compensation
-    between the splat and the resolve (csrc/gains_mosaic.h), every gain within ``[1 / gain_limit, gain_limit]``."""
+    between the splat and the resolve (csrc/gains_mosaic.h), every gain within ``[1 / gain_limit, gain_limit]``; with
+    ``gain_solve='direct'`` (only with ``gains``) the first round's gains come from the direct least-squares solve
+    (csrc/gains_direct.h), with 'rounds' or None from the rounds alone."""
     views, Js = list(views), list(Js)
     if not views:
         raise ValueError('mosaic_of: no view')
@@ -2056,11 +2306,13 @@ def mosaic_of(views: list, Js: list, axes, gsd, bounds=None, batch: int = 32, pl
     surface = None if surface is None else mosaic_surface_tol(surface)
     support = mosaic_support_checked(support, surface, 'mosaic_of')
     gains, gain_limit = mosaic_gains_checked(gains, gain_limit, 'mosaic_of')
+    gain_solve = mosaic_gain_solve_checked(gain_solve, gains, 'mosaic_of')
     batches = [(i, lambda i=i: (views[i:i + batch], Js[i:i + batch])) for i in range(0, len(views), batch)]
     return Mosaic(axes, gsd, views[0].depth.device).run(batches, options, bounds, plain_atomic, **({} if bands is None else {'bands': bands}),
                                                         **({} if surface is None else {'surface': surface}),
                                                         **({} if support is None else {'support': support}),
-                                                        **({} if gains is None else {'gains': gains, 'gain_limit': gain_limit}))
+                                                        **({} if gains is None else {'gains': gains, 'gain_limit': gain_limit}),
+                                                        **({} if gain_solve is None else {'gain_solve': gain_solve}))
 
 
 def device_views_from_scene(scene, device='cuda') -> list[DeviceView]:

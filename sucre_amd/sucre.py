@@ -1425,7 +1425,7 @@ def _mosaic_picture(J: Tensor, stretch) -> np.ndarray:
 
 _MOSAIC_FLAG = {'grid': '--mosaic', 'blend': '--mosaic-blend', 'fill': '--mosaic-fill', 'feather': '--mosaic-feather',
                 'bands': '--mosaic-bands', 'surface': '--mosaic-surface', 'support': '--mosaic-support', 'gains': '--mosaic-gains',
-                'gain_limit': '--mosaic-gain-limit'}
+                'gain_limit': '--mosaic-gain-limit', 'gain_solve': '--mosaic-gain-solve'}
 
 
 def _mosaic_refused(e: ValueError, fields=tuple(_MOSAIC_FLAG)) -> BaseException:
@@ -1447,7 +1447,7 @@ _MOSAIC_PNG = {   # how a row of engine.MOSAIC_OUTPUTS becomes its PNG: (the out
 def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, output_dir: Path, gsd: float | None = None, axes=None,
            stretch=None, device: str = 'cuda', blend: float | None = None, fill: float | None = None, feather: int | None = None,
            bands: int | None = None, surface: float | None = None, support: int | None = None, gains: int | None = None,
-           gain_limit: float | None = None) -> dict:
+           gain_limit: float | None = None, gain_solve: str | None = None) -> dict:
     """One picture of the seabed from a finished restoration: every pixel of ``images`` (``sfm.Image`` objects or names of
     ``colmap_model``; at most ``engine.MAX_VIEWS``, ordinal = position) with a valid depth and a restored colour --
     ``results_dir / <name>.pt``, key ``J`` -- is dropped onto the plane grid ``axes`` (``mosaic_axes`` unless given) of ``gsd``
@@ -1520,7 +1520,17 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
     and key that is not a ``J`` stays as it is, byte for byte; every ``J`` is that of a run without the flag on the images times
     their gains; ``mosaic.pt`` gains ``gains``, ``gain_sums``, ``gain_rms``, ``gain_overlap``, ``gain_rounds`` and ``gain_limit``, and
     one more line is printed after the mosaic's and the surface's.  The rounds remove what overlapping images disagree on; a slow
-    drift along a chain of N images needs on the order of N^2 rounds and is not what the flag is for."""
+    drift along a chain of N images needs on the order of N^2 rounds and is not what the rounds are for.
+
+    ``gain_solve``: with ``gains``, 'direct' (``engine.MOSAIC_GAIN_SOLVES``) -- the rounds' objective solved exactly, once, in place of
+    the first round's solve (csrc/gains_direct.h): per shared cell the colour sums of up to eight images, from them one sum per pair of
+    overlapping images, and one n x n solve per channel on the host with a weak prior towards gain 1.  It removes the drift along a
+    chain -- a lawn-mower transect under a drifting strobe -- that no affordable number of rounds removes; the remaining R - 1 rounds
+    and the measuring pass run unchanged from its table, so ``gain_rms[1]`` shows what it achieved.  A shared cell that more than
+    eight images reach is left out of the solve.  ``mosaic.pt`` gains ``gain_solve``, ``gain_direct``, ``gain_pair_index``,
+    ``gain_pair_words``, ``gain_diag``, ``gain_excluded_cells``, ``gain_shared_cells``, ``gain_kept``, ``gain_components`` and
+    ``gain_prior``, and one more line is printed
+    after the gains'.  'rounds' or None: the rounds alone, every file as without the argument."""
     from . import engine
     sfm.require_gpu(device, 'mosaic')
     images = [colmap_model[im] if isinstance(im, str) else im for im in images]
@@ -1559,6 +1569,12 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
         gains, gain_limit = engine.mosaic_gains_checked(gains, gain_limit, 'mosaic')
     except ValueError as e:
         raise _mosaic_refused(e)
+    if gain_solve is not None and gains is None:
+        raise SystemExit('--mosaic-gain-solve: only with --mosaic-gains R')
+    try:
+        gain_solve = engine.mosaic_gain_solve_checked(gain_solve, gains, 'mosaic')
+    except ValueError as e:
+        raise _mosaic_refused(e)
     results_dir, output_dir = Path(results_dir), Path(output_dir)
     for image in images:   # before anything is decoded
         path = _consistency_file(results_dir, image)
@@ -1593,12 +1609,14 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
                                                      **({} if bands is None else {'bands': bands}),
                                                      **({} if surface is None else {'surface': surface}),
                                                      **({} if support is None else {'support': support}),
-                                                     **({} if gains is None else {'gains': gains, 'gain_limit': gain_limit}))
+                                                     **({} if gains is None else {'gains': gains, 'gain_limit': gain_limit}),
+                                                     **({} if gain_solve is None else {'gain_solve': gain_solve}))
         except ValueError as e:
             # Three refusals of the run belong to a flag: begin's of the grid (--mosaic), normalize's of a cell's sample count
             # (--mosaic-blend) and the gain passes' of a cell's sample count or an image's size (--mosaic-gains).  The options were checked above, so begin and fill have nothing left to refuse in them; every other
-            # ValueError (of a view, of a restored image) passes as it is.
-            raise _mosaic_refused(e, ('grid', 'blend', 'gains'))
+            # ValueError (of a view, of a restored image) passes as it is.  A fourth: the direct solve's of a state that does not
+            # fit the device (--mosaic-gain-solve).
+            raise _mosaic_refused(e, ('grid', 'blend', 'gains', 'gain_solve'))
         out = m.result()
         pictures = [(png, _MOSAIC_PNG[how](out[key], stretch)) for key, (_, _, _, _, png, how) in engine.MOSAIC_OUTPUTS.items()
                     if png is not None and key in out]
@@ -1647,6 +1665,14 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
               + ' '.join(f'{ch} {float(rms[0, c]):.6g} -> {float(rms[-1, c]):.6g}' for c, ch in enumerate('RGB'))
               + f'; largest correction {images[int(far)].name} (gain R {float(g[far, 0]):.6g} G {float(g[far, 1]):.6g} B {float(g[far, 2]):.6g}); '
               f'{clipped} values clipped')
+    if gain_solve is not None:
+        diag, index = out['gain_diag'], out['gain_pair_index']
+        print(f'mosaic gain solve direct: {int((index[:, 0] < index[:, 1]).sum())} overlapping pairs among {int((diag[:, 0] > 0).sum())} images '
+              f'in {out["gain_components"]} connected groups; {out["gain_excluded_cells"]} of {out["gain_shared_cells"]} shared cells hold more than '
+              f'{engine._lib.MOSAIC_GAIN_CELL_IMAGES} images and are left out')
+        if out['gain_kept']:
+            print(f'mosaic gain solve direct: channel {" ".join("RGB"[c] for c in out["gain_kept"])} kept its gains (its system has no finite '
+                  f'positive solution)')
     if blend is not None:
         samples = out['samples'].to(torch.int64)
         total, most, several = int(samples.sum()), int(samples.max()), int((samples > 1).sum())
@@ -1723,6 +1749,13 @@ def _refuse_lone_flags(args) -> None:
             raise SystemExit(f'{flag}: only with {needs} {value}')
 
 
+def _refuse_lone_gain_solve(args) -> None:
+    """--mosaic-gain-solve without --mosaic-gains, refused before any file is opened (beside ``_ONLY_WITH``, whose rows are what
+    they were: looked at after them)."""
+    if getattr(args, 'mosaic_gain_solve', None) is not None and getattr(args, 'mosaic_gains', None) is None:
+        raise SystemExit(f'{_MOSAIC_FLAG["gain_solve"]}: only with --mosaic-gains R')
+
+
 def _refuse_mode_flags(args, mode: str) -> None:
     """What ``mode`` (--mosaic, --check-consistency, --apply-water) does not combine with, refused before any file is opened."""
     for flag, why in _MODE_REFUSES[mode]:
@@ -1732,7 +1765,8 @@ def _refuse_mode_flags(args, mode: str) -> None:
 
 def _refuse_mosaic_values(args, world: int = 1) -> None:
     """The values of --mosaic-gsd, --mosaic-blend, --mosaic-fill, --mosaic-feather, --mosaic-bands, --mosaic-surface,
-    --mosaic-support, --mosaic-gains and --mosaic-gain-limit and the world size a mosaic takes, refused before any file is opened."""
+    --mosaic-support, --mosaic-gains, --mosaic-gain-limit and --mosaic-gain-solve and the world size a mosaic takes, refused before any
+    file is opened."""
     gsd = getattr(args, 'mosaic_gsd', None)
     if gsd is not None and not (np.isfinite(gsd) and gsd > 0):
         raise SystemExit(f'--mosaic-gsd: G must be a finite size > 0 in metres, not {gsd}')
@@ -1762,6 +1796,9 @@ def _refuse_mosaic_values(args, world: int = 1) -> None:
     lo, hi = engine.MOSAIC_GAIN_LIMIT_RANGE
     if limit is not None and not (np.isfinite(limit) and lo <= limit <= hi):
         raise SystemExit(f'{_MOSAIC_FLAG["gain_limit"]}: L must be a finite limit within [{lo:g}, {hi:g}] times, not {limit}')
+    solve = getattr(args, 'mosaic_gain_solve', None)
+    if solve is not None and solve not in engine.MOSAIC_GAIN_SOLVES:
+        raise SystemExit(f'{_MOSAIC_FLAG["gain_solve"]}: S must be {" or ".join(engine.MOSAIC_GAIN_SOLVES)}, not {solve}')
     if world > 1:
         raise SystemExit(f'--mosaic: a world size of {world} is not supported yet: the four phases are separate entries of the library '
                          f'so that ranks can all-reduce bounds, keys and pixel words between them, but that all-reduce is not built; '
@@ -1790,6 +1827,7 @@ def parse_args(args: argparse.Namespace):
     check = getattr(args, 'check_consistency', None)
     mosaic_dir = getattr(args, 'mosaic', None)
     _refuse_lone_flags(args)
+    _refuse_lone_gain_solve(args)
     if mosaic_dir is not None:
         _refuse_mode_flags(args, '--mosaic')
         _refuse_mosaic_values(args, world)
@@ -1875,7 +1913,8 @@ def parse_args(args: argparse.Namespace):
                    blend=getattr(args, 'mosaic_blend', None), fill=getattr(args, 'mosaic_fill', None),
                    feather=getattr(args, 'mosaic_feather', None), bands=getattr(args, 'mosaic_bands', None),
                    surface=getattr(args, 'mosaic_surface', None), support=getattr(args, 'mosaic_support', None),
-                   gains=getattr(args, 'mosaic_gains', None), gain_limit=getattr(args, 'mosaic_gain_limit', None))
+                   gains=getattr(args, 'mosaic_gains', None), gain_limit=getattr(args, 'mosaic_gain_limit', None),
+                   gain_solve=getattr(args, 'mosaic_gain_solve', None))
         elif check is not None:
             if world > 1:   # the targets' records are gathered on rank 0
                 sdist.init_process_group()
@@ -2163,6 +2202,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.extras.add_argument('--mosaic-gain-limit', type=float, metavar='L', default=argparse.SUPPRESS,
                           help='with --mosaic-gains: every gain is kept within [1/L, L] (1..16; 2 unless given; 1 leaves every file as '
                                'it is without the flag)')
+    p.extras.add_argument('--mosaic-gain-solve', type=str, metavar='S', default=argparse.SUPPRESS,
+                          help='with --mosaic-gains: rounds (as without the flag) or direct -- the first round\'s gains come from one '
+                               'exact least-squares solve over all pairs of overlapping images instead: removes a slow drift along '
+                               'a chain of images, which the rounds do not; the remaining R - 1 rounds run after it; adds gain_solve, '
+                               'gain_direct, gain_pair_index, gain_pair_words, gain_diag, gain_excluded_cells, gain_shared_cells, '
+                               'gain_kept, gain_components and gain_prior to mosaic.pt and prints one more line')
     p.extras.add_argument('--common-stretch', action='store_true', default=argparse.SUPPRESS,
                           help='with --shared-water or --apply-water: stretch every <stem>_rgb.png between the SAME per-channel 1st '
                                'and 99th percentile, those of the valid pixels of all images of the request pooled (all ranks), '
