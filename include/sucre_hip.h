@@ -773,10 +773,40 @@ int sucre_view_consistency(int H, int W, int n_views, const sucre_view_t *target
  * slot_sum_dev (8), slot_over_dev (4), pairs_dev (8) or diag_dev (128), n_ordinals outside 1..4096, a table_entries that is no such
  * power of two, a grid of 2^43 cells or more (pairs: its workgroups of 4096 cells must fit a launch), an image of more than 2^26
  * pixels (diag), unknown flags.
+ *
+ * The colour consensus across views (csrc/reject.h): the samples whose colour differs from what the median image of their cell saw,
+ * taken out ahead of the splat.  Integer state, or one IEEE operation per step: the same bits in any order, split and atomic form.
+ * slot_ord_dev: (Hm Wm, SUCRE_MOSAIC_REJECT_SLOTS = 8) uint32, the caller starts every word at all ones (free); slot_over_dev:
+ * (Hm Wm) uint32 and slot_sum_dev: (Hm Wm, 8, 4) int64 -- n, sum Xq x 3 --, both started at zero.
+ *   sucre_mosaic_reject_claim      over ALL images, any split into calls: afterwards a cell's words hold the 8 smallest distinct
+ *                                  ordinals that reach it, ascending, free words last (a chain of atomic minima that carries the
+ *                                  displaced value on), and slot_over[cell] = 1 exactly when a ninth reaches it.
+ *                                  flags: SUCRE_MOSAIC_PLAIN_ATOMIC -- every sample walks the whole chain, without the load of the
+ *                                  cell's words ahead of it and without the runs of a wave's lanes
+ *   sucre_mosaic_reject_sums       after the claim has seen ALL images, over ALL images: a sample whose ordinal is one of its
+ *                                  cell's eight adds 1 and Xq_c = q(J_c) to that slot; any other sample adds nothing.
+ *                                  flags: SUCRE_MOSAIC_PLAIN_ATOMIC -- every sample for itself, without the run sums
+ *   sucre_mosaic_reject_consensus  once, after the sums: per cell views_out = k, the occupied slots; with k >= SUCRE_MOSAIC_REJECT_
+ *                                  MIN_VIEWS = 3 the slots are ordered by Y / n (Y = S_0 + S_1 + S_2; exactly, Y_a n_b < Y_b n_a,
+ *                                  ties by ordinal), the slot at index (k - 1) / 2 is the reference: source_out its ordinal,
+ *                                  ref_out[c] = (float)(((double)S_c / (double)n) 2^-14); otherwise source_out -1 and ref_out NaN.
+ *                                  big_dev (one uint64, started at zero): the slots with n >= 2^20, whose cells get no reference --
+ *                                  a caller stops on a count above 0
+ *   sucre_mosaic_reject_cull       sucre_mosaic_cull with the colour test: J_out gets NaN in every channel of a pixel that does not
+ *                                  take part, or whose cell has a reference, whose ordinal is not source[cell] and for which
+ *                                  fabsf(J_c - ref_c) > tol in any channel.  rejected_dev (uint32 per cell, or NULL): the rejected
+ *                                  samples per cell; counts_dev ((n_ordinals, 16) int64, two words used, or NULL): per image the
+ *                                  samples in cells that have a reference and the samples rejected
+ * All four only enqueue.  Checked before any launch as above, and: a NULL or misaligned slot_ord_dev (32 bytes), slot_over_dev (4),
+ * slot_sum_dev (8), ref_dev / ref_out (4), source (4), views_out (4) or big_dev (8), a misaligned rejected_dev (4) or counts_dev
+ * (128), n_ordinals outside 1..4096 or below first_ordinal + n_images when counts_dev is given, a tol that is not finite and > 0, a
+ * J_out that overlaps an image's J, a grid of more than 2^39 cells (consensus), unknown flags.
  */
 #define SUCRE_MOSAIC_PLAIN_ATOMIC 1u
 #define SUCRE_MOSAIC_GAIN_WORDS 10
 #define SUCRE_MOSAIC_GAIN_SLOTS 8
+#define SUCRE_MOSAIC_REJECT_SLOTS 8
+#define SUCRE_MOSAIC_REJECT_MIN_VIEWS 3
 #define SUCRE_MOSAIC_SUPPORT_MAX 4
 #define SUCRE_MOSAIC_ACC_WORDS 8
 #define SUCRE_MOSAIC_FEATHER_MAX 1024
@@ -847,6 +877,17 @@ int sucre_mosaic_gain_pairs(const sucre_mosaic_grid_t *grid, const uint32_t *spa
 int sucre_mosaic_gain_diag(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
                            const sucre_mosaic_grid_t *grid, const uint32_t *span_dev, const uint32_t *slot_over_dev, int n_ordinals,
                            int64_t *diag_dev, unsigned flags, void *stream);
+int sucre_mosaic_reject_claim(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                              const sucre_mosaic_grid_t *grid, uint32_t *slot_ord_dev, uint32_t *slot_over_dev, unsigned flags,
+                              void *stream);
+int sucre_mosaic_reject_sums(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                             const sucre_mosaic_grid_t *grid, const uint32_t *slot_ord_dev, int64_t *slot_sum_dev, unsigned flags,
+                             void *stream);
+int sucre_mosaic_reject_consensus(const sucre_mosaic_grid_t *grid, const uint32_t *slot_ord_dev, const int64_t *slot_sum_dev,
+                                  float *ref_out, int32_t *source_out, int32_t *views_out, uint64_t *big_dev, void *stream);
+int sucre_mosaic_reject_cull(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                             const sucre_mosaic_grid_t *grid, const float *ref_dev, const int32_t *source_dev, float tol, float *J_out,
+                             uint32_t *rejected_dev, int n_ordinals, int64_t *counts_dev, void *stream);
 
 /*
  * ---- hole filling of the finished mosaic: a bounded push-pull over a pyramid of the grid ------------------------------------------

@@ -32,7 +32,9 @@ MOSAIC_ACC_WORDS = 8        # SUCRE_MOSAIC_ACC_WORDS: int64 words per cell of th
 MOSAIC_GAIN_WORDS = 10      # SUCRE_MOSAIC_GAIN_WORDS: int64 words per image of sucre_mosaic_gain_sums
 MOSAIC_GAIN_ROW_WORDS = 16  # kGainRowWords of csrc/gains_mosaic.h: an image's row of the sums is padded to 128 bytes
 MOSAIC_GAIN_CELL_IMAGES = 8   # SUCRE_MOSAIC_GAIN_SLOTS: images a cell holds sums for in the direct gain solve (csrc/gains_direct.h)
-MOSAIC_GAIN_PAIR_TABLE = 512   # kPairTableMax of csrc/gains_direct.h: the most entries of sucre_mosaic_gain_pairs' LDS table
+MOSAIC_REJECT_CELL_IMAGES = 8   # SUCRE_MOSAIC_REJECT_SLOTS: ordinals a cell keeps for the colour consensus (csrc/reject.h)
+MOSAIC_REJECT_MIN_VIEWS = 3   # SUCRE_MOSAIC_REJECT_MIN_VIEWS: images a cell's consensus takes
+MOSAIC_GAIN_PAIR_TABLE = 512  # kPairTableMax of csrc/gains_direct.h: the most entries of sucre_mosaic_gain_pairs' LDS table
 MOSAIC_FEATHER_MAX = 1024   # SUCRE_MOSAIC_FEATHER_MAX: the widest feather, source pixels
 MOSAIC_BANDS_MAX = 6         # SUCRE_MOSAIC_BANDS_MAX: the most detail bands of a multi-band blend
 MOSAIC_BLOCK_PX = 256       # kMosaicBlockPx of csrc/mosaic.h: an image's words of the feather map start at a multiple of it
@@ -191,6 +193,11 @@ SIGNATURES = {
     'sucre_mosaic_gain_slots': (_i, [_vp, _i, C.POINTER(MosaicImage), _i, C.POINTER(MosaicGrid), _vp, _vp, _vp, _vp, C.c_uint, _vp]),
     'sucre_mosaic_gain_pairs': (_i, [C.POINTER(MosaicGrid), _vp, _vp, _vp, _vp, _i, _vp, _i, C.c_uint, _vp]),
     'sucre_mosaic_gain_diag': (_i, [_vp, _i, C.POINTER(MosaicImage), _i, C.POINTER(MosaicGrid), _vp, _vp, _i, _vp, C.c_uint, _vp]),
+    'sucre_mosaic_reject_claim': (_i, [_vp, _i, C.POINTER(MosaicImage), _i, C.POINTER(MosaicGrid), _vp, _vp, C.c_uint, _vp]),
+    'sucre_mosaic_reject_sums': (_i, [_vp, _i, C.POINTER(MosaicImage), _i, C.POINTER(MosaicGrid), _vp, _vp, C.c_uint, _vp]),
+    'sucre_mosaic_reject_consensus': (_i, [C.POINTER(MosaicGrid), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sucre_mosaic_reject_cull': (_i, [_vp, _i, C.POINTER(MosaicImage), _i, C.POINTER(MosaicGrid), _vp, _vp, C.c_float, _vp, _vp, _i, _vp,
+                                      _vp]),
     'sucre_mosaic_fill_bytes': (C.c_size_t, [_i, _i, _i]),
     'sucre_mosaic_fill_pull': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'sucre_mosaic_fill_push': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

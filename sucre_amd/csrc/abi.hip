@@ -17,6 +17,7 @@
 #include "support.h"
 #include "gains_mosaic.h"
 #include "gains_direct.h"
+#include "reject.h"
 
 namespace sucre {
 
@@ -1333,6 +1334,77 @@ int sucre_mosaic_gain_diag(void *table_dev, int n_images, const sucre_mosaic_ima
     return check_hip(launch_mosaic_gain_diag((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) != 0, table_dev, n_images, images, first_ordinal, g, span_dev,
                                              slot_over_dev, reinterpret_cast<unsigned long long *>(diag_dev), static_cast<hipStream_t>(stream)),
                      "sucre_mosaic_gain_diag");
+}
+
+/* ---- colour consensus across views: a cell's eight smallest ordinals, their sums, the median image, the cull (reject.h) ---- */
+
+int sucre_mosaic_reject_claim(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                              const sucre_mosaic_grid_t *grid, uint32_t *slot_ord_dev, uint32_t *slot_over_dev, unsigned flags,
+                              void *stream) {
+    if (int rc = check_mosaic_images(table_dev, n_images, images, first_ordinal)) return rc;
+    MosaicGrid g;
+    if (int rc = check_mosaic_grid(grid, &g)) return rc;
+    if (!slot_ord_dev || !aligned(slot_ord_dev, 32)) return fail(SUCRE_ERR_ARG, "slot_ord_dev is NULL or not 32-byte aligned");
+    if (!slot_over_dev || !aligned(slot_over_dev, 4)) return fail(SUCRE_ERR_ARG, "slot_over_dev is NULL or not 4-byte aligned");
+    if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
+    return check_hip(launch_mosaic_reject_claim((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) != 0, table_dev, n_images, images, first_ordinal, g,
+                                                slot_ord_dev, slot_over_dev, static_cast<hipStream_t>(stream)), "sucre_mosaic_reject_claim");
+}
+
+int sucre_mosaic_reject_sums(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                             const sucre_mosaic_grid_t *grid, const uint32_t *slot_ord_dev, int64_t *slot_sum_dev, unsigned flags,
+                             void *stream) {
+    if (int rc = check_mosaic_images(table_dev, n_images, images, first_ordinal)) return rc;
+    MosaicGrid g;
+    if (int rc = check_mosaic_grid(grid, &g)) return rc;
+    if (!slot_ord_dev || !aligned(slot_ord_dev, 32)) return fail(SUCRE_ERR_ARG, "slot_ord_dev is NULL or not 32-byte aligned");
+    if (!slot_sum_dev || !aligned(slot_sum_dev, 8)) return fail(SUCRE_ERR_ARG, "slot_sum_dev is NULL or not 8-byte aligned");
+    if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
+    return check_hip(launch_mosaic_reject_sums((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) != 0, table_dev, n_images, images, first_ordinal, g,
+                                               slot_ord_dev, reinterpret_cast<unsigned long long *>(slot_sum_dev),
+                                               static_cast<hipStream_t>(stream)), "sucre_mosaic_reject_sums");
+}
+
+int sucre_mosaic_reject_consensus(const sucre_mosaic_grid_t *grid, const uint32_t *slot_ord_dev, const int64_t *slot_sum_dev,
+                                  float *ref_out, int32_t *source_out, int32_t *views_out, uint64_t *big_dev, void *stream) {
+    MosaicGrid g;
+    if (int rc = check_mosaic_grid(grid, &g)) return rc;
+    if ((uint64_t)g.Hm * (uint64_t)g.Wm > (1ull << 39)) return fail(SUCRE_ERR_ARG, "mosaic of %dx%d cells: one pass takes 2^39 cells", g.Wm, g.Hm);
+    if (!slot_ord_dev || !aligned(slot_ord_dev, 32)) return fail(SUCRE_ERR_ARG, "slot_ord_dev is NULL or not 32-byte aligned");
+    if (!slot_sum_dev || !aligned(slot_sum_dev, 8)) return fail(SUCRE_ERR_ARG, "slot_sum_dev is NULL or not 8-byte aligned");
+    if (!ref_out || !aligned(ref_out, 4)) return fail(SUCRE_ERR_ARG, "ref_out is NULL or not 4-byte aligned");
+    if (!source_out || !aligned(source_out, 4)) return fail(SUCRE_ERR_ARG, "source_out is NULL or not 4-byte aligned");
+    if (!views_out || !aligned(views_out, 4)) return fail(SUCRE_ERR_ARG, "views_out is NULL or not 4-byte aligned");
+    if (!big_dev || !aligned(big_dev, 8)) return fail(SUCRE_ERR_ARG, "big_dev is NULL or not 8-byte aligned");
+    return check_hip(launch_mosaic_reject_consensus(g, slot_ord_dev, reinterpret_cast<const long long *>(slot_sum_dev), ref_out, source_out,
+                                                    views_out, reinterpret_cast<unsigned long long *>(big_dev),
+                                                    static_cast<hipStream_t>(stream)), "sucre_mosaic_reject_consensus");
+}
+
+int sucre_mosaic_reject_cull(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                             const sucre_mosaic_grid_t *grid, const float *ref_dev, const int32_t *source_dev, float tol, float *J_out,
+                             uint32_t *rejected_dev, int n_ordinals, int64_t *counts_dev, void *stream) {
+    if (int rc = check_mosaic_images(table_dev, n_images, images, first_ordinal)) return rc;
+    MosaicGrid g;
+    if (int rc = check_mosaic_grid(grid, &g)) return rc;
+    if (!ref_dev || !aligned(ref_dev, 4)) return fail(SUCRE_ERR_ARG, "ref_dev is NULL or not 4-byte aligned");
+    if (!source_dev || !aligned(source_dev, 4)) return fail(SUCRE_ERR_ARG, "source_dev is NULL or not 4-byte aligned");
+    if (!std::isfinite(tol) || !(tol > 0.0f)) return fail(SUCRE_ERR_ARG, "tol=%g must be finite and > 0", (double)tol);
+    if (!J_out || !aligned(J_out, 4)) return fail(SUCRE_ERR_ARG, "J_out is NULL or not 4-byte aligned");
+    if (rejected_dev && !aligned(rejected_dev, 4)) return fail(SUCRE_ERR_ARG, "rejected_dev is not 4-byte aligned");
+    if (counts_dev) {   // every ordinal of the call has a row
+        if (!aligned(counts_dev, 128)) return fail(SUCRE_ERR_ARG, "counts_dev is not 128-byte aligned");
+        if (int rc = check_gain_rows(n_images, first_ordinal, n_ordinals)) return rc;
+    }
+    // J_out is a buffer of its own, as sucre_mosaic_cull's
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(J_out), o1 = o0 + band_bytes(n_images, images);
+    for (int i = 0; i < n_images; ++i) {
+        const uintptr_t j0 = reinterpret_cast<uintptr_t>(images[i].J), j1 = j0 + (size_t)images[i].H * (size_t)images[i].W * 12;
+        if (j0 < o1 && o0 < j1) return fail(SUCRE_ERR_ARG, "image %d: J_out overlaps the image's J", i);
+    }
+    const MosaicReject out = {rejected_dev, reinterpret_cast<unsigned long long *>(counts_dev)};
+    return check_hip(launch_mosaic_reject_cull(table_dev, n_images, images, first_ordinal, g, ref_dev, source_dev, tol, J_out, out,
+                                               static_cast<hipStream_t>(stream)), "sucre_mosaic_reject_cull");
 }
 
 /* ---- hole filling of the finished mosaic: a bounded push-pull over a pyramid of the grid (fill.h) ---- */

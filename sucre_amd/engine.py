@@ -1034,6 +1034,10 @@ MOSAIC_GAIN_SOLVES = ('rounds', 'direct')   # how the first round's gains are fo
 MOSAIC_GAIN_PRIOR = 2.0 ** -20              # mu of the direct solve: the weight of (g - 1)^2 against the data term
 MOSAIC_GAIN_DIRECT_CELL_BYTES = 292         # the direct solve's slots: 32 + 256 + 4 bytes per cell
 MOSAIC_GAIN_DIRECT_MEMORY = 0.8             # the share of the free device memory the direct solve's state may take
+MOSAIC_REJECT_RANGE = (1e-6, 1e6)           # colour tolerances T a consensus rejection takes, units of J (csrc/reject.h)
+_MOSAIC_REJECT = ('reject tolerance T', MOSAIC_REJECT_RANGE, False, 'colour units', np.float32)   # beside the record, as the surface's
+MOSAIC_REJECT_CELL_BYTES = 292              # the consensus' slots: 32 + 256 + 4 bytes per cell, freed after the consensus
+MOSAIC_REJECT_MEMORY = 0.8                  # the share of the free device memory the consensus' state may take
 
 
 def _mosaic_value(field: str, value, row=None):
@@ -1101,6 +1105,13 @@ def mosaic_support_checked(support, surface, who: str):
         raise _mosaic_refusal('support', f'{who}: the support decides which top the surface test measures against; give the '
                                          f'tolerance too (surface=T)')
     return support
+
+
+def mosaic_reject_checked(reject, who: str = 'mosaic'):
+    """None, or ``reject`` as the float32 tolerance T of the colour consensus in units of ``J``; ValueError (``field``: 'reject')
+    unless it is finite and within ``MOSAIC_REJECT_RANGE`` (``who`` asks: the rejection goes with any other option, so there is
+    no combination to refuse in its name)."""
+    return None if reject is None else _mosaic_value('reject', reject, _MOSAIC_REJECT)
 
 
 def mosaic_gain_rounds(gains) -> int:
@@ -1351,6 +1362,14 @@ MOSAIC_OUTPUTS = {   # key of Mosaic.result() -> (group, trailing shape, dtype, 
     'culled_above': ('support', (), torch.int32, 0, 'mosaic_culled_above.png', 'count'),
     'surface_top': ('support', (), torch.float32, _NAN, None, None),
 }
+MOSAIC_REJECT_OUTPUTS = {   # the rows a colour consensus adds (begin with a reject tolerance; csrc/reject.h): MOSAIC_OUTPUTS' columns, in
+    # a table of their own -- that one keeps its rows and its end --, merged in Mosaic.result() only when a rejection was begun
+    'rejected': ('reject', (), torch.int32, 0, 'mosaic_rejected.png', 'count'),
+    'reject_ref': ('reject', (3,), torch.float32, _NAN, None, None),
+    'reject_source': ('reject', (), torch.int32, -1, None, None),
+    'reject_views': ('reject', (), torch.int32, 0, None, None),
+    'reject_overflow': ('reject', (), torch.bool, False, None, None),
+}
 
 
 class Mosaic:
@@ -1445,7 +1464,24 @@ class Mosaic:
     ``gain_pair_index`` (P,2) int32 and ``gain_pair_words`` (P,4) int64 -- the pairs i <= j with a shared cell, ascending: P_ij x 3
     and the cells --, ``gain_diag`` (n,4) int64, ``gain_excluded_cells`` -- shared cells that more than 8 images reach, left out --,
     ``gain_shared_cells`` -- all the shared cells --, ``gain_kept`` -- the channels (0..2) that kept their gains because their system
-    has no finite positive solution --, ``gain_components`` -- connected groups of the overlap graph -- and ``gain_prior``.  ``gain_rms[1]`` shows what the solve achieved."""
+    has no finite positive solution --, ``gain_components`` -- connected groups of the overlap graph -- and ``gain_prior``.  ``gain_rms[1]`` shows what the solve achieved.
+
+    The colour consensus: ``begin(reject=T)`` -- T in units of ``J`` (``MOSAIC_REJECT_RANGE``; csrc/reject.h).  A transient object
+    that the rendered depth maps do not hold has the seabed's height and its own colour; no height test sees it.  ``begin``
+    allocates ``reject_slot_ord`` ((Hm Wm, 8) int32 bit patterns, all ones: free), ``reject_slot_sum`` ((Hm Wm, 8, 4) int64) and
+    ``reject_slot_over`` ((Hm Wm,) int32): 292 bytes per cell, refused beyond ``MOSAIC_REJECT_MEMORY`` of the free device memory before
+    anything is allocated.  After the surface phase and before ``splat``: ``add_reject_claim(views, Js, first_ordinal)`` over ALL the
+    images -- a cell's words end as the 8 smallest ordinals that reach it, in any order of arrival --, then ``add_reject_sums`` over
+    ALL of them, then ``finish_reject()``: the images of a cell that three or more reach are ordered by their mean brightness there,
+    the lower median is the cell's reference, and the slots are freed.  From then on ``splat`` and every later phase, the gains'
+    included, see through ``rejected_images`` a copy of every (culled) ``J`` with NaN where a sample of another image differs from
+    its cell's reference by more than T in any channel.  The reference image's samples never go, so the grid and the set of filled
+    cells do not change.  ``result()`` then also holds the rows of ``MOSAIC_REJECT_OUTPUTS`` -- ``rejected`` (Hm,Wm) int32,
+    ``reject_ref`` (Hm,Wm,3) float32 (NaN: no consensus), ``reject_source`` (int32, -1), ``reject_views`` (int32: the images that hold
+    slots, at most 8), ``reject_overflow`` (bool: more than 8 reach the cell) --, ``reject_per_image`` (n,2) int64 -- samples in
+    cells with a reference, samples rejected -- and ``reject_tol`` (= T).  ``reject_slot_ord`` (min-merge of the sorted words),
+    ``reject_slot_sum`` (sum) and ``rejected`` (sum) are the tensors a later all-reduce over ranks would combine.  One more buffer
+    of 12 bytes per padded pixel of the largest batch is held."""
 
     def __init__(self, axes, gsd, device):
         _lib.load()
@@ -1482,6 +1518,9 @@ class Mosaic:
         self.gain_solve = self.slot_ord = self.slot_sum = self.slot_over = self.gain_pairs_words = self.gain_diag_words = None
         self.gain_direct = self.gain_kept = None
         self._paired = False
+        self.reject = self.reject_slot_ord = self.reject_slot_sum = self.reject_slot_over = self.reject_counts = None
+        self._reject_out, self._reject_state, self._reject_n = {}, None, 0
+        self._reject_buf = self._held_rejected = None
 
     def _images(self, views: list, Js: list):
         views, Js = list(views), list(Js)
@@ -1536,7 +1575,7 @@ class Mosaic:
         return tuple(bits.view(np.float32).tolist())
 
     def begin(self, bounds=None, blend=None, feather=None, bands=None, surface=None, support=None, gains=None, gain_limit=None,
-              gain_solve=None):
+              reject=None, gain_solve=None):
         """Fixes the grid and allocates; ``blend``: the blend depth H in metres (``MOSAIC_BLEND_RANGE``) -- a pixel whose range
         exceeds its cell's smallest one by d gets the weight ``max(1 - d / H, 0)^2`` -- or None for the best view alone;
         ``feather``: with a blend, the feather width F in source pixels (``MOSAIC_FEATHER_RANGE``), or None for none; ``bands``:
@@ -1546,8 +1585,10 @@ class Mosaic:
         ``gains``: the rounds R of the per-image gain compensation (``MOSAIC_GAIN_ROUNDS_RANGE``), or None for none;
         ``gain_limit``: with ``gains``, the limit L of a gain (``MOSAIC_GAIN_LIMIT_RANGE``), ``MOSAIC_GAIN_LIMIT`` unless given;
         ``gain_solve``: with ``gains``, 'direct' for the direct solve in place of the first round's (``MOSAIC_GAIN_SOLVES``), 'rounds'
-        or None for the rounds alone."""
+        or None for the rounds alone; ``reject``: the tolerance T in units of ``J`` of the colour consensus across views
+        (``MOSAIC_REJECT_RANGE``), or None for none."""
         options = MosaicOptions(blend=blend, feather=feather).checked('Mosaic.begin')   # before anything is allocated
+        reject = mosaic_reject_checked(reject, 'Mosaic.begin')
         gains, gain_limit = mosaic_gains_checked(gains, gain_limit, 'Mosaic.begin')
         gain_solve = mosaic_gain_solve_checked(gain_solve, gains, 'Mosaic.begin')
         blend, feather = options.blend, options.feather
@@ -1568,6 +1609,12 @@ class Mosaic:
                                           f'(SUCRE_MOSAIC_MAX_CELLS); give a coarser grid with --mosaic-gsd'
                                           + ('' if support is None else f' (a support of {support} views holds {8 * support} more bytes per cell: '
                                                                         f'the rank words)'))
+        if reject is not None:   # before anything is allocated
+            need, free = MOSAIC_REJECT_CELL_BYTES * Wm * Hm, _device_free_bytes(self.device)
+            if need > MOSAIC_REJECT_MEMORY * free:
+                raise _mosaic_refusal('reject', f'mosaic reject: {Wm} x {Hm} cells need {need} bytes for the consensus '
+                                                f'({MOSAIC_REJECT_CELL_BYTES} per cell), more than {MOSAIC_REJECT_MEMORY:g} of the {free} free '
+                                                f'on the device; give a coarser grid with --mosaic-gsd')
         self.Hm, self.Wm, self.lo, self.hi = Hm, Wm, (lo_s, lo_t), (hi_s, hi_t)
         g = _lib.MosaicGrid()
         g.axes, g.gsd, g.lo_s, g.lo_t, g.Hm, g.Wm = self._axes_c, float(self.gsd), float(lo_s), float(lo_t), Hm, Wm
@@ -1611,6 +1658,17 @@ class Mosaic:
         if gains is not None:
             self.span = torch.tensor([-1, 0], dtype=torch.int32, device=dev).repeat(Hm * Wm, 1)    # all ones, 0: empty; 8 bytes per cell
             self.acc_gain = torch.zeros((Hm * Wm, _lib.MOSAIC_ACC_WORDS), dtype=torch.int64, device=dev)   # 64 bytes per cell
+        self.reject = reject
+        self.reject_slot_ord = self.reject_slot_sum = self.reject_slot_over = self.reject_counts = None
+        self._reject_out, self._reject_state, self._reject_n, self._reject_buf, self._held_rejected = {}, None, 0, None, None
+        if reject is not None:
+            slots = _lib.MOSAIC_REJECT_CELL_IMAGES
+            self.reject_slot_ord = torch.full((Hm * Wm, slots), -1, dtype=torch.int32, device=dev)    # all ones: free
+            self.reject_slot_sum = torch.zeros((Hm * Wm, slots, 4), dtype=torch.int64, device=dev)
+            self.reject_slot_over = torch.zeros((Hm * Wm,), dtype=torch.int32, device=dev)
+            for key, (_, tail, dtype, empty, _, _) in MOSAIC_REJECT_OUTPUTS.items():
+                self._reject_out[key] = torch.full((Hm, Wm) + tail, empty, dtype=dtype, device=dev)
+            self._reject_state = 'claim'
         return Hm, Wm
 
     def _begun(self, what: str) -> None:
@@ -1693,8 +1751,106 @@ class Mosaic:
         """``_images`` for a phase after the surface test: of the culled ``Js`` when a surface was begun, and, once a gain pass has
         run, of those times their gains (``gained_images``; of the ones ``run`` holds when a single batch is the whole request)."""
         if self._gain_passes == 0:
-            return self._images(views, self._culled(views, Js, first_ordinal, count))
+            return self._images(views, self._cleaned(views, Js, first_ordinal, count))
         return self._images(views, self.gained_images(views, Js, first_ordinal) if self._held_gained is None else self._held_gained)
+
+    # ---- the colour consensus across views (csrc/reject.h) ----
+
+    def _rejecting(self, what: str) -> None:
+        self._begun(what)
+        if self.reject is None:
+            raise ValueError(f'Mosaic.{what}: begin() was not given a reject tolerance, so there is no consensus to form')
+
+    def add_reject_claim(self, views: list, Js: list, first_ordinal: int, plain_atomic: bool = False) -> None:
+        """Lowers ``reject_slot_ord`` to the 8 smallest ordinals of every cell the images reach and sets ``reject_slot_over`` where
+        a ninth arrives (``sucre_mosaic_reject_claim``), over the (culled) images.  Over ALL the images, in any batches and any
+        order, after ``begin`` (with a surface: after ``add_surface`` / ``finish_support``) and before ``add_reject_sums``.
+        ``plain_atomic``: every sample walks the whole chain of atomic minima."""
+        self._rejecting('add_reject_claim')
+        if self._reject_state != 'claim':
+            raise ValueError('Mosaic.add_reject_claim: add_reject_sums() has read the slots already: the claim sees every image first')
+        images = self._images(views, self._culled(views, Js, first_ordinal))
+        self._walk('sucre_mosaic_reject_claim', images, int(first_ordinal), C.byref(self.grid), self.reject_slot_ord,
+                   self.reject_slot_over, _lib.MOSAIC_PLAIN_ATOMIC if plain_atomic else 0)
+        self._reject_n = max(self._reject_n, int(first_ordinal) + images[1])
+
+    def add_reject_sums(self, views: list, Js: list, first_ordinal: int, plain: bool = False) -> None:
+        """Adds every sample's 1 and quantised colour to its image's slot of its cell (``sucre_mosaic_reject_sums``) where the image
+        is one of the cell's eight, over the (culled) images.  Over ALL the images, in any batches and any order, once
+        ``add_reject_claim`` has seen every image and before ``finish_reject``.  ``plain``: every sample for itself."""
+        self._rejecting('add_reject_sums')
+        if self._reject_state == 'done':
+            raise ValueError('Mosaic.add_reject_sums: finish_reject() has formed the consensus already')
+        images = self._images(views, self._culled(views, Js, first_ordinal))
+        if int(first_ordinal) + images[1] > self._reject_n:
+            raise ValueError(f'Mosaic.add_reject_sums: ordinals {int(first_ordinal)}..{int(first_ordinal) + images[1] - 1}, but the claim has '
+                             f'seen {self._reject_n} images: add_reject_claim() over every image comes first (the slots must be final)')
+        self._reject_state = 'sums'
+        self._walk('sucre_mosaic_reject_sums', images, int(first_ordinal), C.byref(self.grid), self.reject_slot_ord, self.reject_slot_sum,
+                   _lib.MOSAIC_PLAIN_ATOMIC if plain else 0)
+
+    def finish_reject(self) -> None:
+        """The consensus of every cell from its slots (``sucre_mosaic_reject_consensus``): ``reject_ref``, ``reject_source`` and
+        ``reject_views``; ``reject_overflow`` from the flags.  Once ``add_reject_sums`` has seen every image and before ``splat``.
+        Waits, and raises ValueError (``field``: 'reject') when an image holds ``MOSAIC_MAX_SAMPLES`` = 2^20 samples or more in
+        one cell (the integer comparison of two means may overflow).  Frees the slots (292 bytes per cell); ``reject_counts``
+        ((n, 16) int64, two words used) is allocated for the n images the claim has seen."""
+        self._rejecting('finish_reject')
+        if self._reject_state != 'sums':
+            raise ValueError('Mosaic.finish_reject: add_reject_claim() and then add_reject_sums() over every image come first'
+                             if self._reject_state == 'claim' else 'Mosaic.finish_reject: the consensus has been formed already')
+        o = self._reject_out
+        big = torch.zeros(1, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().sucre_mosaic_reject_consensus(C.byref(self.grid), *(C.c_void_p(x.data_ptr()) for x in (
+                self.reject_slot_ord, self.reject_slot_sum, o['reject_ref'], o['reject_source'], o['reject_views'], big)), _stream_ptr()))
+        n_big = int(big)
+        if n_big:
+            raise _mosaic_refusal('reject', f'mosaic reject: {n_big} times an image holds {MOSAIC_MAX_SAMPLES} samples or more in one cell, and '
+                                            f'from there on the comparison of two images\' means may overflow; give a finer grid with --mosaic-gsd')
+        o['reject_overflow'].copy_((self.reject_slot_over != 0).view(self.Hm, self.Wm))
+        self.reject_slot_ord = self.reject_slot_sum = self.reject_slot_over = None
+        self.reject_counts = torch.zeros((self._reject_n, _lib.MOSAIC_GAIN_ROW_WORDS), dtype=torch.int64, device=self.device)
+        self._reject_state = 'done'
+
+    def rejected_images(self, views: list, Js: list, first_ordinal: int, count: bool = False, _culled=None) -> list:
+        """The batch's ``Js`` as the phases after the colour consensus see them: per image an (H,W,3) float32 copy of the (culled)
+        ``J`` with NaN in every channel of a pixel that does not take part, or whose cell has a reference, whose image is not the
+        cell's ``reject_source`` and whose colour differs from ``reject_ref`` by more than T in any channel
+        (``sucre_mosaic_reject_cull``).  Valid once ``finish_reject`` has run.  Views into ONE transient buffer of its own, sized to
+        the largest batch seen: the next call overwrites them.  ``count``: the rejected samples are added to ``rejected`` and
+        ``reject_counts`` -- to be asked for in one phase alone (``splat`` does).  Only enqueues."""
+        self._rejecting('rejected_images')
+        if self._reject_state != 'done':
+            raise ValueError('Mosaic.rejected_images: finish_reject() comes first (there is no consensus to test against yet)')
+        images = self._images(views, self._culled(views, Js, first_ordinal) if _culled is None else _culled)
+        arr, n, _, _ = images
+        if int(first_ordinal) + n > self._reject_n:
+            raise ValueError(f'Mosaic.rejected_images: ordinals {int(first_ordinal)}..{int(first_ordinal) + n - 1}, but the claim has seen '
+                             f'{self._reject_n} images')
+        lib = _lib.load()
+        n_bytes = lib.sucre_mosaic_band_bytes(n, arr)
+        if n_bytes == 0:
+            raise _lib.SucreError(f'sucre_mosaic_band_bytes: {lib.sucre_last_error().decode()}')
+        if self._reject_buf is None or self._reject_buf.numel() * 4 < n_bytes:
+            self._reject_buf = torch.empty(n_bytes // 4, dtype=torch.float32, device=self.device)
+        buf, o = self._reject_buf, self._reject_out
+        self._walk('sucre_mosaic_reject_cull', images, int(first_ordinal), C.byref(self.grid), o['reject_ref'], o['reject_source'],
+                   C.c_float(float(self.reject)), buf, o['rejected'] if count else None, int(self._reject_n),
+                   self.reject_counts if count else None)
+        out, at = [], 0
+        for e in arr:
+            out.append(buf[at * 3:(at + e.H * e.W) * 3].view(e.H, e.W, 3))
+            at += -(-(e.H * e.W) // _lib.MOSAIC_BLOCK_PX) * _lib.MOSAIC_BLOCK_PX
+        return out
+
+    def _cleaned(self, views: list, Js: list, first_ordinal: int, count: bool = False) -> list:
+        """The batch's ``Js`` as the phases from the splat on see them, gains apart: culled when a surface was begun, then rejected
+        when a colour consensus was (the ones ``run`` holds when a single batch is the whole request)."""
+        Jc = self._culled(views, Js, first_ordinal, count)
+        if self.reject is None:
+            return Jc
+        return self.rejected_images(views, Js, first_ordinal, count, _culled=Jc) if self._held_rejected is None else self._held_rejected
 
     # ---- the gain compensation (csrc/gains_mosaic.h) ----
 
@@ -1713,7 +1869,7 @@ class Mosaic:
         (``sucre_mosaic_gain_span``).  Over ALL the images, in any batches, once ``splat`` has seen every image and before the first
         gain pass.  ``plain_atomic``: both atomics for every pixel, without the loads that filter them."""
         self._spanned('add_span')
-        self._walk('sucre_mosaic_gain_span', self._images(views, self._culled(views, Js, first_ordinal)), int(first_ordinal),
+        self._walk('sucre_mosaic_gain_span', self._images(views, self._cleaned(views, Js, first_ordinal)), int(first_ordinal),
                    C.byref(self.grid), self.span, _lib.MOSAIC_PLAIN_ATOMIC if plain_atomic else 0)
 
     def _apply_gains(self, views: list, Jc: list, first_ordinal: int) -> list:
@@ -1745,7 +1901,7 @@ class Mosaic:
         self._gaining('gained_images')
         if self.gain_table is None:
             raise ValueError('Mosaic.gained_images: no gain pass has begun, so there is no gain table yet')
-        return self._apply_gains(views, self._culled(views, Js, first_ordinal), first_ordinal)
+        return self._apply_gains(views, self._cleaned(views, Js, first_ordinal), first_ordinal)
 
     def begin_gain_pass(self, n_images: int) -> None:
         """Opens a pass at the gains as they stand: zeroes ``acc_gain``; the first one allocates ``gain_table`` (ones) and
@@ -1773,7 +1929,7 @@ class Mosaic:
         """The reference of the open pass: the blend's accumulate over the gained images into ``acc_gain`` with the smallest normal
         float32 as ``inv_h``, so that every sample weighs 4096 -- the per-sample mean.  Over ALL the images before ``add_gain_sums``."""
         self._in_gain_pass('add_gain_reference')
-        Jg = self._apply_gains(views, self._culled(views, Js, first_ordinal), first_ordinal)
+        Jg = self._apply_gains(views, self._cleaned(views, Js, first_ordinal), first_ordinal)
         self._walk('sucre_mosaic_accumulate', self._images(views, Jg), int(first_ordinal), C.byref(self.grid), self.key,
                    C.c_float(2.0 ** -126), self.acc_gain, _lib.MOSAIC_PLAIN_ATOMIC if plain else 0)
 
@@ -1796,7 +1952,7 @@ class Mosaic:
             if H * W > MOSAIC_GAIN_MAX_PIXELS:
                 raise _mosaic_refusal('gains', f'mosaic gains: {v.name or "a view"} has {W} x {H} pixels, more than the '
                                                f'{MOSAIC_GAIN_MAX_PIXELS} whose 64-bit sums stay below 2^62')
-        images = self._images(views, self._culled(views, Js, first_ordinal))
+        images = self._images(views, self._cleaned(views, Js, first_ordinal))
         if int(first_ordinal) + images[1] > self.gain_table.shape[0]:
             raise ValueError(f'Mosaic.add_gain_sums: ordinals {int(first_ordinal)}..{int(first_ordinal) + images[1] - 1} but the gain '
                              f'table holds {self.gain_table.shape[0]} images')
@@ -1872,7 +2028,7 @@ class Mosaic:
         self.gain_diag_words = torch.zeros((n, _lib.MOSAIC_GAIN_ROW_WORDS), dtype=torch.int64, device=dev)
 
     def _direct_images(self, what: str, views: list, Js: list, first_ordinal: int):
-        images = self._images(views, self._culled(views, Js, first_ordinal))
+        images = self._images(views, self._cleaned(views, Js, first_ordinal))
         if int(first_ordinal) + images[1] > self.gain_table.shape[0]:
             raise ValueError(f'Mosaic.{what}: ordinals {int(first_ordinal)}..{int(first_ordinal) + images[1] - 1} but the gain '
                              f'table holds {self.gain_table.shape[0]} images')
@@ -2171,7 +2327,16 @@ class Mosaic:
                 **({} if self.bands is None else {'bands': self.bands}),
                 **({} if self.surface is None else {'surface_tol': float(self.surface)}),
                 **({} if self.support is None else {**of('support'), 'surface_support': int(self.support)}),
-                **of('fill', 'blend_fill', 'bands_fill'), **self._gain_result()}
+                **self._reject_result(), **of('fill', 'blend_fill', 'bands_fill'), **self._gain_result()}
+
+    def _reject_result(self) -> dict:
+        """The keys of ``result()`` that a colour consensus adds (none without one): the rows of ``MOSAIC_REJECT_OUTPUTS``,
+        ``reject_per_image`` (n,2) int64 -- per image the samples in cells that have a reference and the samples rejected; no row
+        before ``finish_reject`` -- and ``reject_tol`` (= T, a float, the float32 value)."""
+        if self.reject is None:
+            return {}
+        per = torch.zeros((0, 2), dtype=torch.int64, device=self.device) if self.reject_counts is None else self.reject_counts[:, :2].contiguous()
+        return {**self._reject_out, 'reject_per_image': per, 'reject_tol': float(self.reject)}
 
     def _gain_result(self) -> dict:
         """The keys of ``result()`` that a gain compensation adds (none without one); waits for the sums."""
@@ -2202,7 +2367,7 @@ class Mosaic:
                 'gain_components': mosaic_gain_groups(pairs.numpy(), diag.numpy()), 'gain_prior': float(MOSAIC_GAIN_PRIOR)}
 
     def run(self, batches, options: MosaicOptions = MosaicOptions(), bounds=None, plain_atomic: bool = False, bands=None,
-            surface=None, support=None, gains=None, gain_limit=None, gain_solve=None) -> 'Mosaic':
+            surface=None, support=None, gains=None, gain_limit=None, reject=None, gain_solve=None) -> 'Mosaic':
         """Every phase over every batch, in the one order there is: the bounds (unless ``bounds`` is given), ``begin``; with
         ``surface`` (the tolerance T of the surface test, beside the options record) ``add_surface`` -- or, with ``support`` (the
         count M of supporting views, beside the record too; only with a surface), ``add_support`` over every batch for level 0,
@@ -2218,7 +2383,11 @@ class Mosaic:
         accumulate and the bands then see the gained images -- applied anew per phase and batch, unless one batch is the whole
         request: that one is gained once and held.  With ``gain_solve='direct'`` the first pass is followed by ``add_gain_slots``
         over every batch, ``gain_pairs``, ``add_gain_diag`` over every batch and ``solve_gains_direct`` in place of the first
-        ``solve_gains`` (csrc/gains_direct.h); 'rounds' and None: the rounds alone.  Returns the mosaic."""
+        ``solve_gains`` (csrc/gains_direct.h); 'rounds' and None: the rounds alone.  With ``reject`` (the tolerance T of the colour
+        consensus, beside the record; csrc/reject.h) the surface phase is followed by ``add_reject_claim`` over every batch, then
+        ``add_reject_sums`` over every batch, then ``finish_reject``; the splat and every phase after it, the gains' included, then
+        see the rejected copy of the (culled) images -- made anew per phase and batch, unless one batch is the whole request: that
+        one is made once and held.  Returns the mosaic."""
         batches = list(batches)
         if bounds is None:
             for _, load in batches:
@@ -2227,7 +2396,9 @@ class Mosaic:
         support = mosaic_support_checked(support, surface, 'Mosaic.run')
         gains, gain_limit = mosaic_gains_checked(gains, gain_limit, 'Mosaic.run')
         gain_solve = mosaic_gain_solve_checked(gain_solve, gains, 'Mosaic.run')
+        reject = mosaic_reject_checked(reject, 'Mosaic.run')
         self.begin(bounds, blend=options.blend, feather=options.feather, **({} if bands is None else {'bands': bands}),
+                   **({} if reject is None else {'reject': reject}),
                    **({} if surface is None else {'surface': surface}), **({} if support is None else {'support': support}),
                    **({} if gains is None else {'gains': gains, 'gain_limit': gain_limit}),
                    **({} if gain_solve is None else {'gain_solve': gain_solve}))
@@ -2244,6 +2415,15 @@ class Mosaic:
                 first, load = batches[0]
                 self._held = self.culled_images(*load(), first, count=True)
         try:
+            if reject is not None:
+                for first, load in batches:
+                    self.add_reject_claim(*load(), first, plain_atomic=plain_atomic)
+                for first, load in batches:
+                    self.add_reject_sums(*load(), first, plain=plain_atomic)
+                self.finish_reject()
+                if len(batches) == 1:
+                    first, load = batches[0]
+                    self._held_rejected = self.rejected_images(*load(), first, count=True)
             for first, load in batches:
                 self.splat(*load(), first, plain_atomic=plain_atomic)
             if gains is not None:
@@ -2277,14 +2457,14 @@ class Mosaic:
                     self.accumulate_bands(*load(), first, plain=plain_atomic)
                 self.combine_bands()
         finally:
-            self._held = self._held_gained = None
+            self._held = self._held_gained = self._held_rejected = None
         if options.fill is not None:
             self.fill(options.fill)
         return self
 
 
 def mosaic_of(views: list, Js: list, axes, gsd, bounds=None, batch: int = 32, plain_atomic: bool = False, blend=None,
-              fill=None, feather=None, bands=None, surface=None, support=None, gains=None, gain_limit=None,
+              fill=None, feather=None, bands=None, surface=None, support=None, gains=None, gain_limit=None, reject=None,
               gain_solve=None) -> 'Mosaic':
     """``Mosaic.run`` over device-resident ``views`` / ``Js`` (ordinal = position in the list), ``batch`` images per call; with
     ``blend`` (the blend depth H, metres) the accumulate phase and the normalise pass after them (``plain_atomic``: both the
@@ -2295,7 +2475,8 @@ def mosaic_of(views: list, Js: list, axes, gsd, bounds=None, batch: int = 32, pl
     view-supported top instead of the plain minimum (csrc/support.h); with ``gains`` (the rounds R) the per-image gain compensation
     between the splat and the resolve (csrc/gains_mosaic.h), every gain within ``[1 / gain_limit, gain_limit]``; with
     ``gain_solve='direct'`` (only with ``gains``) the first round's gains come from the direct least-squares solve
-    (csrc/gains_direct.h), with 'rounds' or None from the rounds alone."""
+    (csrc/gains_direct.h), with 'rounds' or None from the rounds alone; with ``reject`` (the tolerance T, units of ``J``) the colour
+    consensus across views ahead of the splat (csrc/reject.h)."""
     views, Js = list(views), list(Js)
     if not views:
         raise ValueError('mosaic_of: no view')
@@ -2307,11 +2488,13 @@ def mosaic_of(views: list, Js: list, axes, gsd, bounds=None, batch: int = 32, pl
     support = mosaic_support_checked(support, surface, 'mosaic_of')
     gains, gain_limit = mosaic_gains_checked(gains, gain_limit, 'mosaic_of')
     gain_solve = mosaic_gain_solve_checked(gain_solve, gains, 'mosaic_of')
+    reject = mosaic_reject_checked(reject, 'mosaic_of')
     batches = [(i, lambda i=i: (views[i:i + batch], Js[i:i + batch])) for i in range(0, len(views), batch)]
     return Mosaic(axes, gsd, views[0].depth.device).run(batches, options, bounds, plain_atomic, **({} if bands is None else {'bands': bands}),
                                                         **({} if surface is None else {'surface': surface}),
                                                         **({} if support is None else {'support': support}),
                                                         **({} if gains is None else {'gains': gains, 'gain_limit': gain_limit}),
+                                                        **({} if reject is None else {'reject': reject}),
                                                         **({} if gain_solve is None else {'gain_solve': gain_solve}))
 
 

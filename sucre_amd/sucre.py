@@ -1425,7 +1425,7 @@ def _mosaic_picture(J: Tensor, stretch) -> np.ndarray:
 
 _MOSAIC_FLAG = {'grid': '--mosaic', 'blend': '--mosaic-blend', 'fill': '--mosaic-fill', 'feather': '--mosaic-feather',
                 'bands': '--mosaic-bands', 'surface': '--mosaic-surface', 'support': '--mosaic-support', 'gains': '--mosaic-gains',
-                'gain_limit': '--mosaic-gain-limit', 'gain_solve': '--mosaic-gain-solve'}
+                'gain_limit': '--mosaic-gain-limit', 'gain_solve': '--mosaic-gain-solve', 'reject': '--mosaic-reject'}
 
 
 def _mosaic_refused(e: ValueError, fields=tuple(_MOSAIC_FLAG)) -> BaseException:
@@ -1447,7 +1447,7 @@ _MOSAIC_PNG = {   # how a row of engine.MOSAIC_OUTPUTS becomes its PNG: (the out
 def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, output_dir: Path, gsd: float | None = None, axes=None,
            stretch=None, device: str = 'cuda', blend: float | None = None, fill: float | None = None, feather: int | None = None,
            bands: int | None = None, surface: float | None = None, support: int | None = None, gains: int | None = None,
-           gain_limit: float | None = None, gain_solve: str | None = None) -> dict:
+           gain_limit: float | None = None, reject: float | None = None, gain_solve: str | None = None) -> dict:
     """One picture of the seabed from a finished restoration: every pixel of ``images`` (``sfm.Image`` objects or names of
     ``colmap_model``; at most ``engine.MAX_VIEWS``, ordinal = position) with a valid depth and a restored colour --
     ``results_dir / <name>.pt``, key ``J`` -- is dropped onto the plane grid ``axes`` (``mosaic_axes`` unless given) of ``gsd``
@@ -1530,7 +1530,19 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
     eight images reach is left out of the solve.  ``mosaic.pt`` gains ``gain_solve``, ``gain_direct``, ``gain_pair_index``,
     ``gain_pair_words``, ``gain_diag``, ``gain_excluded_cells``, ``gain_shared_cells``, ``gain_kept``, ``gain_components`` and
     ``gain_prior``, and one more line is printed
-    after the gains'.  'rounds' or None: the rounds alone, every file as without the argument."""
+    after the gains'.  'rounds' or None: the rounds alone, every file as without the argument.
+
+    ``reject``: a tolerance T in units of ``J`` (``engine.MOSAIC_REJECT_RANGE``) of a colour consensus across views ahead of the
+    splat (csrc/reject.h).  The depth maps are rendered from the reconstruction, so a fish, a fin, a caustic band or a particle cloud
+    carries the seabed's height and its own colour: no height test sees it.  Per cell the images that reach it -- the eight earliest
+    when there are more -- are ordered by their mean brightness there, the median one is the cell's reference, and a sample of another
+    image that differs from the reference's mean colour by more than T in any channel takes part in nothing from the splat on, the
+    gain compensation included.  A cell that fewer than three images reach rejects nothing, and the reference's own samples never go:
+    the grid and the filled cells stay those of a run without the argument, and a T that rejects nothing leaves every other file and
+    key byte for byte.  T must exceed the offsets between images that ``gains`` is to remove afterwards: there is no second
+    rejection.  ``mosaic_rejected.png`` (``mosaic_culled_picture`` of the counts) comes next to the other files, ``mosaic.pt`` gains
+    ``rejected``, ``reject_ref``, ``reject_source``, ``reject_views``, ``reject_overflow``, ``reject_per_image`` and ``reject_tol``,
+    and one more line is printed after the surface's and the support's."""
     from . import engine
     sfm.require_gpu(device, 'mosaic')
     images = [colmap_model[im] if isinstance(im, str) else im for im in images]
@@ -1575,6 +1587,10 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
         gain_solve = engine.mosaic_gain_solve_checked(gain_solve, gains, 'mosaic')
     except ValueError as e:
         raise _mosaic_refused(e)
+    try:
+        reject = engine.mosaic_reject_checked(reject, 'mosaic')
+    except ValueError as e:
+        raise _mosaic_refused(e)
     results_dir, output_dir = Path(results_dir), Path(output_dir)
     for image in images:   # before anything is decoded
         path = _consistency_file(results_dir, image)
@@ -1610,15 +1626,18 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
                                                      **({} if surface is None else {'surface': surface}),
                                                      **({} if support is None else {'support': support}),
                                                      **({} if gains is None else {'gains': gains, 'gain_limit': gain_limit}),
+                                                     **({} if reject is None else {'reject': reject}),
                                                      **({} if gain_solve is None else {'gain_solve': gain_solve}))
         except ValueError as e:
             # Three refusals of the run belong to a flag: begin's of the grid (--mosaic), normalize's of a cell's sample count
             # (--mosaic-blend) and the gain passes' of a cell's sample count or an image's size (--mosaic-gains).  The options were checked above, so begin and fill have nothing left to refuse in them; every other
             # ValueError (of a view, of a restored image) passes as it is.  A fourth: the direct solve's of a state that does not
-            # fit the device (--mosaic-gain-solve).
-            raise _mosaic_refused(e, ('grid', 'blend', 'gains', 'gain_solve'))
+            # fit the device (--mosaic-gain-solve).  A fifth: the consensus' of a state that does not fit, or of an image's sample
+            # count in one cell (--mosaic-reject).
+            raise _mosaic_refused(e, ('grid', 'blend', 'gains', 'gain_solve', 'reject'))
         out = m.result()
-        pictures = [(png, _MOSAIC_PNG[how](out[key], stretch)) for key, (_, _, _, _, png, how) in engine.MOSAIC_OUTPUTS.items()
+        pictures = [(png, _MOSAIC_PNG[how](out[key], stretch))
+                    for key, (_, _, _, _, png, how) in {**engine.MOSAIC_OUTPUTS, **engine.MOSAIC_REJECT_OUTPUTS}.items()
                     if png is not None and key in out]
         out = {k: v.cpu() if torch.is_tensor(v) else v for k, v in out.items()}
         surface_counts = None if surface is None else [int(x) for x in m.surface_counts.cpu()]
@@ -1655,6 +1674,15 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
         print(f'mosaic support of {support} views: {int(((out["support"] < support) & filled).sum())} of {n_filled} filled cells rest on '
               f'fewer than {support}; {above} of {part} samples ({100.0 * above / max(1, part):.1f} %) stand more than '
               f'{float(surface):.6g} m above their cell\'s supported top, in {int((out["culled_above"] > 0).sum())} cells')
+    if reject is not None:
+        per = out['reject_per_image']
+        tested, gone = int(per[:, 0].sum()), int(per[:, 1].sum())
+        worst = int(per[:, 1].argmax()) if len(per) else 0
+        print(f'mosaic reject of {float(reject):.6g}: {int(((out["reject_source"] >= 0) & filled).sum())} of {n_filled} filled cells have a '
+              f'consensus of {engine._lib.MOSAIC_REJECT_MIN_VIEWS} or more images ({int(out["reject_overflow"].sum())} hold more than '
+              f'{engine._lib.MOSAIC_REJECT_CELL_IMAGES}: the {engine._lib.MOSAIC_REJECT_CELL_IMAGES} earliest vote); {gone} of {tested} samples '
+              f'({100.0 * gone / max(1, tested):.1f} %) differ from it by more than {float(reject):.6g}, in '
+              f'{int((out["rejected"] > 0).sum())} cells; most rejected {images[worst].name} ({int(per[worst, 1]) if len(per) else 0} samples)')
     if gains is not None:
         g, rms, overlap = out['gains'].double(), out['gain_rms'], out['gain_overlap']
         far = (g.log().abs().max(dim=1).values * (overlap > 0)).argmax() if len(images) else 0
@@ -1756,6 +1784,13 @@ def _refuse_lone_gain_solve(args) -> None:
         raise SystemExit(f'{_MOSAIC_FLAG["gain_solve"]}: only with --mosaic-gains R')
 
 
+def _refuse_lone_reject(args) -> None:
+    """--mosaic-reject without --mosaic, refused before any file is opened (beside ``_ONLY_WITH``, as ``_refuse_lone_gain_solve``:
+    looked at after the table's rows)."""
+    if getattr(args, 'mosaic_reject', None) is not None and getattr(args, 'mosaic', None) is None:
+        raise SystemExit(f'{_MOSAIC_FLAG["reject"]}: only with --mosaic DIR')
+
+
 def _refuse_mode_flags(args, mode: str) -> None:
     """What ``mode`` (--mosaic, --check-consistency, --apply-water) does not combine with, refused before any file is opened."""
     for flag, why in _MODE_REFUSES[mode]:
@@ -1765,8 +1800,8 @@ def _refuse_mode_flags(args, mode: str) -> None:
 
 def _refuse_mosaic_values(args, world: int = 1) -> None:
     """The values of --mosaic-gsd, --mosaic-blend, --mosaic-fill, --mosaic-feather, --mosaic-bands, --mosaic-surface,
-    --mosaic-support, --mosaic-gains, --mosaic-gain-limit and --mosaic-gain-solve and the world size a mosaic takes, refused before any
-    file is opened."""
+    --mosaic-support, --mosaic-gains, --mosaic-gain-limit, --mosaic-gain-solve and --mosaic-reject and the world size a mosaic takes,
+    refused before any file is opened."""
     gsd = getattr(args, 'mosaic_gsd', None)
     if gsd is not None and not (np.isfinite(gsd) and gsd > 0):
         raise SystemExit(f'--mosaic-gsd: G must be a finite size > 0 in metres, not {gsd}')
@@ -1799,6 +1834,10 @@ def _refuse_mosaic_values(args, world: int = 1) -> None:
     solve = getattr(args, 'mosaic_gain_solve', None)
     if solve is not None and solve not in engine.MOSAIC_GAIN_SOLVES:
         raise SystemExit(f'{_MOSAIC_FLAG["gain_solve"]}: S must be {" or ".join(engine.MOSAIC_GAIN_SOLVES)}, not {solve}')
+    tol = getattr(args, 'mosaic_reject', None)
+    lo, hi = engine.MOSAIC_REJECT_RANGE
+    if tol is not None and not (np.isfinite(tol) and lo <= tol <= hi):
+        raise SystemExit(f'{_MOSAIC_FLAG["reject"]}: T must be a finite tolerance within [{lo:g}, {hi:g}] colour units, not {tol}')
     if world > 1:
         raise SystemExit(f'--mosaic: a world size of {world} is not supported yet: the four phases are separate entries of the library '
                          f'so that ranks can all-reduce bounds, keys and pixel words between them, but that all-reduce is not built; '
@@ -1828,6 +1867,7 @@ def parse_args(args: argparse.Namespace):
     mosaic_dir = getattr(args, 'mosaic', None)
     _refuse_lone_flags(args)
     _refuse_lone_gain_solve(args)
+    _refuse_lone_reject(args)
     if mosaic_dir is not None:
         _refuse_mode_flags(args, '--mosaic')
         _refuse_mosaic_values(args, world)
@@ -1914,7 +1954,7 @@ def parse_args(args: argparse.Namespace):
                    feather=getattr(args, 'mosaic_feather', None), bands=getattr(args, 'mosaic_bands', None),
                    surface=getattr(args, 'mosaic_surface', None), support=getattr(args, 'mosaic_support', None),
                    gains=getattr(args, 'mosaic_gains', None), gain_limit=getattr(args, 'mosaic_gain_limit', None),
-                   gain_solve=getattr(args, 'mosaic_gain_solve', None))
+                   reject=getattr(args, 'mosaic_reject', None), gain_solve=getattr(args, 'mosaic_gain_solve', None))
         elif check is not None:
             if world > 1:   # the targets' records are gathered on rank 0
                 sdist.init_process_group()
@@ -2208,6 +2248,16 @@ def build_parser() -> argparse.ArgumentParser:
                                'a chain of images, which the rounds do not; the remaining R - 1 rounds run after it; adds gain_solve, '
                                'gain_direct, gain_pair_index, gain_pair_words, gain_diag, gain_excluded_cells, gain_shared_cells, '
                                'gain_kept, gain_components and gain_prior to mosaic.pt and prints one more line')
+    p.extras.add_argument('--mosaic-reject', type=float, metavar='T', default=argparse.SUPPRESS,
+                          help='with --mosaic: also a colour consensus across views ahead of the splat -- per cell the images that reach '
+                               'it (the 8 earliest when there are more) are ordered by their mean brightness there, the median one is '
+                               'the reference, and a sample of another image that differs from the reference\'s mean colour by more '
+                               'than T (units of J) in any channel takes part in nothing: a fish, a fin or a caustic that the rendered '
+                               'depth maps do not hold no longer wins cells, enters the blend or biases --mosaic-gains; a cell seen by '
+                               'fewer than 3 images rejects nothing; the grid and the filled cells stay those of a run without the '
+                               'flag; T must exceed the offsets --mosaic-gains is to remove; writes mosaic_rejected.png, adds rejected, '
+                               'reject_ref, reject_source, reject_views, reject_overflow, reject_per_image and reject_tol to mosaic.pt '
+                               'and prints one more line')
     p.extras.add_argument('--common-stretch', action='store_true', default=argparse.SUPPRESS,
                           help='with --shared-water or --apply-water: stretch every <stem>_rgb.png between the SAME per-channel 1st '
                                'and 99th percentile, those of the valid pixels of all images of the request pooled (all ranks), '
