@@ -956,13 +956,35 @@ int sucre_mosaic_bounds(void *table_dev, int n_images, const sucre_mosaic_image_
                                    static_cast<hipStream_t>(stream)), "sucre_mosaic_bounds");
 }
 
+
+// The one flag a mosaic phase takes.
+static int check_mosaic_flags(unsigned flags) {
+    if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
+    return SUCRE_OK;
+}
+
+// J_out, the copy of every image's J that a cull or the gains write in the band buffers' layout, against the images' own J: a
+// buffer of its own -- a lane reads its pixel of an image's J and writes it somewhere else in J_out --, unless allow_in_place and an
+// image's J is its very block of J_out (a lane then reads and writes its own pixel alone).
+static int check_copy_out(const float *J_out, int n_images, const sucre_mosaic_image_t *images, bool allow_in_place) {
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(J_out), o1 = o0 + band_bytes(n_images, images);
+    uint64_t at = 0;   // pixels ahead of the image's block
+    for (int i = 0; i < n_images; ++i) {
+        const uintptr_t j0 = reinterpret_cast<uintptr_t>(images[i].J), j1 = j0 + (size_t)images[i].H * (size_t)images[i].W * 12;
+        if (!(allow_in_place && j0 == o0 + at * 12) && j0 < o1 && o0 < j1)
+            return fail(SUCRE_ERR_ARG, allow_in_place ? "image %d: J_out overlaps the image's J without being it" : "image %d: J_out overlaps the image's J", i);
+        at += mosaic_blocks(images[i].H, images[i].W) * kMosaicBlockPx;
+    }
+    return SUCRE_OK;
+}
+
 int sucre_mosaic_splat(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
                        const sucre_mosaic_grid_t *grid, uint64_t *key_dev, unsigned flags, void *stream) {
     if (int rc = check_mosaic_images(table_dev, n_images, images, first_ordinal)) return rc;
     MosaicGrid g;
     if (int rc = check_mosaic_grid(grid, &g)) return rc;
     if (!key_dev || !aligned(key_dev, 8)) return fail(SUCRE_ERR_ARG, "key_dev is NULL or not 8-byte aligned");
-    if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
+    if (int rc = check_mosaic_flags(flags)) return rc;
     return check_hip(launch_mosaic((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) ? kMosaicSplatPlain : kMosaicSplat, table_dev, n_images, images,
                                    first_ordinal, g, nullptr, reinterpret_cast<unsigned long long *>(key_dev), nullptr, MosaicOut{},
                                    static_cast<hipStream_t>(stream)), "sucre_mosaic_splat");
@@ -1019,7 +1041,7 @@ static int mosaic_accumulate(const char *entry, bool feathered, void *table_dev,
         f = {static_cast<const uint32_t *>(feather_dev), (uint32_t)feather_px * (uint32_t)feather_px, 1.0f / (float)feather_px};
     }
     if (!acc_dev || !aligned(acc_dev, 8)) return fail(SUCRE_ERR_ARG, "acc_dev is NULL or not 8-byte aligned");
-    if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
+    if (int rc = check_mosaic_flags(flags)) return rc;
     return check_hip(launch_mosaic_accumulate((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) != 0, table_dev, n_images, images, first_ordinal, g,
                                               reinterpret_cast<const unsigned long long *>(key_dev), inv_h, feathered ? &f : nullptr,
                                               reinterpret_cast<unsigned long long *>(acc_dev), static_cast<hipStream_t>(stream)), entry);
@@ -1130,14 +1152,15 @@ int sucre_mosaic_surface(void *table_dev, int n_images, const sucre_mosaic_image
     MosaicGrid g;
     if (int rc = check_mosaic_grid(grid, &g)) return rc;
     if (!top_dev || !aligned(top_dev, 4)) return fail(SUCRE_ERR_ARG, "top_dev is NULL or not 4-byte aligned");
-    if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
+    if (int rc = check_mosaic_flags(flags)) return rc;
     return check_hip(launch_mosaic_surface((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) != 0, table_dev, n_images, images, first_ordinal, g, top_dev,
                                            static_cast<hipStream_t>(stream)), "sucre_mosaic_surface");
 }
 
-int sucre_mosaic_cull(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
-                      const sucre_mosaic_grid_t *grid, const uint32_t *top_dev, float tol, float *J_out, uint32_t *culled_dev,
-                      uint64_t *counts_dev, void *stream) {
+// Both culls: sucre_mosaic_cull (culled_above_dev NULL, two counters) and sucre_mosaic_cull_supported (three).
+static int mosaic_cull(bool two_sided, const char *what, void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                       const sucre_mosaic_grid_t *grid, const uint32_t *top_dev, float tol, float *J_out, uint32_t *culled_dev,
+                       uint32_t *culled_above_dev, uint64_t *counts_dev, void *stream) {
     if (int rc = check_mosaic_images(table_dev, n_images, images, first_ordinal)) return rc;
     MosaicGrid g;
     if (int rc = check_mosaic_grid(grid, &g)) return rc;
@@ -1145,16 +1168,19 @@ int sucre_mosaic_cull(void *table_dev, int n_images, const sucre_mosaic_image_t 
     if (!std::isfinite(tol) || !(tol > 0.0f)) return fail(SUCRE_ERR_ARG, "tol=%g must be finite and > 0", (double)tol);
     if (!J_out || !aligned(J_out, 4)) return fail(SUCRE_ERR_ARG, "J_out is NULL or not 4-byte aligned");
     if (culled_dev && !aligned(culled_dev, 4)) return fail(SUCRE_ERR_ARG, "culled_dev is not 4-byte aligned");
+    if (culled_above_dev && !aligned(culled_above_dev, 4)) return fail(SUCRE_ERR_ARG, "culled_above_dev is not 4-byte aligned");
     if (counts_dev && !aligned(counts_dev, 8)) return fail(SUCRE_ERR_ARG, "counts_dev is not 8-byte aligned");
-    // J_out is a buffer of its own: a lane reads its pixel of an image's J and writes it somewhere else in J_out
-    const uintptr_t o0 = reinterpret_cast<uintptr_t>(J_out), o1 = o0 + band_bytes(n_images, images);
-    for (int i = 0; i < n_images; ++i) {
-        const uintptr_t j0 = reinterpret_cast<uintptr_t>(images[i].J), j1 = j0 + (size_t)images[i].H * (size_t)images[i].W * 12;
-        if (j0 < o1 && o0 < j1) return fail(SUCRE_ERR_ARG, "image %d: J_out overlaps the image's J", i);
-    }
-    const MosaicCull out = {culled_dev, reinterpret_cast<unsigned long long *>(counts_dev)};
-    return check_hip(launch_mosaic_cull(table_dev, n_images, images, first_ordinal, g, top_dev, tol, J_out, out,
-                                        static_cast<hipStream_t>(stream)), "sucre_mosaic_cull");
+    if (int rc = check_copy_out(J_out, n_images, images, false)) return rc;
+    const MosaicCull out = {culled_dev, culled_above_dev, reinterpret_cast<unsigned long long *>(counts_dev)};
+    return check_hip(launch_mosaic_cull(two_sided, table_dev, n_images, images, first_ordinal, g, top_dev, tol, J_out, out,
+                                        static_cast<hipStream_t>(stream)), what);
+}
+
+int sucre_mosaic_cull(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                      const sucre_mosaic_grid_t *grid, const uint32_t *top_dev, float tol, float *J_out, uint32_t *culled_dev,
+                      uint64_t *counts_dev, void *stream) {
+    return mosaic_cull(false, "sucre_mosaic_cull", table_dev, n_images, images, first_ordinal, grid, top_dev, tol, J_out, culled_dev, nullptr,
+                       counts_dev, stream);
 }
 
 /* ---- view-supported surface: per-cell ranks of the per-image tops, the supported top, the two-sided cull (support.h) ---- */
@@ -1173,7 +1199,7 @@ int sucre_mosaic_support(void *table_dev, int n_images, const sucre_mosaic_image
     if (int rc = check_support_levels(n_levels, g)) return rc;
     if (level < 0 || level >= n_levels) return fail(SUCRE_ERR_ARG, "level=%d outside [0,%d)", level, n_levels);
     if (!rank_dev || !aligned(rank_dev, 8)) return fail(SUCRE_ERR_ARG, "rank_dev is NULL or not 8-byte aligned");
-    if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
+    if (int rc = check_mosaic_flags(flags)) return rc;
     return check_hip(launch_mosaic_support((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) != 0, table_dev, n_images, images, first_ordinal, g, level,
                                            reinterpret_cast<unsigned long long *>(rank_dev), static_cast<hipStream_t>(stream)),
                      "sucre_mosaic_support");
@@ -1194,24 +1220,8 @@ int sucre_mosaic_support_top(const sucre_mosaic_grid_t *grid, int n_levels, cons
 int sucre_mosaic_cull_supported(void *table_dev, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
                                 const sucre_mosaic_grid_t *grid, const uint32_t *top_dev, float tol, float *J_out,
                                 uint32_t *culled_dev, uint32_t *culled_above_dev, uint64_t *counts_dev, void *stream) {
-    if (int rc = check_mosaic_images(table_dev, n_images, images, first_ordinal)) return rc;
-    MosaicGrid g;
-    if (int rc = check_mosaic_grid(grid, &g)) return rc;
-    if (!top_dev || !aligned(top_dev, 4)) return fail(SUCRE_ERR_ARG, "top_dev is NULL or not 4-byte aligned");
-    if (!std::isfinite(tol) || !(tol > 0.0f)) return fail(SUCRE_ERR_ARG, "tol=%g must be finite and > 0", (double)tol);
-    if (!J_out || !aligned(J_out, 4)) return fail(SUCRE_ERR_ARG, "J_out is NULL or not 4-byte aligned");
-    if (culled_dev && !aligned(culled_dev, 4)) return fail(SUCRE_ERR_ARG, "culled_dev is not 4-byte aligned");
-    if (culled_above_dev && !aligned(culled_above_dev, 4)) return fail(SUCRE_ERR_ARG, "culled_above_dev is not 4-byte aligned");
-    if (counts_dev && !aligned(counts_dev, 8)) return fail(SUCRE_ERR_ARG, "counts_dev is not 8-byte aligned");
-    // J_out is a buffer of its own, as sucre_mosaic_cull's
-    const uintptr_t o0 = reinterpret_cast<uintptr_t>(J_out), o1 = o0 + band_bytes(n_images, images);
-    for (int i = 0; i < n_images; ++i) {
-        const uintptr_t j0 = reinterpret_cast<uintptr_t>(images[i].J), j1 = j0 + (size_t)images[i].H * (size_t)images[i].W * 12;
-        if (j0 < o1 && o0 < j1) return fail(SUCRE_ERR_ARG, "image %d: J_out overlaps the image's J", i);
-    }
-    const MosaicCullSupported out = {culled_dev, culled_above_dev, reinterpret_cast<unsigned long long *>(counts_dev)};
-    return check_hip(launch_mosaic_cull_supported(table_dev, n_images, images, first_ordinal, g, top_dev, tol, J_out, out,
-                                                  static_cast<hipStream_t>(stream)), "sucre_mosaic_cull_supported");
+    return mosaic_cull(true, "sucre_mosaic_cull_supported", table_dev, n_images, images, first_ordinal, grid, top_dev, tol, J_out, culled_dev,
+                       culled_above_dev, counts_dev, stream);
 }
 
 /* ---- per-image gain compensation of the mosaic: the span of ordinals per cell, J x gain, the ten sums per image (gains_mosaic.h) ---- */
@@ -1230,7 +1240,7 @@ int sucre_mosaic_gain_span(void *table_dev, int n_images, const sucre_mosaic_ima
     MosaicGrid g;
     if (int rc = check_mosaic_grid(grid, &g)) return rc;
     if (!span_dev || !aligned(span_dev, 8)) return fail(SUCRE_ERR_ARG, "span_dev is NULL or not 8-byte aligned");
-    if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
+    if (int rc = check_mosaic_flags(flags)) return rc;
     return check_hip(launch_mosaic_gain_span((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) != 0, table_dev, n_images, images, first_ordinal, g, span_dev,
                                              static_cast<hipStream_t>(stream)), "sucre_mosaic_gain_span");
 }
@@ -1241,14 +1251,7 @@ int sucre_mosaic_gain_apply(void *table_dev, int n_images, const sucre_mosaic_im
     if (int rc = check_gain_rows(n_images, first_ordinal, n_ordinals)) return rc;
     if (!gains_dev || !aligned(gains_dev, 4)) return fail(SUCRE_ERR_ARG, "gains_dev is NULL or not 4-byte aligned");
     if (!J_out || !aligned(J_out, 4)) return fail(SUCRE_ERR_ARG, "J_out is NULL or not 4-byte aligned");
-    // an image's J is its own block of J_out (a lane reads and writes its own pixel alone) or lies outside J_out altogether
-    const uintptr_t o0 = reinterpret_cast<uintptr_t>(J_out), o1 = o0 + band_bytes(n_images, images);
-    uint64_t at = 0;   // pixels ahead of the image's block
-    for (int i = 0; i < n_images; ++i) {
-        const uintptr_t j0 = reinterpret_cast<uintptr_t>(images[i].J), j1 = j0 + (size_t)images[i].H * (size_t)images[i].W * 12;
-        if (j0 != o0 + at * 12 && j0 < o1 && o0 < j1) return fail(SUCRE_ERR_ARG, "image %d: J_out overlaps the image's J without being it", i);
-        at += mosaic_blocks(images[i].H, images[i].W) * kMosaicBlockPx;
-    }
+    if (int rc = check_copy_out(J_out, n_images, images, true)) return rc;   // an image's J may be its own block of J_out
     return check_hip(launch_mosaic_gain_apply(table_dev, n_images, images, first_ordinal, gains_dev, J_out, static_cast<hipStream_t>(stream)),
                      "sucre_mosaic_gain_apply");
 }
@@ -1267,7 +1270,7 @@ int sucre_mosaic_gain_sums(void *table_dev, int n_images, const sucre_mosaic_ima
     if (!acc_dev || !aligned(acc_dev, 8)) return fail(SUCRE_ERR_ARG, "acc_dev is NULL or not 8-byte aligned");
     if (!gains_dev || !aligned(gains_dev, 4)) return fail(SUCRE_ERR_ARG, "gains_dev is NULL or not 4-byte aligned");
     if (!sums_dev || !aligned(sums_dev, 128)) return fail(SUCRE_ERR_ARG, "sums_dev is NULL or not 128-byte aligned");
-    if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
+    if (int rc = check_mosaic_flags(flags)) return rc;
     return check_hip(launch_mosaic_gain_sums((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) != 0, table_dev, n_images, images, first_ordinal, g, span_dev,
                                              reinterpret_cast<const long long *>(acc_dev), gains_dev,
                                              reinterpret_cast<unsigned long long *>(sums_dev), static_cast<hipStream_t>(stream)),
@@ -1292,7 +1295,7 @@ int sucre_mosaic_gain_slots(void *table_dev, int n_images, const sucre_mosaic_im
     MosaicGrid g;
     if (int rc = check_mosaic_grid(grid, &g)) return rc;
     if (int rc = check_gain_slot_state(span_dev, slot_ord_dev, slot_sum_dev, slot_over_dev, true)) return rc;
-    if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
+    if (int rc = check_mosaic_flags(flags)) return rc;
     return check_hip(launch_mosaic_gain_slots((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) != 0, table_dev, n_images, images, first_ordinal, g, span_dev,
                                               slot_ord_dev, reinterpret_cast<unsigned long long *>(slot_sum_dev), slot_over_dev,
                                               static_cast<hipStream_t>(stream)), "sucre_mosaic_gain_slots");
@@ -1311,7 +1314,7 @@ int sucre_mosaic_gain_pairs(const sucre_mosaic_grid_t *grid, const uint32_t *spa
     if (table_entries == 0) table_entries = kPairTableMax;
     if (table_entries < 1 || table_entries > kPairTableMax || (table_entries & (table_entries - 1)))
         return fail(SUCRE_ERR_ARG, "table_entries=%d is not 0 or a power of two within [1,%d]", table_entries, kPairTableMax);
-    if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
+    if (int rc = check_mosaic_flags(flags)) return rc;
     return check_hip(launch_mosaic_gain_pairs((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) != 0, g, span_dev, slot_ord_dev,
                                               reinterpret_cast<const long long *>(slot_sum_dev), slot_over_dev, n_ordinals,
                                               reinterpret_cast<unsigned long long *>(pairs_dev), table_entries, static_cast<hipStream_t>(stream)),
@@ -1330,7 +1333,7 @@ int sucre_mosaic_gain_diag(void *table_dev, int n_images, const sucre_mosaic_ima
             return fail(SUCRE_ERR_ARG, "image %d: %dx%d pixels, more than the 2^26 whose sums stay below 2^62", i, images[i].W, images[i].H);
     if (int rc = check_gain_slot_state(span_dev, nullptr, nullptr, slot_over_dev, false)) return rc;
     if (!diag_dev || !aligned(diag_dev, 128)) return fail(SUCRE_ERR_ARG, "diag_dev is NULL or not 128-byte aligned");
-    if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
+    if (int rc = check_mosaic_flags(flags)) return rc;
     return check_hip(launch_mosaic_gain_diag((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) != 0, table_dev, n_images, images, first_ordinal, g, span_dev,
                                              slot_over_dev, reinterpret_cast<unsigned long long *>(diag_dev), static_cast<hipStream_t>(stream)),
                      "sucre_mosaic_gain_diag");
@@ -1346,7 +1349,7 @@ int sucre_mosaic_reject_claim(void *table_dev, int n_images, const sucre_mosaic_
     if (int rc = check_mosaic_grid(grid, &g)) return rc;
     if (!slot_ord_dev || !aligned(slot_ord_dev, 32)) return fail(SUCRE_ERR_ARG, "slot_ord_dev is NULL or not 32-byte aligned");
     if (!slot_over_dev || !aligned(slot_over_dev, 4)) return fail(SUCRE_ERR_ARG, "slot_over_dev is NULL or not 4-byte aligned");
-    if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
+    if (int rc = check_mosaic_flags(flags)) return rc;
     return check_hip(launch_mosaic_reject_claim((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) != 0, table_dev, n_images, images, first_ordinal, g,
                                                 slot_ord_dev, slot_over_dev, static_cast<hipStream_t>(stream)), "sucre_mosaic_reject_claim");
 }
@@ -1359,7 +1362,7 @@ int sucre_mosaic_reject_sums(void *table_dev, int n_images, const sucre_mosaic_i
     if (int rc = check_mosaic_grid(grid, &g)) return rc;
     if (!slot_ord_dev || !aligned(slot_ord_dev, 32)) return fail(SUCRE_ERR_ARG, "slot_ord_dev is NULL or not 32-byte aligned");
     if (!slot_sum_dev || !aligned(slot_sum_dev, 8)) return fail(SUCRE_ERR_ARG, "slot_sum_dev is NULL or not 8-byte aligned");
-    if (flags & ~SUCRE_MOSAIC_PLAIN_ATOMIC) return fail(SUCRE_ERR_ARG, "unknown mosaic flags 0x%x", flags);
+    if (int rc = check_mosaic_flags(flags)) return rc;
     return check_hip(launch_mosaic_reject_sums((flags & SUCRE_MOSAIC_PLAIN_ATOMIC) != 0, table_dev, n_images, images, first_ordinal, g,
                                                slot_ord_dev, reinterpret_cast<unsigned long long *>(slot_sum_dev),
                                                static_cast<hipStream_t>(stream)), "sucre_mosaic_reject_sums");
@@ -1396,12 +1399,7 @@ int sucre_mosaic_reject_cull(void *table_dev, int n_images, const sucre_mosaic_i
         if (!aligned(counts_dev, 128)) return fail(SUCRE_ERR_ARG, "counts_dev is not 128-byte aligned");
         if (int rc = check_gain_rows(n_images, first_ordinal, n_ordinals)) return rc;
     }
-    // J_out is a buffer of its own, as sucre_mosaic_cull's
-    const uintptr_t o0 = reinterpret_cast<uintptr_t>(J_out), o1 = o0 + band_bytes(n_images, images);
-    for (int i = 0; i < n_images; ++i) {
-        const uintptr_t j0 = reinterpret_cast<uintptr_t>(images[i].J), j1 = j0 + (size_t)images[i].H * (size_t)images[i].W * 12;
-        if (j0 < o1 && o0 < j1) return fail(SUCRE_ERR_ARG, "image %d: J_out overlaps the image's J", i);
-    }
+    if (int rc = check_copy_out(J_out, n_images, images, false)) return rc;
     const MosaicReject out = {rejected_dev, reinterpret_cast<unsigned long long *>(counts_dev)};
     return check_hip(launch_mosaic_reject_cull(table_dev, n_images, images, first_ordinal, g, ref_dev, source_dev, tol, J_out, out,
                                                static_cast<hipStream_t>(stream)), "sucre_mosaic_reject_cull");

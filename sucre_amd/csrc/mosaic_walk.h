@@ -64,13 +64,12 @@ __device__ __forceinline__ T run_sum(T x, int left) {
     return x;
 }
 
-// The walk of every phase: the workgroup's image, the lane's pixel and what mosaic_pixel says of it.  False for a lane past the
-// image's last pixel and for a pixel that does not take part.
-__device__ __forceinline__ bool mosaic_walk(const MosaicImage *__restrict__ table, int n_images, const MosaicGrid &g,
-                                            const MosaicImage *__restrict__ *image, uint32_t *pixel, MosaicPixel *m) {
-    const MosaicImage *__restrict__ im = mosaic_block_image(table, n_images);
+// What a walk says of the lane's pixel once the workgroup's image is found: pixel threadIdx.x of 256-pixel block `block` of the launch
+// in `im`.  False for a lane past the image's last pixel and for a pixel that does not take part.
+__device__ __forceinline__ bool mosaic_walk_image(const MosaicImage *__restrict__ im, uint32_t block, const MosaicGrid &g,
+                                                  const MosaicImage *__restrict__ *image, uint32_t *pixel, MosaicPixel *m) {
     const uint32_t W = (uint32_t)im->W, n_px = (uint32_t)im->H * W;   // H, W <= 32767: below 2^30
-    const uint32_t p = (blockIdx.x - im->block0) * kMosaicBlockPx + threadIdx.x;
+    const uint32_t p = (block - im->block0) * kMosaicBlockPx + threadIdx.x;
     const bool inside = p < n_px;
     float Kinv[9], R[9], t[3];
 #pragma unroll
@@ -85,25 +84,43 @@ __device__ __forceinline__ bool mosaic_walk(const MosaicImage *__restrict__ tabl
     return inside && m->in;
 }
 
+// The walk of every phase: the workgroup's image, the lane's pixel and what mosaic_pixel says of it.
+__device__ __forceinline__ bool mosaic_walk(const MosaicImage *__restrict__ table, int n_images, const MosaicGrid &g,
+                                            const MosaicImage *__restrict__ *image, uint32_t *pixel, MosaicPixel *m) {
+    return mosaic_walk_image(mosaic_block_image(table, n_images), blockIdx.x, g, image, pixel, m);
+}
+
 // The walk of 256-pixel block `block` of the launch's grid, for a kernel whose workgroups each walk several (mosaic_block_image_at:
-// a second copy for the same reason); the pixel's numbers come from the one mosaic_pixel.
+// a second copy of the search alone, mosaic.h says why); the pixel's numbers come from the one mosaic_pixel.
 __device__ __forceinline__ bool mosaic_walk_at(const MosaicImage *__restrict__ table, int n_images, const MosaicGrid &g, uint32_t block,
                                                const MosaicImage *__restrict__ *image, uint32_t *pixel, MosaicPixel *m) {
-    const MosaicImage *__restrict__ im = mosaic_block_image_at(table, n_images, block);
-    const uint32_t W = (uint32_t)im->W, n_px = (uint32_t)im->H * W;
-    const uint32_t p = (block - im->block0) * kMosaicBlockPx + threadIdx.x;
-    const bool inside = p < n_px;
-    float Kinv[9], R[9], t[3];
+    return mosaic_walk_image(mosaic_block_image_at(table, n_images, block), block, g, image, pixel, m);
+}
+
+// ---- what the kernels that write a copy of J share (surface.hip's cull, one- and two-sided; reject.hip's) ----
+
+constexpr uint32_t kMosaicCountBlocks = 32;   // 256-pixel blocks a workgroup of a cull's counting form walks, one after the other
+
+// The lane's pixel of the copy: it sits where the lane sits in the launch, pixel block 256 + threadIdx.x behind `J_out`; J bit for
+// bit where the pixel is kept, the NaN 0x7fc00000 in all three channels where it is not.
+__device__ __forceinline__ void mosaic_store_copy(float *__restrict__ J_out, uint32_t block, bool keep, const MosaicPixel &m) {
+    const float none = __uint_as_float(0x7fc00000u);
+    float *__restrict__ o = J_out + ((size_t)block * kMosaicBlockPx + threadIdx.x) * 3;
 #pragma unroll
-    for (int i = 0; i < 9; ++i) { Kinv[i] = im->Kinv[i]; R[i] = im->R[i]; }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) t[i] = im->t[i];
-    const bool pin = pinhole_form(Kinv);
-    *m = MosaicPixel{};
-    if (inside) *m = mosaic_pixel(im, Kinv, pin, R, t, g.axes, p, W);
-    *image = im;
-    *pixel = p;
-    return inside && m->in;
+    for (int c = 0; c < 3; ++c) o[c] = keep ? m.J[c] : none;
+}
+
+// The launches of a cull over images[0 .. n): those of a phase (mosaic_for_each_launch, 32 images each), every one told its grid --
+// one workgroup per kMosaicCountBlocks blocks in the counting form, one per block otherwise --, its part of J_out and its blocks.
+template <typename Launch>
+static hipError_t mosaic_for_each_cull_launch(void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                                              hipStream_t s, bool counting, float *J_out, Launch launch) {
+    size_t base = 0;   // floats ahead of this launch's first pixel
+    mosaic_for_each_launch(table, n_images, images, first_ordinal, s, [&](uint32_t nb, const MosaicImage *entries, int nl) {
+        launch(dim3(counting ? (nb + kMosaicCountBlocks - 1) / kMosaicCountBlocks : nb), entries, nl, J_out + base, nb);
+        base += (size_t)nb * kMosaicBlockPx * 3;
+    });
+    return hipGetLastError();
 }
 
 }  // namespace sucre

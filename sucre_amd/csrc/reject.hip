@@ -5,8 +5,6 @@
 
 namespace sucre {
 
-constexpr uint32_t kRejectCountBlocks = 32;   // 256-pixel blocks per workgroup of the cull's counting form (surface.hip's)
-
 // Whether this lane is the first of a run of adjacent lanes of its wave that share `cell` (`part`: the lane has one).  Every lane of
 // the wave calls it.  `left`: lanes from this one to the end of its run, this one included.
 __device__ __forceinline__ bool reject_run_head(bool part, size_t cell, int *left) {
@@ -170,15 +168,15 @@ __global__ __launch_bounds__(256) void mosaic_reject_consensus_kernel(size_t n_c
     views[cell] = k;
 }
 
-// surface.hip's cull with the colour test.  kCount: a workgroup walks kRejectCountBlocks consecutive 256-pixel blocks and adds its
+// surface.hip's cull with the colour test (the same block loop, store and launches: mosaic_walk.h).  kCount: a workgroup walks kMosaicCountBlocks consecutive 256-pixel blocks and adds its
 // two sums to its image's row when the image changes and at the end (gain_flush).
 template <bool kCount>
 __global__ __launch_bounds__(256) void mosaic_reject_cull_kernel(const MosaicImage *__restrict__ table, int n_images, const MosaicGrid g,
                                                                  const float *__restrict__ ref, const int32_t *__restrict__ source, float tol,
                                                                  float *__restrict__ J_out, const MosaicReject out, uint32_t n_blocks) {
     __shared__ long long part[4][kRejectCountWords];
-    const uint32_t b0 = kCount ? blockIdx.x * kRejectCountBlocks : blockIdx.x;
-    const uint32_t b1 = kCount ? (n_blocks - b0 < kRejectCountBlocks ? n_blocks : b0 + kRejectCountBlocks) : b0 + 1;
+    const uint32_t b0 = kCount ? blockIdx.x * kMosaicCountBlocks : blockIdx.x;
+    const uint32_t b1 = kCount ? (n_blocks - b0 < kMosaicCountBlocks ? n_blocks : b0 + kMosaicCountBlocks) : b0 + 1;
     long long w[kRejectCountWords] = {0, 0};   // of this lane: samples in cells with a reference, samples rejected
     const MosaicImage *__restrict__ cur = mosaic_block_image_at(table, n_images, b0);
     for (uint32_t block = b0; block < b1; ++block) {
@@ -205,13 +203,7 @@ __global__ __launch_bounds__(256) void mosaic_reject_cull_kernel(const MosaicIma
                 for (int c = 0; c < 3; ++c) reject = reject || fabsf(m.J[c] - r[c]) > tol;
             }
         }
-        if (inside) {
-            const bool keep = in && !reject;
-            const float none = __uint_as_float(0x7fc00000u);
-            float *__restrict__ o = J_out + ((size_t)block * kMosaicBlockPx + threadIdx.x) * 3;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) o[c] = keep ? m.J[c] : none;
-        }
+        if (inside) mosaic_store_copy(J_out, block, in && !reject, m);
         if (reject && out.rejected) __hip_atomic_fetch_add(out.rejected + cell, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if constexpr (kCount) {
             w[0] += has_ref ? 1 : 0;
@@ -250,17 +242,13 @@ hipError_t launch_mosaic_reject_consensus(const MosaicGrid &grid, const uint32_t
 hipError_t launch_mosaic_reject_cull(void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
                                      const MosaicGrid &grid, const float *ref, const int32_t *source, float tol, float *J_out,
                                      const MosaicReject &out, hipStream_t s) {
-    size_t base = 0;   // floats ahead of this launch's first pixel
-    mosaic_for_each_launch(table, n_images, images, first_ordinal, s, [&](uint32_t nb, const MosaicImage *entries, int nl) {
+    return mosaic_for_each_cull_launch(table, n_images, images, first_ordinal, s, out.counts != nullptr, J_out,
+                                       [&](dim3 blocks, const MosaicImage *entries, int nl, float *J_launch, uint32_t nb) {
         if (out.counts)
-            hipLaunchKernelGGL((mosaic_reject_cull_kernel<true>), dim3((nb + kRejectCountBlocks - 1) / kRejectCountBlocks), dim3(256), 0, s,
-                               entries, nl, grid, ref, source, tol, J_out + base, out, nb);
+            hipLaunchKernelGGL((mosaic_reject_cull_kernel<true>), blocks, dim3(256), 0, s, entries, nl, grid, ref, source, tol, J_launch, out, nb);
         else
-            hipLaunchKernelGGL((mosaic_reject_cull_kernel<false>), dim3(nb), dim3(256), 0, s, entries, nl, grid, ref, source, tol, J_out + base,
-                               out, nb);
-        base += (size_t)nb * kMosaicBlockPx * 3;
+            hipLaunchKernelGGL((mosaic_reject_cull_kernel<false>), blocks, dim3(256), 0, s, entries, nl, grid, ref, source, tol, J_launch, out, nb);
     });
-    return hipGetLastError();
 }
 
 }  // namespace sucre

@@ -34,12 +34,12 @@
 //              level r's word and skips the atomic when the stored key is not above its own (the splat's filter: a stale value
 //              can only be larger); else the splat's 64-bit atomicMin.  No LDS, no scratch.
 // support_top  one lane per cell, no image read: top, support, surface_source from the n_levels words of the cell.
-// cull         surface.h's cull with the second side (a sibling kernel: surface.hip is not touched, so its one-sided
-//              instantiations compile from the source they had): the same J_out copy in the same layout; culled (uint32 per cell)
+// cull         surface.h's cull with the second side (surface.hip's one kernel, the side a template argument; launch_mosaic_cull
+//              with two_sided): the same J_out copy in the same layout; culled (uint32 per cell)
 //              counts the samples culled below, culled_above those culled above; counts (uint64 x 3): culled below, culled above,
 //              samples with a cell, by the 32-blocks-per-workgroup scheme, at most one atomic per counter and workgroup.
-// Registers (gfx950, -O3; the build's support.rpt): support 10 VGPR / 58 SGPR in both forms, support_top 9 / 24, the cull 12 / 70,
-// its counting form 17 / 84; 8 waves per SIMD everywhere, no scratch, LDS only in the counting cull (48 bytes).
+// Registers (gfx950, -O3; the build's support.rpt, the cull's in surface.rpt): support 10 VGPR / 58 SGPR in both forms, support_top
+// 9 / 24, the two-sided cull 12 / 70, its counting form 17 / 84 (the one-sided 12 / 68 and 17 / 78, 32 bytes of LDS); 8 waves per SIMD everywhere, no scratch, LDS only in the counting cull (48 bytes).
 // Measured on one MI355X, 65 resident images of 1080p, 74 pixels per cell, in ONE run (tools/mosaic_support_time.py,
 // profiles/mosaic_support_time.txt), next to the splat's 0.87 ms, sucre_mosaic_surface's 0.75 ms and invert_kernel's 0.61 ms in
 // the same run: levels 0, 1, 2, 3 take 0.77, 0.92, 1.04 and 1.15 ms with the load ahead of the atomic -- 0.89 to 1.33 of the splat:
@@ -56,12 +56,6 @@ namespace sucre {
 constexpr int kSupportMax = 4;          // the most views a supported surface asks for (SUCRE_MOSAIC_SUPPORT_MAX)
 static_assert(kSupportMax == SUCRE_MOSAIC_SUPPORT_MAX, "the most supporting views is public");
 
-struct MosaicCullSupported {   // what a two-sided cull launch writes besides J_out
-    uint32_t *culled;               // per cell: culled below; or NULL
-    uint32_t *culled_above;         // per cell: culled above; or NULL
-    unsigned long long *counts;     // culled below, culled above, samples with a cell; or NULL
-};
-
 // Level `level` of the ranks over images[0 .. n): the launches of a phase of mosaic.h; rank: lowered at that level, read below it.
 hipError_t launch_mosaic_support(bool plain, void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
                                  const MosaicGrid &grid, int level, unsigned long long *rank, hipStream_t s);
@@ -69,10 +63,5 @@ hipError_t launch_mosaic_support(bool plain, void *table, int n_images, const su
 // The supported top of every cell from its n_levels rank words (one launch); support, source: may be NULL.
 hipError_t launch_mosaic_support_top(const MosaicGrid &grid, int n_levels, const unsigned long long *rank, uint32_t *top, int32_t *support,
                                      int32_t *source, hipStream_t s);
-
-// The two-sided cull over images[0 .. n) into J_out (band_bytes of bands.h for the same images); top: read.
-hipError_t launch_mosaic_cull_supported(void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
-                                        const MosaicGrid &grid, const uint32_t *top, float tol, float *J_out,
-                                        const MosaicCullSupported &out, hipStream_t s);
 
 }  // namespace sucre

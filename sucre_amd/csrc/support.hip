@@ -1,12 +1,11 @@
-// View-supported surface of the seabed mosaic for gfx950 (sucre_mosaic_support, sucre_mosaic_support_top,
-// sucre_mosaic_cull_supported; the description: support.h).
+// View-supported surface of the seabed mosaic for gfx950 (sucre_mosaic_support, sucre_mosaic_support_top; the description:
+// support.h.  The two-sided cull of sucre_mosaic_cull_supported is surface.hip's cull kernel with its second side).
 #include "support.h"
 #include "mosaic_walk.h"
 #include "order_key.h"
 
 namespace sucre {
 
-constexpr uint32_t kCullCountBlocks = 32;   // 256-pixel blocks per workgroup of the cull's counting form (surface.hip's)
 constexpr unsigned long long kNoRank = ~0ull;
 
 // One lane per pixel, one level per launch.  The levels below `level` are final (earlier passes over all images): plain loads.
@@ -55,58 +54,6 @@ __global__ __launch_bounds__(256) void mosaic_support_top_kernel(size_t n_cells,
     if (source) source[cell] = n ? (int32_t)(uint32_t)last : -1;
 }
 
-// surface.hip's cull with the second side: a sample more than tol ABOVE its cell's top goes too, and is counted apart.
-template <bool kCount>
-__global__ __launch_bounds__(256) void mosaic_cull_supported_kernel(const MosaicImage *__restrict__ table, int n_images, const MosaicGrid g,
-                                                                    const uint32_t *__restrict__ top, float tol, float *__restrict__ J_out,
-                                                                    const MosaicCullSupported out, uint32_t n_blocks) {
-    const uint32_t b0 = kCount ? blockIdx.x * kCullCountBlocks : blockIdx.x;
-    const uint32_t b1 = kCount ? (n_blocks - b0 < kCullCountBlocks ? n_blocks : b0 + kCullCountBlocks) : b0 + 1;
-    uint32_t n_below = 0, n_above = 0, n_cell = 0;   // of this wave
-    for (uint32_t block = b0; block < b1; ++block) {
-        const MosaicImage *__restrict__ im;
-        uint32_t p;
-        MosaicPixel m;
-        const bool in = mosaic_walk_at(table, n_images, g, block, &im, &p, &m);
-        const bool inside = p < (uint32_t)im->H * (uint32_t)im->W;
-        size_t cell = 0;
-        const bool has_cell = in && mosaic_cell(g, m, &cell);
-        bool below = false, above = false;
-        if (has_cell) {
-            const uint32_t k = top[cell];
-            if (k != ~0u) {   // a cell the support phase has not seen culls nothing
-                const float d = m.a_n - key_value(k);
-                below = d > tol;
-                above = d < -tol;
-            }
-        }
-        if (inside) {
-            const bool keep = in && !below && !above;
-            const float none = __uint_as_float(0x7fc00000u);
-            float *__restrict__ o = J_out + ((size_t)block * kMosaicBlockPx + threadIdx.x) * 3;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) o[c] = keep ? m.J[c] : none;
-        }
-        if (below && out.culled) __hip_atomic_fetch_add(out.culled + cell, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (above && out.culled_above) __hip_atomic_fetch_add(out.culled_above + cell, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if constexpr (kCount) {
-            n_below += (uint32_t)__popcll(__ballot(below));
-            n_above += (uint32_t)__popcll(__ballot(above));
-            n_cell += (uint32_t)__popcll(__ballot(has_cell));
-        }
-    }
-    if constexpr (kCount) {
-        __shared__ uint32_t part[4][3];
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        if (lane == 0) { part[wave][0] = n_below; part[wave][1] = n_above; part[wave][2] = n_cell; }
-        __syncthreads();
-        if (threadIdx.x < 3) {
-            const uint32_t x = (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
-            if (x) __hip_atomic_fetch_add(out.counts + threadIdx.x, (unsigned long long)x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
-
 hipError_t launch_mosaic_support(bool plain, void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
                                  const MosaicGrid &grid, int level, unsigned long long *rank, hipStream_t s) {
     mosaic_for_each_launch(table, n_images, images, first_ordinal, s, [&](uint32_t nb, const MosaicImage *entries, int nl) {
@@ -121,22 +68,6 @@ hipError_t launch_mosaic_support_top(const MosaicGrid &grid, int n_levels, const
     const size_t n_cells = (size_t)grid.Hm * (size_t)grid.Wm;   // the caller has checked that the workgroups fit a launch
     hipLaunchKernelGGL(mosaic_support_top_kernel, dim3((uint32_t)((n_cells + 255) / 256)), dim3(256), 0, s, n_cells, n_levels, rank, top,
                        support, source);
-    return hipGetLastError();
-}
-
-hipError_t launch_mosaic_cull_supported(void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
-                                        const MosaicGrid &grid, const uint32_t *top, float tol, float *J_out,
-                                        const MosaicCullSupported &out, hipStream_t s) {
-    size_t base = 0;   // floats ahead of this launch's first pixel
-    mosaic_for_each_launch(table, n_images, images, first_ordinal, s, [&](uint32_t nb, const MosaicImage *entries, int nl) {
-        if (out.counts)
-            hipLaunchKernelGGL((mosaic_cull_supported_kernel<true>), dim3((nb + kCullCountBlocks - 1) / kCullCountBlocks), dim3(256), 0, s,
-                               entries, nl, grid, top, tol, J_out + base, out, nb);
-        else
-            hipLaunchKernelGGL((mosaic_cull_supported_kernel<false>), dim3(nb), dim3(256), 0, s, entries, nl, grid, top, tol, J_out + base, out,
-                               nb);
-        base += (size_t)nb * kMosaicBlockPx * 3;
-    });
     return hipGetLastError();
 }
 

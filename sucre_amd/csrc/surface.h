@@ -22,7 +22,7 @@
 // The feather then fades towards a culled region as it does towards a NaN patch: it is a seam.
 // THE SURFACE IS A PLAIN MINIMUM: one spurious high sample -- a fish, a bad depth -- owns its cell and culls the seabed under it
 // (the best view has the same weakness with the nearest sample).  The remedy is support.h: the top that M different images reach,
-// and a cull on both sides of it; this file's two kernels stay as they are, and its M = 1 is this surface bit for bit.
+// and a cull on both sides of it -- this file's cull kernel with its second side compiled in --; its M = 1 is this surface bit for bit.
 //
 // surface  the walk of mosaic.h (one lane per pixel, 32 images per launch): atomicMin(top[cell], order_key(a_n)), uint32 per cell,
 //          empty: all ones.  Unless SUCRE_MOSAIC_PLAIN_ATOMIC is given, top[cell] is loaded first and the atomic skipped when the
@@ -52,16 +52,19 @@
 namespace sucre {
 
 struct MosaicCull {   // what a cull launch writes besides J_out
-    uint32_t *culled;               // per cell, or NULL
-    unsigned long long *counts;     // culled samples, samples with a cell; or NULL
+    uint32_t *culled;               // per cell: culled (two-sided: culled below); or NULL
+    uint32_t *culled_above;         // two-sided, per cell: culled above; or NULL.  Not read by the one-sided cull
+    unsigned long long *counts;     // culled samples, samples with a cell -- two-sided: culled below, culled above, samples with a
+                                    // cell --; or NULL
 };
 
 // The surface phase over images[0 .. n): the launches of a phase of mosaic.h; top: lowered.
 hipError_t launch_mosaic_surface(bool plain, void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
                                  const MosaicGrid &grid, uint32_t *top, hipStream_t s);
 
-// The cull over images[0 .. n) into J_out (band_bytes of bands.h for the same images); top: read.
-hipError_t launch_mosaic_cull(void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal, const MosaicGrid &grid,
-                              const uint32_t *top, float tol, float *J_out, const MosaicCull &out, hipStream_t s);
+// The cull over images[0 .. n) into J_out (band_bytes of bands.h for the same images); top: read.  two_sided: support.h's cull, the
+// same kernel with its second side and its third counter.
+hipError_t launch_mosaic_cull(bool two_sided, void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                              const MosaicGrid &grid, const uint32_t *top, float tol, float *J_out, const MosaicCull &out, hipStream_t s);
 
 }  // namespace sucre

@@ -1,11 +1,10 @@
-// Surface test of the seabed mosaic for gfx950 (sucre_mosaic_surface, sucre_mosaic_cull; the description: surface.h).
+// Surface test of the seabed mosaic for gfx950 (sucre_mosaic_surface, sucre_mosaic_cull and, with its second side,
+// sucre_mosaic_cull_supported; the description: surface.h, of the second side: support.h).
 #include "surface.h"
 #include "mosaic_walk.h"
 #include "order_key.h"
 
 namespace sucre {
-
-constexpr uint32_t kCullCountBlocks = 32;   // 256-pixel blocks per workgroup of the cull's counting form
 
 template <bool kPlain>
 __global__ __launch_bounds__(256) void mosaic_surface_kernel(const MosaicImage *__restrict__ table, int n_images, const MosaicGrid g,
@@ -24,17 +23,19 @@ __global__ __launch_bounds__(256) void mosaic_surface_kernel(const MosaicImage *
     atomicMin(top + cell, mine);
 }
 
-// One lane per pixel; the lane's pixel of J_out sits where the lane sits in the launch: pixel block 256 + threadIdx.x behind `J_out`.
-// kCount: every workgroup's two atomics land on one cache line (measured: 6.4 ms for 65 images of 1080p against 0.82 ms without the
-// counters, the bounds phase's finding), so a workgroup of the counting form walks kCullCountBlocks consecutive 256-pixel blocks
-// of the grid, one after the other, sums its waves' ballots as it goes and adds to each counter at most once at the end.
-template <bool kCount>
+// One lane per pixel; the lane's pixel of J_out: mosaic_store_copy.  kTwoSided (support.h): a sample more than tol ABOVE its cell's
+// top goes too, and is counted apart.  kCount: every workgroup's atomics land on one cache line (measured: 6.4 ms for 65 images of
+// 1080p against 0.82 ms without the counters, the bounds phase's finding), so a workgroup of the counting form walks
+// kMosaicCountBlocks consecutive 256-pixel blocks of the grid, one after the other, sums its waves' ballots as it goes and adds to
+// each counter -- culled below, (two-sided: culled above,) samples with a cell -- at most once at the end.
+template <bool kCount, bool kTwoSided>
 __global__ __launch_bounds__(256) void mosaic_cull_kernel(const MosaicImage *__restrict__ table, int n_images, const MosaicGrid g,
                                                           const uint32_t *__restrict__ top, float tol, float *__restrict__ J_out,
                                                           const MosaicCull out, uint32_t n_blocks) {
-    const uint32_t b0 = kCount ? blockIdx.x * kCullCountBlocks : blockIdx.x;
-    const uint32_t b1 = kCount ? (n_blocks - b0 < kCullCountBlocks ? n_blocks : b0 + kCullCountBlocks) : b0 + 1;
-    uint32_t n_culled = 0, n_cell = 0;   // of this wave
+    constexpr int kWords = kTwoSided ? 3 : 2;
+    const uint32_t b0 = kCount ? blockIdx.x * kMosaicCountBlocks : blockIdx.x;
+    const uint32_t b1 = kCount ? (n_blocks - b0 < kMosaicCountBlocks ? n_blocks : b0 + kMosaicCountBlocks) : b0 + 1;
+    uint32_t n_below = 0, n_above = 0, n_cell = 0;   // of this wave
     for (uint32_t block = b0; block < b1; ++block) {
         const MosaicImage *__restrict__ im;
         uint32_t p;
@@ -43,30 +44,36 @@ __global__ __launch_bounds__(256) void mosaic_cull_kernel(const MosaicImage *__r
         const bool inside = p < (uint32_t)im->H * (uint32_t)im->W;
         size_t cell = 0;
         const bool has_cell = in && mosaic_cell(g, m, &cell);
-        bool cull = false;
+        bool below = false, above = false;
         if (has_cell) {
             const uint32_t k = top[cell];
-            cull = k != ~0u && m.a_n - key_value(k) > tol;   // a cell the surface phase has not seen culls nothing
+            if (k != ~0u) {   // a cell the surface phase has not seen culls nothing
+                const float d = m.a_n - key_value(k);
+                below = d > tol;
+                if constexpr (kTwoSided) above = d < -tol;
+            }
         }
-        if (inside) {
-            const bool keep = in && !cull;
-            const float none = __uint_as_float(0x7fc00000u);
-            float *__restrict__ o = J_out + ((size_t)block * kMosaicBlockPx + threadIdx.x) * 3;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) o[c] = keep ? m.J[c] : none;
+        if (inside) mosaic_store_copy(J_out, block, in && !below && !above, m);
+        if (below && out.culled) __hip_atomic_fetch_add(out.culled + cell, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if constexpr (kTwoSided) {
+            if (above && out.culled_above) __hip_atomic_fetch_add(out.culled_above + cell, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        if (cull && out.culled) __hip_atomic_fetch_add(out.culled + cell, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if constexpr (kCount) {
-            n_culled += (uint32_t)__popcll(__ballot(cull));
+            n_below += (uint32_t)__popcll(__ballot(below));
+            if constexpr (kTwoSided) n_above += (uint32_t)__popcll(__ballot(above));
             n_cell += (uint32_t)__popcll(__ballot(has_cell));
         }
     }
     if constexpr (kCount) {
-        __shared__ uint32_t part[4][2];
+        __shared__ uint32_t part[4][kWords];
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        if (lane == 0) { part[wave][0] = n_culled; part[wave][1] = n_cell; }
+        if (lane == 0) {
+            part[wave][0] = n_below;
+            if constexpr (kTwoSided) part[wave][1] = n_above;
+            part[wave][kWords - 1] = n_cell;
+        }
         __syncthreads();
-        if (threadIdx.x < 2) {
+        if (threadIdx.x < kWords) {
             const uint32_t x = (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
             if (x) __hip_atomic_fetch_add(out.counts + threadIdx.x, (unsigned long long)x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -82,18 +89,22 @@ hipError_t launch_mosaic_surface(bool plain, void *table, int n_images, const su
     return hipGetLastError();
 }
 
-hipError_t launch_mosaic_cull(void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal, const MosaicGrid &grid,
+template <bool kTwoSided>
+static hipError_t launch_cull(void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal, const MosaicGrid &grid,
                               const uint32_t *top, float tol, float *J_out, const MosaicCull &out, hipStream_t s) {
-    size_t base = 0;   // floats ahead of this launch's first pixel
-    mosaic_for_each_launch(table, n_images, images, first_ordinal, s, [&](uint32_t nb, const MosaicImage *entries, int nl) {
+    return mosaic_for_each_cull_launch(table, n_images, images, first_ordinal, s, out.counts != nullptr, J_out,
+                                       [&](dim3 blocks, const MosaicImage *entries, int nl, float *J_launch, uint32_t nb) {
         if (out.counts)
-            hipLaunchKernelGGL((mosaic_cull_kernel<true>), dim3((nb + kCullCountBlocks - 1) / kCullCountBlocks), dim3(256), 0, s, entries, nl, grid,
-                               top, tol, J_out + base, out, nb);
+            hipLaunchKernelGGL((mosaic_cull_kernel<true, kTwoSided>), blocks, dim3(256), 0, s, entries, nl, grid, top, tol, J_launch, out, nb);
         else
-            hipLaunchKernelGGL((mosaic_cull_kernel<false>), dim3(nb), dim3(256), 0, s, entries, nl, grid, top, tol, J_out + base, out, nb);
-        base += (size_t)nb * kMosaicBlockPx * 3;
+            hipLaunchKernelGGL((mosaic_cull_kernel<false, kTwoSided>), blocks, dim3(256), 0, s, entries, nl, grid, top, tol, J_launch, out, nb);
     });
-    return hipGetLastError();
+}
+
+hipError_t launch_mosaic_cull(bool two_sided, void *table, int n_images, const sucre_mosaic_image_t *images, int first_ordinal,
+                              const MosaicGrid &grid, const uint32_t *top, float tol, float *J_out, const MosaicCull &out, hipStream_t s) {
+    return two_sided ? launch_cull<true>(table, n_images, images, first_ordinal, grid, top, tol, J_out, out, s)
+                     : launch_cull<false>(table, n_images, images, first_ordinal, grid, top, tol, J_out, out, s);
 }
 
 }  // namespace sucre

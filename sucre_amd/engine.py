@@ -12,7 +12,7 @@ import ctypes as C
 import math
 import os
 import threading
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 
 import numpy as np
 import torch
@@ -997,53 +997,60 @@ MOSAIC_MAX_SAMPLES = 1 << 20       # samples of one cell from which the blend's 
 MOSAIC_FILL_RANGE = (1e-6, 1e6)    # fill reaches R a mosaic takes, metres
 MOSAIC_FEATHER_RANGE = (1, 1024)   # feather widths F a blend takes, source pixels (csrc/mosaic.h, "The feather")
 MOSAIC_BANDS_RANGE = (1, 6)        # detail bands K a multi-band blend takes (csrc/bands.h): filter steps 1 .. 2^(K-1) source pixels
-MOSAIC_VALUES = {   # field of MosaicOptions -> (what it is, range, integral, unit, type of the checked value), in the order checked
-    'blend': ('blend depth H', MOSAIC_BLEND_RANGE, False, 'metres', np.float32),
-    'fill': ('fill reach R', MOSAIC_FILL_RANGE, False, 'metres', float),
-    'feather': ('feather width F', MOSAIC_FEATHER_RANGE, True, 'source pixels', int),
-}
-
-
-def _mosaic_refusal(field: str, text: str) -> ValueError:
-    """A ValueError whose ``field`` tells a caller which of its flags to name: the field of ``MosaicOptions`` at fault, or 'grid'
-    where ``Mosaic.begin`` finds no grid to make."""
-    e = ValueError(text)
-    e.field = field
-    return e
-
-
-_MOSAIC_BANDS = ('band count K', MOSAIC_BANDS_RANGE, True, 'bands', int)   # a row like MOSAIC_VALUES': the band count travels beside
-#                                                                            the options record, not inside it
-
-
 MOSAIC_SURFACE_RANGE = (1e-6, 1e6)   # surface tolerances T a mosaic takes, metres (csrc/surface.h)
-_MOSAIC_SURFACE = ('surface tolerance T', MOSAIC_SURFACE_RANGE, False, 'metres', np.float32)   # beside the record, as the band count
-
-
-MOSAIC_SUPPORT_RANGE = (1, 4)   # views M whose agreement a supported surface asks for (csrc/support.h)
-_MOSAIC_SUPPORT = ('supporting views M', MOSAIC_SUPPORT_RANGE, True, 'views', int)   # beside the record, as the surface tolerance
-
-
+MOSAIC_SUPPORT_RANGE = (1, 4)        # views M whose agreement a supported surface asks for (csrc/support.h)
 MOSAIC_GAIN_ROUNDS_RANGE = (1, 64)      # rounds R of the per-image gain compensation (csrc/gains_mosaic.h)
 MOSAIC_GAIN_LIMIT_RANGE = (1.0, 16.0)   # limits L a gain is clamped to: 1/L <= g <= L
 MOSAIC_GAIN_LIMIT = 2.0                 # the limit unless one is given
 MOSAIC_GAIN_MAX_PIXELS = 1 << 26        # pixels of one image from which the gain sums' int64 words may pass 2^62
-_MOSAIC_GAINS = ('gain rounds R', MOSAIC_GAIN_ROUNDS_RANGE, True, 'rounds', int)   # beside the record, as the supporting views
-_MOSAIC_GAIN_LIMIT = ('gain limit L', MOSAIC_GAIN_LIMIT_RANGE, False, 'times', float)
 MOSAIC_GAIN_SOLVES = ('rounds', 'direct')   # how the first round's gains are found (csrc/gains_direct.h: 'direct')
 MOSAIC_GAIN_PRIOR = 2.0 ** -20              # mu of the direct solve: the weight of (g - 1)^2 against the data term
 MOSAIC_GAIN_DIRECT_CELL_BYTES = 292         # the direct solve's slots: 32 + 256 + 4 bytes per cell
 MOSAIC_GAIN_DIRECT_MEMORY = 0.8             # the share of the free device memory the direct solve's state may take
 MOSAIC_REJECT_RANGE = (1e-6, 1e6)           # colour tolerances T a consensus rejection takes, units of J (csrc/reject.h)
-_MOSAIC_REJECT = ('reject tolerance T', MOSAIC_REJECT_RANGE, False, 'colour units', np.float32)   # beside the record, as the surface's
 MOSAIC_REJECT_CELL_BYTES = 292              # the consensus' slots: 32 + 256 + 4 bytes per cell, freed after the consensus
 MOSAIC_REJECT_MEMORY = 0.8                  # the share of the free device memory the consensus' state may take
+MOSAIC_VALUES = {   # field of MosaicOptions -> (what it is, range, integral, unit, type of the checked value, the command line's letter,
+    # the command line's words for it), in the order checked.  A choice has its values in place of the range and None for
+    # ``integral``, the unit and the words.
+    'blend': ('blend depth H', MOSAIC_BLEND_RANGE, False, 'metres', np.float32, 'H', 'a finite depth'),
+    'fill': ('fill reach R', MOSAIC_FILL_RANGE, False, 'metres', float, 'R', 'a finite reach'),
+    'feather': ('feather width F', MOSAIC_FEATHER_RANGE, True, 'source pixels', int, 'F', 'an integer'),
+    'bands': ('band count K', MOSAIC_BANDS_RANGE, True, 'bands', int, 'K', 'an integer'),
+    'surface': ('surface tolerance T', MOSAIC_SURFACE_RANGE, False, 'metres', np.float32, 'T', 'a finite tolerance'),
+    'support': ('supporting views M', MOSAIC_SUPPORT_RANGE, True, 'views', int, 'M', 'an integer'),
+    'gains': ('gain rounds R', MOSAIC_GAIN_ROUNDS_RANGE, True, 'rounds', int, 'R', 'an integer'),
+    'gain_limit': ('gain limit L', MOSAIC_GAIN_LIMIT_RANGE, False, 'times', float, 'L', 'a finite limit'),
+    'gain_solve': ('gain solve', MOSAIC_GAIN_SOLVES, None, None, str, 'S', None),
+    'reject': ('reject tolerance T', MOSAIC_REJECT_RANGE, False, 'colour units', np.float32, 'T', 'a finite tolerance'),
+}
+MOSAIC_NEEDS = [   # (field, the field it only goes with, why), in the order MosaicOptions.checked looks at them, after every value
+    ('feather', 'blend', 'a feather is a factor of the blend\'s weight; give the blend depth too (blend=H)'),
+    ('bands', 'blend', 'the bands are blended with the blend\'s weights; give the blend depth too (blend=H)'),
+    ('support', 'surface', 'the support decides which top the surface test measures against; give the tolerance too (surface=T)'),
+    ('gain_limit', 'gains', 'the limit clamps the gains the rounds find; give the rounds too (gains=R)'),
+    ('gain_solve', 'gains', 'the solve finds the gains of the first round; give the rounds too (gains=R)'),
+]
 
 
-def _mosaic_value(field: str, value, row=None):
-    """``value`` as ``MOSAIC_VALUES[field]`` (or ``row``) describes it, or ValueError unless it is finite, within the range and,
-    where the table says so, an integral number and no bool."""
-    what, (lo, hi), integral, unit, kind = MOSAIC_VALUES[field] if row is None else row
+def _mosaic_refusal(field: str, text: str, needs: str = None) -> ValueError:
+    """A ValueError whose ``field`` tells a caller which of its flags to name: the field of ``MosaicOptions`` at fault, or 'grid'
+    where ``Mosaic.begin`` finds no grid to make.  ``needs``: the field that ``field`` was given without (a row of ``MOSAIC_NEEDS``),
+    None for every other refusal."""
+    e = ValueError(text)
+    e.field, e.needs = field, needs
+    return e
+
+
+def _mosaic_value(field: str, value):
+    """``value`` as ``MOSAIC_VALUES[field]`` describes it, or ValueError unless it is finite, within the range and, where the
+    table says so, an integral number and no bool -- or, for a choice, one of its strings."""
+    what, span, integral, unit, kind, _, _ = MOSAIC_VALUES[field]
+    if integral is None:
+        if not isinstance(value, str) or value not in span:
+            raise _mosaic_refusal(field, f'mosaic {what} must be one of {" or ".join(span)}, not {value!r}')
+        return value
+    lo, hi = span
     try:
         x = float(value)
     except (TypeError, ValueError):
@@ -1060,6 +1067,9 @@ def _mosaic_value(field: str, value, row=None):
                                      f'not {value}')
     return kind(x)
 
+
+# One value each as the table describes it (the returned type: its fifth column), or ValueError with ``field``; a whole request goes
+# through ``MosaicOptions.checked``.
 
 def mosaic_blend_depth(blend) -> np.float32:
     """``blend`` as the float32 blend depth H, or ValueError unless it is finite and within ``MOSAIC_BLEND_RANGE``."""
@@ -1078,64 +1088,43 @@ def mosaic_fill_reach(fill) -> float:
 
 
 def mosaic_band_count(bands) -> int:
-    """``bands`` as the number K of detail bands of a multi-band blend, or ValueError (``field``: 'bands') unless it is an integral
-    number, no bool, within ``MOSAIC_BANDS_RANGE``."""
-    return _mosaic_value('bands', bands, _MOSAIC_BANDS)
+    """``bands`` as the number K of detail bands of a multi-band blend, or ValueError unless it is an integral number, no bool,
+    within ``MOSAIC_BANDS_RANGE``."""
+    return _mosaic_value('bands', bands)
 
 
 def mosaic_surface_tol(surface) -> np.float32:
-    """``surface`` as the float32 tolerance T of the surface test in metres, or ValueError (``field``: 'surface') unless it is finite
-    and within ``MOSAIC_SURFACE_RANGE``."""
-    return _mosaic_value('surface', surface, _MOSAIC_SURFACE)
+    """``surface`` as the float32 tolerance T of the surface test in metres, or ValueError unless it is finite and within
+    ``MOSAIC_SURFACE_RANGE``."""
+    return _mosaic_value('surface', surface)
 
 
 def mosaic_support_views(support) -> int:
-    """``support`` as the number M of views a supported surface rests on, or ValueError (``field``: 'support') unless it is an
-    integral number, no bool, within ``MOSAIC_SUPPORT_RANGE``."""
-    return _mosaic_value('support', support, _MOSAIC_SUPPORT)
-
-
-def mosaic_support_checked(support, surface, who: str):
-    """None, or M as ``mosaic_support_views`` returns it; ValueError (``field``: 'support') for a support without a surface
-    tolerance, in the name of ``who``."""
-    if support is None:
-        return None
-    support = mosaic_support_views(support)
-    if surface is None:
-        raise _mosaic_refusal('support', f'{who}: the support decides which top the surface test measures against; give the '
-                                         f'tolerance too (surface=T)')
-    return support
-
-
-def mosaic_reject_checked(reject, who: str = 'mosaic'):
-    """None, or ``reject`` as the float32 tolerance T of the colour consensus in units of ``J``; ValueError (``field``: 'reject')
-    unless it is finite and within ``MOSAIC_REJECT_RANGE`` (``who`` asks: the rejection goes with any other option, so there is
-    no combination to refuse in its name)."""
-    return None if reject is None else _mosaic_value('reject', reject, _MOSAIC_REJECT)
+    """``support`` as the number M of views a supported surface rests on, or ValueError unless it is an integral number, no bool,
+    within ``MOSAIC_SUPPORT_RANGE``."""
+    return _mosaic_value('support', support)
 
 
 def mosaic_gain_rounds(gains) -> int:
-    """``gains`` as the number R of rounds of the gain compensation, or ValueError (``field``: 'gains') unless it is an integral
-    number, no bool, within ``MOSAIC_GAIN_ROUNDS_RANGE``."""
-    return _mosaic_value('gains', gains, _MOSAIC_GAINS)
+    """``gains`` as the number R of rounds of the gain compensation, or ValueError unless it is an integral number, no bool, within
+    ``MOSAIC_GAIN_ROUNDS_RANGE``."""
+    return _mosaic_value('gains', gains)
 
 
 def mosaic_gain_limit(gain_limit) -> float:
-    """``gain_limit`` as the limit L of a gain, or ValueError (``field``: 'gain_limit') unless it is finite and within
-    ``MOSAIC_GAIN_LIMIT_RANGE``."""
-    return _mosaic_value('gain_limit', gain_limit, _MOSAIC_GAIN_LIMIT)
+    """``gain_limit`` as the limit L of a gain, or ValueError unless it is finite and within ``MOSAIC_GAIN_LIMIT_RANGE``."""
+    return _mosaic_value('gain_limit', gain_limit)
 
 
-def mosaic_gains_checked(gains, gain_limit, who: str):
-    """``(None, None)``, or ``(R, L)`` as ``mosaic_gain_rounds`` and ``mosaic_gain_limit`` return them (L: ``MOSAIC_GAIN_LIMIT``
-    unless given); ValueError (``field``: 'gain_limit') for a limit without rounds, in the name of ``who``."""
-    if gain_limit is not None:
-        gain_limit = mosaic_gain_limit(gain_limit)
-    if gains is None:
-        if gain_limit is not None:
-            raise _mosaic_refusal('gain_limit', f'{who}: the limit clamps the gains the rounds find; give the rounds too (gains=R)')
-        return None, None
-    return mosaic_gain_rounds(gains), MOSAIC_GAIN_LIMIT if gain_limit is None else gain_limit
+def mosaic_gain_solve_name(gain_solve) -> str:
+    """``gain_solve`` itself, or ValueError unless it is one of the strings of ``MOSAIC_GAIN_SOLVES``."""
+    return _mosaic_value('gain_solve', gain_solve)
+
+
+def mosaic_reject_tol(reject) -> np.float32:
+    """``reject`` as the float32 tolerance T of the colour consensus in units of ``J``, or ValueError unless it is finite and within
+    ``MOSAIC_REJECT_RANGE``."""
+    return _mosaic_value('reject', reject)
 
 
 def mosaic_gain_solve(sums, G, limit):
@@ -1169,18 +1158,6 @@ def _device_free_bytes(device) -> int:
     """The free memory of ``device`` in bytes, as the driver reports it now."""
     with torch.cuda.device(device):
         return int(torch.cuda.mem_get_info()[0])
-
-
-def mosaic_gain_solve_checked(gain_solve, gains, who: str):
-    """None for the rounds alone (``gain_solve`` None or 'rounds'), or 'direct'; ValueError (``field``: 'gain_solve') for any other
-    value, and for a solve without rounds (``gains`` None), in the name of ``who``."""
-    if gain_solve is None:
-        return None
-    if not isinstance(gain_solve, str) or gain_solve not in MOSAIC_GAIN_SOLVES:
-        raise _mosaic_refusal('gain_solve', f'mosaic gain solve must be one of {" or ".join(MOSAIC_GAIN_SOLVES)}, not {gain_solve!r}')
-    if gains is None:
-        raise _mosaic_refusal('gain_solve', f'{who}: the solve finds the gains of the first round; give the rounds too (gains=R)')
-    return 'direct' if gain_solve == 'direct' else None
 
 
 def mosaic_gain_pair_matrix(pairs, word: int) -> np.ndarray:
@@ -1275,16 +1252,6 @@ def mosaic_gain_rms(sums) -> list:
     return [math.sqrt(sum(row[7 + c] for row in rows) / n) / 16384.0 if n else 0.0 for c in range(3)]
 
 
-def mosaic_bands_checked(bands, blend, who: str):
-    """None, or K as ``mosaic_band_count`` returns it; ValueError (``field``: 'bands') for bands without a blend, in the name of ``who``."""
-    if bands is None:
-        return None
-    bands = mosaic_band_count(bands)
-    if blend is None:
-        raise _mosaic_refusal('bands', f'{who}: the bands are blended with the blend\'s weights; give the blend depth too (blend=H)')
-    return bands
-
-
 def mosaic_band_plan(H, F, K) -> list:
     """The ``K + 1`` pairs ``(H_j, F_j)`` a multi-band blend of blend depth ``H``, feather ``F`` (None: none) and ``K`` detail bands
     blends its bands with, detail band 0 (the finest) first and the residual last: the residual takes the user's ``(H, F)``, detail
@@ -1299,18 +1266,46 @@ def mosaic_band_plan(H, F, K) -> list:
 
 @dataclass(frozen=True)
 class MosaicOptions:
-    """What a mosaic can be asked for beyond the best view: ``blend``, the blend depth H in metres; ``feather``, with a blend, the
-    feather width F in source pixels; ``fill``, the reach R in metres of the hole filling.  None: not asked for."""
+    """What a mosaic can be asked for beyond the best view, None: not asked for.  ``blend``, the blend depth H in metres;
+    ``feather``, with a blend, the feather width F in source pixels; ``fill``, the reach R in metres of the hole filling;
+    ``bands``, with a blend, the number K of detail bands of the multi-band blend; ``surface``, the tolerance T in metres of the
+    surface test; ``support``, with a surface, the number M of views the top must rest on; ``gains``, the rounds R of the per-image
+    gain compensation; ``gain_limit``, with gains, the limit L of a gain; ``gain_solve``, with gains, 'direct' for the direct solve
+    in place of the first round's ('rounds': the rounds alone); ``reject``, the tolerance T in units of ``J`` of the colour
+    consensus across views.  The ranges, units and checked types are the rows of ``MOSAIC_VALUES``."""
     blend: float = None
     feather: int = None
     fill: float = None
+    bands: int = None
+    surface: float = None
+    support: int = None
+    gains: int = None
+    gain_limit: float = None
+    gain_solve: str = None
+    reject: float = None
+
+    def over(self, **fields) -> 'MosaicOptions':
+        """The record with ``fields`` laid over it; TypeError for a name that is no field."""
+        return replace(self, **fields) if fields else self
+
+    def asked(self) -> dict:
+        """The fields that were asked for (not None), by name, in the record's order."""
+        return {f: getattr(self, f) for f in self.__dataclass_fields__ if getattr(self, f) is not None}
 
     def checked(self, who: str = 'MosaicOptions') -> 'MosaicOptions':
-        """The record with float32 H, int F and float R.  ValueError (``field``: the option at fault) for a value ``MOSAIC_VALUES``
-        does not take -- blend, fill, feather in this order -- and then for a feather without a blend, in the name of ``who``."""
+        """The record with every value as the type of its row of ``MOSAIC_VALUES``; the one place that checks a request.
+        ValueError (``field``: the option at fault) for a value its row does not take, the rows in the table's order, and then for
+        an option given without the one it goes with, the rows of ``MOSAIC_NEEDS`` in their order, in the name of ``who``.  With
+        gains and no limit the limit is ``MOSAIC_GAIN_LIMIT``; the solve 'rounds' is None, the rounds alone.  A checked record
+        passes a second check unchanged."""
         values = {f: None if getattr(self, f) is None else _mosaic_value(f, getattr(self, f)) for f in MOSAIC_VALUES}
-        if values['feather'] is not None and values['blend'] is None:
-            raise _mosaic_refusal('feather', f'{who}: a feather is a factor of the blend\'s weight; give the blend depth too (blend=H)')
+        for field, needs, why in MOSAIC_NEEDS:
+            if values[field] is not None and values[needs] is None:
+                raise _mosaic_refusal(field, f'{who}: {why}', needs)
+        if values['gains'] is not None and values['gain_limit'] is None:
+            values['gain_limit'] = MOSAIC_GAIN_LIMIT
+        if values['gain_solve'] == 'rounds':
+            values['gain_solve'] = None
         return MosaicOptions(**values)
 
 
@@ -1337,7 +1332,8 @@ _NAN = float('nan')
 MOSAIC_OUTPUTS = {   # key of Mosaic.result() -> (group, trailing shape, dtype, value of an empty cell, PNG of --mosaic, how it is made)
     # groups: 'best' (the best view; begin), 'blend' (begin with a blend), 'bands' (begin with bands), 'fill' (fill), 'blend_fill'
     # (fill with a blend), 'bands_fill' (fill with bands), 'surface' (begin with a surface tolerance), 'support' (begin with a
-    # support; the last rows: older rows keep their places).  An empty value of None: the kernel writes every cell.  How: 'stretch'
+    # support), 'reject' (begin with a reject tolerance; csrc/reject.h).  Mosaic.result() puts the groups in its own order, not the
+    # rows'.  An empty value of None: the kernel writes every cell.  How: 'stretch'
     # (sucre._mosaic_picture), 'bytes', 'source', 'mask', 'height', 'count'.
     'J': ('best', (3,), torch.float32, _NAN, 'mosaic.png', 'stretch'),
     'raw': ('best', (3,), torch.uint8, 0, 'mosaic_raw.png', 'bytes'),
@@ -1361,15 +1357,13 @@ MOSAIC_OUTPUTS = {   # key of Mosaic.result() -> (group, trailing shape, dtype, 
     'surface_source': ('support', (), torch.int32, -1, None, None),
     'culled_above': ('support', (), torch.int32, 0, 'mosaic_culled_above.png', 'count'),
     'surface_top': ('support', (), torch.float32, _NAN, None, None),
-}
-MOSAIC_REJECT_OUTPUTS = {   # the rows a colour consensus adds (begin with a reject tolerance; csrc/reject.h): MOSAIC_OUTPUTS' columns, in
-    # a table of their own -- that one keeps its rows and its end --, merged in Mosaic.result() only when a rejection was begun
     'rejected': ('reject', (), torch.int32, 0, 'mosaic_rejected.png', 'count'),
     'reject_ref': ('reject', (3,), torch.float32, _NAN, None, None),
     'reject_source': ('reject', (), torch.int32, -1, None, None),
     'reject_views': ('reject', (), torch.int32, 0, None, None),
     'reject_overflow': ('reject', (), torch.bool, False, None, None),
 }
+MOSAIC_REJECT_OUTPUTS = {key: row for key, row in MOSAIC_OUTPUTS.items() if row[0] == 'reject'}   # the rows a colour consensus adds
 
 
 class Mosaic:
@@ -1383,6 +1377,16 @@ class Mosaic:
     dtypes and empty values are the rows of ``MOSAIC_OUTPUTS``.  ``views``:
     ``DeviceView`` with uint8 colours; ``Js``: their (H,W,3) float32 device images.  The words a later all-reduce over ranks would
     combine are tensors: ``bounds_words`` (int32 x 4), ``key`` (int64, min), ``pix`` (int32 bit patterns of uint32, unsigned min).
+
+    What is asked for beyond the best view is ONE ``MosaicOptions``, a record of ten fields (``blend, feather, fill, bands, surface,
+    support, gains, gain_limit, gain_solve, reject``; the rows of ``MOSAIC_VALUES``): ``begin``, ``run`` and ``mosaic_of`` take the
+    record, or its fields as keywords laid over it -- ``begin(blend=H)`` below is that --, and ``MosaicOptions.checked`` is the one
+    place that checks them.  What a phase sees of the images is ONE chain of copies, ``_seen``: ``J`` -> culled (with a surface) ->
+    rejected (with a colour consensus) -> gained (once a gain pass has run), every stage in one transient buffer of its own.
+    ``add_reject_claim`` and ``add_reject_sums`` see the culled images; ``splat`` -- the one phase that counts what the culling
+    stages take --, ``add_span``, ``add_gain_sums``, ``add_gain_slots`` and ``add_gain_diag`` the culled and rejected ones, un-gained;
+    ``add_gain_reference`` those times the gains as they stand; ``resolve``, ``gather``, ``accumulate`` and ``accumulate_bands`` the
+    gained ones.
 
     The blend: ``begin(blend=H)`` also allocates ``acc`` ((Hm Wm, 8) int64, zeros: per cell the fixed-point sums ``wq Jq`` x 3,
     ``wq rgb`` x 3, ``wq`` and the sample count -- csrc/mosaic.h, "The blend"; the tensor a later all-reduce (sum) over ranks would
@@ -1499,28 +1503,31 @@ class Mosaic:
             raise ValueError(f'Mosaic: gsd must be finite and > 0, not {gsd}')
         self._axes_c = (C.c_float * 9)(*a.tolist())
         self.bounds_words = torch.tensor([-1, -1, 0, 0], dtype=torch.int32, device=self.device)   # two min keys, two max keys
+        self._reset()
+
+    def _reset(self, options: MosaicOptions = MosaicOptions()) -> None:
+        """All the state a ``begin`` decides, as it is before the grid is fixed: the checked ``options`` under their public names,
+        no tensor, no pass counted, nothing held."""
         self.grid = None
-        self.Hm = self.Wm = None
-        self.lo = self.hi = None
+        self.Hm = self.Wm = self.lo = self.hi = None
         self.key = self.pix = None
-        self._out = {}   # the outputs allocated so far, in the order of MOSAIC_OUTPUTS
-        self.blend = self.inv_h = self.acc = None
-        self.feather = self.feather_counts = self._feather_buf = None
+        self._out = {}        # the outputs allocated so far (rows of MOSAIC_OUTPUTS)
+        self._copies = {}     # stage of the chain -> its transient buffer of J copies (_copy)
+        self._held = {}       # stage of the chain -> the copies run() holds when one batch is the whole request
+        self.blend, self.feather, self.bands, self.surface, self.support = options.blend, options.feather, options.bands, options.surface, options.support
+        self.gains, self.gain_limit, self.gain_solve, self.reject = options.gains, options.gain_limit, options.gain_solve, options.reject
+        self.inv_h = self.acc = None
+        self.feather_counts = self._feather_buf = None
         self.fill_reach = self.fill_levels = self.pyramid = None
-        self.bands = self.band_plan = self.acc_bands = self._band_bufs = None
-        self.surface = self.top = self.surface_counts = self._cull_buf = self._held = None
-        self.support = self.rank = self.support_counts = None
-        self.gains = self.gain_limit = self.span = self.acc_gain = self.gain_table = self.gain_sums_words = self._gain_buf = None
-        self._gain_passes = 0
-        self._gain_open = False
-        self._splatted = False
-        self._held_gained = None
-        self.gain_solve = self.slot_ord = self.slot_sum = self.slot_over = self.gain_pairs_words = self.gain_diag_words = None
-        self.gain_direct = self.gain_kept = None
-        self._paired = False
-        self.reject = self.reject_slot_ord = self.reject_slot_sum = self.reject_slot_over = self.reject_counts = None
-        self._reject_out, self._reject_state, self._reject_n = {}, None, 0
-        self._reject_buf = self._held_rejected = None
+        self.band_plan = self.acc_bands = self._band_bufs = None
+        self.top = self.surface_counts = None
+        self.rank = self.support_counts = None
+        self.span = self.acc_gain = self.gain_table = self.gain_sums_words = None
+        self._gain_passes, self._gain_open, self._splatted = 0, False, False
+        self.slot_ord = self.slot_sum = self.slot_over = self.gain_pairs_words = self.gain_diag_words = None
+        self.gain_direct, self.gain_kept, self._paired = None, None, False
+        self.reject_slot_ord = self.reject_slot_sum = self.reject_slot_over = self.reject_counts = None
+        self._reject_state, self._reject_n = None, 0
 
     def _images(self, views: list, Js: list):
         views, Js = list(views), list(Js)
@@ -1547,13 +1554,16 @@ class Mosaic:
         table = torch.empty(_lib.load().sucre_mosaic_table_bytes(len(views)), dtype=torch.uint8, device=self.device)
         return arr, len(views), table, keep
 
-    def _walk(self, entry: str, images, *rest) -> None:
-        """One entry of the library that walks images, on the current stream: ``entry(table, n, images, *rest, stream)`` with
-        ``images`` as ``_images`` returns them and the tensors of ``rest`` as their addresses."""
-        arr, n, table, _ = images
-        rest = [C.c_void_p(x.data_ptr()) if torch.is_tensor(x) else x for x in rest]
+    def _call(self, entry: str, *args) -> None:
+        """One entry of the library on the current stream: ``entry(*args, stream)``, the tensors of ``args`` as their addresses."""
+        args = [C.c_void_p(x.data_ptr()) if torch.is_tensor(x) else x for x in args]
         with torch.cuda.device(self.device):
-            _lib.check(getattr(_lib.load(), entry)(C.c_void_p(table.data_ptr()), n, arr, *rest, _stream_ptr()))
+            _lib.check(getattr(_lib.load(), entry)(*args, _stream_ptr()))
+
+    def _walk(self, entry: str, images, *rest) -> None:
+        """One entry that walks images: ``entry(table, n, images, *rest, stream)`` with ``images`` as ``_images`` returns them."""
+        arr, n, table, _ = images
+        self._call(entry, table, n, arr, *rest)
 
     def _allocate(self, group: str) -> None:
         """The outputs of ``group`` (``MOSAIC_OUTPUTS``), every cell empty."""
@@ -1562,6 +1572,41 @@ class Mosaic:
                 shape = (self.Hm, self.Wm) + tail
                 self._out[key] = torch.empty(shape, dtype=dtype, device=self.device) if empty is None \
                     else torch.full(shape, empty, dtype=dtype, device=self.device)
+
+    @staticmethod
+    def _offsets(arr) -> list:
+        """Per image of ``arr`` the index of its first pixel in a buffer of the band-buffer layout (csrc/bands.h): image after image,
+        every one rounded up to ``MOSAIC_BLOCK_PX`` = 256 pixels."""
+        first, at = [], 0
+        for e in arr:
+            first.append(at)
+            at += -(-(e.H * e.W) // _lib.MOSAIC_BLOCK_PX) * _lib.MOSAIC_BLOCK_PX
+        return first
+
+    def _per_image(self, buf, arr, channels: int = 3) -> list:
+        """Per image of ``arr`` its (H,W,channels) view -- (H,W) for one channel -- into ``buf``, a buffer of that layout."""
+        return [buf[at * channels:(at + e.H * e.W) * channels].view(*((e.H, e.W, channels) if channels > 1 else (e.H, e.W)))
+                for e, at in zip(arr, self._offsets(arr))]
+
+    def _band_bytes(self, images) -> int:
+        """The bytes of one float32 x 3 buffer of that layout for ``images`` (``sucre_mosaic_band_bytes``)."""
+        arr, n, _, _ = images
+        lib = _lib.load()
+        n_bytes = lib.sucre_mosaic_band_bytes(n, arr)
+        if n_bytes == 0:
+            raise _lib.SucreError(f'sucre_mosaic_band_bytes: {lib.sucre_last_error().decode()}')
+        return n_bytes
+
+    def _copy(self, stage: str, entry: str, images, head, tail=()) -> list:
+        """A walking entry that writes a copy of every ``J`` in that layout: ``entry(.., *head, buffer, *tail, stream)`` into the ONE
+        transient buffer of ``stage``, grown to the largest batch seen (12 bytes per padded pixel).  Returns the per-image
+        (H,W,3) views into it: the stage's next call overwrites them.  Only enqueues."""
+        n_bytes = self._band_bytes(images)
+        buf = self._copies.get(stage)
+        if buf is None or buf.numel() * 4 < n_bytes:
+            buf = self._copies[stage] = torch.empty(n_bytes // 4, dtype=torch.float32, device=self.device)
+        self._walk(entry, images, *head, buf, *tail)
+        return self._per_image(buf, images[0])
 
     def add_bounds(self, views: list, Js: list) -> None:
         self._walk('sucre_mosaic_bounds', self._images(views, Js), self._axes_c, self.bounds_words)
@@ -1574,27 +1619,15 @@ class Mosaic:
         bits = np.where(k & 0x80000000, k & 0x7fffffff, ~k).astype(np.uint32)   # key_value of csrc/order_key.h
         return tuple(bits.view(np.float32).tolist())
 
-    def begin(self, bounds=None, blend=None, feather=None, bands=None, surface=None, support=None, gains=None, gain_limit=None,
-              reject=None, gain_solve=None):
-        """Fixes the grid and allocates; ``blend``: the blend depth H in metres (``MOSAIC_BLEND_RANGE``) -- a pixel whose range
-        exceeds its cell's smallest one by d gets the weight ``max(1 - d / H, 0)^2`` -- or None for the best view alone;
-        ``feather``: with a blend, the feather width F in source pixels (``MOSAIC_FEATHER_RANGE``), or None for none; ``bands``:
-        with a blend, the number K of detail bands of the multi-band blend (``MOSAIC_BANDS_RANGE``), or None for none;
-        ``surface``: the tolerance T in metres of the surface test (``MOSAIC_SURFACE_RANGE``), or None for none; ``support``: with
-        a surface, the number M of views the top must rest on (``MOSAIC_SUPPORT_RANGE``), or None for the plain minimum;
-        ``gains``: the rounds R of the per-image gain compensation (``MOSAIC_GAIN_ROUNDS_RANGE``), or None for none;
-        ``gain_limit``: with ``gains``, the limit L of a gain (``MOSAIC_GAIN_LIMIT_RANGE``), ``MOSAIC_GAIN_LIMIT`` unless given;
-        ``gain_solve``: with ``gains``, 'direct' for the direct solve in place of the first round's (``MOSAIC_GAIN_SOLVES``), 'rounds'
-        or None for the rounds alone; ``reject``: the tolerance T in units of ``J`` of the colour consensus across views
-        (``MOSAIC_REJECT_RANGE``), or None for none."""
-        options = MosaicOptions(blend=blend, feather=feather).checked('Mosaic.begin')   # before anything is allocated
-        reject = mosaic_reject_checked(reject, 'Mosaic.begin')
-        gains, gain_limit = mosaic_gains_checked(gains, gain_limit, 'Mosaic.begin')
-        gain_solve = mosaic_gain_solve_checked(gain_solve, gains, 'Mosaic.begin')
-        blend, feather = options.blend, options.feather
-        bands = mosaic_bands_checked(bands, blend, 'Mosaic.begin')
-        surface = None if surface is None else mosaic_surface_tol(surface)
-        support = mosaic_support_checked(support, surface, 'Mosaic.begin')
+    def begin(self, bounds=None, options: MosaicOptions = None, **fields):
+        """Fixes the grid and allocates what ``options`` (a ``MosaicOptions``; ``fields``: fields of the record laid over it, so
+        ``begin(blend=H, feather=F)`` is a request too) ask for; checked here (``MosaicOptions.checked``), before anything is
+        allocated.  ``blend``: a pixel whose range exceeds its cell's smallest one by d gets the weight ``max(1 - d / H, 0)^2``;
+        without it the best view alone.  ``fill`` is checked and not acted on: the hole filling is a call of its own (``fill(R)``; ``run``
+        makes it)."""
+        options = (options or MosaicOptions()).over(**fields).checked('Mosaic.begin')
+        blend, feather, bands, surface, support = options.blend, options.feather, options.bands, options.surface, options.support
+        gains, reject = options.gains, options.reject
         if bounds is None:
             bounds = self.bounds()
             if bounds is None:
@@ -1615,6 +1648,7 @@ class Mosaic:
                 raise _mosaic_refusal('reject', f'mosaic reject: {Wm} x {Hm} cells need {need} bytes for the consensus '
                                                 f'({MOSAIC_REJECT_CELL_BYTES} per cell), more than {MOSAIC_REJECT_MEMORY:g} of the {free} free '
                                                 f'on the device; give a coarser grid with --mosaic-gsd')
+        self._reset(options)
         self.Hm, self.Wm, self.lo, self.hi = Hm, Wm, (lo_s, lo_t), (hi_s, hi_t)
         g = _lib.MosaicGrid()
         g.axes, g.gsd, g.lo_s, g.lo_t, g.Hm, g.Wm = self._axes_c, float(self.gsd), float(lo_s), float(lo_t), Hm, Wm
@@ -1622,52 +1656,35 @@ class Mosaic:
         dev = self.device
         self.key = torch.full((Hm * Wm,), -1, dtype=torch.int64, device=dev)    # all ones: empty
         self.pix = torch.full((Hm * Wm,), -1, dtype=torch.int32, device=dev)
-        self._out = {}
         self._allocate('best')
-        self.blend, self.inv_h, self.acc = blend, None, None
-        self.fill_reach = self.fill_levels = self.pyramid = None
-        self.feather, self.feather_counts, self._feather_buf = feather, None, None
         if feather is not None:
             self.feather_counts = torch.zeros(2, dtype=torch.int64, device=dev)
         if blend is not None:
             self.inv_h = np.float32(1) / blend
             self.acc = torch.zeros((Hm * Wm, _lib.MOSAIC_ACC_WORDS), dtype=torch.int64, device=dev)
             self._allocate('blend')
-        self.bands, self.band_plan, self.acc_bands, self._band_bufs = bands, None, None, None
         if bands is not None:
             self.band_plan = mosaic_band_plan(blend, feather, bands)
             self.acc_bands = torch.zeros((bands + 1, Hm * Wm, _lib.MOSAIC_ACC_WORDS), dtype=torch.int64, device=dev)
             self._allocate('bands')
-        self.surface, self.top, self.surface_counts, self._cull_buf, self._held = surface, None, None, None, None
         if surface is not None:
             self.top = torch.full((Hm * Wm,), -1, dtype=torch.int32, device=dev)    # all ones: empty
             self.surface_counts = torch.zeros(2, dtype=torch.int64, device=dev)
             self._allocate('surface')
-        self.support, self.rank, self.support_counts = support, None, None
         if support is not None:
             self.rank = torch.full((support, Hm * Wm), -1, dtype=torch.int64, device=dev)    # all ones: empty; 8 M bytes per cell
             self.support_counts = torch.zeros(3, dtype=torch.int64, device=dev)
             self.surface_counts = self.support_counts[::2]   # culled below, samples with a cell: the surface test's two, the same memory
             self._allocate('support')
-        self.gains, self.gain_limit = gains, gain_limit
-        self.span = self.acc_gain = self.gain_table = self.gain_sums_words = self._gain_buf = None
-        self._gain_passes, self._gain_open, self._splatted, self._held_gained = 0, False, False, None
-        self.gain_solve = gain_solve
-        self.slot_ord = self.slot_sum = self.slot_over = self.gain_pairs_words = self.gain_diag_words = None
-        self.gain_direct, self.gain_kept, self._paired = None, None, False
         if gains is not None:
             self.span = torch.tensor([-1, 0], dtype=torch.int32, device=dev).repeat(Hm * Wm, 1)    # all ones, 0: empty; 8 bytes per cell
             self.acc_gain = torch.zeros((Hm * Wm, _lib.MOSAIC_ACC_WORDS), dtype=torch.int64, device=dev)   # 64 bytes per cell
-        self.reject = reject
-        self.reject_slot_ord = self.reject_slot_sum = self.reject_slot_over = self.reject_counts = None
-        self._reject_out, self._reject_state, self._reject_n, self._reject_buf, self._held_rejected = {}, None, 0, None, None
         if reject is not None:
             slots = _lib.MOSAIC_REJECT_CELL_IMAGES
             self.reject_slot_ord = torch.full((Hm * Wm, slots), -1, dtype=torch.int32, device=dev)    # all ones: free
             self.reject_slot_sum = torch.zeros((Hm * Wm, slots, 4), dtype=torch.int64, device=dev)
             self.reject_slot_over = torch.zeros((Hm * Wm,), dtype=torch.int32, device=dev)
-            for key, (_, tail, dtype, empty, _, _) in MOSAIC_REJECT_OUTPUTS.items():
-                self._reject_out[key] = torch.full((Hm, Wm) + tail, empty, dtype=dtype, device=dev)
+            self._allocate('reject')
             self._reject_state = 'claim'
         return Hm, Wm
 
@@ -1704,10 +1721,8 @@ class Mosaic:
         """``top``, ``support`` and ``surface_source`` of every cell from its ranks (``sucre_mosaic_support_top``), once
         ``add_support`` has run every level over every image and before ``splat``.  Only enqueues."""
         self._supported('finish_support')
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().sucre_mosaic_support_top(C.byref(self.grid), int(self.support), C.c_void_p(self.rank.data_ptr()),
-                                                            C.c_void_p(self.top.data_ptr()), C.c_void_p(self._out['support'].data_ptr()),
-                                                            C.c_void_p(self._out['surface_source'].data_ptr()), _stream_ptr()))
+        self._call('sucre_mosaic_support_top', C.byref(self.grid), int(self.support), self.rank, self.top, self._out['support'],
+                   self._out['surface_source'])
 
     def culled_images(self, views: list, Js: list, first_ordinal: int, count: bool = False) -> list:
         """The batch's ``Js`` as the phases after the surface test see them: per image an (H,W,3) float32 copy of ``J`` with NaN in
@@ -1718,41 +1733,29 @@ class Mosaic:
         counted once (``splat`` does).  With a support the cull has two sides (``sucre_mosaic_cull_supported``): a sample more than T
         above its cell's supported top goes too, counted in ``culled_above`` and ``support_counts``.  Only enqueues."""
         self._surfaced('culled_images')
-        images = self._images(views, Js)
-        arr, n, _, _ = images
-        lib = _lib.load()
-        n_bytes = lib.sucre_mosaic_band_bytes(n, arr)
-        if n_bytes == 0:
-            raise _lib.SucreError(f'sucre_mosaic_band_bytes: {lib.sucre_last_error().decode()}')
-        if self._cull_buf is None or self._cull_buf.numel() * 4 < n_bytes:
-            self._cull_buf = torch.empty(n_bytes // 4, dtype=torch.float32, device=self.device)
-        buf = self._cull_buf
+        head = (int(first_ordinal), C.byref(self.grid), self.top, C.c_float(float(self.surface)))
+        o = self._out
         if self.support is None:
-            self._walk('sucre_mosaic_cull', images, int(first_ordinal), C.byref(self.grid), self.top, C.c_float(float(self.surface)), buf,
-                       self._out['culled'] if count else None, self.surface_counts if count else None)
-        else:
-            self._walk('sucre_mosaic_cull_supported', images, int(first_ordinal), C.byref(self.grid), self.top,
-                       C.c_float(float(self.surface)), buf, self._out['culled'] if count else None,
-                       self._out['culled_above'] if count else None, self.support_counts if count else None)
-        out, at = [], 0
-        for e in arr:
-            out.append(buf[at * 3:(at + e.H * e.W) * 3].view(e.H, e.W, 3))
-            at += -(-(e.H * e.W) // _lib.MOSAIC_BLOCK_PX) * _lib.MOSAIC_BLOCK_PX
-        return out
+            tail = (o['culled'], self.surface_counts) if count else (None, None)
+            return self._copy('cull', 'sucre_mosaic_cull', self._images(views, Js), head, tail)
+        tail = (o['culled'], o['culled_above'], self.support_counts) if count else (None, None, None)
+        return self._copy('cull', 'sucre_mosaic_cull_supported', self._images(views, Js), head, tail)
 
-    def _culled(self, views: list, Js: list, first_ordinal: int, count: bool = False) -> list:
-        """The batch's ``Js`` as the phases after the surface test see them, gains apart: the culled ones when a surface was begun
-        (the ones ``run`` holds when a single batch is the whole request: culled once, the same bits)."""
-        if self.surface is None:
-            return Js
-        return self.culled_images(views, Js, first_ordinal, count) if self._held is None else self._held
-
-    def _phase_images(self, views: list, Js: list, first_ordinal: int, count: bool = False):
-        """``_images`` for a phase after the surface test: of the culled ``Js`` when a surface was begun, and, once a gain pass has
-        run, of those times their gains (``gained_images``; of the ones ``run`` holds when a single batch is the whole request)."""
-        if self._gain_passes == 0:
-            return self._images(views, self._cleaned(views, Js, first_ordinal, count))
-        return self._images(views, self.gained_images(views, Js, first_ordinal) if self._held_gained is None else self._held_gained)
+    def _seen(self, views: list, Js: list, first_ordinal: int, upto: str, count: bool = False) -> list:
+        """The batch's ``Js`` as a phase sees them: through the stages of the one chain -- 'cull' (with a surface test:
+        ``culled_images``), 'reject' (with a colour consensus: its cull of the copy so far), 'gain' (once a gain pass has run: the
+        copy so far times the gains) -- up to and including ``upto``, each stage of the copy the stage before it left; a stage
+        that was not begun passes its input on.  A stage ``run`` holds (one batch is the whole request) is not made again: the
+        same bits.  ``count``: the culling stages add what they take to their counters -- one phase alone asks (``splat``)."""
+        stages = (('cull', self.surface is not None, lambda J: self.culled_images(views, J, first_ordinal, count)),
+                  ('reject', self.reject is not None, lambda J: self._reject_cull(views, J, first_ordinal, count)),
+                  ('gain', self._gain_passes > 0, lambda J: self._apply_gains(views, J, first_ordinal)))
+        for stage, begun, make in stages:
+            if begun:
+                Js = self._held[stage] if stage in self._held else make(Js)
+            if stage == upto:
+                return Js
+        raise ValueError(f'Mosaic: no stage {upto!r}')
 
     # ---- the colour consensus across views (csrc/reject.h) ----
 
@@ -1769,7 +1772,7 @@ class Mosaic:
         self._rejecting('add_reject_claim')
         if self._reject_state != 'claim':
             raise ValueError('Mosaic.add_reject_claim: add_reject_sums() has read the slots already: the claim sees every image first')
-        images = self._images(views, self._culled(views, Js, first_ordinal))
+        images = self._images(views, self._seen(views, Js, first_ordinal, 'cull'))
         self._walk('sucre_mosaic_reject_claim', images, int(first_ordinal), C.byref(self.grid), self.reject_slot_ord,
                    self.reject_slot_over, _lib.MOSAIC_PLAIN_ATOMIC if plain_atomic else 0)
         self._reject_n = max(self._reject_n, int(first_ordinal) + images[1])
@@ -1781,7 +1784,7 @@ class Mosaic:
         self._rejecting('add_reject_sums')
         if self._reject_state == 'done':
             raise ValueError('Mosaic.add_reject_sums: finish_reject() has formed the consensus already')
-        images = self._images(views, self._culled(views, Js, first_ordinal))
+        images = self._images(views, self._seen(views, Js, first_ordinal, 'cull'))
         if int(first_ordinal) + images[1] > self._reject_n:
             raise ValueError(f'Mosaic.add_reject_sums: ordinals {int(first_ordinal)}..{int(first_ordinal) + images[1] - 1}, but the claim has '
                              f'seen {self._reject_n} images: add_reject_claim() over every image comes first (the slots must be final)')
@@ -1799,11 +1802,10 @@ class Mosaic:
         if self._reject_state != 'sums':
             raise ValueError('Mosaic.finish_reject: add_reject_claim() and then add_reject_sums() over every image come first'
                              if self._reject_state == 'claim' else 'Mosaic.finish_reject: the consensus has been formed already')
-        o = self._reject_out
+        o = self._out
         big = torch.zeros(1, dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().sucre_mosaic_reject_consensus(C.byref(self.grid), *(C.c_void_p(x.data_ptr()) for x in (
-                self.reject_slot_ord, self.reject_slot_sum, o['reject_ref'], o['reject_source'], o['reject_views'], big)), _stream_ptr()))
+        self._call('sucre_mosaic_reject_consensus', C.byref(self.grid), self.reject_slot_ord, self.reject_slot_sum, o['reject_ref'],
+                   o['reject_source'], o['reject_views'], big)
         n_big = int(big)
         if n_big:
             raise _mosaic_refusal('reject', f'mosaic reject: {n_big} times an image holds {MOSAIC_MAX_SAMPLES} samples or more in one cell, and '
@@ -1813,44 +1815,29 @@ class Mosaic:
         self.reject_counts = torch.zeros((self._reject_n, _lib.MOSAIC_GAIN_ROW_WORDS), dtype=torch.int64, device=self.device)
         self._reject_state = 'done'
 
-    def rejected_images(self, views: list, Js: list, first_ordinal: int, count: bool = False, _culled=None) -> list:
+    def rejected_images(self, views: list, Js: list, first_ordinal: int, count: bool = False) -> list:
         """The batch's ``Js`` as the phases after the colour consensus see them: per image an (H,W,3) float32 copy of the (culled)
         ``J`` with NaN in every channel of a pixel that does not take part, or whose cell has a reference, whose image is not the
         cell's ``reject_source`` and whose colour differs from ``reject_ref`` by more than T in any channel
         (``sucre_mosaic_reject_cull``).  Valid once ``finish_reject`` has run.  Views into ONE transient buffer of its own, sized to
         the largest batch seen: the next call overwrites them.  ``count``: the rejected samples are added to ``rejected`` and
         ``reject_counts`` -- to be asked for in one phase alone (``splat`` does).  Only enqueues."""
+        return self._reject_cull(views, self._seen(views, Js, first_ordinal, 'cull'), first_ordinal, count)
+
+    def _reject_cull(self, views: list, Jc: list, first_ordinal: int, count: bool = False) -> list:
+        """``rejected_images`` of the culled ``Jc``: the chain's stage 'reject'."""
         self._rejecting('rejected_images')
         if self._reject_state != 'done':
             raise ValueError('Mosaic.rejected_images: finish_reject() comes first (there is no consensus to test against yet)')
-        images = self._images(views, self._culled(views, Js, first_ordinal) if _culled is None else _culled)
-        arr, n, _, _ = images
+        images = self._images(views, Jc)
+        n = images[1]
         if int(first_ordinal) + n > self._reject_n:
             raise ValueError(f'Mosaic.rejected_images: ordinals {int(first_ordinal)}..{int(first_ordinal) + n - 1}, but the claim has seen '
                              f'{self._reject_n} images')
-        lib = _lib.load()
-        n_bytes = lib.sucre_mosaic_band_bytes(n, arr)
-        if n_bytes == 0:
-            raise _lib.SucreError(f'sucre_mosaic_band_bytes: {lib.sucre_last_error().decode()}')
-        if self._reject_buf is None or self._reject_buf.numel() * 4 < n_bytes:
-            self._reject_buf = torch.empty(n_bytes // 4, dtype=torch.float32, device=self.device)
-        buf, o = self._reject_buf, self._reject_out
-        self._walk('sucre_mosaic_reject_cull', images, int(first_ordinal), C.byref(self.grid), o['reject_ref'], o['reject_source'],
-                   C.c_float(float(self.reject)), buf, o['rejected'] if count else None, int(self._reject_n),
-                   self.reject_counts if count else None)
-        out, at = [], 0
-        for e in arr:
-            out.append(buf[at * 3:(at + e.H * e.W) * 3].view(e.H, e.W, 3))
-            at += -(-(e.H * e.W) // _lib.MOSAIC_BLOCK_PX) * _lib.MOSAIC_BLOCK_PX
-        return out
-
-    def _cleaned(self, views: list, Js: list, first_ordinal: int, count: bool = False) -> list:
-        """The batch's ``Js`` as the phases from the splat on see them, gains apart: culled when a surface was begun, then rejected
-        when a colour consensus was (the ones ``run`` holds when a single batch is the whole request)."""
-        Jc = self._culled(views, Js, first_ordinal, count)
-        if self.reject is None:
-            return Jc
-        return self.rejected_images(views, Js, first_ordinal, count, _culled=Jc) if self._held_rejected is None else self._held_rejected
+        o = self._out
+        return self._copy('reject', 'sucre_mosaic_reject_cull', images,
+                          (int(first_ordinal), C.byref(self.grid), o['reject_ref'], o['reject_source'], C.c_float(float(self.reject))),
+                          (o['rejected'] if count else None, int(self._reject_n), self.reject_counts if count else None))
 
     # ---- the gain compensation (csrc/gains_mosaic.h) ----
 
@@ -1869,39 +1856,28 @@ class Mosaic:
         (``sucre_mosaic_gain_span``).  Over ALL the images, in any batches, once ``splat`` has seen every image and before the first
         gain pass.  ``plain_atomic``: both atomics for every pixel, without the loads that filter them."""
         self._spanned('add_span')
-        self._walk('sucre_mosaic_gain_span', self._images(views, self._cleaned(views, Js, first_ordinal)), int(first_ordinal),
+        self._walk('sucre_mosaic_gain_span', self._images(views, self._seen(views, Js, first_ordinal, 'reject')), int(first_ordinal),
                    C.byref(self.grid), self.span, _lib.MOSAIC_PLAIN_ATOMIC if plain_atomic else 0)
 
     def _apply_gains(self, views: list, Jc: list, first_ordinal: int) -> list:
-        """``Jc`` times the gains of their ordinals (``sucre_mosaic_gain_apply``) as views into the ONE transient buffer
-        ``_gain_buf``, sized to the largest batch seen: the next call overwrites them."""
+        """``Jc`` times the gains of their ordinals (``sucre_mosaic_gain_apply``), the chain's stage 'gain': views into the ONE
+        transient buffer of that stage, sized to the largest batch seen: the next call overwrites them."""
         images = self._images(views, Jc)
-        arr, n, _, _ = images
-        if int(first_ordinal) + n > self.gain_table.shape[0]:
+        n, table = images[1], self.gain_table
+        if int(first_ordinal) + n > table.shape[0]:
             raise ValueError(f'Mosaic: ordinals {int(first_ordinal)}..{int(first_ordinal) + n - 1} but the gain table holds '
-                             f'{self.gain_table.shape[0]} images (begin_gain_pass fixes the count)')
-        lib = _lib.load()
-        n_bytes = lib.sucre_mosaic_band_bytes(n, arr)
-        if n_bytes == 0:
-            raise _lib.SucreError(f'sucre_mosaic_band_bytes: {lib.sucre_last_error().decode()}')
-        if self._gain_buf is None or self._gain_buf.numel() * 4 < n_bytes:
-            self._gain_buf = torch.empty(n_bytes // 4, dtype=torch.float32, device=self.device)
-        buf = self._gain_buf
-        self._walk('sucre_mosaic_gain_apply', images, int(first_ordinal), self.gain_table, int(self.gain_table.shape[0]), buf)
-        out, at = [], 0
-        for e in arr:
-            out.append(buf[at * 3:(at + e.H * e.W) * 3].view(e.H, e.W, 3))
-            at += -(-(e.H * e.W) // _lib.MOSAIC_BLOCK_PX) * _lib.MOSAIC_BLOCK_PX
-        return out
+                             f'{table.shape[0]} images (begin_gain_pass fixes the count)')
+        return self._copy('gain', 'sucre_mosaic_gain_apply', images, (int(first_ordinal), table, int(table.shape[0])))
 
     def gained_images(self, views: list, Js: list, first_ordinal: int) -> list:
-        """The batch's ``Js`` as the phases after the gain compensation see them: per image the (H,W,3) float32 culled ``J`` (``J``
-        itself without a surface test) times the image's gain, one float32 multiply per channel; a NaN stays a NaN.  Valid once a
-        gain pass has begun (the gain table exists then).  Views into one transient buffer; only enqueues."""
+        """The batch's ``Js`` as the phases after the gain compensation see them: per image the (H,W,3) float32 culled and rejected
+        ``J`` (``J`` itself without a surface test and a consensus) times the image's gain, one float32 multiply per channel; a
+        NaN stays a NaN.  Valid once a gain pass has begun (the gain table exists then).  Views into one transient buffer; only
+        enqueues."""
         self._gaining('gained_images')
         if self.gain_table is None:
             raise ValueError('Mosaic.gained_images: no gain pass has begun, so there is no gain table yet')
-        return self._apply_gains(views, self._cleaned(views, Js, first_ordinal), first_ordinal)
+        return self._apply_gains(views, self._seen(views, Js, first_ordinal, 'reject'), first_ordinal)
 
     def begin_gain_pass(self, n_images: int) -> None:
         """Opens a pass at the gains as they stand: zeroes ``acc_gain``; the first one allocates ``gain_table`` (ones) and
@@ -1929,7 +1905,7 @@ class Mosaic:
         """The reference of the open pass: the blend's accumulate over the gained images into ``acc_gain`` with the smallest normal
         float32 as ``inv_h``, so that every sample weighs 4096 -- the per-sample mean.  Over ALL the images before ``add_gain_sums``."""
         self._in_gain_pass('add_gain_reference')
-        Jg = self._apply_gains(views, self._cleaned(views, Js, first_ordinal), first_ordinal)
+        Jg = self._apply_gains(views, self._seen(views, Js, first_ordinal, 'reject'), first_ordinal)
         self._walk('sucre_mosaic_accumulate', self._images(views, Jg), int(first_ordinal), C.byref(self.grid), self.key,
                    C.c_float(2.0 ** -126), self.acc_gain, _lib.MOSAIC_PLAIN_ATOMIC if plain else 0)
 
@@ -1952,7 +1928,7 @@ class Mosaic:
             if H * W > MOSAIC_GAIN_MAX_PIXELS:
                 raise _mosaic_refusal('gains', f'mosaic gains: {v.name or "a view"} has {W} x {H} pixels, more than the '
                                                f'{MOSAIC_GAIN_MAX_PIXELS} whose 64-bit sums stay below 2^62')
-        images = self._images(views, self._cleaned(views, Js, first_ordinal))
+        images = self._images(views, self._seen(views, Js, first_ordinal, 'reject'))
         if int(first_ordinal) + images[1] > self.gain_table.shape[0]:
             raise ValueError(f'Mosaic.add_gain_sums: ordinals {int(first_ordinal)}..{int(first_ordinal) + images[1] - 1} but the gain '
                              f'table holds {self.gain_table.shape[0]} images')
@@ -2028,7 +2004,7 @@ class Mosaic:
         self.gain_diag_words = torch.zeros((n, _lib.MOSAIC_GAIN_ROW_WORDS), dtype=torch.int64, device=dev)
 
     def _direct_images(self, what: str, views: list, Js: list, first_ordinal: int):
-        images = self._images(views, self._cleaned(views, Js, first_ordinal))
+        images = self._images(views, self._seen(views, Js, first_ordinal, 'reject'))
         if int(first_ordinal) + images[1] > self.gain_table.shape[0]:
             raise ValueError(f'Mosaic.{what}: ordinals {int(first_ordinal)}..{int(first_ordinal) + images[1] - 1} but the gain '
                              f'table holds {self.gain_table.shape[0]} images')
@@ -2059,10 +2035,8 @@ class Mosaic:
         self._slotted('gain_pairs')
         if self._paired:
             raise ValueError('Mosaic.gain_pairs: the pairs have been added already')
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().sucre_mosaic_gain_pairs(C.byref(self.grid), *(C.c_void_p(x.data_ptr()) for x in (
-                self.span, self.slot_ord, self.slot_sum, self.slot_over)), int(self.gain_table.shape[0]),
-                C.c_void_p(self.gain_pairs_words.data_ptr()), int(table_entries), _lib.MOSAIC_PLAIN_ATOMIC if plain else 0, _stream_ptr()))
+        self._call('sucre_mosaic_gain_pairs', C.byref(self.grid), self.span, self.slot_ord, self.slot_sum, self.slot_over,
+                   int(self.gain_table.shape[0]), self.gain_pairs_words, int(table_entries), _lib.MOSAIC_PLAIN_ATOMIC if plain else 0)
         self._paired = True
 
     def add_gain_diag(self, views: list, Js: list, first_ordinal: int, plain: bool = False) -> None:
@@ -2094,18 +2068,19 @@ class Mosaic:
     def splat(self, views: list, Js: list, first_ordinal: int, plain_atomic: bool = False) -> None:
         self._begun('splat')
         self._splatted = True
-        self._walk('sucre_mosaic_splat', self._phase_images(views, Js, first_ordinal, count=True), int(first_ordinal), C.byref(self.grid),
-                   self.key, _lib.MOSAIC_PLAIN_ATOMIC if plain_atomic else 0)
+        seen = self._seen(views, Js, first_ordinal, 'gain', count=self._gain_passes == 0)   # the one phase that counts what is culled
+        self._walk('sucre_mosaic_splat', self._images(views, seen), int(first_ordinal), C.byref(self.grid), self.key,
+                   _lib.MOSAIC_PLAIN_ATOMIC if plain_atomic else 0)
 
     def resolve(self, views: list, Js: list, first_ordinal: int) -> None:
         self._begun('resolve')
-        self._walk('sucre_mosaic_resolve', self._phase_images(views, Js, first_ordinal), int(first_ordinal), C.byref(self.grid), self.key,
-                   self.pix)
+        self._walk('sucre_mosaic_resolve', self._images(views, self._seen(views, Js, first_ordinal, 'gain')), int(first_ordinal),
+                   C.byref(self.grid), self.key, self.pix)
 
     def gather(self, views: list, Js: list, first_ordinal: int) -> None:
         self._begun('gather')
-        self._walk('sucre_mosaic_gather', self._phase_images(views, Js, first_ordinal), int(first_ordinal), C.byref(self.grid), self.key,
-                   self.pix, *(self._out[k] for k in ('J', 'raw', 'source', 'pixel', 'range')))
+        self._walk('sucre_mosaic_gather', self._images(views, self._seen(views, Js, first_ordinal, 'gain')), int(first_ordinal),
+                   C.byref(self.grid), self.key, self.pix, *(self._out[k] for k in ('J', 'raw', 'source', 'pixel', 'range')))
 
     def _blending(self, what: str) -> None:
         self._begun(what)
@@ -2117,7 +2092,7 @@ class Mosaic:
         smallest range then).  ``plain``: eight atomics per pixel instead of eight per run of a wave's lanes (the same ``acc``).
         With a feather the batch's map is formed first (``sucre_mosaic_feather``) and the feathered phase reads it."""
         self._blending('accumulate')
-        images = self._phase_images(views, Js, first_ordinal)
+        images = self._images(views, self._seen(views, Js, first_ordinal, 'gain'))
         head = (int(first_ordinal), C.byref(self.grid), self.key, C.c_float(float(self.inv_h)))
         tail = (self.acc, _lib.MOSAIC_PLAIN_ATOMIC if plain else 0)
         if self.feather is None:
@@ -2144,11 +2119,7 @@ class Mosaic:
             buf = torch.empty(n_bytes, dtype=torch.uint8, device=self.device)    # (4-byte aligned: the allocator's blocks are)
         self._walk('sucre_mosaic_feather', images, int(F), buf)
         words = buf[:n_bytes // 6 * 4].view(torch.int32)   # the dist2 words; the uint16 scratch sits behind them
-        maps, at = [], 0
-        for e in arr:
-            maps.append(words[at:at + e.H * e.W].view(e.H, e.W))
-            at += -(-(e.H * e.W) // _lib.MOSAIC_BLOCK_PX) * _lib.MOSAIC_BLOCK_PX
-        return buf, maps
+        return buf, self._per_image(words, arr, 1)
 
     def feather_map(self, views: list, Js: list, F) -> list:
         """Per image the (H,W) int32 ``dist2`` of csrc/mosaic.h, "The feather": ``min(D2, F^2)`` with D2 the squared distance in
@@ -2161,18 +2132,10 @@ class Mosaic:
     def _band_buffers(self, images, bufs=None):
         """Three float32 buffers of one band each for ``images`` (``sucre_mosaic_band_bytes``; ``bufs`` when they are large enough)
         and, per image, the index of its first pixel in them."""
-        arr, n, _, _ = images
-        lib = _lib.load()
-        n_bytes = lib.sucre_mosaic_band_bytes(n, arr)
-        if n_bytes == 0:
-            raise _lib.SucreError(f'sucre_mosaic_band_bytes: {lib.sucre_last_error().decode()}')
+        n_bytes = self._band_bytes(images)
         if bufs is None or bufs[0].numel() * 4 < n_bytes:
             bufs = [torch.empty(n_bytes // 4, dtype=torch.float32, device=self.device) for _ in range(3)]
-        first, at = [], 0
-        for e in arr:
-            first.append(at)
-            at += -(-(e.H * e.W) // _lib.MOSAIC_BLOCK_PX) * _lib.MOSAIC_BLOCK_PX
-        return bufs, first
+        return bufs, self._offsets(images[0])
 
     def _band_levels(self, images, K: int, bufs):
         """Enqueues the K levels of ``sucre_mosaic_band_split`` over ``images``, S ping-ponging between ``bufs[0]`` and ``bufs[1]``,
@@ -2190,11 +2153,11 @@ class Mosaic:
         take part.  Needs no ``begin``; only enqueues (reading a band waits for it)."""
         K = mosaic_band_count(K)
         images = self._images(views, Js)
-        bufs, first = self._band_buffers(images)
-        stacks = [[] for _ in first]
+        bufs, _ = self._band_buffers(images)
+        stacks = [[] for _ in images[0]]
         for _, buf in self._band_levels(images, K, bufs):
-            for stack, e, at in zip(stacks, images[0], first):
-                stack.append(buf[at * 3:(at + e.H * e.W) * 3].view(e.H, e.W, 3).clone())
+            for stack, band in zip(stacks, self._per_image(buf, images[0])):
+                stack.append(band.clone())
         return stacks
 
     def _banding(self, what: str) -> None:
@@ -2224,7 +2187,7 @@ class Mosaic:
         at the user's F and from the true J, and every band reads it: ``dist2 = min(D2, F^2)`` tells ``dist2 >= F_j^2`` and holds
         every root below it for any ``F_j <= F``.  ``plain``: as ``accumulate``.  ``acc`` and ``feather_counts`` are not touched."""
         self._banding('accumulate_bands')
-        images = self._phase_images(views, Js, first_ordinal)
+        images = self._images(views, self._seen(views, Js, first_ordinal, 'gain'))
         self._band_bufs, first = self._band_buffers(images, self._band_bufs)
         if self.feather is not None:
             self._feather_buf, _ = self._feather_pass(images, self.feather, self._feather_buf)
@@ -2237,9 +2200,7 @@ class Mosaic:
         in float32 from the residual to the finest band.  Valid once ``accumulate_bands`` has seen every image (``normalize`` has
         checked the sample bound: the residual's counts are the blend's); only enqueues."""
         self._banding('combine_bands')
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().sucre_mosaic_band_combine(C.byref(self.grid), self.bands + 1, C.c_void_p(self.acc_bands.data_ptr()),
-                                                             C.c_void_p(self._out['J_multiband'].data_ptr()), _stream_ptr()))
+        self._call('sucre_mosaic_band_combine', C.byref(self.grid), self.bands + 1, self.acc_bands, self._out['J_multiband'])
 
     def normalize(self, check: bool = True) -> None:
         """The per-cell pass from ``acc`` to the four blended outputs; waits for it, and raises ValueError when a cell holds
@@ -2247,11 +2208,7 @@ class Mosaic:
         pass (for measurements: the caller looks at ``samples`` itself)."""
         self._blending('normalize')
         o = self._out
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().sucre_mosaic_normalize(C.byref(self.grid), C.c_void_p(self.acc.data_ptr()),
-                                                          C.c_void_p(o['J_blend'].data_ptr()), C.c_void_p(o['raw_blend'].data_ptr()),
-                                                          C.c_void_p(o['weight'].data_ptr()), C.c_void_p(o['samples'].data_ptr()),
-                                                          _stream_ptr()))
+        self._call('sucre_mosaic_normalize', C.byref(self.grid), self.acc, o['J_blend'], o['raw_blend'], o['weight'], o['samples'])
         if not check:
             return
         most = int(o['samples'].max())
@@ -2284,17 +2241,15 @@ class Mosaic:
         if self.bands is not None:
             pairs.append(('bands_fill', 'J_multiband', 'raw_blend', 'J_multiband_filled', None))
         o = self._out
-        with torch.cuda.device(dev):
-            for group, J, raw, J_to, raw_to in pairs:
+        for group, J, raw, J_to, raw_to in pairs:
+            with torch.cuda.device(dev):
                 self._allocate(group)
                 # (the blend's own levels are not a result: a blended colour is always finite, a best-view one need not be)
                 level = o['fill_level'] if group == 'fill' else torch.empty_like(o['fill_level'])
                 raw_filled = torch.empty_like(o[raw]) if raw_to is None else o[raw_to]
-                base = (Hm, Wm, L, C.c_void_p(o[J].data_ptr()), C.c_void_p(o[raw].data_ptr()), C.c_void_p(o['source'].data_ptr()),
-                        C.c_void_p(self.pyramid.data_ptr()))
-                _lib.check(lib.sucre_mosaic_fill_pull(*base, _stream_ptr()))
-                _lib.check(lib.sucre_mosaic_fill_push(*base, C.c_void_p(o[J_to].data_ptr()), C.c_void_p(raw_filled.data_ptr()),
-                                                      C.c_void_p(level.data_ptr()), _stream_ptr()))
+            base = (Hm, Wm, L, o[J], o[raw], o['source'], self.pyramid)
+            self._call('sucre_mosaic_fill_pull', *base)
+            self._call('sucre_mosaic_fill_push', *base, o[J_to], raw_filled, level)
         return L
 
     def result(self) -> dict:
@@ -2321,13 +2276,16 @@ class Mosaic:
             self._out['surface'].copy_(heights(self.top))
         if self.support is not None:
             self._out['surface_top'].copy_(heights((self.rank[0] >> 32).to(torch.int32)))
-        def of(*groups):
-            return {key: t for key, t in self._out.items() if MOSAIC_OUTPUTS[key][0] in groups}
+        of = self._outputs   # the groups in result()'s own order, which is not the order of the table's rows
         return {**of('best', 'blend', 'bands', 'surface'), **({} if self.feather is None else {'feather': self.feather}),
                 **({} if self.bands is None else {'bands': self.bands}),
                 **({} if self.surface is None else {'surface_tol': float(self.surface)}),
                 **({} if self.support is None else {**of('support'), 'surface_support': int(self.support)}),
                 **self._reject_result(), **of('fill', 'blend_fill', 'bands_fill'), **self._gain_result()}
+
+    def _outputs(self, *groups) -> dict:
+        """The allocated outputs of ``groups`` (``MOSAIC_OUTPUTS``), in the order they were allocated."""
+        return {key: t for key, t in self._out.items() if MOSAIC_OUTPUTS[key][0] in groups}
 
     def _reject_result(self) -> dict:
         """The keys of ``result()`` that a colour consensus adds (none without one): the rows of ``MOSAIC_REJECT_OUTPUTS``,
@@ -2336,7 +2294,7 @@ class Mosaic:
         if self.reject is None:
             return {}
         per = torch.zeros((0, 2), dtype=torch.int64, device=self.device) if self.reject_counts is None else self.reject_counts[:, :2].contiguous()
-        return {**self._reject_out, 'reject_per_image': per, 'reject_tol': float(self.reject)}
+        return {**self._outputs('reject'), 'reject_per_image': per, 'reject_tol': float(self.reject)}
 
     def _gain_result(self) -> dict:
         """The keys of ``result()`` that a gain compensation adds (none without one); waits for the sums."""
@@ -2366,136 +2324,96 @@ class Mosaic:
                 'gain_shared_cells': int(shared.sum()), 'gain_kept': [int(c) for c in self.gain_kept],
                 'gain_components': mosaic_gain_groups(pairs.numpy(), diag.numpy()), 'gain_prior': float(MOSAIC_GAIN_PRIOR)}
 
-    def run(self, batches, options: MosaicOptions = MosaicOptions(), bounds=None, plain_atomic: bool = False, bands=None,
-            surface=None, support=None, gains=None, gain_limit=None, reject=None, gain_solve=None) -> 'Mosaic':
-        """Every phase over every batch, in the one order there is: the bounds (unless ``bounds`` is given), ``begin``; with
-        ``surface`` (the tolerance T of the surface test, beside the options record) ``add_surface`` -- or, with ``support`` (the
-        count M of supporting views, beside the record too; only with a surface), ``add_support`` over every batch for level 0,
-        then for level 1, ... and ``finish_support``: M passes, and ``add_surface`` does not run --; ``splat``,
-        ``resolve`` and ``gather``; with a blend ``accumulate`` and then ``normalize``; with ``bands`` (the count K of a multi-band
-        blend, beside the options record; only with a blend) ``accumulate_bands`` and then ``combine_bands``; with a fill ``fill``.  ``batches``: a
-        sequence of ``(first_ordinal, load)``, ``load()`` returning the batch's ``(views, Js)`` -- called once per phase, so a
-        caller may hold only some of the images at a time; ``options``: as ``MosaicOptions.checked`` returns them;
-        ``plain_atomic``: the surface, the splat and the accumulate phase in their plain forms.  With a surface test every phase
-        culls its batch anew, unless one batch is the whole request: that one is culled once.  With ``gains`` (the rounds R of the
-        gain compensation, beside the record; ``gain_limit``: its limit L) the splat is followed by ``add_span`` over every batch,
-        R times ``gain_pass`` and ``solve_gains``, and one more ``gain_pass`` that measures the final state; resolve, gather,
-        accumulate and the bands then see the gained images -- applied anew per phase and batch, unless one batch is the whole
-        request: that one is gained once and held.  With ``gain_solve='direct'`` the first pass is followed by ``add_gain_slots``
-        over every batch, ``gain_pairs``, ``add_gain_diag`` over every batch and ``solve_gains_direct`` in place of the first
-        ``solve_gains`` (csrc/gains_direct.h); 'rounds' and None: the rounds alone.  With ``reject`` (the tolerance T of the colour
-        consensus, beside the record; csrc/reject.h) the surface phase is followed by ``add_reject_claim`` over every batch, then
-        ``add_reject_sums`` over every batch, then ``finish_reject``; the splat and every phase after it, the gains' included, then
-        see the rejected copy of the (culled) images -- made anew per phase and batch, unless one batch is the whole request: that
-        one is made once and held.  Returns the mosaic."""
+    def run(self, batches, options: MosaicOptions = None, bounds=None, plain_atomic: bool = False, **fields) -> 'Mosaic':
+        """Every phase over every batch, in the one order there is.  ``batches``: a sequence of ``(first_ordinal, load)``,
+        ``load()`` returning the batch's ``(views, Js)`` -- called once per phase, so a caller may hold only some of the images at a
+        time; ``options``: a ``MosaicOptions`` (``fields``: fields of the record laid over it), checked here;
+        ``plain_atomic``: every phase that has one in its plain form.  The order: the bounds (unless ``bounds`` is given), ``begin``;
+        with a surface ``add_surface`` -- or, with a support of M views, ``add_support`` over every batch for level 0, then for
+        level 1, ... and ``finish_support``: M passes, and ``add_surface`` does not run --; with a reject tolerance
+        ``add_reject_claim`` over every batch, then ``add_reject_sums`` over every batch, then ``finish_reject``; ``splat``; with
+        gains ``add_span`` over every batch, R times ``gain_pass`` and ``solve_gains`` -- with the direct solve the first pass is
+        followed by ``add_gain_slots`` over every batch, ``gain_pairs``, ``add_gain_diag`` over every batch and
+        ``solve_gains_direct`` in place of the first ``solve_gains`` --, and one more ``gain_pass`` that measures the final state;
+        ``resolve`` and ``gather``; with a blend ``accumulate`` and then ``normalize``; with bands ``accumulate_bands`` and then
+        ``combine_bands``; with a fill ``fill``.  What a phase sees is the chain of ``_seen``: the claim and the sums of the
+        consensus see the culled images; the splat, the span and the sums, slots and diag of the gains the culled and rejected ones;
+        the gains' reference those times the gains as they stand; resolve, gather, accumulate and the bands the gained ones.  Every
+        stage of the chain is made anew per phase and batch, unless one batch is the whole request: then each stage is made once,
+        when the phases that fill it are through, and held until the run ends -- the same bits.  Returns the mosaic."""
         batches = list(batches)
+        options = (options or MosaicOptions()).over(**fields).checked('Mosaic.run')
         if bounds is None:
             for _, load in batches:
                 self.add_bounds(*load())
-        bands = mosaic_bands_checked(bands, options.blend, 'Mosaic.run')
-        support = mosaic_support_checked(support, surface, 'Mosaic.run')
-        gains, gain_limit = mosaic_gains_checked(gains, gain_limit, 'Mosaic.run')
-        gain_solve = mosaic_gain_solve_checked(gain_solve, gains, 'Mosaic.run')
-        reject = mosaic_reject_checked(reject, 'Mosaic.run')
-        self.begin(bounds, blend=options.blend, feather=options.feather, **({} if bands is None else {'bands': bands}),
-                   **({} if reject is None else {'reject': reject}),
-                   **({} if surface is None else {'surface': surface}), **({} if support is None else {'support': support}),
-                   **({} if gains is None else {'gains': gains, 'gain_limit': gain_limit}),
-                   **({} if gain_solve is None else {'gain_solve': gain_solve}))
-        if surface is not None:
-            if support is None:
-                for first, load in batches:
-                    self.add_surface(*load(), first, plain_atomic=plain_atomic)
-            else:
-                for level in range(support):
-                    for first, load in batches:
-                        self.add_support(*load(), first, level, plain_atomic=plain_atomic)
-                self.finish_support()
+        self.begin(bounds, **{f: x for f, x in options.asked().items() if f != 'fill'})   # (the fill is a call of its own, below)
+
+        def over_batches(phase, *args, **kw):
+            for first, load in batches:
+                phase(*load(), first, *args, **kw)
+
+        def hold(stage, make, **kw):   # one batch is the whole request: the stage's copy is made once
             if len(batches) == 1:
                 first, load = batches[0]
-                self._held = self.culled_images(*load(), first, count=True)
+                self._held[stage] = make(*load(), first, **kw)
+
+        self._held = {}
         try:
-            if reject is not None:
-                for first, load in batches:
-                    self.add_reject_claim(*load(), first, plain_atomic=plain_atomic)
-                for first, load in batches:
-                    self.add_reject_sums(*load(), first, plain=plain_atomic)
+            if options.surface is not None:
+                if options.support is None:
+                    over_batches(self.add_surface, plain_atomic=plain_atomic)
+                else:
+                    for level in range(options.support):
+                        over_batches(self.add_support, level, plain_atomic=plain_atomic)
+                    self.finish_support()
+                hold('cull', self.culled_images, count=True)
+            if options.reject is not None:
+                over_batches(self.add_reject_claim, plain_atomic=plain_atomic)
+                over_batches(self.add_reject_sums, plain=plain_atomic)
                 self.finish_reject()
-                if len(batches) == 1:
-                    first, load = batches[0]
-                    self._held_rejected = self.rejected_images(*load(), first, count=True)
-            for first, load in batches:
-                self.splat(*load(), first, plain_atomic=plain_atomic)
-            if gains is not None:
-                for first, load in batches:
-                    self.add_span(*load(), first, plain_atomic=plain_atomic)
-                for r in range(gains):
+                hold('reject', self.rejected_images, count=True)
+            over_batches(self.splat, plain_atomic=plain_atomic)
+            if options.gains is not None:
+                over_batches(self.add_span, plain_atomic=plain_atomic)
+                for r in range(options.gains):
                     self.gain_pass(batches, plain=plain_atomic)
-                    if r == 0 and gain_solve == 'direct':
-                        for first, load in batches:
-                            self.add_gain_slots(*load(), first, plain=plain_atomic)
+                    if r == 0 and options.gain_solve == 'direct':
+                        over_batches(self.add_gain_slots, plain=plain_atomic)
                         self.gain_pairs(plain=plain_atomic)
-                        for first, load in batches:
-                            self.add_gain_diag(*load(), first, plain=plain_atomic)
+                        over_batches(self.add_gain_diag, plain=plain_atomic)
                         self.solve_gains_direct()
                     else:
                         self.solve_gains()
                 self.gain_pass(batches, plain=plain_atomic)
-                if len(batches) == 1:
-                    first, load = batches[0]
-                    self._held_gained = self.gained_images(*load(), first)
-            phases = [(self.resolve, {}), (self.gather, {})]
+                hold('gain', self.gained_images)
+            over_batches(self.resolve)
+            over_batches(self.gather)
             if options.blend is not None:
-                phases.append((self.accumulate, {'plain': plain_atomic}))
-            for phase, kw in phases:
-                for first, load in batches:
-                    phase(*load(), first, **kw)
-            if options.blend is not None:
+                over_batches(self.accumulate, plain=plain_atomic)
                 self.normalize()
-            if bands is not None:
-                for first, load in batches:
-                    self.accumulate_bands(*load(), first, plain=plain_atomic)
+            if options.bands is not None:
+                over_batches(self.accumulate_bands, plain=plain_atomic)
                 self.combine_bands()
         finally:
-            self._held = self._held_gained = self._held_rejected = None
+            self._held = {}
         if options.fill is not None:
             self.fill(options.fill)
         return self
 
 
-def mosaic_of(views: list, Js: list, axes, gsd, bounds=None, batch: int = 32, plain_atomic: bool = False, blend=None,
-              fill=None, feather=None, bands=None, surface=None, support=None, gains=None, gain_limit=None, reject=None,
-              gain_solve=None) -> 'Mosaic':
-    """``Mosaic.run`` over device-resident ``views`` / ``Js`` (ordinal = position in the list), ``batch`` images per call; with
-    ``blend`` (the blend depth H, metres) the accumulate phase and the normalise pass after them (``plain_atomic``: both the
-    splat and the accumulate phase in their plain forms), with ``feather`` (the width F, source pixels; only with ``blend``) the
-    feathered one; with ``bands`` (the count K of detail bands; only with ``blend``) the multi-band blend after them; with ``fill``
-    (the reach R, metres) the hole filling after all of them (``MosaicOptions``); with ``surface`` (the tolerance T, metres) the
-    surface test ahead of the splat (csrc/surface.h), with ``support`` (the count M of views; only with ``surface``) against the
-    view-supported top instead of the plain minimum (csrc/support.h); with ``gains`` (the rounds R) the per-image gain compensation
-    between the splat and the resolve (csrc/gains_mosaic.h), every gain within ``[1 / gain_limit, gain_limit]``; with
-    ``gain_solve='direct'`` (only with ``gains``) the first round's gains come from the direct least-squares solve
-    (csrc/gains_direct.h), with 'rounds' or None from the rounds alone; with ``reject`` (the tolerance T, units of ``J``) the colour
-    consensus across views ahead of the splat (csrc/reject.h)."""
+def mosaic_of(views: list, Js: list, axes, gsd, bounds=None, batch: int = 32, plain_atomic: bool = False, options: MosaicOptions = None,
+              **fields) -> 'Mosaic':
+    """``Mosaic.run`` over device-resident ``views`` / ``Js`` (ordinal = position in the list), ``batch`` images per call;
+    ``options``: a ``MosaicOptions`` (``fields``: fields of the record laid over it -- ``blend=H``, ``fill=R``, ``surface=T``, ...),
+    checked before anything is allocated; ``plain_atomic``: every phase that has one in its plain form."""
     views, Js = list(views), list(Js)
     if not views:
         raise ValueError('mosaic_of: no view')
     if len(views) > MAX_VIEWS:
         raise ValueError(f'mosaic_of: {len(views)} images, at most {MAX_VIEWS}')
-    options = MosaicOptions(blend=blend, feather=feather, fill=fill).checked('mosaic_of')   # before anything is allocated
-    bands = mosaic_bands_checked(bands, options.blend, 'mosaic_of')
-    surface = None if surface is None else mosaic_surface_tol(surface)
-    support = mosaic_support_checked(support, surface, 'mosaic_of')
-    gains, gain_limit = mosaic_gains_checked(gains, gain_limit, 'mosaic_of')
-    gain_solve = mosaic_gain_solve_checked(gain_solve, gains, 'mosaic_of')
-    reject = mosaic_reject_checked(reject, 'mosaic_of')
+    options = (options or MosaicOptions()).over(**fields).checked('mosaic_of')   # before anything is allocated
     batches = [(i, lambda i=i: (views[i:i + batch], Js[i:i + batch])) for i in range(0, len(views), batch)]
-    return Mosaic(axes, gsd, views[0].depth.device).run(batches, options, bounds, plain_atomic, **({} if bands is None else {'bands': bands}),
-                                                        **({} if surface is None else {'surface': surface}),
-                                                        **({} if support is None else {'support': support}),
-                                                        **({} if gains is None else {'gains': gains, 'gain_limit': gain_limit}),
-                                                        **({} if reject is None else {'reject': reject}),
-                                                        **({} if gain_solve is None else {'gain_solve': gain_solve}))
+    return Mosaic(axes, gsd, views[0].depth.device).run(batches, options, bounds, plain_atomic)
 
 
 def device_views_from_scene(scene, device='cuda') -> list[DeviceView]:

@@ -1453,7 +1453,7 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
     ``results_dir / <name>.pt``, key ``J`` -- is dropped onto the plane grid ``axes`` (``mosaic_axes`` unless given) of ``gsd``
     metres per cell (``mosaic_default_gsd`` unless given; printed), and the pixel seen through the least water wins its cell
     (``engine.Mosaic``; csrc/mosaic.h).  Holes stay empty unless ``fill`` is given.  Every file is checked before any image is decoded.
-    ``blend``, ``feather`` and ``fill`` are checked as one ``engine.MosaicOptions``; the images are cut into batches here (at most
+    Every option below is a field of one ``engine.MosaicOptions``, built and checked here once; the images are cut into batches here (at most
     ``MOSAIC_IMAGES_PER_CALL``, and what fits the cache together) and ``engine.Mosaic.run`` takes every phase over every batch.  The
     restored images stay on the device across the four phases within ``consistency_cache_budget`` and are read again per phase
     otherwise: the same bits either way.  The PNGs are those of the rows of ``engine.MOSAIC_OUTPUTS``.  Writes ``mosaic.png``
@@ -1553,44 +1553,15 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
     if stretch is not None:
         stretch = check_stretch(stretch)
     try:
-        options = engine.MosaicOptions(blend=blend, feather=feather, fill=fill).checked()
+        options = engine.MosaicOptions(blend=blend, feather=feather, fill=fill, bands=bands, surface=surface, support=support, gains=gains,
+                                       gain_limit=gain_limit, gain_solve=gain_solve, reject=reject).checked('mosaic')
     except ValueError as e:
-        if e.field == 'feather' and blend is None:
-            raise SystemExit('--mosaic-feather: only with --mosaic-blend H')
+        if e.needs is not None:   # an option without the one it goes with: in the command line's words
+            raise SystemExit(f'{_MOSAIC_FLAG[e.field]}: only with {_MOSAIC_FLAG[e.needs]} {engine.MOSAIC_VALUES[e.needs][5]}')
         raise _mosaic_refused(e)
-    blend, feather, fill = options.blend, options.feather, options.fill
-    try:
-        bands = None if bands is None else engine.mosaic_band_count(bands)
-    except ValueError as e:
-        raise _mosaic_refused(e)
-    if bands is not None and blend is None:
-        raise SystemExit('--mosaic-bands: only with --mosaic-blend H')
-    try:
-        surface = None if surface is None else engine.mosaic_surface_tol(surface)
-    except ValueError as e:
-        raise _mosaic_refused(e)
-    try:
-        support = None if support is None else engine.mosaic_support_views(support)
-    except ValueError as e:
-        raise _mosaic_refused(e)
-    if support is not None and surface is None:
-        raise SystemExit('--mosaic-support: only with --mosaic-surface T')
-    if gain_limit is not None and gains is None:
-        raise SystemExit('--mosaic-gain-limit: only with --mosaic-gains R')
-    try:
-        gains, gain_limit = engine.mosaic_gains_checked(gains, gain_limit, 'mosaic')
-    except ValueError as e:
-        raise _mosaic_refused(e)
-    if gain_solve is not None and gains is None:
-        raise SystemExit('--mosaic-gain-solve: only with --mosaic-gains R')
-    try:
-        gain_solve = engine.mosaic_gain_solve_checked(gain_solve, gains, 'mosaic')
-    except ValueError as e:
-        raise _mosaic_refused(e)
-    try:
-        reject = engine.mosaic_reject_checked(reject, 'mosaic')
-    except ValueError as e:
-        raise _mosaic_refused(e)
+    blend, feather, fill, bands, surface, support = (options.blend, options.feather, options.fill, options.bands, options.surface,
+                                                     options.support)
+    gains, gain_limit, gain_solve, reject = options.gains, options.gain_limit, options.gain_solve, options.reject
     results_dir, output_dir = Path(results_dir), Path(output_dir)
     for image in images:   # before anything is decoded
         path = _consistency_file(results_dir, image)
@@ -1621,13 +1592,7 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
             del depths
             print(f'--mosaic: ground sample distance {float(gsd):.6g} m (twice the median pixel footprint; --mosaic-gsd sets it).')
         try:
-            m = engine.Mosaic(axes, gsd, device).run([(first, lambda batch=batch: resident(batch)) for first, batch in batches], options,
-                                                     **({} if bands is None else {'bands': bands}),
-                                                     **({} if surface is None else {'surface': surface}),
-                                                     **({} if support is None else {'support': support}),
-                                                     **({} if gains is None else {'gains': gains, 'gain_limit': gain_limit}),
-                                                     **({} if reject is None else {'reject': reject}),
-                                                     **({} if gain_solve is None else {'gain_solve': gain_solve}))
+            m = engine.Mosaic(axes, gsd, device).run([(first, lambda batch=batch: resident(batch)) for first, batch in batches], options)
         except ValueError as e:
             # Three refusals of the run belong to a flag: begin's of the grid (--mosaic), normalize's of a cell's sample count
             # (--mosaic-blend) and the gain passes' of a cell's sample count or an image's size (--mosaic-gains).  The options were checked above, so begin and fill have nothing left to refuse in them; every other
@@ -1637,7 +1602,7 @@ def mosaic(images: list, colmap_model: sfm.COLMAPModel, results_dir: Path, outpu
             raise _mosaic_refused(e, ('grid', 'blend', 'gains', 'gain_solve', 'reject'))
         out = m.result()
         pictures = [(png, _MOSAIC_PNG[how](out[key], stretch))
-                    for key, (_, _, _, _, png, how) in {**engine.MOSAIC_OUTPUTS, **engine.MOSAIC_REJECT_OUTPUTS}.items()
+                    for key, (_, _, _, _, png, how) in engine.MOSAIC_OUTPUTS.items()
                     if png is not None and key in out]
         out = {k: v.cpu() if torch.is_tensor(v) else v for k, v in out.items()}
         surface_counts = None if surface is None else [int(x) for x in m.surface_counts.cpu()]
@@ -1767,6 +1732,7 @@ _ONLY_WITH = [   # (flag, the flag it needs, that one's value), in the order the
     ('--mosaic-feather', '--mosaic-blend', 'H'), ('--mosaic-bands', '--mosaic-blend', 'H'),
     ('--mosaic-gain-limit', '--mosaic-gains', 'R'), ('--mosaic-gains', '--mosaic', 'DIR'),
     ('--mosaic-support', '--mosaic-surface', 'T'), ('--mosaic-surface', '--mosaic', 'DIR'),
+    ('--mosaic-gain-solve', '--mosaic-gains', 'R'), ('--mosaic-reject', '--mosaic', 'DIR'),
 ]
 
 
@@ -1775,20 +1741,6 @@ def _refuse_lone_flags(args) -> None:
     for flag, needs, value in _ONLY_WITH:
         if getattr(args, flag[2:].replace('-', '_'), None) is not None and getattr(args, needs[2:].replace('-', '_'), None) is None:
             raise SystemExit(f'{flag}: only with {needs} {value}')
-
-
-def _refuse_lone_gain_solve(args) -> None:
-    """--mosaic-gain-solve without --mosaic-gains, refused before any file is opened (beside ``_ONLY_WITH``, whose rows are what
-    they were: looked at after them)."""
-    if getattr(args, 'mosaic_gain_solve', None) is not None and getattr(args, 'mosaic_gains', None) is None:
-        raise SystemExit(f'{_MOSAIC_FLAG["gain_solve"]}: only with --mosaic-gains R')
-
-
-def _refuse_lone_reject(args) -> None:
-    """--mosaic-reject without --mosaic, refused before any file is opened (beside ``_ONLY_WITH``, as ``_refuse_lone_gain_solve``:
-    looked at after the table's rows)."""
-    if getattr(args, 'mosaic_reject', None) is not None and getattr(args, 'mosaic', None) is None:
-        raise SystemExit(f'{_MOSAIC_FLAG["reject"]}: only with --mosaic DIR')
 
 
 def _refuse_mode_flags(args, mode: str) -> None:
@@ -1806,38 +1758,18 @@ def _refuse_mosaic_values(args, world: int = 1) -> None:
     if gsd is not None and not (np.isfinite(gsd) and gsd > 0):
         raise SystemExit(f'--mosaic-gsd: G must be a finite size > 0 in metres, not {gsd}')
     from . import engine
-    for field, letter, kind, last in (('blend', 'H', 'a finite depth', '{}'), ('fill', 'R', 'a finite reach', '{}'), ('feather', 'F', 'an integer', '{:g}')):
+    for field, (_, span, integral, unit, _, letter, words) in engine.MOSAIC_VALUES.items():
         value = getattr(args, 'mosaic_' + field, None)
-        _, (lo, hi), integral, unit, _ = engine.MOSAIC_VALUES[field]
-        if value is not None and not (np.isfinite(value) and lo <= value <= hi and (not integral or value == int(value))):
-            raise SystemExit(f'{_MOSAIC_FLAG[field]}: {letter} must be {kind} within [{lo:g}, {hi:g}] {unit}, not {last.format(value)}')
-    bands = getattr(args, 'mosaic_bands', None)
-    lo, hi = engine.MOSAIC_BANDS_RANGE
-    if bands is not None and not (np.isfinite(bands) and lo <= bands <= hi and bands == int(bands)):
-        raise SystemExit(f'{_MOSAIC_FLAG["bands"]}: K must be an integer within [{lo:g}, {hi:g}] bands, not {bands:g}')
-    tol = getattr(args, 'mosaic_surface', None)
-    lo, hi = engine.MOSAIC_SURFACE_RANGE
-    if tol is not None and not (np.isfinite(tol) and lo <= tol <= hi):
-        raise SystemExit(f'{_MOSAIC_FLAG["surface"]}: T must be a finite tolerance within [{lo:g}, {hi:g}] metres, not {tol}')
-    views = getattr(args, 'mosaic_support', None)
-    lo, hi = engine.MOSAIC_SUPPORT_RANGE
-    if views is not None and not (np.isfinite(views) and lo <= views <= hi and views == int(views)):
-        raise SystemExit(f'{_MOSAIC_FLAG["support"]}: M must be an integer within [{lo:g}, {hi:g}] views, not {views:g}')
-    rounds = getattr(args, 'mosaic_gains', None)
-    lo, hi = engine.MOSAIC_GAIN_ROUNDS_RANGE
-    if rounds is not None and not (np.isfinite(rounds) and lo <= rounds <= hi and rounds == int(rounds)):
-        raise SystemExit(f'{_MOSAIC_FLAG["gains"]}: R must be an integer within [{lo:g}, {hi:g}] rounds, not {rounds:g}')
-    limit = getattr(args, 'mosaic_gain_limit', None)
-    lo, hi = engine.MOSAIC_GAIN_LIMIT_RANGE
-    if limit is not None and not (np.isfinite(limit) and lo <= limit <= hi):
-        raise SystemExit(f'{_MOSAIC_FLAG["gain_limit"]}: L must be a finite limit within [{lo:g}, {hi:g}] times, not {limit}')
-    solve = getattr(args, 'mosaic_gain_solve', None)
-    if solve is not None and solve not in engine.MOSAIC_GAIN_SOLVES:
-        raise SystemExit(f'{_MOSAIC_FLAG["gain_solve"]}: S must be {" or ".join(engine.MOSAIC_GAIN_SOLVES)}, not {solve}')
-    tol = getattr(args, 'mosaic_reject', None)
-    lo, hi = engine.MOSAIC_REJECT_RANGE
-    if tol is not None and not (np.isfinite(tol) and lo <= tol <= hi):
-        raise SystemExit(f'{_MOSAIC_FLAG["reject"]}: T must be a finite tolerance within [{lo:g}, {hi:g}] colour units, not {tol}')
+        if value is None:
+            continue
+        if integral is None:   # a choice
+            if value not in span:
+                raise SystemExit(f'{_MOSAIC_FLAG[field]}: {letter} must be {" or ".join(span)}, not {value}')
+            continue
+        lo, hi = span
+        if not (np.isfinite(value) and lo <= value <= hi and (not integral or value == int(value))):
+            raise SystemExit(f'{_MOSAIC_FLAG[field]}: {letter} must be {words} within [{lo:g}, {hi:g}] {unit}, not '
+                             + (f'{value:g}' if integral else f'{value}'))
     if world > 1:
         raise SystemExit(f'--mosaic: a world size of {world} is not supported yet: the four phases are separate entries of the library '
                          f'so that ranks can all-reduce bounds, keys and pixel words between them, but that all-reduce is not built; '
@@ -1866,8 +1798,6 @@ def parse_args(args: argparse.Namespace):
     check = getattr(args, 'check_consistency', None)
     mosaic_dir = getattr(args, 'mosaic', None)
     _refuse_lone_flags(args)
-    _refuse_lone_gain_solve(args)
-    _refuse_lone_reject(args)
     if mosaic_dir is not None:
         _refuse_mode_flags(args, '--mosaic')
         _refuse_mosaic_values(args, world)
@@ -1950,11 +1880,7 @@ def parse_args(args: argparse.Namespace):
     try:
         if mosaic_dir is not None:
             mosaic(images, colmap_model, mosaic_dir, args.output_dir, gsd=getattr(args, 'mosaic_gsd', None), stretch=stretch, device=device,
-                   blend=getattr(args, 'mosaic_blend', None), fill=getattr(args, 'mosaic_fill', None),
-                   feather=getattr(args, 'mosaic_feather', None), bands=getattr(args, 'mosaic_bands', None),
-                   surface=getattr(args, 'mosaic_surface', None), support=getattr(args, 'mosaic_support', None),
-                   gains=getattr(args, 'mosaic_gains', None), gain_limit=getattr(args, 'mosaic_gain_limit', None),
-                   reject=getattr(args, 'mosaic_reject', None), gain_solve=getattr(args, 'mosaic_gain_solve', None))
+                   **{field: getattr(args, 'mosaic_' + field, None) for field in _MOSAIC_FLAG if field != 'grid'})
         elif check is not None:
             if world > 1:   # the targets' records are gathered on rank 0
                 sdist.init_process_group()

@@ -102,7 +102,7 @@ def test_every_tensor_equals_the_restatement(key):
     base = ref.mosaic(hv, want['Js'], axes, gsd, bounds=want['bounds'])
     for k in BEST:
         assert same_bits(run.result()[k], base[k]), (key, k)
-    assert run.reject_slot_ord is None and run._held_rejected is None
+    assert run.reject_slot_ord is None and run._held == {}      # nothing of the run is held after it
 
 
 def test_the_consensus_sees_the_surface_culled_images():
@@ -359,7 +359,7 @@ def test_the_entries_check_their_arguments_before_any_launch():
             ('sucre_mosaic_reject_sums', (m.reject_slot_ord, m.reject_slot_sum, 4), 'unknown mosaic flags')):
         with pytest.raises(_lib.SucreError, match=text):
             m._walk(entry, images, 0, _lib.C.byref(m.grid), *rest)
-    o = m._reject_out
+    o = m._out
     buf = torch.empty(2 * 96 * 64 * 3 + 1024, dtype=torch.float32, device=DEV)
     counts = torch.zeros((2, 16), dtype=torch.int64, device=DEV)
     cull = lambda *rest: m._walk('sucre_mosaic_reject_cull', images, *rest)

@@ -174,11 +174,13 @@ def test_the_functions_refuse_bands_without_a_blend_and_a_bad_count(tmp_path, mo
         assert str(e.value.code) == text and not (tmp_path / 'out').exists()
 
 
-def test_the_options_record_and_its_table_are_what_they_were():
-    assert [f.name for f in dataclasses.fields(engine.MosaicOptions)] == ['blend', 'feather', 'fill']
-    assert list(engine.MOSAIC_VALUES) == ['blend', 'fill', 'feather']
-    assert engine.MOSAIC_VALUES['feather'] == ('feather width F', (1, 1024), True, 'source pixels', int)
-    assert 'bands' not in engine.MOSAIC_VALUES and not hasattr(engine.MosaicOptions(), 'bands')
+def test_the_options_record_and_its_table_hold_the_bands():
+    assert [f.name for f in dataclasses.fields(engine.MosaicOptions)][:4] == ['blend', 'feather', 'fill', 'bands']
+    assert list(engine.MOSAIC_VALUES)[:4] == ['blend', 'fill', 'feather', 'bands']
+    assert engine.MOSAIC_VALUES['feather'] == ('feather width F', (1, 1024), True, 'source pixels', int, 'F', 'an integer')
+    assert engine.MOSAIC_VALUES['bands'] == ('band count K', (1, 6), True, 'bands', int, 'K', 'an integer')
+    assert engine.MOSAIC_VALUES['bands'][1] is engine.MOSAIC_BANDS_RANGE and engine.MosaicOptions().bands is None
+    assert ('bands', 'blend') in [row[:2] for row in engine.MOSAIC_NEEDS]
     assert list(engine.MOSAIC_OUTPUTS)[:9] == ['J', 'raw', 'source', 'pixel', 'range', 'J_blend', 'raw_blend', 'weight', 'samples']
     group, tail, dtype, empty, png, how = engine.MOSAIC_OUTPUTS['J_multiband']
     assert (group, tail, dtype, png, how) == ('bands', (3,), torch.float32, 'mosaic_multiband.png', 'stretch') and np.isnan(empty)

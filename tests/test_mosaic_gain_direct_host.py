@@ -235,24 +235,34 @@ def test_the_overflow_rule_counts_different_images():
 def test_the_solve_is_checked_like_the_other_values():
     assert engine.MOSAIC_GAIN_SOLVES == ('rounds', 'direct') and engine.MOSAIC_GAIN_PRIOR == 2.0 ** -20
     assert _lib.MOSAIC_GAIN_CELL_IMAGES == 8 == dref.SLOTS
-    assert engine.mosaic_gain_solve_checked(None, None, 'x') is None and engine.mosaic_gain_solve_checked(None, 3, 'x') is None
-    assert engine.mosaic_gain_solve_checked('rounds', 3, 'x') is None and engine.mosaic_gain_solve_checked('direct', 3, 'x') == 'direct'
+    def checked(gain_solve, gains, who):
+        return engine.MosaicOptions(gain_solve=gain_solve, gains=gains).checked(who).gain_solve
+    assert checked(None, None, 'x') is None and checked(None, 3, 'x') is None
+    assert checked('rounds', 3, 'x') is None and checked('direct', 3, 'x') == 'direct'
     for bad in ('Direct', 'exact', '', 1, True, 2.5):
         with pytest.raises(ValueError, match='mosaic gain solve must be one of rounds or direct') as e:
-            engine.mosaic_gain_solve_checked(bad, 3, 'x')
+            checked(bad, 3, 'x')
         assert e.value.field == 'gain_solve'
     for solve in ('rounds', 'direct'):
         with pytest.raises(ValueError, match=r'who: the solve finds the gains of the first round.*\(gains=R\)') as e:
-            engine.mosaic_gain_solve_checked(solve, None, 'who')
+            checked(solve, None, 'who')
         assert e.value.field == 'gain_solve'
     view = SimpleNamespace(depth=SimpleNamespace(device=torch.device('cpu')))
     for kw, who in ((dict(gains=2, gain_solve='exact'), 'must be one of'), (dict(gain_solve='direct'), 'mosaic_of: the solve finds')):
         with pytest.raises(ValueError, match=who) as e:       # before a Mosaic is made
             engine.mosaic_of([view], [None], torch.eye(3), 0.1, **kw)
         assert e.value.field == 'gain_solve'
-    for f in (engine.mosaic_of, engine.Mosaic.run, engine.Mosaic.begin, sucre.mosaic):      # a new keyword, placed last
-        assert list(inspect.signature(f).parameters)[-1] == 'gain_solve'
-        assert inspect.signature(f).parameters['gain_solve'].default is None
+    assert list(inspect.signature(sucre.mosaic).parameters)[-1] == 'gain_solve'      # a new keyword, placed last
+    assert inspect.signature(sucre.mosaic).parameters['gain_solve'].default is None
+    for f in (engine.mosaic_of, engine.Mosaic.run, engine.Mosaic.begin):      # these take it as a field of the record, and no other name
+        last = list(inspect.signature(f).parameters.values())[-1]
+        assert last.kind is inspect.Parameter.VAR_KEYWORD and 'options' in inspect.signature(f).parameters
+    assert engine.MosaicOptions().gain_solve is None and engine.MosaicOptions().over(gain_solve='direct').gain_solve == 'direct'
+    with pytest.raises(TypeError):
+        engine.MosaicOptions().over(gain_solver='direct')
+    with pytest.raises(TypeError):
+        engine.mosaic_of([view], [None], torch.eye(3), 0.1, gain_solver='direct')
+    assert engine.MOSAIC_VALUES['gain_solve'] == ('gain solve', ('rounds', 'direct'), None, None, str, 'S', None)
     for name in ('sucre_mosaic_gain_slots', 'sucre_mosaic_gain_pairs', 'sucre_mosaic_gain_diag'):
         assert name in _lib.SIGNATURES
     for name in ('add_gain_slots', 'gain_pairs', 'add_gain_diag', 'solve_gains_direct'):

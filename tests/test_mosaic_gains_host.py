@@ -98,13 +98,17 @@ def test_the_rounds_and_the_limit_are_checked_like_the_other_values():
         with pytest.raises(ValueError, match=r'mosaic gain limit L must be finite and within \[1, 16\] times') as e:
             engine.mosaic_gain_limit(bad)
         assert e.value.field == 'gain_limit'
-    assert engine.mosaic_gains_checked(None, None, 'x') == (None, None)
-    assert engine.mosaic_gains_checked(3, None, 'x') == (3, 2.0) and engine.mosaic_gains_checked(3.0, 4, 'x') == (3, 4.0)
+    def checked(gains, gain_limit, who):
+        o = engine.MosaicOptions(gains=gains, gain_limit=gain_limit).checked(who)
+        assert (o.gains is None or type(o.gains) is int) and (o.gain_limit is None or type(o.gain_limit) is float)
+        return o.gains, o.gain_limit
+    assert checked(None, None, 'x') == (None, None)
+    assert checked(3, None, 'x') == (3, 2.0) and checked(3.0, 4, 'x') == (3, 4.0)
     with pytest.raises(ValueError, match=r'who: the limit clamps the gains .* \(gains=R\)') as e:
-        engine.mosaic_gains_checked(None, 2.0, 'who')
+        checked(None, 2.0, 'who')
     assert e.value.field == 'gain_limit'
     with pytest.raises(ValueError) as e:          # the limit's value before the missing rounds
-        engine.mosaic_gains_checked(None, 17, 'who')
+        checked(None, 17, 'who')
     assert e.value.field == 'gain_limit' and 'within' in str(e.value)
     view = SimpleNamespace(depth=SimpleNamespace(device=torch.device('cpu')))
     with pytest.raises(ValueError, match='gain rounds R') as e:       # before a Mosaic is made
@@ -116,20 +120,24 @@ def test_the_rounds_and_the_limit_are_checked_like_the_other_values():
 
 
 def test_the_pinned_tables_are_extended_and_not_reordered():
-    assert [f.name for f in dataclasses.fields(engine.MosaicOptions)] == ['blend', 'feather', 'fill']
-    assert list(engine.MOSAIC_VALUES) == ['blend', 'fill', 'feather']
+    assert [f.name for f in dataclasses.fields(engine.MosaicOptions)][:8] == ['blend', 'feather', 'fill', 'bands', 'surface', 'support', 'gains',
+                                                                              'gain_limit']
+    assert list(engine.MOSAIC_VALUES)[:8] == ['blend', 'fill', 'feather', 'bands', 'surface', 'support', 'gains', 'gain_limit']
+    assert engine.MOSAIC_VALUES['gains'] == ('gain rounds R', (1, 64), True, 'rounds', int, 'R', 'an integer')
+    assert engine.MOSAIC_VALUES['gain_limit'] == ('gain limit L', (1.0, 16.0), False, 'times', float, 'L', 'a finite limit')
+    assert engine.MOSAIC_VALUES['gains'][1] is engine.MOSAIC_GAIN_ROUNDS_RANGE and engine.MOSAIC_VALUES['gain_limit'][1] is engine.MOSAIC_GAIN_LIMIT_RANGE
     rows = list(engine.MOSAIC_OUTPUTS)
     assert rows[:13] == ['J', 'raw', 'source', 'pixel', 'range', 'J_blend', 'raw_blend', 'weight', 'samples', 'J_multiband', 'surface',
                          'culled', 'fill_level']
-    assert rows[13:] == ['J_filled', 'raw_filled', 'J_blend_filled', 'raw_blend_filled', 'J_multiband_filled', 'support', 'surface_source',
-                         'culled_above', 'surface_top']
+    assert rows[13:22] == ['J_filled', 'raw_filled', 'J_blend_filled', 'raw_blend_filled', 'J_multiband_filled', 'support', 'surface_source',
+                           'culled_above', 'surface_top']
     assert not any('gain' in k for k in rows)
     assert sucre._MOSAIC_FLAG['gains'] == '--mosaic-gains' and sucre._MOSAIC_FLAG['gain_limit'] == '--mosaic-gain-limit'
     assert sucre._ONLY_WITH[:5] == [('--mosaic-gsd', '--mosaic', 'DIR'), ('--mosaic-blend', '--mosaic', 'DIR'), ('--mosaic-fill', '--mosaic', 'DIR'),
                                     ('--mosaic-feather', '--mosaic-blend', 'H'), ('--mosaic-bands', '--mosaic-blend', 'H')]
     assert sucre._ONLY_WITH[5:7] == [('--mosaic-gain-limit', '--mosaic-gains', 'R'), ('--mosaic-gains', '--mosaic', 'DIR')]
-    assert sucre._ONLY_WITH[-2:] == [('--mosaic-support', '--mosaic-surface', 'T'), ('--mosaic-surface', '--mosaic', 'DIR')]
-    assert len(sucre._ONLY_WITH) == 9
+    assert sucre._ONLY_WITH[7:9] == [('--mosaic-support', '--mosaic-surface', 'T'), ('--mosaic-surface', '--mosaic', 'DIR')]
+    assert sucre._ONLY_WITH[9:] == [('--mosaic-gain-solve', '--mosaic-gains', 'R'), ('--mosaic-reject', '--mosaic', 'DIR')]
     assert _lib.MOSAIC_GAIN_WORDS == 10 and _lib.MOSAIC_GAIN_ROW_WORDS * 8 == 128
     for name in ('sucre_mosaic_gain_span', 'sucre_mosaic_gain_apply', 'sucre_mosaic_gain_sums'):
         assert name in _lib.SIGNATURES

@@ -23,13 +23,16 @@ FREE = 0xffffffff
 def test_the_tolerance_is_checked_like_the_other_values():
     assert engine.MOSAIC_REJECT_RANGE == (1e-6, 1e6)
     assert _lib.MOSAIC_REJECT_CELL_IMAGES == 8 == rref.SLOTS and _lib.MOSAIC_REJECT_MIN_VIEWS == 3 == rref.MIN_VIEWS
-    assert engine.mosaic_reject_checked(None, 'x') is None
+    def checked(reject, who):
+        return engine.MosaicOptions(reject=reject).checked(who).reject
+    assert checked(None, 'x') is None
     for good in (1e-6, 0.15, 1, 1e6, np.float32(1e-6), '0.5'):
-        T = engine.mosaic_reject_checked(good, 'x')
+        T = checked(good, 'x')
+        assert engine.mosaic_reject_tol(good) == T and type(engine.mosaic_reject_tol(good)) is np.float32
         assert type(T) is np.float32 and T == np.float32(float(good))
     for bad in (0, -0.1, 5e-7, 1.0000001e6, float('nan'), float('inf'), 'T', ()):
         with pytest.raises(ValueError, match=r'mosaic reject tolerance T must be finite and within \[1e-06, 1e\+06\] colour units') as e:
-            engine.mosaic_reject_checked(bad, 'x')
+            checked(bad, 'x')
         assert e.value.field == 'reject'
     view = SimpleNamespace(depth=SimpleNamespace(device=torch.device('cpu')))
     with pytest.raises(ValueError, match='reject tolerance') as e:       # before a Mosaic is made
@@ -38,22 +41,27 @@ def test_the_tolerance_is_checked_like_the_other_values():
 
 
 def test_the_keyword_stands_ahead_of_the_last_one_and_the_tables_keep_their_rows():
-    for f in (engine.mosaic_of, engine.Mosaic.run, engine.Mosaic.begin, sucre.mosaic):
-        names = list(inspect.signature(f).parameters)
-        assert names[-2:] == ['reject', 'gain_solve'], f
-        assert inspect.signature(f).parameters['reject'].default is None
+    names = list(inspect.signature(sucre.mosaic).parameters)
+    assert names[-2:] == ['reject', 'gain_solve'] and inspect.signature(sucre.mosaic).parameters['reject'].default is None
+    for f in (engine.mosaic_of, engine.Mosaic.run, engine.Mosaic.begin):      # these take it as a field of the record
+        assert list(inspect.signature(f).parameters.values())[-1].kind is inspect.Parameter.VAR_KEYWORD, f
+    assert engine.MosaicOptions().reject is None and engine.MosaicOptions().over(reject=0.5).reject == 0.5
     for name in ('sucre_mosaic_reject_claim', 'sucre_mosaic_reject_sums', 'sucre_mosaic_reject_consensus', 'sucre_mosaic_reject_cull'):
         assert name in _lib.SIGNATURES
     for name in ('add_reject_claim', 'add_reject_sums', 'finish_reject', 'rejected_images'):
         assert callable(getattr(engine.Mosaic, name))
-    assert not any('reject' in k for k in engine.MOSAIC_OUTPUTS) and list(engine.MOSAIC_OUTPUTS)[-4:] == \
-        ['support', 'surface_source', 'culled_above', 'surface_top']
+    assert list(engine.MOSAIC_OUTPUTS)[-9:-5] == ['support', 'surface_source', 'culled_above', 'surface_top']
+    assert list(engine.MOSAIC_OUTPUTS)[-5:] == list(engine.MOSAIC_REJECT_OUTPUTS)      # the rows of the one table, its last group
+    assert [k for k, row in engine.MOSAIC_OUTPUTS.items() if row[0] == 'reject'] == list(engine.MOSAIC_REJECT_OUTPUTS)
     assert list(engine.MOSAIC_REJECT_OUTPUTS) == ['rejected', 'reject_ref', 'reject_source', 'reject_views', 'reject_overflow']
     assert all(len(row) == 6 and row[0] == 'reject' for row in engine.MOSAIC_REJECT_OUTPUTS.values())
     assert engine.MOSAIC_REJECT_OUTPUTS['rejected'][4:] == ('mosaic_rejected.png', 'count')
-    assert not set(engine.MOSAIC_REJECT_OUTPUTS) & set(engine.MOSAIC_OUTPUTS)
-    assert [f.name for f in engine.MosaicOptions.__dataclass_fields__.values()] == ['blend', 'feather', 'fill']
-    assert 'reject' not in engine.MOSAIC_VALUES and len(sucre._ONLY_WITH) == 9
+    assert all(engine.MOSAIC_OUTPUTS[k] is row for k, row in engine.MOSAIC_REJECT_OUTPUTS.items())
+    assert [f.name for f in engine.MosaicOptions.__dataclass_fields__.values()] == ['blend', 'feather', 'fill', 'bands', 'surface', 'support', 'gains', 'gain_limit', 'gain_solve', 'reject']
+    assert list(engine.MOSAIC_VALUES) == ['blend', 'fill', 'feather', 'bands', 'surface', 'support', 'gains', 'gain_limit', 'gain_solve', 'reject']
+    assert engine.MOSAIC_VALUES['reject'] == ('reject tolerance T', (1e-6, 1e6), False, 'colour units', np.float32, 'T', 'a finite tolerance')
+    assert engine.MOSAIC_VALUES['reject'][1] is engine.MOSAIC_REJECT_RANGE
+    assert len(sucre._ONLY_WITH) == 11 and sucre._ONLY_WITH[-1] == ('--mosaic-reject', '--mosaic', 'DIR')
     assert sucre._MOSAIC_FLAG['reject'] == '--mosaic-reject'
 
 

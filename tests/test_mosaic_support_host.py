@@ -220,24 +220,31 @@ def test_the_view_count_is_checked_like_the_other_values():
     with pytest.raises(ValueError, match=r'mosaic_of: the support decides which top .* \(surface=T\)') as e:
         engine.mosaic_of([view], [None], torch.eye(3), 0.1, support=2)
     assert e.value.field == 'support'
-    assert engine.mosaic_support_checked(None, None, 'x') is None and engine.mosaic_support_checked(2.0, np.float32(0.1), 'x') == 2
+    assert engine.MosaicOptions().checked('x').support is None
+    both = engine.MosaicOptions(support=2.0, surface=np.float32(0.1)).checked('x')
+    assert both.support == 2 and type(both.support) is int
+    with pytest.raises(ValueError, match=r'who: the support decides which top .* \(surface=T\)') as e:
+        engine.MosaicOptions(support=2).checked('who')
+    assert e.value.field == 'support'
 
 
 def test_the_pinned_tables_are_extended_and_not_reordered():
-    assert [f.name for f in dataclasses.fields(engine.MosaicOptions)] == ['blend', 'feather', 'fill']
-    assert list(engine.MOSAIC_VALUES) == ['blend', 'fill', 'feather'] and 'support' not in engine.MOSAIC_VALUES
+    assert [f.name for f in dataclasses.fields(engine.MosaicOptions)][:6] == ['blend', 'feather', 'fill', 'bands', 'surface', 'support']
+    assert list(engine.MOSAIC_VALUES)[:6] == ['blend', 'fill', 'feather', 'bands', 'surface', 'support']
+    assert engine.MOSAIC_VALUES['support'] == ('supporting views M', (1, 4), True, 'views', int, 'M', 'an integer')
+    assert engine.MOSAIC_VALUES['support'][1] is engine.MOSAIC_SUPPORT_RANGE
     rows = list(engine.MOSAIC_OUTPUTS)
     assert rows[:13] == ['J', 'raw', 'source', 'pixel', 'range', 'J_blend', 'raw_blend', 'weight', 'samples', 'J_multiband', 'surface',
                          'culled', 'fill_level']
     assert rows[13:18] == ['J_filled', 'raw_filled', 'J_blend_filled', 'raw_blend_filled', 'J_multiband_filled']
-    assert rows[18:] == ['support', 'surface_source', 'culled_above', 'surface_top']
+    assert rows[18:22] == ['support', 'surface_source', 'culled_above', 'surface_top']
     nan = engine.MOSAIC_OUTPUTS['range'][3]
     assert engine.MOSAIC_OUTPUTS['support'] == ('support', (), torch.int32, 0, None, None)
     assert engine.MOSAIC_OUTPUTS['surface_source'] == ('support', (), torch.int32, -1, None, None)
     assert engine.MOSAIC_OUTPUTS['culled_above'] == ('support', (), torch.int32, 0, 'mosaic_culled_above.png', 'count')
     assert engine.MOSAIC_OUTPUTS['surface_top'] == ('support', (), torch.float32, nan, None, None) and nan != nan
     assert sucre._MOSAIC_FLAG['support'] == '--mosaic-support'
-    assert sucre._ONLY_WITH[-2:] == [('--mosaic-support', '--mosaic-surface', 'T'), ('--mosaic-surface', '--mosaic', 'DIR')]
+    assert sucre._ONLY_WITH[7:9] == [('--mosaic-support', '--mosaic-surface', 'T'), ('--mosaic-surface', '--mosaic', 'DIR')]
     assert sucre._ONLY_WITH[:5] == [('--mosaic-gsd', '--mosaic', 'DIR'), ('--mosaic-blend', '--mosaic', 'DIR'), ('--mosaic-fill', '--mosaic', 'DIR'),
                                     ('--mosaic-feather', '--mosaic-blend', 'H'), ('--mosaic-bands', '--mosaic-blend', 'H')]
 
@@ -289,7 +296,7 @@ class Recorder(engine.Mosaic):
     log, begun = [], []
 
     def __init__(self, axes, gsd, device):
-        self._held = None
+        self._held = {}
 
     def add_bounds(self, views, Js):
         self.log.append(('add_bounds', None, len(views)))
@@ -314,7 +321,7 @@ class Recorder(engine.Mosaic):
 
 for _name in ('splat', 'resolve', 'gather'):
     def _phase(self, views, Js, first_ordinal, _name=_name, **kw):
-        self.log.append((_name, first_ordinal, len(views), self._held))
+        self.log.append((_name, first_ordinal, len(views), self._held.get('cull')))
     setattr(Recorder, _name, _phase)
 
 
@@ -336,7 +343,7 @@ def test_run_takes_every_level_over_every_batch_before_the_next(recorder):
     phase = lambda name: [(name, 0, 2, None), (name, 2, 1, None)]
     assert recorder.log == [('add_bounds', None, 2), ('add_bounds', None, 1), ('begin', None, None)] + levels \
         + [('finish_support', None, None)] + phase('splat') + phase('resolve') + phase('gather')
-    assert m._held is None
+    assert m._held == {}
 
 
 def test_a_single_batch_is_culled_once_after_the_top_is_formed(recorder):

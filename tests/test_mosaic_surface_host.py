@@ -144,8 +144,10 @@ def test_the_tolerance_is_checked_like_the_other_values():
 
 
 def test_the_pinned_tables_are_what_they_were():
-    assert [f.name for f in dataclasses.fields(engine.MosaicOptions)] == ['blend', 'feather', 'fill']
-    assert list(engine.MOSAIC_VALUES) == ['blend', 'fill', 'feather'] and 'surface' not in engine.MOSAIC_VALUES
+    assert [f.name for f in dataclasses.fields(engine.MosaicOptions)][:5] == ['blend', 'feather', 'fill', 'bands', 'surface']
+    assert list(engine.MOSAIC_VALUES)[:5] == ['blend', 'fill', 'feather', 'bands', 'surface']
+    assert engine.MOSAIC_VALUES['surface'] == ('surface tolerance T', (1e-6, 1e6), False, 'metres', np.float32, 'T', 'a finite tolerance')
+    assert engine.MOSAIC_VALUES['surface'][1] is engine.MOSAIC_SURFACE_RANGE
     rows = list(engine.MOSAIC_OUTPUTS)
     assert rows[:10] == ['J', 'raw', 'source', 'pixel', 'range', 'J_blend', 'raw_blend', 'weight', 'samples', 'J_multiband']
     assert rows[10:12] == ['surface', 'culled'] and rows[12] == 'fill_level'
@@ -153,7 +155,7 @@ def test_the_pinned_tables_are_what_they_were():
     assert engine.MOSAIC_OUTPUTS['surface'][3] != engine.MOSAIC_OUTPUTS['surface'][3]      # NaN
     assert engine.MOSAIC_OUTPUTS['culled'] == ('surface', (), torch.int32, 0, 'mosaic_culled.png', 'count')
     assert set(sucre._MOSAIC_PNG) >= {how for *_, how in engine.MOSAIC_OUTPUTS.values() if how}
-    assert sucre._MOSAIC_FLAG['surface'] == '--mosaic-surface' and sucre._ONLY_WITH[-1] == ('--mosaic-surface', '--mosaic', 'DIR')
+    assert sucre._MOSAIC_FLAG['surface'] == '--mosaic-surface' and sucre._ONLY_WITH[8] == ('--mosaic-surface', '--mosaic', 'DIR')
 
 
 BASE = ['--image-dir', 'i', '--depth-dir', 'd', '--model-dir', 'm', '--output-dir', 'o', '--image-name', 'x.png']
@@ -212,7 +214,7 @@ class Recorder(engine.Mosaic):
     log, begun = [], []
 
     def __init__(self, axes, gsd, device):
-        self._held = None
+        self._held = {}
 
     def add_bounds(self, views, Js):
         self.log.append(('add_bounds', None, len(views)))
@@ -234,7 +236,7 @@ class Recorder(engine.Mosaic):
 
 for _name in ('splat', 'resolve', 'gather', 'accumulate'):
     def _phase(self, views, Js, first_ordinal, _name=_name, **kw):
-        self.log.append((_name, first_ordinal, len(views), self._held))
+        self.log.append((_name, first_ordinal, len(views), self._held.get('cull')))
     setattr(Recorder, _name, _phase)
 
 
@@ -256,7 +258,7 @@ def test_run_takes_the_surface_over_every_batch_before_the_splat(recorder):
     assert recorder.log == [('add_bounds', None, 2), ('add_bounds', None, 1), ('begin', None, None), ('add_surface', 0, 2),
                             ('add_surface', 2, 1)] + phase('splat') + phase('resolve') + phase('gather') + phase('accumulate') \
         + [('normalize', None, None)]
-    assert m._held is None
+    assert m._held == {}
 
 
 def test_a_single_batch_is_culled_once_and_counted_then(recorder):
@@ -264,7 +266,7 @@ def test_a_single_batch_is_culled_once_and_counted_then(recorder):
     m = engine.mosaic_of(VIEWS, [object()] * 3, torch.eye(3), 0.25, surface=0.05)
     assert recorder.log == [('add_bounds', None, 3), ('begin', None, None), ('add_surface', 0, 3), ('culled_images', 0, True),
                             ('splat', 0, 3, held), ('resolve', 0, 3, held), ('gather', 0, 3, held)]
-    assert m._held is None       # nothing of one run is left for the next
+    assert m._held == {}       # nothing of one run is left for the next
 
 
 def test_without_the_flag_begin_is_not_given_it(recorder):

@@ -93,7 +93,7 @@ def main():
     rows.append(('sums, every sample for itself', timed(m.reject_slot_sum.zero_, lambda: over(m.add_reject_sums, plain=True), args.reps)))
     assert torch.equal(m.reject_slot_sum, want_sum)
 
-    o, big = m._reject_out, torch.zeros(1, dtype=torch.int64, device=dev)
+    o, big = m._out, torch.zeros(1, dtype=torch.int64, device=dev)
 
     def consensus():
         _lib.check(_lib.load().sucre_mosaic_reject_consensus(C.byref(m.grid), *(C.c_void_p(x.data_ptr()) for x in (
