@@ -105,6 +105,20 @@ constexpr bool kPairedBuilt = SUCRE_PAIRED_J != 0;
 #endif
 constexpr bool kStagedTerms = SUCRE_STAGED_TERMS != 0;
 
+// fit.hip: in fit_grad_kernel (L, F and the one-launch kernel) a pass over a 24-bit range-code store is compiled on its own, its
+// format tests folded away, and a strip's run of unmasked full chunks is straight-line code unrolled by the ring -- the slot a
+// compile-time constant (the ds_read offset behind ONE lane address), the wait the one immediate, level j's red converted from
+// byte 3 of code word j where it lies (1, the product: stream_strips' kLaneBytes, accumulate_chunk_z24; the producer side -- which
+// item goes to which slot, the DMAs, the stores, the waits' immediates -- and every value's operations are untouched, so the same
+// bits) -- or the per-chunk step for every chunk, the form until round 13 (0: make VARIANT=generic EXTRA=-DSUCRE_STRAIGHT_CHUNKS=0
+// gives the parent's instruction sequences, tools/isa_digest.py).  The straight run stands on the yields of SUCRE_STAGED_TERMS: a
+// build without them keeps the text it had before either knob (tests/test_staged_host.py pins it).
+// (tests/test_straight_chunks_host.py builds the 0 form, so that it cannot rot.)
+#if !defined(SUCRE_STRAIGHT_CHUNKS)
+#define SUCRE_STRAIGHT_CHUNKS 1
+#endif
+constexpr bool kStraightChunks = SUCRE_STRAIGHT_CHUNKS != 0 && kStagedTerms;
+
 // fit.hip, timing only: every wave of a J-parameter launch records when it entered and left its strips (100 MHz wall clock) --
 // how much of a launch is its ragged end (tools/exp/wave_times.py).
 #ifdef SUCRE_EXP_WAVE_TIMES

@@ -170,6 +170,33 @@ __device__ __forceinline__ void accumulate_level(float z, const uint32_t (&k)[3]
     for (int c = 0; c < 3; ++c) grad_terms<kScaledB>(z, fast_exp2(z * w.nb[c]), fast_exp2(z * w.ng[c]), k[c], valid, w.B[c], J[c], c, acc);
 }
 
+// An unmasked full chunk of the 24-bit range-code store with its colours where they lie (experiment.h SUCRE_STRAIGHT_CHUNKS):
+// level j's red is byte 3 of code word j (wd[j]: v_cvt_f32_ubyte3), green and blue are the bytes of cg and cb.  accumulate_chunk's
+// terms in accumulate_chunk's order -- the same (float)k enters the same fma -- without the three instructions that gather the
+// red bytes into one word for v_cvt_f32_ubyte0..3 to pick apart again.
+template <bool kScaledB, bool kYield>
+__device__ __forceinline__ void accumulate_chunk_z24(const float (&zz)[kGroupLv], const uint32_t (&wd)[kGroupLv], uint32_t cg, uint32_t cb,
+                                                     const Water &w, const float (&J)[3], Acc &acc) {
+    if (kExpNoCompute) {  // ablation build only (experiment.h): touch the data, skip the model
+        acc.cost += (zz[0] + zz[1]) + (zz[2] + zz[3]) + (float)(wd[0] ^ wd[1] ^ cg ^ cb);
+        return;
+    }
+    Exps e;
+    chunk_exps(zz, w, e);
+#pragma unroll
+    for (int j = 0; j < kGroupLv; ++j) {
+        const uint32_t k[3] = {wd[j] >> 24, (cg >> (8 * j)) & 255u, (cb >> (8 * j)) & 255u};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) grad_terms<kScaledB, kYield>(zz[j], e.a[j][c], e.g[j][c], k[c], true, w.B[c], J[c], c, acc);
+    }
+    // The chunk ends here, for the compiler too (no instruction): in the straight run the next use of these sums is the next chunk's,
+    // in another basic block, and the compiler sank their accumulations there -- the residuals and exponentials they wait for then
+    // lived across the next item's issue, through scratch memory.
+#pragma unroll
+    for (int c = 0; c < 3; ++c) asm volatile("" : "+v"(acc.pa[c]), "+v"(acc.pb[c]), "+v"(acc.sB[c]), "+v"(acc.sGZ[c]));
+    asm volatile("" : "+v"(acc.cost));
+}
+
 // Closed-form mode in ONE pass over the observations (sucre.py:141 + 142-147 with J a constant of the backward pass).
 // Write y = I - B(1-g) (free of J) and let Jp be the pixel's J of the previous iteration.  With the provisional
 // residual p = y - Jp a, the re-solved J = sum y a / sum a^2 is Jp + dJ, dJ = N/D, N = sum p a, D = sum a^2, the true
@@ -455,6 +482,35 @@ __device__ __forceinline__ void read_chunk(const uint8_t *sp, int lane, float (&
     cc[0] = cp[0]; cc[1] = cp[1]; cc[2] = cp[2];   // R, G, B words of the lane's four levels, side by side (layout.h)
 }
 
+// The same for an unmasked full chunk of the 24-bit range-code store, from the lane's own record at LDS address lane_addr + kOff
+// (lane_addr = ring + lane * kLaneZ24, kOff the slot: stream_strips' straight run): the four ranges, and the code words, green and
+// blue words as they lie (accumulate_chunk_z24).  Three ds_read_b64 with the slot in their 16-bit offsets, by hand: the compiler
+// merges two of them into a ds_read2_b64, whose offsets are eight bits of eight bytes, and adds the second and third slot to the
+// address once per chunk.  The wait stands in the same statement (what the compiler emits behind its own reads: the arithmetic
+// starts with these words), so no copy of a destination can come between the two.
+constexpr int kLaneZ24 = 24;
+template <uint32_t kOff>
+__device__ __forceinline__ void read_chunk_z24(uint32_t lane_addr, uint32_t zoff, float (&zz)[kGroupLv], uint32_t (&wd)[kGroupLv], uint32_t &cg, uint32_t &cb) {
+    static_assert(kOff + 16u < 65536u, "a ds_read offset");
+    uint64_t a, b, c;
+    asm volatile(
+        "ds_read_b64 %0, %3 offset:%4\n\t"
+        "ds_read_b64 %1, %3 offset:%5\n\t"
+        "ds_read_b64 %2, %3 offset:%6\n\t"
+        "s_waitcnt lgkmcnt(0)"
+        : "=&v"(a), "=&v"(b), "=&v"(c)
+        : "v"(lane_addr), "n"(kOff), "n"(kOff + 8u), "n"(kOff + 16u)
+        : "memory");
+    wd[0] = (uint32_t)a; wd[1] = (uint32_t)(a >> 32); wd[2] = (uint32_t)b; wd[3] = (uint32_t)(b >> 32);
+#pragma unroll
+    for (int j = 0; j < kGroupLv; ++j) {
+        uint32_t bits;
+        asm("v_mad_u32_u24 %0, %1, 1, %2" : "=v"(bits) : "v"(wd[j]), "s"(zoff));   // bits(z) = code + offset (read_chunk)
+        zz[j] = __uint_as_float(bits);
+    }
+    cg = (uint32_t)c; cb = (uint32_t)(c >> 32);
+}
+
 // Level j of a short chunk (r < 4 levels, rows of r) in a ring slot.
 template <int kFmt>
 __device__ __forceinline__ void read_level(const uint8_t *sp, int lane, uint32_t r, uint32_t j, float &z, uint32_t (&k)[3], const RangeCodes &rc) {
@@ -523,7 +579,14 @@ struct StreamChain {
 // kStart = 3 (kStreamF, layout.h): a strip begins with THREE items -- J plane, G plane, moments -- and on_J(slot pointer, which)
 // is called for each in turn.  The waits need no other change: what a step may leave outstanding depends on how many items were
 // issued behind the one it consumes and on whether the last strip's stores were issued behind it, not on what the items are.
-template <int kFmt, int kStores, bool kMoments, bool kPrimed = false, class Chain = NoChain, int kStart = 1, class OnJ, class OnChunk, class OnTail, class OnEnd>
+//
+// kLaneBytes > 0 (experiment.h SUCRE_STRAIGHT_CHUNKS): a lane's record of a full chunk is kLaneBytes bytes at slot + lane * kLaneBytes,
+// and the strip's run of unmasked full chunks is straight-line code unrolled by the ring (straight_run): on_chunk(lane address,
+// Straight<slot offset>{}).  The items, their slots, the DMAs and the waits are the per-chunk step's; only what it
+// re-derived per chunk -- the slot of item i and of item i + kAhead, `behind` -- is a constant of the position in the unrolled body.
+template <uint32_t kOff> struct Straight { static constexpr uint32_t off = kOff; };
+constexpr bool kStraightRun = kStraightChunks && kRing == 3;   // (the run is written for the product's ring)
+template <int kFmt, int kStores, bool kMoments, bool kPrimed = false, class Chain = NoChain, int kStart = 1, int kLaneBytes = 0, class OnJ, class OnChunk, class OnTail, class OnEnd>
 __device__ __forceinline__ void stream_strips(FitLds &lds, const PlanItem *__restrict__ plan, const StripEntry *__restrict__ strip_list,
                                               uint32_t K, const uint8_t *__restrict__ ws, int wave, int lane, uint32_t fullB, OnJ on_J,
                                               OnChunk on_chunk, OnTail on_tail, OnEnd on_end, Chain *chain = nullptr) {
@@ -579,6 +642,35 @@ __device__ __forceinline__ void stream_strips(FitLds &lds, const PlanItem *__res
         ++i;
         return sp;
     };
+    // A run of n >= 1 unmasked full chunks that starts with `behind` used up: the step above with its slots as constants.  Item i sits
+    // in slot q of the ring and item i + kAhead goes to slot q - 1.  The run has a head that brings cs round to slot 0 (0-2 chunks),
+    // a loop of whole turns of the ring with one exit, and a remainder of 0-2 chunks.
+    constexpr bool kStraight = kLaneBytes > 0;
+    static_assert(!kStraight || !kChain, "a chained stream starts with the `behind` the previous image left");
+    static_assert(!kStraight || (kRing == 3 && kRing * kSlot <= 65536), "three slots, their offsets ds_read immediates");
+    const uint32_t lane_addr = ring0 + (uint32_t)lane * (uint32_t)kLaneBytes;
+    auto straight_step = [&](auto slot) {
+        if constexpr (kStraight) {
+            constexpr uint32_t q = decltype(slot)::value;
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (the reads of item i - 1: step)
+            issue(nxt, (uint32_t)(((q + kRing - 1u) % kRing) * kSlot));
+            nxt = items[i + (uint32_t)kAhead + 1u];
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * kAhead) : "memory");
+            ++i;
+            on_chunk(lane_addr, Straight<q * kSlot>{});
+        }
+    };
+    auto straight_run = [&](uint32_t n) {
+        const std::integral_constant<uint32_t, 0> s0; const std::integral_constant<uint32_t, 1> s1; const std::integral_constant<uint32_t, 2> s2;
+        if (cs == (uint32_t)kSlot) { straight_step(s1); --n; cs = 2u * kSlot; }
+        if (cs == 2u * kSlot && n != 0u) { straight_step(s2); --n; cs = 0u; }
+        if (cs == 0u) {
+            const uint32_t turns = n / 3u, rest = n - 3u * turns;
+            for (uint32_t t = 0; t < turns; ++t) { straight_step(s0); straight_step(s1); straight_step(s2); }
+            if (rest != 0u) { straight_step(s0); cs = (uint32_t)kSlot; }
+            if (rest == 2u) { straight_step(s1); cs = 2u * kSlot; }
+        }
+    };
     ItemRegs se;
     if constexpr (kChain) se = chain->se0; else se = strips[0];
     for (uint32_t k = 0; k < K; ++k) {
@@ -593,7 +685,15 @@ __device__ __forceinline__ void stream_strips(FitLds &lds, const PlanItem *__res
         } else {
             on_J(step());
         }
-        for (uint32_t g = 0; g < nu; ++g) on_chunk(step(), false);
+        if constexpr (kStraight) {
+            // `behind` can be non-zero for the first kAhead steps of a strip only: the chunks among them take the step above
+            constexpr uint32_t kPeel = kStart < kAhead ? (uint32_t)(kAhead - kStart) : 0u;
+            uint32_t g = 0;
+            for (; g < kPeel && g < nu; ++g) on_chunk(step(), false);
+            if (g < nu) straight_run(nu - g);
+        } else {
+            for (uint32_t g = 0; g < nu; ++g) on_chunk(step(), false);
+        }
         for (uint32_t g = 0; g < nm; ++g) on_chunk(step(), true);
         if (r) on_tail(step(), r);
         if (kMoments) on_end(strip, step());
@@ -784,32 +884,43 @@ __device__ __forceinline__ void store_stepped(float *p, float v) {
 // the wave's items, steps J of every strip, and keeps adding the lane's shares of the global sums to acc / sBeta.
 // kScaledB: the pass's chunk arithmetic in the B-scaled form (grad_terms); acc.sB then holds B sum r (1 - g).  The caller picks it
 // with ONE wave-uniform branch per pass (run_grad_pass) from scaled_b_ok of the pass's own B.
-template <int kFmt, bool kScaledB, bool kPrimed = false, class Chain = NoChain>
+// kZ24 (picked at the same place; experiment.h SUCRE_STRAIGHT_CHUNKS): the store holds 24-bit range codes -- the pass is compiled for
+// that format alone (rz: the format tests of read_chunk and read_level fold away) with its unmasked full chunks as a straight run.
+template <int kFmt, bool kScaledB, bool kPrimed = false, class Chain = NoChain, bool kZ24 = false>
 __device__ __forceinline__ void grad_pass(FitLds &lds, const PlanItem *__restrict__ plan, const StripEntry *__restrict__ strips, uint32_t n_strips_wave,
                                           const uint8_t *__restrict__ ws, float *__restrict__ state, int wave, int lane,
                                           const Water &w, float gscale, const AdamCoef &co, Acc &acc, float (&sBeta)[3], const RangeCodes &rc,
                                           Chain *chain = nullptr) {
     float J[3] = {0.f, 0.f, 0.f};
-    stream_strips<kFmt, 9, true, kPrimed, Chain>(
+    static_assert(!kZ24 || kFmt == 0, "range codes stand for float32 ranges");
+    const RangeCodes rc24 = {true, false, rc.zoff, rc.fullB};
+    const RangeCodes &rz = kZ24 ? rc24 : rc;
+    constexpr bool kYield = kStagedTerms && !Chain::kOn;   // (not in a batch launch: accumulate_chunk)
+    stream_strips<kFmt, 9, true, kPrimed, Chain, 1, kZ24 ? kLaneZ24 : 0>(
         lds, plan, strips, n_strips_wave, ws, wave, lane, rc.fullB,
         [&](const uint8_t *sp) {  // J plane
             const float *f = reinterpret_cast<const float *>(sp);
 #pragma unroll
             for (int c = 0; c < 3; ++c) { J[c] = f[c * kStripPx + lane]; acc.pa[c] = 0.f; acc.pb[c] = 0.f; }
         },
-        [&](const uint8_t *sp, bool masked) {  // chunk of four levels
+        [&](auto sp, auto how) {  // chunk of four levels (how: masked or not; Straight<slot>: sp is the LDS address of the lane's records)
             float zz[kGroupLv];
-            uint32_t cc[3];
-            read_chunk<kFmt>(sp, lane, zz, cc, rc, masked);
-            constexpr bool kYield = kStagedTerms && !Chain::kOn;   // (not in a batch launch: accumulate_chunk)
-            if (masked) accumulate_chunk<true, kScaledB, kYield>(zz, cc, w, J, acc);
-            else accumulate_chunk<false, kScaledB, kYield>(zz, cc, w, J, acc);
+            if constexpr (!std::is_same_v<decltype(how), bool>) {
+                uint32_t wd[kGroupLv], cg, cb;
+                read_chunk_z24<decltype(how)::off>(sp, rz.zoff, zz, wd, cg, cb);
+                accumulate_chunk_z24<kScaledB, kYield>(zz, wd, cg, cb, w, J, acc);
+            } else {
+                uint32_t cc[3];
+                read_chunk<kFmt>(sp, lane, zz, cc, rz, how);
+                if (how) accumulate_chunk<true, kScaledB, kYield>(zz, cc, w, J, acc);
+                else accumulate_chunk<false, kScaledB, kYield>(zz, cc, w, J, acc);
+            }
         },
         [&](const uint8_t *sp, uint32_t r) {  // the strip's short last chunk
             for (uint32_t j = 0; j < r; ++j) {
                 float z;
                 uint32_t k[3];
-                read_level<kFmt>(sp, lane, r, j, z, k, rc);
+                read_level<kFmt>(sp, lane, r, j, z, k, rz);
                 accumulate_level<kScaledB>(z, k, w, J, acc);
             }
         },
@@ -840,11 +951,19 @@ __device__ __forceinline__ bool pass_scaled_b(const Water &w) {
     return kScaledBBuilt && __builtin_amdgcn_readfirstlane((int)scaled_b_ok(w.B[0], w.B[1], w.B[2])) != 0;
 }
 
-template <int kFmt, bool kPrimed = false, class Chain = NoChain>
+// kPickZ24 (fit_grad_kernel): the store kind is taken here too -- 24-bit range codes or everything else (grad_pass' kZ24).
+template <int kFmt, bool kPrimed = false, class Chain = NoChain, bool kPickZ24 = false>
 __device__ __forceinline__ void run_grad_pass(bool scaled, FitLds &lds, const PlanItem *__restrict__ plan, const StripEntry *__restrict__ strips,
                                               uint32_t n_strips_wave, const uint8_t *__restrict__ ws, float *__restrict__ state, int wave, int lane,
                                               const Water &w, float gscale, const AdamCoef &co, Acc &acc, float (&sBeta)[3], const RangeCodes &rc,
                                               Chain *chain = nullptr) {
+    if constexpr (kPickZ24) {
+        if (rc.z24) {   // (wave-uniform)
+            if (kScaledBBuilt && scaled) grad_pass<kFmt, true, kPrimed, Chain, true>(lds, plan, strips, n_strips_wave, ws, state, wave, lane, w, gscale, co, acc, sBeta, rc, chain);
+            else grad_pass<kFmt, false, kPrimed, Chain, true>(lds, plan, strips, n_strips_wave, ws, state, wave, lane, w, gscale, co, acc, sBeta, rc, chain);
+            return;
+        }
+    }
     if (kScaledBBuilt && scaled) grad_pass<kFmt, true, kPrimed, Chain>(lds, plan, strips, n_strips_wave, ws, state, wave, lane, w, gscale, co, acc, sBeta, rc, chain);
     else grad_pass<kFmt, false, kPrimed, Chain>(lds, plan, strips, n_strips_wave, ws, state, wave, lane, w, gscale, co, acc, sBeta, rc, chain);
 }
@@ -864,35 +983,45 @@ __device__ __forceinline__ void run_grad_pass(bool scaled, FitLds &lds, const Pl
 // the reduction trees are plan 0's: J, the moments, the water parameters and the log keep every bit (tests/test_gpu_paired.py).
 // The water step and the log row of both iterations are the launches' own finishers, unchanged.  Nothing is pending when F ends.
 // ---------------------------------------------------------------------------------------------------------------
-template <int kFmt, bool kScaledB, int kPair>
+template <int kFmt, bool kScaledB, int kPair, bool kZ24 = false>   // kZ24: as in grad_pass
 __device__ __forceinline__ void pair_pass(FitLds &lds, const PlanItem *__restrict__ plan, const StripEntry *__restrict__ strips, uint32_t n_strips_wave,
                                           const uint8_t *__restrict__ ws, float *__restrict__ state, float *__restrict__ gplane, int wave, int lane,
                                           const Water &w, float gscale, const AdamCoef &co_prev, const AdamCoef &co, Acc &acc, float (&sBeta)[3],
                                           const RangeCodes &rc) {
     static_assert(kPair == 1 || kPair == 2, "L or F");
     float J[3] = {0.f, 0.f, 0.f}, G[3] = {0.f, 0.f, 0.f}, M[3] = {0.f, 0.f, 0.f}, V[3] = {0.f, 0.f, 0.f};
+    static_assert(!kZ24 || kFmt == 0, "range codes stand for float32 ranges");
+    const RangeCodes rc24 = {true, false, rc.zoff, rc.fullB};
+    const RangeCodes &rz = kZ24 ? rc24 : rc;
+    constexpr int kLaneBytes = kZ24 ? kLaneZ24 : 0;
     auto begin = [&](const uint8_t *sp) {  // J plane
         const float *f = reinterpret_cast<const float *>(sp);
 #pragma unroll
         for (int c = 0; c < 3; ++c) { J[c] = f[c * kStripPx + lane]; acc.pa[c] = 0.f; acc.pb[c] = 0.f; }
     };
-    auto on_chunk = [&](const uint8_t *sp, bool masked) {  // chunk of four levels
+    auto on_chunk = [&](auto sp, auto how) {  // chunk of four levels (how: masked or not; Straight<slot>: sp is the LDS address of the lane's records)
         float zz[kGroupLv];
-        uint32_t cc[3];
-        read_chunk<kFmt>(sp, lane, zz, cc, rc, masked);
-        if (masked) accumulate_chunk<true, kScaledB>(zz, cc, w, J, acc);
-        else accumulate_chunk<false, kScaledB>(zz, cc, w, J, acc);
+        if constexpr (!std::is_same_v<decltype(how), bool>) {
+            uint32_t wd[kGroupLv], cg, cb;
+            read_chunk_z24<decltype(how)::off>(sp, rz.zoff, zz, wd, cg, cb);
+            accumulate_chunk_z24<kScaledB, kStagedTerms>(zz, wd, cg, cb, w, J, acc);
+        } else {
+            uint32_t cc[3];
+            read_chunk<kFmt>(sp, lane, zz, cc, rz, how);
+            if (how) accumulate_chunk<true, kScaledB>(zz, cc, w, J, acc);
+            else accumulate_chunk<false, kScaledB>(zz, cc, w, J, acc);
+        }
     };
     auto on_tail = [&](const uint8_t *sp, uint32_t r) {  // the strip's short last chunk
         for (uint32_t j = 0; j < r; ++j) {
             float z;
             uint32_t k[3];
-            read_level<kFmt>(sp, lane, r, j, z, k, rc);
+            read_level<kFmt>(sp, lane, r, j, z, k, rz);
             accumulate_level<kScaledB>(z, k, w, J, acc);
         }
     };
     if constexpr (kPair == 1) {
-        stream_strips<kFmt, 3, false>(
+        stream_strips<kFmt, 3, false, false, NoChain, 1, kLaneBytes>(
             lds, plan, strips, n_strips_wave, ws, wave, lane, rc.fullB, begin, on_chunk, on_tail,
             [&](uint32_t strip, const uint8_t *) {  // the gradient of this pixel's J, for F to step with
                 float *gp = gplane + (size_t)strip * (3 * kStripPx);
@@ -909,7 +1038,7 @@ __device__ __forceinline__ void pair_pass(FitLds &lds, const PlanItem *__restric
                 }
             });
     } else {
-        stream_strips<kFmt, 9, false, false, NoChain, 3>(
+        stream_strips<kFmt, 9, false, false, NoChain, 3, kLaneBytes>(
             lds, plan, strips, n_strips_wave, ws, wave, lane, rc.fullB,
             [&](const uint8_t *sp, auto which) {
                 const float *f = reinterpret_cast<const float *>(sp);
@@ -996,8 +1125,12 @@ __global__ __launch_bounds__(256, kFitWaves) void fit_grad_kernel(const uint8_t 
     float sBeta[3] = {0.f, 0.f, 0.f};
     if (kExpWaveTimes && lane == 0 && wid < kExpWaveSlots) g_exp_wave_times[0][wid] = wall_clock64();
     if constexpr (kPair == 0) {
-        run_grad_pass<kFmt>(pass_scaled_b(w), lds, plan + (size_t)wid * plan_stride, plan_strips + (size_t)wid * plan_kmax, n_mine, ws, state, wave, lane, w, gscale, co, acc, sBeta, rc);
-    } else {   // (one wave-uniform branch per pass, as run_grad_pass takes it)
+        run_grad_pass<kFmt, false, NoChain, kStraightRun && kFmt == 0>(pass_scaled_b(w), lds, plan + (size_t)wid * plan_stride, plan_strips + (size_t)wid * plan_kmax, n_mine, ws, state, wave, lane, w, gscale, co, acc, sBeta, rc);
+    } else if (kStraightRun && kFmt == 0 && rc.z24) {   // (one wave-uniform branch per pass for the store kind and the form, as run_grad_pass takes it)
+        constexpr bool kZ24 = kStraightRun && kFmt == 0;
+        if (pass_scaled_b(w)) pair_pass<kFmt, true, kPair, kZ24>(lds, plan + (size_t)wid * plan_stride, plan_strips + (size_t)wid * plan_kmax, n_mine, ws, state, gplane, wave, lane, w, gscale, co_prev, co, acc, sBeta, rc);
+        else pair_pass<kFmt, false, kPair, kZ24>(lds, plan + (size_t)wid * plan_stride, plan_strips + (size_t)wid * plan_kmax, n_mine, ws, state, gplane, wave, lane, w, gscale, co_prev, co, acc, sBeta, rc);
+    } else {
         if (pass_scaled_b(w)) pair_pass<kFmt, true, kPair>(lds, plan + (size_t)wid * plan_stride, plan_strips + (size_t)wid * plan_kmax, n_mine, ws, state, gplane, wave, lane, w, gscale, co_prev, co, acc, sBeta, rc);
         else pair_pass<kFmt, false, kPair>(lds, plan + (size_t)wid * plan_stride, plan_strips + (size_t)wid * plan_kmax, n_mine, ws, state, gplane, wave, lane, w, gscale, co_prev, co, acc, sBeta, rc);
     }
