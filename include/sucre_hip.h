@@ -952,6 +952,46 @@ int sucre_light_group_iter(void *group_dev, int n_images, int step, double lr, d
 int sucre_light_group_finish(void *group_dev, int n_images, int step, double lr, double beta1, double beta2, double eps,
                              unsigned flags, uint64_t n_obs_total, double *trace_dev, void *stream);
 
+/*
+ * ---- standard errors of the water parameters and of J --------------------------------------------------------------------
+ * How well the observations determine what the fit reports: one float64 streaming pass over the DENSE store of a matched (or
+ * imported), finalised and fitted workspace that forms, for every observation of every KEPT view at the workspace's CURRENT
+ * parameters and CURRENT J (as sucre_fit_residuals* reads them), per channel c -- channels do not couple --
+ *     a = exp(-beta z),  g = exp(-gamma z)                                      SUCRe.forward, sucre.py:79-82; z: sucre.py:52-53
+ *     dJ = a,  dB = 1 - g,  dbeta = -J z a,  dgamma = B z g,  r = I - (J a + B dB)       the Jacobian of sucre.py:144's residual
+ * and sums the Gauss-Newton normal equations with every pixel's own J eliminated:
+ *     per pixel p:  A_p = sum dJ^2,  b_p = sum dJ (dB, dbeta, dgamma),  k_p = b_p / A_p
+ *     H = sum_obs d d^T - sum_p b_p b_p^T / A_p   with d = (dB, dbeta, dgamma),   SSR = sum r^2
+ * from which  s^2 = SSR / (N - P - 3),  cov(B, beta, gamma) = s^2 H^-1  and  sigma_J(p)^2 = s^2 (1 / A_p + k_p^T H^-1 k_p)
+ * follow on the host.  z, J, B, beta, gamma and I are the float32 numbers of the residual pass (with SUCRE_OBS_U16MM the range
+ * 0.001f * clamp(rint(1000 z), 1, 65535); uint8 colours as float32(k / 255)) promoted to float64; everything behind is float64,
+ * one IEEE operation per step: the elimination is a 30-65x cancellation in a matrix of scaled condition number 1e3 - 3e4, and
+ * float32 sums leave H wrong by 5e-4 - 9e-4 relative.
+ *   count_dev   int32   (H,W)       observations of the pixel over the kept views
+ *   jterms_dev  float32 (H,W,3,4)   per channel {1 / A_p, k_B, k_beta, k_gamma}; 0 where count is 0
+ *   sums_dev    float64 [SUCRE_UNCERTAINTY_WORDS]
+ *                 word 0  N, the observations           word 1  P, the pixels with at least one
+ *                 word 2  pixels that have observations but no finite positive A_p in some channel: nothing is eliminated for
+ *                         them and their jterms are 0 (their observations still stand in N, SSR and sum d d^T, so a caller
+ *                         must not trust the sums of an image where this word is not 0)
+ *                 words 3 + 7 c ..: H_BB, H_Bbeta, H_Bgamma, H_betabeta, H_betagamma, H_gammagamma, SSR of channel c
+ * The workspaces are only read.  scratch_dev: sucre_uncertainty_scratch_bytes() bytes of caller-owned device memory, 16-byte
+ * aligned, that must stay untouched until the pass has run; every sum is formed in a fixed order (no atomics), so two calls
+ * give the same bits.  obs_format: as for sucre_fit_residuals.  sucre_fit_uncertainty_ext: the same for a workspace with
+ * float32 colours, flags = SUCRE_FIT_EXT_COLOUR (the nine parameters are the first nine of `lws`).  The light model is not
+ * built: flags = 0 and SUCRE_FIT_EXT_BOTH are refused -- the lamp's ten parameters would have to join (B, beta, gamma), and
+ * errors conditional on a fixed lamp would understate.  Arguments are checked before anything is launched: NULL or misaligned
+ * pointers, a bad geometry, an unknown format or such flags give SUCRE_ERR_ARG and a message that names the reason.
+ * Limits: Gauss-Newton at the current point, not necessarily at the minimum; observations are taken as independent with one
+ * variance per channel, so errors shared by views (depth maps, poses) are not in it.
+ */
+#define SUCRE_UNCERTAINTY_WORDS 24
+size_t sucre_uncertainty_scratch_bytes(int H, int W, int n_views);
+int sucre_fit_uncertainty(const void *ws, int H, int W, int n_views, int obs_format, int32_t *count_dev, float *jterms_dev,
+                          double *sums_dev, void *scratch_dev, void *stream);
+int sucre_fit_uncertainty_ext(const void *ws, const void *lws, int H, int W, int n_views, unsigned flags /* SUCRE_FIT_EXT_COLOUR */,
+                              int32_t *count_dev, float *jterms_dev, double *sums_dev, void *scratch_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

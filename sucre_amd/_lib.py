@@ -25,6 +25,7 @@ OBS_FORMATS = {'f32': OBS_F32, 'u16mm': OBS_U16MM, 'f32plain': OBS_F32_PLAIN, 'f
 WS_VIEW_COUNT, WS_VIEW_KEEP, WS_N_OBS, WS_PARAMS, WS_SUMS, WS_N_OBS_TOTAL, WS_STORE_FORMAT, WS_STATE, WS_PAIR_GRADIENT = range(9)
 INVERT_LIGHT, INVERT_FLOAT_COLOUR = 1, 2
 INVERT_MAX_IMAGES = 4096   # kInvertMaxImages of csrc/invert.h: images per sucre_invert_images call
+UNCERTAINTY_WORDS = 24     # SUCRE_UNCERTAINTY_WORDS: float64 words of sucre_fit_uncertainty's sums
 CONSISTENCY_STATS = 26     # kConsistStats of csrc/consist.h: columns of a view's row of sucre_view_consistency's stats
 MOSAIC_PLAIN_ATOMIC = 1     # SUCRE_MOSAIC_PLAIN_ATOMIC: sucre_mosaic_splat without the load that filters its atomics;
 #                             sucre_mosaic_accumulate with eight atomics per pixel instead of eight per run of a wave's lanes
@@ -155,6 +156,9 @@ SIGNATURES = {
     'sucre_residual_scratch_bytes': (C.c_size_t, [_i, _i, _i]),
     'sucre_fit_residuals': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'sucre_fit_residuals_ext': (_i, [_vp, _vp, _i, _i, _i, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
+    'sucre_uncertainty_scratch_bytes': (C.c_size_t, [_i, _i, _i]),
+    'sucre_fit_uncertainty': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'sucre_fit_uncertainty_ext': (_i, [_vp, _vp, _i, _i, _i, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
     'sucre_trim_scratch_bytes': (C.c_size_t, [_i, _i, _i]),
     'sucre_trim_outliers': (_i, [_vp, _i, _i, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
     'sucre_trim_outliers_ext': (_i, [_vp, _vp, _i, _i, _i, C.c_uint, _d, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -1562,3 +1562,54 @@ int sucre_light_group_finish(void *group_dev, int n_images, int step, double lr,
 }
 
 }  // extern "C"
+
+/* ---- standard errors of the water parameters and of J ------------------------------------------------------------------- */
+
+namespace sucre {
+static int check_uncertainty_outputs(const int32_t *count_dev, const float *jterms_dev, const double *sums_dev, const void *scratch_dev) {
+    if (!count_dev || !jterms_dev || !sums_dev || !scratch_dev) return fail(SUCRE_ERR_ARG, "count_dev / jterms_dev / sums_dev / scratch_dev is NULL");
+    if (!aligned(count_dev, 4) || !aligned(jterms_dev, 16) || !aligned(sums_dev, 8)) return fail(SUCRE_ERR_ARG, "outputs must be 4 / 16 / 8-byte aligned");
+    if (!aligned(scratch_dev, 16)) return fail(SUCRE_ERR_ARG, "scratch_dev must be 16-byte aligned");
+    return SUCRE_OK;
+}
+}  // namespace sucre
+
+extern "C" {
+
+size_t sucre_uncertainty_scratch_bytes(int H, int W, int n_views) {
+    Layout L;
+    if (!make_layout(H, W, n_views, &L)) {
+        fail(SUCRE_ERR_ARG, "invalid geometry H=%d W=%d n_views=%d", H, W, n_views);
+        return 0;
+    }
+    return uncertainty_scratch_bytes(L);
+}
+
+int sucre_fit_uncertainty(const void *ws, int H, int W, int n_views, int obs_format, int32_t *count_dev, float *jterms_dev,
+                          double *sums_dev, void *scratch_dev, void *stream) {
+    Layout L;
+    if (int rc = check_ws(ws, H, W, n_views, &L)) return rc;
+    if (obs_format != SUCRE_OBS_F32 && obs_format != SUCRE_OBS_U16MM && obs_format != SUCRE_OBS_F32_PLAIN && obs_format != SUCRE_OBS_F32_Z26)
+        return fail(SUCRE_ERR_ARG, "unknown observation format %d", obs_format);
+    if (int rc = check_uncertainty_outputs(count_dev, jterms_dev, sums_dev, scratch_dev)) return rc;
+    return check_hip(launch_uncertainty(L, static_cast<const uint8_t *>(ws), obs_format == SUCRE_OBS_U16MM ? SUCRE_OBS_U16MM : SUCRE_OBS_F32,
+                                        count_dev, jterms_dev, sums_dev, scratch_dev, static_cast<hipStream_t>(stream)),
+                     "sucre_fit_uncertainty");
+}
+
+int sucre_fit_uncertainty_ext(const void *ws, const void *lws, int H, int W, int n_views, unsigned flags, int32_t *count_dev,
+                              float *jterms_dev, double *sums_dev, void *scratch_dev, void *stream) {
+    Layout L;
+    if (int rc = check_ws(ws, H, W, n_views, &L)) return rc;
+    if (int rc = check_lws(lws)) return rc;
+    if (flags & ~(SUCRE_FIT_EXT_COLOUR | SUCRE_FIT_EXT_BOTH)) return fail(SUCRE_ERR_ARG, "unknown flags 0x%x", flags);
+    if (flags != SUCRE_FIT_EXT_COLOUR)
+        return fail(SUCRE_ERR_ARG, "flags 0x%x name the light model, whose uncertainty is not built: the lamp's parameters would have to "
+                                   "join B, beta, gamma (only SUCRE_FIT_EXT_COLOUR is taken)", flags);
+    if (int rc = check_uncertainty_outputs(count_dev, jterms_dev, sums_dev, scratch_dev)) return rc;
+    return check_hip(launch_uncertainty_colour(L, static_cast<const uint8_t *>(ws), static_cast<const uint8_t *>(lws), count_dev,
+                                               jterms_dev, sums_dev, scratch_dev, static_cast<hipStream_t>(stream)),
+                     "sucre_fit_uncertainty_ext");
+}
+
+}  // extern "C"

@@ -145,4 +145,11 @@ hipError_t launch_light_group_iter(void *group, int n_images, const Layout *L, u
 hipError_t launch_light_group_finish(void *group, int n_images, const Layout *L, uint8_t *const *ws, uint8_t *const *lws, int step,
                                      const AdamCoef &co_prev, unsigned flags, uint64_t n_obs_total, double *trace_prev, hipStream_t s);
 
+// standard errors of the water parameters and of J (uncertainty.h, uncertainty.hip)
+size_t uncertainty_scratch_bytes(const Layout &L);
+hipError_t launch_uncertainty(const Layout &L, const uint8_t *ws, int fmt, int32_t *count, float *jterms, double *sums, void *scratch,
+                              hipStream_t s);
+hipError_t launch_uncertainty_colour(const Layout &L, const uint8_t *ws, const uint8_t *lws, int32_t *count, float *jterms, double *sums,
+                                     void *scratch, hipStream_t s);
+
 }  // namespace sucre

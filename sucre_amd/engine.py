@@ -552,6 +552,36 @@ class Restoration:
                 _lib.check(self.lib.sucre_fit_residuals(ws, H, W, n, self._fmt, *outs, self._sp()))
         return count, ssr, stats
 
+    def uncertainty(self):
+        """The float64 statistics behind the standard errors of B, beta, gamma and J at the fit as it stands
+        (``sucre_fit_uncertainty``): ``(count, jterms, sums)`` on the device -- int32 (H,W) observations per pixel over the kept
+        views, float32 (H,W,3,4) per channel ``{1 / A_p, k_B, k_beta, k_gamma}`` (0 where ``count`` is 0), float64
+        [``_lib.UNCERTAINTY_WORDS``] = N, P, pixels without a finite positive A_p, then per channel H_BB, H_Bbeta, H_Bgamma,
+        H_betabeta, H_betagamma, H_gammagamma, SSR: the Gauss-Newton normal matrix of (B, beta, gamma) with every pixel's J
+        eliminated (csrc/uncertainty.h).  ``water_uncertainty(sums)`` and ``j_standard_error(jterms, count, result)`` turn them
+        into covariances and sigma_J.  One pass over the dense store, enqueued on the current stream without a host wait; the
+        workspace is only read; two calls give the same bits.  The light model is refused: its ten parameters would have to join
+        (B, beta, gamma)."""
+        if self.light:
+            raise NotImplementedError('uncertainty: not built for the light model -- the lamp\'s ten parameters would have to join '
+                                      'B, beta, gamma, and errors conditional on a fixed lamp would understate')
+        count = torch.empty((self.H, self.W), dtype=torch.int32, device=self.device)
+        jterms = torch.empty((self.H, self.W, 3, 4), dtype=torch.float32, device=self.device)
+        sums = torch.empty(_lib.UNCERTAINTY_WORDS, dtype=torch.float64, device=self.device)
+        nbytes = self.lib.sucre_uncertainty_scratch_bytes(self.H, self.W, self.n_views)
+        if nbytes == 0:
+            raise _lib.SucreError(self.lib.sucre_last_error().decode())
+        # torch's caching allocator keeps the block for this stream until the launches queued here have run
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        ws, H, W, n = self._geom
+        outs = (C.c_void_p(count.data_ptr()), C.c_void_p(jterms.data_ptr()), C.c_void_p(sums.data_ptr()), C.c_void_p(scratch.data_ptr()))
+        with torch.cuda.device(self.device):
+            if self.float_colour:
+                _lib.check(self.lib.sucre_fit_uncertainty_ext(ws, C.c_void_p(self.lws.data_ptr()), H, W, n, self._ext_flag, *outs, self._sp()))
+            else:
+                _lib.check(self.lib.sucre_fit_uncertainty(ws, H, W, n, self._fmt, *outs, self._sp()))
+        return count, jterms, sums
+
     def trim_outliers(self, k_sigma: float, residuals=None):
         """One round of the outlier trim (``sucre_trim_outliers``): drops from the store every observation of a kept view whose
         residual at the fit as it stands has r_c^2 > tau^2_c = float32(k_sigma^2 S_c / N) in any channel (N, S_c: observations
@@ -663,6 +693,69 @@ class Restoration:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.sucre_export_J(ws, H, W, n, C.c_void_p(out.data_ptr()), self._sp()))
         return out
+
+
+WATER_NAMES = ('B', 'beta', 'gamma')   # the order of every 3-vector and 3x3 matrix of water_uncertainty
+
+
+def water_uncertainty(sums) -> dict:
+    """Covariance of (B, beta, gamma) per channel from the 24 float64 words of ``Restoration.uncertainty`` (or of
+    ``sucre.pooled_uncertainty``), on the host in float64 numpy: ``s2 = SSR / dof`` with ``dof = N - P - 3``, ``cov = s2 H^-1``.
+    H is scaled by its diagonal before it is inverted (its entries span orders of magnitude; the scaled matrix has condition
+    number 1e3 - 3e4 on the project's scenes).  Returns a dict of arrays, first axis the channel R, G, B, parameters in the order
+    ``WATER_NAMES``: ``cov`` (3,3,3), ``se`` (3,3), ``corr`` (3,3,3), ``cond`` (3,) of the scaled matrix, ``s2`` (3,), ``normal``
+    (3,3,3) = H, ``well_posed`` (3,) bool, and the scalars ``dof``, ``n_obs``, ``n_pixels`` (int).  A channel with ``dof <= 0``, with
+    an H or SSR that is not finite, with an H that is not positive definite, or of an image in which some observed pixel had no
+    finite positive A_p (word 2) gets NaN and ``well_posed`` False; nothing raises.
+    Gauss-Newton at the point the sums were taken at, not necessarily a minimum; observations count as independent with one
+    variance per channel, so errors that views share (depth maps, poses) are not in it."""
+    w = np.asarray(sums.detach().cpu().numpy() if torch.is_tensor(sums) else sums, np.float64).reshape(-1)
+    if w.size != _lib.UNCERTAINTY_WORDS:
+        raise ValueError(f'water_uncertainty: {_lib.UNCERTAINTY_WORDS} words expected, not {w.size}')
+    head_ok = bool(np.isfinite(w[:3]).all())
+    n_obs, n_pixels = (int(round(w[0])), int(round(w[1]))) if head_ok else (0, 0)
+    dof = n_obs - n_pixels - 3
+    out = {'cov': np.full((3, 3, 3), np.nan), 'se': np.full((3, 3), np.nan), 'corr': np.full((3, 3, 3), np.nan),
+           'cond': np.full(3, np.nan), 's2': np.full(3, np.nan), 'normal': np.zeros((3, 3, 3)), 'well_posed': np.zeros(3, bool),
+           'dof': dof, 'n_obs': n_obs, 'n_pixels': n_pixels}
+    for c in range(3):
+        hBB, hBb, hBg, hbb, hbg, hgg, ssr = w[3 + 7 * c:10 + 7 * c]
+        Hc = np.array([[hBB, hBb, hBg], [hBb, hbb, hbg], [hBg, hbg, hgg]])
+        out['normal'][c] = Hc
+        d = np.diag(Hc)
+        if not (head_ok and w[2] == 0 and dof > 0 and np.isfinite(Hc).all() and np.isfinite(ssr) and ssr >= 0 and (d > 0).all()):
+            continue
+        scale = np.sqrt(d)
+        Hs = Hc / np.outer(scale, scale)
+        try:
+            np.linalg.cholesky(Hs)   # positive definite, or not determined
+            inv = np.linalg.inv(Hs)
+        except np.linalg.LinAlgError:
+            continue
+        if not (np.isfinite(inv).all() and (np.diag(inv) > 0).all()):
+            continue
+        s2 = ssr / dof
+        cov = s2 * inv / np.outer(scale, scale)
+        root = np.sqrt(np.diag(inv))
+        out['cov'][c], out['se'][c], out['s2'][c] = cov, np.sqrt(np.diag(cov)), s2
+        out['corr'][c] = inv / np.outer(root, root)
+        out['cond'][c] = np.linalg.cond(Hs)
+        out['well_posed'][c] = True
+    return out
+
+
+def j_standard_error(jterms: torch.Tensor, count: torch.Tensor, result: dict) -> torch.Tensor:
+    """float32 (H,W,3): ``sigma_J = sqrt(s2 / A_p + k_p^T cov k_p)`` per pixel and channel from the ``jterms`` and ``count`` of
+    ``Restoration.uncertainty`` and the dict of ``water_uncertainty`` -- torch in float64 where ``jterms`` lives.  NaN where
+    ``count`` is 0, where the pixel had no finite positive A_p, and in a channel that is not well posed."""
+    t = jterms.to(torch.float64)
+    cov = torch.as_tensor(np.asarray(result['cov'], np.float64), device=t.device)   # (3 channels, 3, 3)
+    s2 = torch.as_tensor(np.asarray(result['s2'], np.float64), device=t.device)
+    k = t[..., 1:]                                                       # (H, W, 3, 3)
+    var = s2 * t[..., 0] + torch.einsum('hwci,cij,hwcj->hwc', k, cov, k)
+    seen = ((count > 0) & (t[..., 0] > 0).all(dim=-1)).unsqueeze(-1)
+    posed = torch.as_tensor(np.asarray(result['well_posed'], bool), device=t.device)
+    return torch.where(seen & posed, var.sqrt(), torch.full_like(var, float('nan'))).to(torch.float32)
 
 
 def fit_batch(restorations: list, num_iter: int = 200, lr: float = 0.05, use_closed_form: bool = False, betas=(0.9, 0.999),

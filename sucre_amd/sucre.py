@@ -418,7 +418,7 @@ def snapshot_stops(num_iter: int, save_interval: int | None) -> list[tuple[int, 
 @dataclasses.dataclass(frozen=True)
 class _Extras:
     """What a restoration can be asked for beyond the reference's arguments: --save-quality; --trim-outliers, --trim-rounds;
-    --view-gains, --gain-rounds, --gain-limit; the ``(lo, hi)`` of --stretch-from.  Built from the command line (``_run_request``),
+    --view-gains, --gain-rounds, --gain-limit; the ``(lo, hi)`` of --stretch-from; --save-uncertainty.  Built from the command line (``_run_request``),
     from the keywords of ``restore_images`` and from those of ``adam``; everything between them hands the record on."""
     save_quality: bool = False
     trim_outliers: float = None
@@ -427,6 +427,7 @@ class _Extras:
     gain_rounds: int = 1
     gain_limit: float = 2.0
     stretch: tuple = None
+    save_uncertainty: bool = False
 
     def checked(self, save_interval: int = None) -> '_Extras':
         """The record with its stretch as ``check_stretch`` returns it.  ``ValueError`` for a value out of range, for gains next
@@ -455,10 +456,11 @@ _NO_EXTRAS = _Extras()
 
 class _Job:
     """One image between ``_restore_submit`` (everything enqueued, nothing waited for) and ``_restore_finish``.  ``extras``: what
-    was asked for; ``trace``: the last fit's; ``quality``, ``trim``, ``gains``: the records of --save-quality and of every round."""
+    was asked for; ``trace``: the last fit's; ``quality``, ``trim``, ``gains``: the records of --save-quality and of every round;
+    ``uncertainty``: that of --save-uncertainty, ``pooled_uncertainty``: the ``engine.water_uncertainty`` of a shared fit's pooled sums."""
     extras = _NO_EXTRAS
     params0 = None   # the start of every fit, on the host; None: read from the module (``adam``)
-    trace = quality = trim = gains = None
+    trace = quality = trim = gains = uncertainty = pooled_uncertainty = None
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -467,7 +469,7 @@ class _Job:
 def adam(sucre: SUCRe, matches_data: loader.MatchesData, lr: float = 0.05, num_iter: int = 200, batch_size: int = 1,
          save_dir: Path = None, save_interval: int = None, device: str = 'cpu', verbose: bool = True,
          trim_outliers: float = None, trim_rounds: int = 1, view_gains: bool = False, gain_rounds: int = 1,
-         gain_limit: float = 2.0, _job: _Job = None) -> SUCRe:
+         gain_limit: float = 2.0, save_uncertainty: bool = False, _job: _Job = None) -> SUCRe:
     """``num_iter`` steps of ``torch.optim.Adam(lr)`` on the least-squares cost (sucre.py:124-157).
 
     ``batch_size`` is accepted for compatibility: the engine always uses the full batch in one pass, which is
@@ -481,10 +483,16 @@ def adam(sucre: SUCRe, matches_data: loader.MatchesData, lr: float = 0.05, num_i
     them out of the store -> fit anew from the same initial values with the same ``num_iter`` (``_enqueue_gains``);
     ``sucre._gains`` holds every round's record.  Not together with ``trim_outliers``.
 
-    ``_job`` (internal, ``_restore_one``): its ``extras`` stand in for the five keywords above and may ask for the quality pass
+    ``save_uncertainty`` (not a reference argument): behind the last fit, the float64 pass of ``engine.Restoration.uncertainty``;
+    ``sucre._uncertainty`` holds its ``(count, jterms, sums)`` on the device (``engine.water_uncertainty``,
+    ``engine.j_standard_error``).  Not with the light model.
+
+    ``_job`` (internal, ``_restore_one``): its ``extras`` stand in for the six keywords above and may ask for the quality pass
     behind the last fit; it receives the records."""
     extras = _job.extras if _job is not None else _Extras(trim_outliers=trim_outliers, trim_rounds=trim_rounds, view_gains=view_gains,
-                                                          gain_rounds=gain_rounds, gain_limit=gain_limit)
+                                                          gain_rounds=gain_rounds, gain_limit=gain_limit, save_uncertainty=save_uncertainty)
+    if extras.save_uncertainty and sucre.light_model:
+        raise NotImplementedError(_NO_LIGHT_UNCERTAINTY)
     extras = extras.checked(save_interval if save_dir is not None else None)
     job = _Job(sucre=sucre, matches_data=matches_data, extras=extras)   # (no params0: every fit starts from what the module holds)
     print(f'Solve least squares with Adam optimizer ({num_iter} iterations).')
@@ -512,12 +520,15 @@ def adam(sucre: SUCRe, matches_data: loader.MatchesData, lr: float = 0.05, num_i
     # (no snapshot stops in the rounds: nothing has been pulled into the model yet, so each starts from the same values again)
     _enqueue_refits([job], fit_again)
     _enqueue_quality(job)   # --save-quality: the pass right behind the fit, read with the results
+    _enqueue_uncertainty(job)
+    if job.uncertainty is not None:
+        sucre._uncertainty = job.uncertainty
     if job.trim is not None:
         sucre._trim = job.trim
     if job.gains is not None:
         sucre._gains = job.gains
     if _job is not None:
-        _job.quality, _job.trim, _job.gains = job.quality, job.trim, job.gains
+        _job.quality, _job.trim, _job.gains, _job.uncertainty = job.quality, job.trim, job.gains, job.uncertainty
     _pull_results(sucre, resto)
     return sucre
 
@@ -602,6 +613,99 @@ def _write_quality(job) -> None:
         worst = int(per_view.argmax())
         line += f'; worst kept view {views[worst]} (RMS {per_view[worst]:.4f})'
     print(line)
+
+
+# ---- --save-uncertainty: how well the observations determine B, beta, gamma and J -----------------------------------------------
+_NO_LIGHT_UNCERTAINTY = ('the uncertainty of a light-model fit is not built: the lamp\'s ten parameters would have to join B, beta, '
+                         'gamma, and errors conditional on a fixed lamp would understate')
+_CHANNELS = 'RGB'
+
+
+def _enqueue_uncertainty(job) -> None:
+    """The float64 pass on the current stream, no host wait: (count, jterms, sums) on the device."""
+    if job.extras.save_uncertainty:
+        job.uncertainty = job.resto.uncertainty()
+
+
+def pooled_uncertainty(sums_list: list, group=None) -> torch.Tensor:
+    """The 24 float64 words of several images' ``engine.Restoration.uncertainty`` added up, on the host: H, SSR, N and P (and the
+    pixels without an A) of a fit that shares its water add over the images -- in the order of the list within this rank, then
+    through ``dist.all_reduce_sum`` across the ranks of ``group``.  RCCL reduces device tensors only (``dist.fit_shared_water``
+    moves its observation count for the same reason): under an 'nccl' group the 24 words go to this rank's device -- that of the
+    sums, the current one for host sums --, are reduced there and come back.  ``engine.water_uncertainty`` of the result is the
+    shared parameters' covariance."""
+    import torch.distributed as tdist
+
+    from . import _lib
+    total = torch.zeros(_lib.UNCERTAINTY_WORDS, dtype=torch.float64)
+    for sums in sums_list:
+        total = total + sums.detach().to('cpu', torch.float64).reshape(-1)
+    if tdist.is_initialized() and tdist.get_backend(group) == 'nccl':
+        dev = next((s.device for s in sums_list if s.is_cuda), None)
+        comm = total.to(dev if dev is not None else torch.device('cuda', torch.cuda.current_device()))
+        sdist.all_reduce_sum(comm, group)
+        return comm.cpu()
+    sdist.all_reduce_sum(total, group)
+    return total
+
+
+def uncertainty_image(J_se: np.ndarray) -> np.ndarray:
+    """8-bit grey: ``uint8(255 * min(1, sqrt(mean_c sigma_J^2) / QUALITY_RMS_FULL_SCALE))``, 0 where nothing is observed (or the
+    channel's water is not determined: sigma_J is NaN there)."""
+    var = np.asarray(J_se, np.float64) ** 2
+    rms = np.sqrt(np.nan_to_num(var.mean(axis=-1), nan=0.0, posinf=np.inf))
+    return np.uint8(255.0 * np.minimum(1.0, rms / QUALITY_RMS_FULL_SCALE))
+
+
+def _uncertainty_record(result: dict) -> dict:
+    """What ``engine.water_uncertainty`` returned (with the ``sums`` it was made from) as the tensors of a .pt file."""
+    t = lambda x, dt=torch.float64: torch.as_tensor(np.asarray(x), dtype=dt)   # noqa: E731
+    se = t(result['se'])
+    return {'B_se': se[:, 0:1].clone(), 'beta_se': se[:, 1:2].clone(), 'gamma_se': se[:, 2:3].clone(), 'cov': t(result['cov']),
+            'corr': t(result['corr']), 'cond': t(result['cond']), 's2': t(result['s2']), 'dof': int(result['dof']),
+            'n_obs': int(result['n_obs']), 'n_pixels': int(result['n_pixels']), 'normal': t(result['normal']),
+            'sums': t(result['sums']), 'well_posed': t(result['well_posed'], torch.bool)}
+
+
+def _uncertainty_line(result: dict, J_se: np.ndarray = None) -> str:
+    from .engine import WATER_NAMES
+    se, ok = np.asarray(result['se']), np.asarray(result['well_posed'], bool)
+    parts = [f'{name} ± ' + '/'.join(f'{se[c, i]:.4g}' if ok[c] else 'n/a' for c in range(3)) for i, name in enumerate(WATER_NAMES)]
+    line = 'standard errors ' + ', '.join(parts)
+    if ok.any():
+        corr = np.where(ok[:, None, None], np.asarray(result['corr']), 0.0)
+        pairs = [(abs(corr[c, i, j]), c, i, j) for c in range(3) for i in range(3) for j in range(i + 1, 3)]
+        _, c, i, j = max(pairs)
+        line += f'; strongest correlation {WATER_NAMES[i]}~{WATER_NAMES[j]} {corr[c, i, j]:.3f} ({_CHANNELS[c]})'
+    if J_se is not None:
+        med = [np.nanmedian(J_se[..., c]) if np.isfinite(J_se[..., c]).any() else np.nan for c in range(3)]
+        line += '; median sigma_J ' + ' '.join(f'{_CHANNELS[c]} {med[c]:.4g}' for c in range(3))
+    for c in np.nonzero(~ok)[0]:
+        line += f'; channel {_CHANNELS[c]}: the water parameters are not determined by these observations (dof {int(result["dof"])})'
+    return line
+
+
+def _uncertainty_on_host(job) -> dict:
+    """The record of --save-uncertainty with sigma_J made where the terms are (``engine.j_standard_error``), then on the host.  With
+    a shared fit the covariance is the pooled one (``job.pooled_uncertainty``); ``sums`` stay the image's own."""
+    from . import engine
+    count, jterms, sums = job.uncertainty
+    own = sums.cpu()
+    result = dict(job.pooled_uncertainty) if job.pooled_uncertainty is not None else engine.water_uncertainty(own)
+    J_se = engine.j_standard_error(jterms, count, result).cpu()
+    result['sums'] = own.numpy()
+    return {**_uncertainty_record(result), 'J_se': J_se, 'count': count.cpu(), 'result': result}
+
+
+def _write_uncertainty(job) -> None:
+    """``<stem>_uncertainty.pt``, ``<stem>_uncertainty.png`` and one printed line."""
+    record = dict(job.uncertainty)   # host tensors (_restore_finish)
+    result = record.pop('result')
+    stem = Path(job.image.name).stem
+    torch.save(record, job.output_dir / f'{stem}_uncertainty.pt')
+    J_se = record['J_se'].numpy()
+    _save_png(PILImage.fromarray(uncertainty_image(J_se)), job.output_dir / f'{stem}_uncertainty.png')
+    print(f'{job.image.name}: ' + _uncertainty_line(result, J_se))
 
 
 # ---- --trim-outliers: sigma-clip single observations on the device, fit again ------------------------------------------
@@ -789,6 +893,7 @@ def _restore_enqueue_fits(jobs: list) -> None:
         _enqueue_refits(members, fit)
         for job in members:
             _enqueue_quality(job)
+            _enqueue_uncertainty(job)
 
 
 def fit_batch_size(images: list, light_model: bool = False, in_flight: int = 2, n_views: int | None = None, device='cuda') -> int:
@@ -839,6 +944,8 @@ def _restore_finish(job: _Job, keep_matches: bool, writers: ThreadPoolExecutor |
     if job.quality is not None:
         job.quality = tuple(t.cpu() for t in job.quality)
     job.trim, job.gains = _rounds_on_host(job.trim), _rounds_on_host(job.gains)
+    if job.uncertainty is not None:
+        job.uncertainty = _uncertainty_on_host(job)
     if keep_matches and job.matches_file.restoration._views_dev is not None:   # freshly matched (not loaded from this
         if job.trim is not None:                                               # very file); needs the live workspace
             print(f'Keep {job.matches_file.save(survivors=True)} (the observations that survived the trim).')
@@ -865,6 +972,8 @@ def _write_outputs(job: _Job, keep_matches: bool, log: bool = False) -> None:
         _write_trim(job)
     if job.gains is not None:
         _write_gains(job)
+    if job.uncertainty is not None:
+        _write_uncertainty(job)
     torch.save({**sucre.cpu().state_dict(), 'J': sucre.J.detach().cpu()},
                (job.output_dir / job.image.name).with_suffix('.pt'))
     if not keep_matches and job.matches_path.exists():
@@ -1703,6 +1812,7 @@ def _given(args, flag: str) -> bool:
 
 _NOTHING_SHARED, _NO_TRIM, _NO_GAINS = 'nothing is fitted, so nothing is shared', 'there is no fit to trim', 'there is no fit to estimate gains from'
 _NO_RESIDUALS, _NO_SNAPSHOT = 'there is no fit, hence no residuals', 'there are no iterations to snapshot'
+_NO_UNCERTAINTY = 'there is no fit, hence no normal equations to take standard errors from'
 _NO_PARAMETERS, _NO_PICTURE = 'no parameters are read: the restored images are', 'no picture of J is written'
 _MODE_REFUSES = {   # mode -> (flag, why), in the order they are looked at
     '--mosaic': [('--shared-water', _NOTHING_SHARED),
@@ -1711,7 +1821,8 @@ _MODE_REFUSES = {   # mode -> (flag, why), in the order they are looked at
                  ('--trim-outliers', _NO_TRIM), ('--view-gains', _NO_GAINS), ('--save-quality', _NO_RESIDUALS),
                  ('--save-interval', _NO_SNAPSHOT), ('--params-path', _NO_PARAMETERS), ('--keep-matches', 'nothing is matched'),
                  ('--common-stretch', 'the mosaic is one picture: it is stretched by its own percentiles, or by --stretch-from'),
-                 ('--image-scale', 'resized images have float32 colours, and the raw mosaic takes uint8')],
+                 ('--image-scale', 'resized images have float32 colours, and the raw mosaic takes uint8'),
+                 ('--save-uncertainty', _NO_UNCERTAINTY)],
     '--check-consistency': [('--shared-water', _NOTHING_SHARED),
                             ('--apply-water', 'restore first, into the directory to check, then check it'),
                             ('--trim-outliers', _NO_TRIM), ('--view-gains', _NO_GAINS), ('--save-quality', _NO_RESIDUALS),
@@ -1719,11 +1830,11 @@ _MODE_REFUSES = {   # mode -> (flag, why), in the order they are looked at
                             ('--keep-matches', 'no match list is kept: the pairs are compared where they are found'),
                             ('--common-stretch', _NO_PICTURE), ('--stretch-from', _NO_PICTURE),
                             ('--image-scale', 'resized images have float32 colours, and the raw comparison reads uint8'),
-                            ('--mosaic', 'make the mosaic in a run of its own')],
+                            ('--mosaic', 'make the mosaic in a run of its own'), ('--save-uncertainty', _NO_UNCERTAINTY)],
     '--apply-water': [('--shared-water', _NOTHING_SHARED), ('--trim-outliers', _NO_TRIM), ('--view-gains', _NO_GAINS),
                       ('--save-quality', 'a single-view inversion has no residuals'), ('--save-interval', _NO_SNAPSHOT),
                       ('--params-path', 'the parameters come from the --apply-water file'), ('--keep-matches', 'nothing is matched'),
-                      ('--mosaic', 'restore first, then make the mosaic of that directory')],
+                      ('--mosaic', 'restore first, then make the mosaic of that directory'), ('--save-uncertainty', _NO_UNCERTAINTY)],
 }
 
 
@@ -1815,6 +1926,8 @@ def parse_args(args: argparse.Namespace):
     _refuse_gain_flags(args)
     if shared:
         _refuse_shared_flags(args)
+    if getattr(args, 'save_uncertainty', False) and args.light_model:
+        raise SystemExit(f'--save-uncertainty: --light-model does not combine with it ({_NO_LIGHT_UNCERTAINTY}); drop one of the two flags')
     # torch's CPU thread pool follows the machine's CPU count; inside a container with a CPU quota that many spinning
     # threads only get the process throttled (147 CPU-seconds for 64 images on a 256-CPU box with a 16-CPU quota)
     local_world = max(1, int(os.environ.get('LOCAL_WORLD_SIZE', world)))
@@ -2020,8 +2133,16 @@ def restore_shared_water(images: list, colmap_model: sfm.COLMAPModel, args, imag
     group = engine.HipWaterGroup(restos, lr=args.learning_rate, use_closed_form=args.use_closed_form, trace=trace,
                                  params0=jobs[0].params0)
     sdist.fit_shared_water(group, T)
-    for job in jobs:   # --save-quality: behind the group's finish, per image, before anything is read
+    for job in jobs:   # --save-quality, --save-uncertainty: behind the group's finish, per image, before anything is read
         _enqueue_quality(job)
+        _enqueue_uncertainty(job)
+    pooled = None
+    if extras.save_uncertainty:   # H, SSR, N and P add over the images of all ranks; every image's J_se uses the pooled covariance
+        sums_list = [job.uncertainty[2] for job in jobs]
+        pooled_sums = pooled_uncertainty(sums_list)
+        pooled = {**engine.water_uncertainty(pooled_sums), 'sums': pooled_sums.numpy()}
+        for job in jobs:
+            job.pooled_uncertainty = pooled
     trace = trace.cpu().numpy()
     _log_trace(trace, 0)
     for job, resto in zip(jobs, restos):
@@ -2036,6 +2157,13 @@ def restore_shared_water(images: list, colmap_model: sfm.COLMAPModel, args, imag
         _restore_finish(job, args.keep_matches)
     if rank == 0:
         torch.save({**shared, 'trace': torch.from_numpy(trace), 'images': list(request)}, Path(args.output_dir) / 'shared_water.pt')
+    if pooled is not None:   # (every rank takes part in the gather)
+        per_image = [x for part in sdist.all_gather_objects([(job.image.name, job.uncertainty['sums']) for job in jobs]) for x in part]
+        if rank == 0:
+            by_name = dict(per_image)
+            torch.save({**_uncertainty_record(pooled), 'images': list(request), 'image_sums': torch.stack([by_name[name] for name in request])},
+                       Path(args.output_dir) / 'shared_water_uncertainty.pt')
+            print('shared water: ' + _uncertainty_line(pooled))
 
 
 class _Parser(argparse.ArgumentParser):
@@ -2099,6 +2227,12 @@ def build_parser() -> argparse.ArgumentParser:
                           help='also write, per image, <stem>_quality.pt (observations and squared residuals of the fit per pixel and '
                         'per neighbour view), <stem>_coverage.png and <stem>_residual.png, and print the RMS residual and the '
                         'worst-fitting view')
+    p.extras.add_argument('--save-uncertainty', action='store_true', default=argparse.SUPPRESS,
+                          help='also write, per image, <stem>_uncertainty.pt (standard errors, covariance and correlation of B, beta, '
+                               'gamma per channel from the Gauss-Newton normal equations of the fit, summed in float64 on the device, '
+                               'and the standard error of J per pixel) and <stem>_uncertainty.png, and print the standard errors; '
+                               'with --shared-water the sums are pooled over all images (shared_water_uncertainty.pt); tells a '
+                               'survey whose water is determined from one whose residuals are merely small')
     p.extras.add_argument('--trim-outliers', type=float, metavar='K', default=argparse.SUPPRESS,
                           help='after the fit, drop every observation whose residual exceeds K times the RMS residual of its '
                                'channel (never a pixel\'s last ones) and fit again from the same start; also writes, per image, '
